@@ -44,6 +44,21 @@ UNET_BYTES_PER_GRID = 499.6e6          # fused-minimum activation traffic
 UNET_PARAM_BYTES_PER_STEP = 1.25e9     # 124.6 MB x (1 fwd + 2 bwd + 7 Adam)
 VAE_FLOP_PER_GRID = 33.73e9            # VAE 3 x 2.126 + perceptual 3 x 9.116 GFLOP
 PMC_TRAFFIC_FILES = ("r6_pmc_traffic.json", "r5_pmc_traffic.json", "r4_pmc_traffic.json", "r3_pmc_traffic.json", "r2_pmc_traffic.json", "r1_pmc_traffic.json")
+DUMP_STATE_VALUES = 1 << 22            # --dump-outputs: at most this many float32 values of the model state (16 MB)
+
+
+def dump_unet_outputs(unet, out_dir):
+    """--dump-outputs: what the last timed U-Net step computed, so that two builds can be compared output for output.
+    unet_metric_sums.npy (float64): the step's loss / metric sums (ics_unet_metric_sums: sum lsoft, sum lsig, tp,
+    predicted, wr tp, wr possible, voxels).  unet_state.npy (float32): the parameters and BatchNorm moving statistics
+    the step leaves, flattened in the engine's tensor order; above DUMP_STATE_VALUES values, those at the sorted indices
+    PCG64(0) draws -- the same indices for the same model."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "unet_metric_sums.npy"), np.array(list(unet.metric_sums().values()), np.float64))
+    state = np.concatenate([a.ravel() for a in unet.get_weights().values()])
+    if state.size > DUMP_STATE_VALUES:
+        state = state[np.sort(np.random.default_rng(0).choice(state.size, DUMP_STATE_VALUES, replace=False))]
+    np.save(os.path.join(out_dir, "unet_state.npy"), state.astype(np.float32))
 
 
 def cpu_baseline(batch=32, d=32):
@@ -154,7 +169,14 @@ def main():
     ap.add_argument("--no-inference", action="store_true", help="skip the predict / generate blocks of the contract line")
     ap.add_argument("--sync-bn", action="store_true", help="data parallel: global-batch BatchNorm statistics")
     ap.add_argument("--dump-rows", type=str, default=None, help="write the per-launch-site profile rows (JSON) here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed U-Net step computed as DIR/<name>.npy (dump_unet_outputs); "
+                         "unet workload, one process without a communicator")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "unet" or args.gpus != 1):
+        ap.error("--dump-outputs needs --workload unet and --gpus 1")
 
     # --gpus N > 1 without a launcher: become the launcher BEFORE any HIP call (icsg3d_amd/launcher.py); a mismatch
     # between --gpus and WORLD_SIZE, or fewer than N visible GPUs, exits non-zero -- never an n_gpus: 1 line for --gpus 8
@@ -185,6 +207,9 @@ def main():
     # to exercise it on a 1-GPU box
     force = os.environ.get("ICSG3D_BENCH_FORCE_DIST") == "1" and "RANK" in os.environ
     use_dist = world > 1 or force
+    if args.dump_outputs and use_dist:
+        # with a communicator the head's metric sums are only finalised on the steps that ask for the metrics
+        raise SystemExit("--dump-outputs: not on the data-parallel path (ICSG3D_BENCH_FORCE_DIST)")
     dist = None
     json_fd = None
     if use_dist:
@@ -210,10 +235,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def timed(step, engines, profiled, step_profile=None):
+    def timed(step, engines, profiled, step_profile=None, after_timed=None):
         """W warm-up steps, then EXACTLY K steps between barrier + device sync on both sides; max over ranks.
         step_profile: the step of the untimed all-events pass when it must differ (joint: the two engines serialised, so
-        that a kernel's event bracket does not time a kernel of the other stream it shares the chip with)."""
+        that a kernel's event bracket does not time a kernel of the other stream it shares the chip with).
+        after_timed: called once after the K timed steps, before any further step changes the engines' state."""
         def barrier(where="barrier"):
             wd.beat(where + ": device sync")
             for e in engines:
@@ -262,6 +288,9 @@ def main():
         barrier("after the timed steps")
         elapsed = max_over_ranks(time.perf_counter() - t0)
         timed.gpu_active_s = gpu_ms * 1e-3
+        if after_timed is not None:
+            wd.beat("after the timed steps: reading outputs")
+            after_timed()
         rows = [r for e in profiled for r in e.profile_rows()]
         for e in profiled:
             e.profile_enable(False)
@@ -326,7 +355,9 @@ def main():
                 raise SystemExit("RCCL communicator has %d ranks, --gpus %d" % (got, world))
 
     if args.workload == "unet":
-        elapsed, elapsed_plain, rows_live, rows = timed(lambda: unet.train_step_resident(False), [unet], [unet])
+        dump = (lambda: dump_unet_outputs(unet, args.dump_outputs)) if args.dump_outputs else None
+        elapsed, elapsed_plain, rows_live, rows = timed(lambda: unet.train_step_resident(False), [unet], [unet],
+                                                        after_timed=dump)
         unet_launches = timed.kernel_launches_per_step
         gpu_active_s = timed.gpu_active_s
         sustained = soak(lambda: unet.train_step_resident(False), [unet], elapsed_plain / args.steps * 1e3) \
@@ -654,8 +685,7 @@ def main():
                 out["unet_plus_vae"] = {"ms_per_batch": round(out["ms_per_step"] + ms_v, 3),
                                         "value": round(world * B / ((out["ms_per_step"] + ms_v) * 1e-3), 2),
                                         "unit": "voxel-grids/s"}
-                # a reader of `metric` + `value` alone must not take `value` for the U-Net+VAE pair
-                out["metric"] += " (= %.1f voxel-grids/s, U-Net step + DFC-VAE step per batch)" % out["unet_plus_vae"]["value"]
+                # `metric` names the measurement, the same text on every run: the pair's measured rate is in unet_plus_vae only
             else:
                 out = {"metric": "voxel-grids/s (fwd+bwd) for %d^3 %s at batch %d per GPU" % (d, args.workload, B),
                        "n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
