@@ -35,11 +35,20 @@ class VaeConfig(C.Structure):
                 ("bn_unbias", C.c_int)]
 
 
+class Structures(C.Structure):
+    """ics_structures: site arrays [count][max_sites] (rows >= nsites[i] are never read)."""
+    _fields_ = [("count", C.c_int), ("max_sites", C.c_int), ("nsites", C.POINTER(C.c_int32)),
+                ("xyz", C.POINTER(C.c_double)), ("z", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double)),
+                ("abc", C.POINTER(C.c_double))]
+
+
 _F = C.POINTER(C.c_float)
 _U8 = C.POINTER(C.c_uint8)
 _I32 = C.POINTER(C.c_int32)
 _I64 = C.POINTER(C.c_int64)
 _H = C.c_void_p
+_D = C.POINTER(C.c_double)
+_ST = C.POINTER(Structures)
 
 # name -> (restype, argtypes); every symbol include/icsg3d.h declares
 SIGNATURES = {
@@ -76,6 +85,9 @@ SIGNATURES = {
     "ics_op_label_boxes": (C.c_int, [_I32, _I32, C.c_int, C.c_int, C.c_int, _I32, _I32, _I32]),
     "ics_op_watershed_split": (C.c_int, [_I32, _I32, _I32, C.c_int, C.c_int, _I32]),
     "ics_op_component_bounds": (C.c_int, [_I32, _I32, C.c_int, _I32, _I32, C.c_int, C.c_int, C.c_double, _I64]),
+    "ics_op_voxelise": (C.c_int, [_ST, _I32, C.c_int, C.c_int, C.c_double, C.c_double, _D, _D, _D]),
+    "ics_unet_voxelise_batch": (C.c_int, [_H, _ST, _I32, C.c_int, C.c_double, C.c_double]),
+    "ics_vae_voxelise_batch": (C.c_int, [_H, _ST, _I32, C.c_int, C.c_double, C.c_double, _F, _F]),
     "ics_op_region_stats": (C.c_int, [_I32, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I32]),
     "ics_net_destroy": (C.c_int, [_H]),
     "ics_net_sync": (C.c_int, [_H]),
@@ -160,6 +172,10 @@ def u8ptr(a):
 
 def i32ptr(a):
     return a.ctypes.data_as(_I32) if a is not None else None
+
+
+def f64ptr(a):
+    return a.ctypes.data_as(_D) if a is not None else None
 
 
 def i64ptr(a):

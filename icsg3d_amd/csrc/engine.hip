@@ -7,6 +7,7 @@
 #include "common.h"
 #include "elementwise.h"
 #include "segment.h"
+#include "voxelise.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -283,6 +284,7 @@ struct Net {
   hipEvent_t timer_ev[2] = {nullptr, nullptr};   // ics_net_timer_start / _stop
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
+  VoxStage vox;                       // ics_*_voxelise_batch: pinned staging of a batch's site table (voxelise.h)
 
   // VAE specifics
   Net* pm = nullptr;
@@ -2520,6 +2522,21 @@ int ics_unet_metric_sums(ics_net* net, double sums[7]) {
   return 0;
 }
 
+// create_matrices.py's grids (utils.py:88-144, :193-222) computed into the resident batch instead of uploaded from
+// the loader of unet/data.py:81-100 (x = M or [M, p], labels = S) -- bit-identical to ics_unet_upload_batch of the
+// loader's arrays over ics_op_voxelise's output.  Enqueued only.
+int ics_unet_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t* jobs, int batch, double eps_frac,
+                            double label_frac) {
+  ICS_TRY(require_kind(net, 0));
+  Net& n = net->n;
+  ICS_CHECK(batch >= 1 && batch <= n.maxB, "batch exceeds max_batch");
+  ICS_CHECK(n.C == 1 || n.C == 4, "voxelise feeds engines with 1 (M) or 4 (M, p) input channels");
+  ICS_TRY(voxelise_check(s, jobs, batch, n.d, eps_frac, label_frac, n.ncls));
+  ICS_TRY(voxelise_engine(n.st, n.vox, s, jobs, batch, n.d, eps_frac, label_frac, n.x_in, n.C, n.labels, nullptr, 0));
+  n.resident_batch = batch;
+  return 0;
+}
+
 // ---------------------------------------------------------------- VAE entry points
 int ics_vae_encode(ics_net* net, const float* x, const float* cond, const float* eps, int batch, float* z_mean,
                    float* z_log_var, float* z) {
@@ -2555,6 +2572,21 @@ int ics_vae_upload_batch(ics_net* net, const float* x, const float* cond, const 
   ICS_TRY(require_kind(net, 1));
   ICS_TRY(vae_upload(net->n, x, cond, eps, batch));
   ICS_HIP(hipStreamSynchronize(net->n.st));
+  return 0;
+}
+// The VAE's x (vae/data.py:56-63 over create_matrices.py's files) computed in place; cond / eps as ics_vae_upload_batch.
+int ics_vae_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t* jobs, int batch, double eps_frac,
+                           double label_frac, const float* cond, const float* eps) {
+  ICS_TRY(require_kind(net, 1));
+  Net& n = net->n;
+  ICS_CHECK(cond && eps, "null argument");
+  ICS_CHECK(batch >= 1 && batch <= n.maxB, "batch exceeds max_batch");
+  ICS_CHECK(n.C == 1 || n.C == 4, "voxelise feeds engines with 1 (M) or 4 (M, p) input channels");
+  ICS_TRY(voxelise_check(s, jobs, batch, n.d, eps_frac, label_frac, 0));
+  const VoxBlob blobs[2] = {{cond, n.cond_in, (size_t)batch * n.ncond * sizeof(float)},
+                            {eps, n.eps_in, (size_t)batch * n.latent * sizeof(float)}};
+  ICS_TRY(voxelise_engine(n.st, n.vox, s, jobs, batch, n.d, eps_frac, label_frac, n.x_in, n.C, nullptr, blobs, 2));
+  n.resident_batch = batch;
   return 0;
 }
 int ics_vae_train_step_resident(ics_net* net, float* metrics) {
@@ -2759,6 +2791,12 @@ int ics_release_caches() {
 }
 #undef tl_op_stream
 
+int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac, double label_frac,
+                    double* M, double* S, double* p) {
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return voxelise_op(st, s, jobs, njobs, d, eps_frac, label_frac, M, S, p);
+}
 int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
                        int32_t* labels, int32_t* nlabels, int32_t* stats) {
   hipStream_t st;

@@ -3,6 +3,7 @@
  * engine construction (tensor tables, BN slab, workspace planners), named tensor I/O, train / test / predict
  * call chains (launch planning, split-K and bucket bookkeeping, profiler rows), the data-parallel entry points,
  * the fused inference tail, optimizer-state export and destruction.  Kernels do not run; results are not checked. */
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,87 @@ static int tensor_io(ics_net* net) {
     if (ics_net_set_tensor(net, name, buf, cnt + 1) == 0) { fprintf(stderr, "size check missing for %s\n", name); return 1; }
     free(buf);
   }
+  return 0;
+}
+
+/* Voxelisation: the host-pointer op (valid and invalid arguments, internal chunking) and both engine feeds; padding rows
+ * beyond nsites are left out of the allocation's reach by a max_sites stride that is larger than any nsites. */
+static int voxelise_walk(ics_net* unet, ics_net* vae, int d, int B, const float* cond, const float* eps) {
+  enum { NS = 3, MS = 5 };
+  int32_t nsites[NS] = {1, 5, 3};
+  double xyz[NS * MS * 3], z[NS * MS], sigma[NS * MS], abc[NS * 3];
+  for (int i = 0; i < NS * MS; ++i) {
+    xyz[3 * i] = 0.1 * i; xyz[3 * i + 1] = 0.2 * (i % 4); xyz[3 * i + 2] = 0.05 * i;
+    z[i] = 1 + i % 90; sigma[i] = 0.5 + 0.1 * (i % 3);
+  }
+  for (int i = 0; i < NS * 3; ++i) abc[i] = 3.0 + i;
+  ics_structures s = {NS, MS, nsites, xyz, z, sigma, abc};
+  const int nj = 7;
+  int32_t jobs[7 * 4] = {0, -1, -1, -1, 1, 0, 1, 2, 2, 2, 2, 2, 1, 1, -1, 0, 0, -1, -1, -1, 2, 0, 0, 0, 1, 2, 1, 0};
+  const int dv = 6;
+  const size_t V = (size_t)dv * dv * dv;
+  double* M = (double*)malloc(nj * V * 8);
+  double* S = (double*)malloc(nj * V * 8);
+  double* p = (double*)malloc(nj * V * 24);
+  OK(ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p));
+  OK(ics_op_voxelise(&s, jobs, nj, dv, 0.1, 0.6, NULL, S, NULL));
+  OK(ics_op_voxelise(&s, jobs, nj, dv, 0.1, 0.6, NULL, NULL, NULL));
+  {   /* more jobs than one chunk holds */
+    const int big = 2100;
+    int32_t* bj = (int32_t*)malloc((size_t)big * 16);
+    for (int j = 0; j < big; ++j) { bj[4 * j] = j % NS; bj[4 * j + 1] = j % 4 - 1; bj[4 * j + 2] = -1; bj[4 * j + 3] = (j / 4) % 3; }
+    double* bM = (double*)malloc((size_t)big * 8 * 8 * 8 * 8);
+    OK(ics_op_voxelise(&s, bj, big, 8, 0.25, 1.0, bM, NULL, NULL));
+    free(bj); free(bM);
+  }
+  /* every invalid argument is refused with a message, and nothing is written */
+  int bad = 0;
+  ics_structures t = s;
+  bad += ics_op_voxelise(NULL, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, NULL, nj, dv, 0.25, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, jobs, 0, dv, 0.25, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, jobs, nj, 1, 0.25, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, jobs, nj, 300, 0.25, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, jobs, nj, dv, -0.1, 1.0, M, S, p) == 0;
+  bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, NAN, M, S, p) == 0;
+  t.xyz = NULL; bad += ics_op_voxelise(&t, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; t = s;
+  t.count = 0; bad += ics_op_voxelise(&t, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; t = s;
+  t.max_sites = 4; bad += ics_op_voxelise(&t, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; t = s;   /* nsites 5 > stride */
+  jobs[4] = 3; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; jobs[4] = 1;
+  jobs[5] = 3; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; jobs[5] = 0;
+  jobs[6] = -2; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; jobs[6] = 1;
+  nsites[1] = 0; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; nsites[1] = 5;
+  nsites[1] = 300; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; nsites[1] = 5;
+  sigma[MS + 2] = 0.0; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; sigma[MS + 2] = 0.5;
+  sigma[MS + 2] = INFINITY; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; sigma[MS + 2] = 0.5;
+  abc[4] = -1.0; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; abc[4] = 4.0;
+  xyz[3 * MS + 1] = NAN; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; xyz[3 * MS + 1] = 0.2;
+  z[MS] = -1.0; bad += ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p) == 0; z[MS] = 1.0;
+  if (bad) { fprintf(stderr, "voxelise: %d invalid argument sets accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "voxelise: no error message\n"); return 1; }
+  OK(ics_op_voxelise(&s, jobs, nj, dv, 0.25, 1.0, M, S, p));     /* still usable */
+  free(M); free(S); free(p);
+  /* engine feeds: a batch of B jobs at the engines' grid */
+  int32_t* ej = (int32_t*)malloc((size_t)B * 16);
+  for (int b = 0; b < B; ++b) { ej[4 * b] = b % NS; ej[4 * b + 1] = b % 3; ej[4 * b + 2] = -1; ej[4 * b + 3] = 1; }
+  OK(ics_unet_voxelise_batch(unet, &s, ej, B, 0.25, 1.0));
+  OK(ics_unet_train_step_resident(unet, NULL));
+  OK(ics_unet_predict_resident(unet, 1, 0.8f));
+  OK(ics_vae_voxelise_batch(vae, &s, ej, B, 0.25, 1.0, cond, eps));
+  OK(ics_vae_train_step_resident(vae, NULL));
+  OK(ics_unet_voxelise_batch(unet, &s, ej, 1, 0.1, 0.6));
+  bad = 0;
+  bad += ics_unet_voxelise_batch(unet, &s, ej, B + 1, 0.25, 1.0) == 0;
+  bad += ics_unet_voxelise_batch(vae, &s, ej, B, 0.25, 1.0) == 0;
+  bad += ics_vae_voxelise_batch(unet, &s, ej, B, 0.25, 1.0, cond, eps) == 0;
+  bad += ics_vae_voxelise_batch(vae, &s, ej, B, 0.25, 1.0, NULL, eps) == 0;
+  bad += ics_unet_voxelise_batch(NULL, &s, ej, B, 0.25, 1.0) == 0;
+  z[MS] = 95.0; bad += ics_unet_voxelise_batch(unet, &s, ej, B, 0.25, 1.0) == 0; z[MS] = 1.0;
+  z[MS] = 2.5; bad += ics_unet_voxelise_batch(unet, &s, ej, B, 0.25, 1.0) == 0; z[MS] = 1.0;
+  z[MS] = 95.0; OK(ics_vae_voxelise_batch(vae, &s, ej, B, 0.25, 1.0, cond, eps)); z[MS] = 1.0;   /* no class-id rule */
+  if (bad) { fprintf(stderr, "voxelise feed: %d invalid argument sets accepted\n", bad); return 1; }
+  free(ej);
+  (void)d;
   return 0;
 }
 
@@ -100,6 +182,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_unet_train_step_resident(unet, NULL));
   OK(ics_vae_upload_batch(vae, x, cond, eps, B));
   OK(ics_vae_train_step_resident(vae, mv));
+  if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (ics_unet_train_step(unet, x, lab, B + 1, mm) == 0) { fprintf(stderr, "max_batch check missing\n"); return 1; }
   int rows = 0;
   OK(ics_net_profile_count(unet, &rows));

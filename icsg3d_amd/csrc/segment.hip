@@ -603,6 +603,7 @@ struct ScratchTL {
 };
 thread_local ScratchTL tl_scratch_holder;
 #define tl_scratch (tl_scratch_holder.s)
+}  // namespace
 int scratch_get(size_t bytes, unsigned char** out) {
   int dev = 0;
   ICS_HIP(hipGetDevice(&dev));
@@ -618,7 +619,6 @@ int scratch_get(size_t bytes, unsigned char** out) {
   *out = s.p;
   return 0;
 }
-}  // namespace
 void segment_release_scratch() {
   if (tl_scratch.p) (void)hipFree(tl_scratch.p);
   tl_scratch = Scratch{};

@@ -16,6 +16,13 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _jobs4(jobs):
+    jobs = np.ascontiguousarray(jobs, np.int32)
+    if jobs.ndim != 2 or jobs.shape[1] != 4:
+        raise ValueError("jobs must be (B, 4) int32 {structure, r0, r1, r2}, got %s" % (jobs.shape,))
+    return jobs
+
+
 class _Net:
     """Common handle plumbing: named tensors, gradients, profiling, data-parallel comm."""
 
@@ -260,6 +267,15 @@ class UnetEngine(_Net):
         lab = self._labels(labels, x.shape[0])
         L.check(self._lib.ics_unet_upload_batch(self._h, L.fptr(x), L.u8ptr(lab), x.shape[0]))
 
+    def voxelise_batch(self, structs, jobs, eps_frac=0.25, label_frac=1.0):
+        """create_matrices.py's grids of `jobs` (matrices.make_jobs) computed straight into the resident batch: x = M
+        or [M, p], labels = S -- what upload_batch of UnetDataGenerator's arrays over the saved files would upload,
+        bit for bit.  Enqueued only; train_step_resident / predict_resident follow."""
+        jobs = _jobs4(jobs)
+        cs = structs.c_struct()
+        L.check(self._lib.ics_unet_voxelise_batch(self._h, C.byref(cs), L.i32ptr(jobs), len(jobs), float(eps_frac),
+                                                  float(label_frac)))
+
     def predict_resident(self, labels_only=False, thresh=0.8):
         """model.predict on the uploaded batch, enqueued only; the outputs stay in HBM (benchmark path)."""
         L.check(self._lib.ics_unet_predict_resident(self._h, 1 if labels_only else 0, float(thresh)))
@@ -382,6 +398,20 @@ class VaeEngine(_Net):
     def upload_batch(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)
         L.check(self._lib.ics_vae_upload_batch(self._h, L.fptr(x), L.fptr(cond), L.fptr(eps), B))
+
+    def voxelise_batch(self, structs, jobs, cond, eps, eps_frac=0.25, label_frac=1.0):
+        """As UnetEngine.voxelise_batch for the VAE's input; cond (B, cond_shape) and eps (B, latent_dim) are
+        uploaded as by upload_batch."""
+        jobs = _jobs4(jobs)
+        B = len(jobs)
+        cond, eps = _f32(cond), _f32(eps)
+        if cond.shape != (B, self.cond_shape):
+            raise ValueError("bad cond shape %s" % (cond.shape,))
+        if eps.shape != (B, self.latent_dim):
+            raise ValueError("bad eps shape %s" % (eps.shape,))
+        cs = structs.c_struct()
+        L.check(self._lib.ics_vae_voxelise_batch(self._h, C.byref(cs), L.i32ptr(jobs), B, float(eps_frac),
+                                                 float(label_frac), L.fptr(cond), L.fptr(eps)))
 
     def train_step_resident(self, want_metrics=False):
         if want_metrics:

@@ -207,6 +207,43 @@ int ics_vae_decode_to_unet_atoms(ics_net* vae, ics_net* unet, const float* z, co
                                  float* density, float* coord_minmax, int32_t* regions, int32_t* counts,
                                  int32_t* atom_stats, int64_t* convexity_bounds);
 
+/* ---------------------------------------------------------------- voxelisation (create_matrices.py)
+ * The arrays create_matrices.py saves per crystal (reference create_matrices.py:117-190), computed on the device in
+ * the reference's semantics -- no periodic images, lattice angles ignored, fp64:
+ *   M density  (2 pi)^-1.5 sum_s exp(-D^2 / (2 sigma_s^2)) Z_s / sigma_s^3      utils.density_matrix (utils.py:97-144)
+ *   S species  0 when no site has D < sigma_s*label_frac, that site's Z when one does, else Z of argmin_s D over ALL sites
+ *              (the double loop of utils.py:117-134; ties to the first site)
+ *   p          p[i,j,k] = (x_i, y_j, z_k), x = linspace(0, a + 2*eps*a, d+1)[:-1]  utils.coordinate_grid (utils.py:88-94)
+ * with D the euclidean distance from site s to the voxel centre linspace(-a*eps, a + a*eps, d+1)[:-1] + dv/2 per axis
+ * (utils.py:102-115), flat voxel order product(x, y, z): M[i,j,k] has i along a.
+ * A job = {structure, r0, r1, r2}: structure index, then up to three quarter turns applied in order, each an index into
+ * [(0,1), (0,2), (1,2)] or -1 for none.  scipy.ndimage.rotate(X, 90, axes, reshape=False, mode="nearest") as
+ * random_rotation_3d (utils.py:193-222) calls it equals np.rot90(X, 1, axes) on these grids, and that is what is applied
+ * (p's channels are not permuted: only positions move, as in the reference). */
+typedef struct ics_structures {
+  int count, max_sites;  /* site arrays are [count][max_sites]; rows >= nsites[i] are never read                 */
+  const int32_t* nsites; /* [count], 1..256                                                                       */
+  const double* xyz;     /* [count][max_sites][3] cartesian = min-shifted frac * abc (utils.py:83-84, create_matrices.py:140) */
+  const double* z;       /* [count][max_sites] atomic numbers                                                    */
+  const double* sigma;   /* [count][max_sites] Gaussian width = sigma_frac * ionic radius (create_matrices.py:150)  */
+  const double* abc;     /* [count][3] lattice lengths (create_matrices.py:129)                                  */
+} ics_structures;
+/* HOST pointers in and out.  jobs [njobs][4]; outputs each optional (NULL): M, S [njobs][d][d][d], p [njobs][d][d][d][3],
+ * float64.  d in [2, 256].  Any njobs: chunked internally under a device-memory budget (the calling thread's scratch,
+ * freed by ics_release_caches).  Synchronous. */
+int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac, double label_frac,
+                    double* M, double* S, double* p);
+/* The same grids written straight into the engine's resident batch (what ics_unet_upload_batch / ics_vae_upload_batch
+ * would upload from the loaders of unet/data.py / vae/data.py over the saved files, bit for bit: float32 rounded from the
+ * same fp64 values): x = M (C = 1) or [M, p] (C = 4); the U-Net's uint8 labels = S (Z must be a class id < num_classes);
+ * the VAE's cond / eps are uploaded as by ics_vae_upload_batch.  Enqueued on the engine's stream (the ~1 KB of site data
+ * per job goes through pinned memory); *_train_step_resident / ics_unet_predict_resident then run unchanged.
+ * jobs [batch][4], batch <= max_batch, the engine's own d; in_channels must be 1 or 4. */
+int ics_unet_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t* jobs, int batch, double eps_frac,
+                            double label_frac);
+int ics_vae_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t* jobs, int batch, double eps_frac,
+                           double label_frac, const float* cond, const float* eps);
+
 /* ---------------------------------------------------------------- common to both engines */
 int ics_net_destroy(ics_net* net);
 int ics_net_sync(ics_net* net);
