@@ -88,6 +88,9 @@ SIGNATURES = {
     "ics_op_voxelise": (C.c_int, [_ST, _I32, C.c_int, C.c_int, C.c_double, C.c_double, _D, _D, _D]),
     "ics_unet_voxelise_batch": (C.c_int, [_H, _ST, _I32, C.c_int, C.c_double, C.c_double]),
     "ics_vae_voxelise_batch": (C.c_int, [_H, _ST, _I32, C.c_int, C.c_double, C.c_double, _F, _F]),
+    "ics_vae_reconstruct_resident_to_unet_atoms": (C.c_int, [_H, _H, C.c_float, C.c_int, C.c_int, _U8, _U8, _F, _F,
+                                                            _I32, _I32, _I32, _I64]),
+    "ics_op_match_emd": (C.c_int, [_D, _I32, _D, _I32, C.c_int, _D, _I32]),
     "ics_op_region_stats": (C.c_int, [_I32, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I32]),
     "ics_net_destroy": (C.c_int, [_H]),
     "ics_net_sync": (C.c_int, [_H]),

@@ -8,6 +8,7 @@
 #include "elementwise.h"
 #include "segment.h"
 #include "voxelise.h"
+#include "match.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -2613,16 +2614,14 @@ int ics_vae_test_step(ics_net* net, const float* x, const float* cond, const flo
 // the density channel (watershed input) and the coordinate channels' min/max (to_lattice_params).
 // device part of the tail: decoder -> U-Net -> labels; leaves species / mask (uint8 [M] each) and aux (density [M] |
 // minmax [B][3][2]) in the U-Net head's gradient buffer, which no inference path reads
-static int decode_to_labels_device(Net& n, Net& u, const float* z, const float* cond, int batch, float thresh,
-                                   bool want_density, bool want_minmax, unsigned char** d_species_out,
-                                   unsigned char** d_mask_out, float** d_aux_out) {
-  ICS_CHECK(z && cond, "null argument");
+static int tail_check(const Net& n, const Net& u, int batch) {
   ICS_CHECK(u.d == n.d && u.C == n.C && u.device == n.device, "U-Net / VAE engines do not match (grid, channels, device)");
   ICS_CHECK(batch >= 1 && batch <= n.maxB && batch <= u.maxB, "batch exceeds max_batch");
-  const size_t lat = n.latent, W = lat + n.ncond;
-  ICS_HIP(hipStreamSynchronize(u.st));
-  ICS_HIP(hipMemcpy2DAsync(n.zc, W * 4, z, lat * 4, lat * 4, batch, hipMemcpyHostToDevice, n.st));
-  ICS_HIP(hipMemcpy2DAsync(n.zc + lat, W * 4, cond, n.ncond * 4, n.ncond * 4, batch, hipMemcpyHostToDevice, n.st));
+  return 0;
+}
+// the compute of the tail from [z | cond] already in n.zc (checked by tail_check, the U-Net's stream drained)
+static int decode_to_labels_compute(Net& n, Net& u, int batch, float thresh, bool want_density, bool want_minmax,
+                                    unsigned char** d_species_out, unsigned char** d_mask_out, float** d_aux_out) {
   ICS_TRY(vae_decode_fwd(n, batch, false));
   hipStream_t saved = u.st;
   u.st = n.st;
@@ -2648,6 +2647,18 @@ static int decode_to_labels_device(Net& n, Net& u, const float* z, const float* 
   ICS_TRY(rc);
   *d_species_out = d_species; *d_mask_out = d_mask; *d_aux_out = d_aux;
   return 0;
+}
+// z / cond from the host into n.zc, then the compute
+static int decode_to_labels_device(Net& n, Net& u, const float* z, const float* cond, int batch, float thresh,
+                                   bool want_density, bool want_minmax, unsigned char** d_species_out,
+                                   unsigned char** d_mask_out, float** d_aux_out) {
+  ICS_CHECK(z && cond, "null argument");
+  ICS_TRY(tail_check(n, u, batch));
+  const size_t lat = n.latent, W = lat + n.ncond;
+  ICS_HIP(hipStreamSynchronize(u.st));
+  ICS_HIP(hipMemcpy2DAsync(n.zc, W * 4, z, lat * 4, lat * 4, batch, hipMemcpyHostToDevice, n.st));
+  ICS_HIP(hipMemcpy2DAsync(n.zc + lat, W * 4, cond, n.ncond * 4, n.ncond * 4, batch, hipMemcpyHostToDevice, n.st));
+  return decode_to_labels_compute(n, u, batch, thresh, want_density, want_minmax, d_species_out, d_mask_out, d_aux_out);
 }
 
 static int tail_copy_out(Net& n, int batch, const unsigned char* d_species, const unsigned char* d_mask,
@@ -2731,6 +2742,31 @@ int ics_vae_decode_to_unet_atoms(ics_net* vae, ics_net* unet, const float* z, co
   return 0;
 }
 
+// eval.py:163-175: the reconstruction chain on the resident batch.  The encoder's sampling leaves [z | cond] in zc
+// (launch_sampling), where ics_vae_decode would have uploaded them: nothing crosses to the host before the atoms.
+int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, float thresh, int min_voxels,
+                                               int max_atoms, uint8_t* species, uint8_t* mask, float* density,
+                                               float* coord_minmax, int32_t* regions, int32_t* counts,
+                                               int32_t* atom_stats, int64_t* convexity_bounds) {
+  ICS_TRY(require_kind(vae, 1));
+  ICS_TRY(require_kind(unet, 0));
+  Net& n = vae->n;
+  const int batch = n.resident_batch;
+  ICS_CHECK(batch > 0, "no resident batch: call ics_vae_upload_batch or ics_vae_voxelise_batch first");
+  ICS_CHECK(counts && atom_stats && max_atoms >= 1, "null argument");
+  ICS_TRY(tail_check(n, unet->n, batch));
+  ICS_HIP(hipStreamSynchronize(unet->n.st));
+  ICS_TRY(vae_encode_fwd(n, batch, false));
+  unsigned char *d_species, *d_mask;
+  float* d_aux;
+  ICS_TRY(decode_to_labels_compute(n, unet->n, batch, thresh, density != nullptr, coord_minmax != nullptr, &d_species,
+                                   &d_mask, &d_aux));
+  ICS_TRY(tail_copy_out(n, batch, d_species, d_mask, d_aux, species, mask, density, coord_minmax));
+  ICS_TRY(segment_to_host(n, d_mask, d_species, batch, n.d, min_voxels, max_atoms, unet->n.ncls, regions, counts,
+                          atom_stats, convexity_bounds));
+  return 0;
+}
+
 int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch, int d, int min_voxels, int max_atoms,
                          int num_species, int32_t* regions, int32_t* counts, int32_t* atom_stats, int64_t* convexity_bounds) {
   ICS_CHECK(mask && species && batch >= 1 && max_atoms >= 1 && min_voxels >= 0, "bad segmentation arguments");
@@ -2796,6 +2832,13 @@ int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int
   hipStream_t st;
   ICS_TRY(op_stream(&st));
   return voxelise_op(st, s, jobs, njobs, d, eps_frac, label_frac, M, S, p);
+}
+int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
+                     double* emd, int32_t* match) {
+  ICS_TRY(match_emd_check(a, a_off, b, b_off, batch, emd));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return match_emd_op(st, a, a_off, b, b_off, batch, emd, match);
 }
 int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
                        int32_t* labels, int32_t* nlabels, int32_t* stats) {

@@ -119,6 +119,89 @@ static int voxelise_walk(ics_net* unet, ics_net* vae, int d, int B, const float*
   return 0;
 }
 
+/* Batched matching: valid batches (both orientations, empty sets, the 2048-point limit, more points than one chunk
+ * holds) and every refused argument, after which the op still works. */
+static int match_walk(void) {
+  enum { NB = 4 };
+  int32_t ao[NB + 1] = {0, 3, 3, 10, 12}, bo[NB + 1] = {0, 5, 7, 9, 9};
+  double a[12 * 3], b[9 * 3], emd[NB];
+  int32_t match[12];
+  for (int i = 0; i < 36; ++i) a[i] = 0.37 * i - 2.0;
+  for (int i = 0; i < 27; ++i) b[i] = 1.0 - 0.21 * i;
+  OK(ics_op_match_emd(a, ao, b, bo, NB, emd, match));
+  OK(ics_op_match_emd(a, ao, b, bo, NB, emd, NULL));
+  OK(ics_op_match_emd(b, bo, a, ao, NB, emd, match));
+  {   /* 1030 samples of 2048 x 2048 points: more than one chunk's point budget */
+    const int ns = 1030, np = 2048;
+    double* big = (double*)calloc((size_t)ns * np * 3, sizeof(double));
+    int32_t* off = (int32_t*)malloc((ns + 1) * sizeof(int32_t));
+    double* e = (double*)malloc(ns * sizeof(double));
+    int32_t* m = (int32_t*)malloc((size_t)ns * np * sizeof(int32_t));
+    for (int k = 0; k <= ns; ++k) off[k] = k * np;
+    OK(ics_op_match_emd(big, off, big, off, ns, e, m));
+    off[1] = np + 1;   /* a set above the limit */
+    if (ics_op_match_emd(big, off, big, off, 1, e, m) == 0) { fprintf(stderr, "match: 2049 points accepted\n"); return 1; }
+    free(big); free(off); free(e); free(m);
+  }
+  int bad = 0;
+  bad += ics_op_match_emd(a, ao, b, bo, 0, emd, match) == 0;
+  bad += ics_op_match_emd(a, NULL, b, bo, NB, emd, match) == 0;
+  bad += ics_op_match_emd(a, ao, b, bo, NB, NULL, match) == 0;
+  bad += ics_op_match_emd(NULL, ao, b, bo, NB, emd, match) == 0;
+  ao[0] = 1; bad += ics_op_match_emd(a, ao, b, bo, NB, emd, match) == 0; ao[0] = 0;
+  ao[2] = 2; bad += ics_op_match_emd(a, ao, b, bo, NB, emd, match) == 0; ao[2] = 3;
+  a[7] = NAN; bad += ics_op_match_emd(a, ao, b, bo, NB, emd, match) == 0; a[7] = 0.5;
+  b[20] = INFINITY; bad += ics_op_match_emd(a, ao, b, bo, NB, emd, match) == 0; b[20] = 0.5;
+  b[20] = 1e200; bad += ics_op_match_emd(a, ao, b, bo, NB, emd, match) == 0; b[20] = 0.5;
+  if (bad) { fprintf(stderr, "match: %d invalid argument sets accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "match: no error message\n"); return 1; }
+  OK(ics_op_match_emd(a, ao, b, bo, NB, emd, match));     /* still usable */
+  return 0;
+}
+
+/* The reconstruction chain's refusals: no resident batch, a U-Net of other channels, a resident batch above the U-Net's
+ * max_batch. */
+static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const ics_unet_config* uc, const float* x,
+                                const float* cond, const float* eps, int B) {
+  int32_t counts[2 * 8];
+  int32_t* stats = (int32_t*)malloc((size_t)B * 16 * 11 * sizeof(int32_t));
+  ics_net* v2 = NULL;
+  int bad = 0;
+  OK(ics_vae_create(vc, unet, &v2));
+  bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, unet, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
+                                                    NULL) == 0;
+  OK(ics_vae_upload_batch(v2, x, cond, eps, B));
+  bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, unet, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, NULL, stats,
+                                                    NULL) == 0;
+  bad += ics_vae_reconstruct_resident_to_unet_atoms(unet, v2, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
+                                                    NULL) == 0;
+  {
+    ics_unet_config u2 = *uc;
+    u2.in_channels = uc->in_channels == 1 ? 4 : 1;
+    ics_net* un2 = NULL;
+    OK(ics_unet_create(&u2, &un2));
+    bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, un2, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
+                                                      NULL) == 0;
+    OK(ics_net_destroy(un2));
+  }
+  if (B > 1) {
+    ics_unet_config u3 = *uc;
+    u3.max_batch = B - 1;
+    ics_net* un3 = NULL;
+    OK(ics_unet_create(&u3, &un3));
+    bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, un3, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts,
+                                                      stats, NULL) == 0;
+    OK(ics_vae_upload_batch(v2, x, cond, eps, B - 1));
+    OK(ics_vae_reconstruct_resident_to_unet_atoms(v2, un3, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
+                                                  NULL));
+    OK(ics_net_destroy(un3));
+  }
+  OK(ics_net_destroy(v2));
+  free(stats);
+  if (bad) { fprintf(stderr, "reconstruct: %d invalid calls accepted\n", bad); return 1; }
+  return 0;
+}
+
 static int run(int d, int C, int B, int with_comm) {
   const size_t M = (size_t)B * d * d * d;
   ics_unet_config uc = {C, 95, d, B, 1e-3f, 0.f, 1, 1, with_comm == 2};
@@ -175,6 +258,9 @@ static int run(int d, int C, int B, int with_comm) {
       int32_t* stats = (int32_t*)malloc((size_t)b * 64 * 11 * sizeof(int32_t));
       { int64_t* bnd = calloc((size_t)b * 64 * 8, 8); OK(ics_vae_decode_to_unet_atoms(vae, unet, z, cond, b, 0.8f, 3, 64, sp, mk, rec, minmax, regions, counts, stats, bnd)); free(bnd); }
       OK(ics_vae_decode_to_unet_atoms(vae, unet, z, cond, b, 0.8f, 3, 64, NULL, NULL, NULL, NULL, NULL, counts, stats, NULL));
+      OK(ics_vae_upload_batch(vae, x, cond, eps, b));     /* the same chain from the resident batch */
+      { int64_t* bnd = calloc((size_t)b * 64 * 8, 8); OK(ics_vae_reconstruct_resident_to_unet_atoms(vae, unet, 0.8f, 3, 64, sp, mk, rec, minmax, regions, counts, stats, bnd)); free(bnd); }
+      OK(ics_vae_reconstruct_resident_to_unet_atoms(vae, unet, 0.8f, 3, 64, NULL, NULL, NULL, NULL, NULL, counts, stats, NULL));
       free(regions); free(stats);
     }
   }
@@ -183,6 +269,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_upload_batch(vae, x, cond, eps, B));
   OK(ics_vae_train_step_resident(vae, mv));
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
+  if (reconstruct_refusals(unet, &vc, &uc, x, cond, eps, B)) return 1;
   if (ics_unet_train_step(unet, x, lab, B + 1, mm) == 0) { fprintf(stderr, "max_batch check missing\n"); return 1; }
   int rows = 0;
   OK(ics_net_profile_count(unet, &rows));
@@ -240,6 +327,7 @@ int main(void) {
   if (run(32, 1, 5, 0)) return 1;      /* plans that are not monotone in the batch: 3 grids on a 5-grid handle need more
                                           BatchNorm-backward blocks than 5 do (the engine's capacity checks fire if a
                                           workspace was sized for max_batch alone, round 6) */
+  if (match_walk()) return 1;
   {   /* single-op entry points */
     const int B = 1, S = 8, Cin = 32, Cout = 64;
     size_t nx = (size_t)B * S * S * S * Cin, ny = (size_t)B * S * S * S * Cout, nw = (size_t)27 * Cin * Cout;

@@ -297,6 +297,7 @@ class VaeEngine(_Net):
         self.unet = unet   # keep the perceptual engine alive
         self.in_channels, self.cond_shape, self.latent_dim, self.d, self.max_batch = (
             in_channels, cond_shape, latent_dim, d, max_batch)
+        self._resident = 0   # batch of the engine's resident inputs (every call that uploads x, cond, eps sets it)
         cfg = L.VaeConfig(in_channels, cond_shape, latent_dim, (C.c_int * 4)(*filters), d, max_batch, lr,
                           alpha, beta, (C.c_float * 4)(*pm_layer_weights), 1 if bn_unbias else 0)
         L.check(self._lib.ics_vae_create(C.byref(cfg), unet._h if unet is not None else None, C.byref(self._h)))
@@ -323,6 +324,7 @@ class VaeEngine(_Net):
             s = slice(i, i + self.max_batch)
             L.check(self._lib.ics_vae_encode(self._h, L.fptr(x[s]), L.fptr(cond[s]), L.fptr(eps[s]), x[s].shape[0],
                                              L.fptr(zm[s]), L.fptr(zlv[s]), L.fptr(z[s])))
+            self._resident = x[s].shape[0]
         return zm, zlv, z
 
     def decode(self, z, cond):
@@ -383,21 +385,58 @@ class VaeEngine(_Net):
                 "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
                 "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed}
 
+    def reconstruct_to_atoms(self, unet, x=None, cond=None, eps=None, thresh=0.8, min_voxels=3, max_atoms=512,
+                             want_density=True, want_regions=False):
+        """vae.model.predict([M, cond]) -> unet.model.predict -> argmax / threshold -> components + statistics
+        (eval.py:163-175) in one device-resident chain: encode, sample z with the batch's eps (F8), decode, segment.
+        With x (and cond, eps) the batch is uploaded first (upload_batch); without, the resident batch placed by
+        upload_batch / voxelise_batch is used and left unchanged.  Returns decode_to_atoms' dict, bit for bit what
+        decode_to_atoms(unet, encode(x, cond, eps)[2], cond) returns."""
+        from .watershed import STAT_FIELDS, _atoms_from_stats
+        if x is not None:
+            self.upload_batch(x, cond, eps)
+        elif cond is not None or eps is not None:
+            raise ValueError("cond / eps go with x; the resident batch carries its own")
+        B = self._resident
+        if not B:
+            raise RuntimeError("no resident batch: call upload_batch or voxelise_batch first")
+        d = self.d
+        sp = np.empty((B, d, d, d), np.uint8)
+        mk = np.empty((B, d, d, d), np.uint8)
+        dens = np.empty((B, d, d, d), np.float32) if want_density else None
+        reg = np.empty((B, d, d, d), np.int32) if want_regions else None
+        mm = np.zeros((B, 3, 2), np.float32)
+        counts = np.zeros((B, 2), np.int32)
+        stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
+        bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None
+        L.check(self._lib.ics_vae_reconstruct_resident_to_unet_atoms(
+            self._h, unet._h, float(thresh), int(min_voxels), int(max_atoms), L.u8ptr(sp), L.u8ptr(mk),
+            L.fptr(dens) if want_density else None, L.fptr(mm), L.i32ptr(reg) if want_regions else None,
+            L.i32ptr(counts), L.i32ptr(stats), L.i64ptr(bounds) if bounds is not None else None))
+        failed = counts[:, 1] > max_atoms
+        counts[failed, 1] = 0
+        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm, "regions": reg,
+                "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
+                "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed}
+
     def train_step(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)
         m = np.zeros(4, np.float32)
         L.check(self._lib.ics_vae_train_step(self._h, L.fptr(x), L.fptr(cond), L.fptr(eps), B, L.fptr(m)))
+        self._resident = B
         return m
 
     def test_step(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)
         m = np.zeros(4, np.float32)
         L.check(self._lib.ics_vae_test_step(self._h, L.fptr(x), L.fptr(cond), L.fptr(eps), B, L.fptr(m)))
+        self._resident = B
         return m
 
     def upload_batch(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)
         L.check(self._lib.ics_vae_upload_batch(self._h, L.fptr(x), L.fptr(cond), L.fptr(eps), B))
+        self._resident = B
 
     def voxelise_batch(self, structs, jobs, cond, eps, eps_frac=0.25, label_frac=1.0):
         """As UnetEngine.voxelise_batch for the VAE's input; cond (B, cond_shape) and eps (B, latent_dim) are
@@ -412,6 +451,7 @@ class VaeEngine(_Net):
         cs = structs.c_struct()
         L.check(self._lib.ics_vae_voxelise_batch(self._h, C.byref(cs), L.i32ptr(jobs), B, float(eps_frac),
                                                  float(label_frac), L.fptr(cond), L.fptr(eps)))
+        self._resident = B
 
     def train_step_resident(self, want_metrics=False):
         if want_metrics:

@@ -24,6 +24,12 @@ def _rotated_names(base_name, n_rot):
 def data_split(path, n=None, frac=0.80, n_rot=10, shuffle=True, seed=28):
     """Train/validation split of the matrices under <path>/density_matrices -> (training_ids, validation_ids)."""
     listing = sorted(f for f in os.listdir(path + "/density_matrices") if f.endswith(".npy"))
+    return data_split_names(listing, n, frac, n_rot, shuffle, seed)
+
+
+def data_split_names(listing, n=None, frac=0.80, n_rot=10, shuffle=True, seed=28):
+    """data_split over a sorted list of "<id>[_rot_k].npy" names instead of a directory listing (eval.py --from_sites
+    names the matrices the site files would give)."""
     base = [f for f in listing if "_rot_" not in f][:n]
     if shuffle:
         if seed is not None:

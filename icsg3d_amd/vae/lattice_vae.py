@@ -267,6 +267,33 @@ class LatticeDFCVAE(DataParallelMixin):
             refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
         return out
 
+    def reconstruct_segment_atoms(self, M, cond, unet, eps=None, thresh=0.8, min_voxels=3, max_atoms=512, split=True,
+                                  max_iters=5, want_regions=False):
+        """eval.py:163-175 + watershed_clustering: model.predict([M, cond]) (encode, sample z with eps -- a normal draw
+        by default, as the reference's predict -- decode), then the U-Net, argmax / threshold and the atoms, one
+        device-resident chain per max_batch chunk (VaeEngine.reconstruct_to_atoms); with split=True refine_atoms
+        follows as in decode_segment_atoms.  Returns decode_segment_atoms' dict for the whole batch."""
+        M = np.asarray(M)
+        n = len(M)
+        if eps is None:
+            eps = np.random.normal(size=(n, self.latent_dim))
+        cond, eps = np.asarray(cond), np.asarray(eps)
+        eng = self._engine(min(n, self.batch_size or 32))
+        ueng = unet._engine(min(n, eng.max_batch))
+        mb = min(eng.max_batch, ueng.max_batch)
+        parts = [eng.reconstruct_to_atoms(ueng, M[i:i + mb], cond[i:i + mb], eps[i:i + mb], thresh, min_voxels,
+                                          max_atoms, want_regions=want_regions or split) for i in range(0, n, mb)]
+        out = {}
+        for k, v in parts[0].items():
+            if k == "atoms":
+                out[k] = [a for p in parts for a in p[k]]
+            else:
+                out[k] = None if v is None else np.concatenate([p[k] for p in parts])
+        if split:
+            from ..watershed import refine_atoms
+            refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
+        return out
+
     def save_(self, weights, model="saved_models/vae.h5"):
         self.model.load_weights(weights)
         self.model.save(model)

@@ -244,6 +244,28 @@ int ics_unet_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t
 int ics_vae_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t* jobs, int batch, double eps_frac,
                            double label_frac, const float* cond, const float* eps);
 
+/* ---------------------------------------------------------------- evaluation (eval.py)
+ * vae.model.predict([M, cond]) -> unet.model.predict -> argmax / (sig >= thresh) -> components + statistics
+ * (eval.py:163-175 + watershed.py:190-203) on the batch placed by ics_vae_upload_batch / ics_vae_voxelise_batch (its eps
+ * is the sampling draw, F8); learning phase 0.  Outputs as ics_vae_decode_to_unet_atoms, each optional except counts /
+ * atom_stats; bit-identical to ics_vae_encode of the same batch followed by ics_vae_decode_to_unet_atoms of its z.
+ * Refused: no resident batch, a U-Net of another d or C, a resident batch above the U-Net's max_batch.  The resident
+ * batch is left unchanged. */
+int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, float thresh, int min_voxels,
+                                               int max_atoms, uint8_t* species, uint8_t* mask, float* density,
+                                               float* coord_minmax, int32_t* regions, int32_t* counts,
+                                               int32_t* atom_stats, int64_t* convexity_bounds);
+/* emd()  (eval.py:45-53): per sample b, the minimum-cost one-to-one matching between point sets
+ * A_b = a[a_off[b] .. a_off[b+1]) and B_b = b[b_off[b] .. b_off[b+1]) (float64 xyz, Angstrom) under euclidean distance;
+ * emd[b] = matched distance sum / min(|A_b|, |B_b|) -- NaN when either set is empty, as the reference's 0/0.
+ * match (optional) [a_off[batch]]: index into B_b of each point of A_b, -1 for an unmatched point.
+ * Exact, fp64 (shortest augmenting paths with potentials, one workgroup per sample); results are the same run to run.
+ * Refused, naming the sample, with nothing written: a set above 2048 points, offsets that do not start at 0 or
+ * decrease, batch < 1, a coordinate that is not finite or exceeds 1e150 in magnitude.
+ * HOST pointers, any batch (chunked internally), synchronous, the calling thread's op stream. */
+int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
+                     double* emd, int32_t* match);
+
 /* ---------------------------------------------------------------- common to both engines */
 int ics_net_destroy(ics_net* net);
 int ics_net_sync(ics_net* net);
