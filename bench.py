@@ -4,11 +4,16 @@
 One "step" = one U-Net training step (forward, loss, backward, BN moving-stat update, Adam) on a
 batch of 32 synthetic 32^3 x 1 voxel grids per GPU, inputs resident in HBM when the timed region
 starts (BASELINE.json configs[1]; weak scaling over N GPUs, gradients all-reduced with RCCL in buckets
-overlapped with the backward pass).  The same JSON line carries a `secondary` block for the other half
-of BASELINE.json's metric, the DFC-VAE step (configs[2]), timed right after the U-Net region.
-Prints ONE JSON line on rank 0.
+overlapped with the backward pass).  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, W warm-up steps, the untimed two-step pass that picks
+the dominant kernel, the K timed steps, the --dump-outputs files, one finiteness check.  --full adds the rest, after
+the timed steps: the same K steps with no events (kernel launches per step), the `sustained` soak, the `secondary`
+block for the other half of BASELINE.json's metric (the DFC-VAE step, configs[2]), the inference blocks and the CPU
+baseline.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...        (no launcher: starts the line above as a child process before touching the GPU,
@@ -157,16 +162,21 @@ def main():
     ap.add_argument("--d", "--dim", dest="d", type=int, default=32,
                     help="grid edge (torch.distributed.run's own parser rejects --d as an ambiguous abbreviation: the "
                          "self-launch forwards it as --dim)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the events-off repeat of "
+                         "the K steps, the sustained soak, the DFC-VAE secondary block, the inference blocks, the CPU "
+                         "baseline (the --soak-seconds / --no-* options below narrow a --full run)")
     ap.add_argument("--soak-seconds", type=float, default=10.0,
-                    help="after the timed region: the same U-Net step for at least this long, reported as `sustained` "
-                         "(never `value`); 0 skips it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the DFC-VAE block (profiling runs)")
+                    help="--full: after the timed region, the same U-Net step for at least this long, reported as "
+                         "`sustained` (never `value`); 0 skips it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the DFC-VAE block (profiling runs)")
     ap.add_argument("--workload", choices=("unet", "vae", "joint", "predict", "generate"), default="unet",
-                    help="unet = the contract line (BASELINE configs[1] + the configs[2] secondary block + the two inference "
-                         "blocks); vae / joint = profiling runs of the DFC-VAE step alone / U-Net + DFC-VAE step per iteration; "
+                    help="unet = the contract line (BASELINE configs[1]; with --full + the configs[2] secondary block + the "
+                         "two inference blocks); vae / joint = profiling runs of the DFC-VAE step alone / U-Net + DFC-VAE step per iteration; "
                          "predict = configs[0] (U-Net forward-only, 16 grids); generate = decoder -> U-Net -> labels -> atoms")
-    ap.add_argument("--no-inference", action="store_true", help="skip the predict / generate blocks of the contract line")
+    ap.add_argument("--no-inference", action="store_true",
+                    help="--full: skip the predict / generate blocks of the contract line")
     ap.add_argument("--sync-bn", action="store_true", help="data parallel: global-batch BatchNorm statistics")
     ap.add_argument("--dump-rows", type=str, default=None, help="write the per-launch-site profile rows (JSON) here")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -239,7 +249,8 @@ def main():
         """W warm-up steps, then EXACTLY K steps between barrier + device sync on both sides; max over ranks.
         step_profile: the step of the untimed all-events pass when it must differ (joint: the two engines serialised, so
         that a kernel's event bracket does not time a kernel of the other stream it shares the chip with).
-        after_timed: called once after the K timed steps, before any further step changes the engines' state."""
+        after_timed: called once after the K timed steps, before any further step changes the engines' state.
+        The events-off repeat of the K steps runs with --full only; without it elapsed_plain is None."""
         def barrier(where="barrier"):
             wd.beat(where + ": device sync")
             for e in engines:
@@ -300,8 +311,11 @@ def main():
         if args.dump_rows and rank == 0:
             with open(args.dump_rows, "a") as f:
                 f.write(json.dumps({"steps": args.steps, "rows": rows}) + "\n")
-        # the same K steps without the per-launch events (what a training job sees); the library counts every kernel
-        # it enqueues (ics_kernel_launches): the per-step difference is the number rocprofv3 --kernel-trace shows
+        timed.kernel_launches_per_step = None
+        if not args.full:
+            return elapsed, None, rows, rows_all
+        # --full: the same K steps without the per-launch events (what a training job sees); the library counts every
+        # kernel it enqueues (ics_kernel_launches): the per-step difference is the number rocprofv3 --kernel-trace shows
         barrier("before the events-off steps")
         n0 = lib.ics_kernel_launches()
         t0 = time.perf_counter()
@@ -361,7 +375,7 @@ def main():
         unet_launches = timed.kernel_launches_per_step
         gpu_active_s = timed.gpu_active_s
         sustained = soak(lambda: unet.train_step_resident(False), [unet], elapsed_plain / args.steps * 1e3) \
-            if args.soak_seconds > 0 else None
+            if args.full and args.soak_seconds > 0 else None
         metrics = unet.train_step_resident(True)   # untimed: sanity that the job is still finite
         if not np.all(np.isfinite(metrics)):
             raise SystemExit("non-finite training metrics: %s" % metrics)
@@ -409,13 +423,13 @@ def main():
                                               "backward pass" % comm["buckets_last_step"]) if comm["nranks"] else "none"},
                 # value / ms_per_step: the K timed steps, with HIP events around the launch sites of the dominant kernel only
                 # (the roofline's denominator is measured over exactly those steps; the per-kernel table comes from an
-                # untimed pass with events around every launch); the same K steps with no events at all:
-                "ms_per_step_events_off": round(elapsed_plain / args.steps * 1e3, 3),
-                "value_events_off": round(world * B * args.steps / elapsed_plain, 2),
-                # device kernels the library enqueues per step (counted at every launch site; = the ics:: rows of
-                # rocprofv3 --kernel-trace for the same command); profiler_brackets = timed launch SITES, several
-                # kernels can sit inside one
-                "kernel_launches_per_step": round(unet_launches, 1),
+                # untimed pass with events around every launch); --full: the same K steps with no events at all, and
+                # the device kernels the library enqueues per step over them (counted at every launch site; = the ics::
+                # rows of rocprofv3 --kernel-trace for the same command)
+                **({"ms_per_step_events_off": round(elapsed_plain / args.steps * 1e3, 3),
+                    "value_events_off": round(world * B * args.steps / elapsed_plain, 2),
+                    "kernel_launches_per_step": round(unet_launches, 1)} if args.full else {}),
+                # profiler_brackets = timed launch SITES, several kernels can sit inside one
                 "profiler_brackets_per_step": round(sum(v["launches"] for v in kern.values()) / args.steps, 1),
                 # achieved / frac: the multiply-adds the kernel ISSUES to the matrix cores per second over the fp32 MFMA
                 # peak (<= 1 by construction: the matrix-core utilisation).  The Winograd kernels' profile rows carry
@@ -611,7 +625,7 @@ def main():
                                                "parallelism": "dp1"}}
         out.update({k: v for k, v in blk.items() if k != "workload"})
         out["ms_per_step"] = out["ms_per_call"]
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             wd.pause("CPU baseline subprocess (no collective in it)")
             cb = cpu_baseline(B, d)
             out["cpu_baseline"] = {"value": cb.get(args.workload, {}).get("value"), "unit": "voxel-grids/s", "cores": cb["cores"],
@@ -619,8 +633,9 @@ def main():
         else:
             out["cpu_baseline"] = None
 
-    # ---- DFC-VAE step (BASELINE configs[2]): encoder + decoder + frozen perceptual U-Net (batch-statistics BN)
-    if args.workload in ("unet", "vae", "joint") and not (args.workload == "unet" and args.no_secondary):
+    # ---- DFC-VAE step (BASELINE configs[2]): encoder + decoder + frozen perceptual U-Net (batch-statistics BN); for the
+    # unet workload the `secondary` block of a --full run
+    if args.workload in ("vae", "joint") or (args.workload == "unet" and args.full and not args.no_secondary):
         pm = unet if args.workload == "unet" else UnetEngine(in_channels=C, d=d, max_batch=B)
         if pm is not unet:
             pm.set_weights(PU)
@@ -663,13 +678,14 @@ def main():
                                 "LatticeDFCVAE train step (encoder + decoder + frozen perceptual U-Net c1..c10 x2 fwd "
                                 "+ bwd-data, Adam), %d x %d^3 x 1 grids per GPU (BASELINE.json configs[2])" % (B, d)),
                    "value": round(world * B * args.steps / elapsed_v, 2), "unit": "voxel-grids/s",
-                   "ms_per_step": round(ms_v, 3), "ms_per_step_events_off": round(elapsed_v_plain / args.steps * 1e3, 3),
+                   "ms_per_step": round(ms_v, 3),
+                   **({"ms_per_step_events_off": round(elapsed_v_plain / args.steps * 1e3, 3)} if args.full else {}),
                    "gpu_active_s": round(gpu_active_v, 5),
                    "steps": args.steps, "warmup": args.warmup,
                    "executed_tflop_per_step": round(exec_flop / 1e12, 3),
                    "compute_frac": round(exec_flop / (ms_v * 1e-3) / (PEAK_FP32_TFLOPS * 1e12), 4),
                    "algorithmic_tflop_per_step": round(VAE_FLOP_PER_GRID * (d / 32.0) ** 3 * B / 1e12, 3),
-                   "kernel_launches_per_step": round(timed.kernel_launches_per_step, 1),
+                   **({"kernel_launches_per_step": round(timed.kernel_launches_per_step, 1)} if args.full else {}),
                    "profiler_brackets_per_step": round(sum(v["launches"] for v in kern.values()) / args.steps, 1),
                    # tflops = MFMA work executed per second (Winograd rows x 64/216), as roofline.achieved
                    "dominant_kernel": {"kernel": dom_name,
@@ -704,10 +720,10 @@ def main():
                 out["detail"] = blk
                 out["cpu_baseline"] = None
 
-    if args.workload == "unet" and world == 1 and not args.no_inference:
+    if args.workload == "unet" and world == 1 and args.full and not args.no_inference:
         out["inference"] = {"predict": predict_block(unet), "generate": generate_block(unet)}
     if rank == 0:
-        if args.workload == "unet" and world == 1 and not args.no_cpu_baseline:
+        if args.workload == "unet" and world == 1 and args.full and not args.no_cpu_baseline:
             wd.pause("CPU baseline subprocess (no collective in it)")
             out["cpu_baseline"] = cpu_baseline(B, d)
             if "secondary" in out and out["cpu_baseline"].get("vae"):

@@ -8,15 +8,15 @@ OUT=$ROOT/gpurun_out/refresh_$TAG
 mkdir -p $OUT
 cd $ROOT
 if [ -z "$SKIP_TESTS" ]; then python -m pytest tests -m gpu -q > $OUT/tests.log 2>&1; tail -3 $OUT/tests.log; fi
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench.json
-python bench.py --workload joint --no-cpu-baseline > $OUT/bench_joint.json 2> $OUT/bench_joint.err
-python bench.py --workload joint --d 64 --batch 8 --no-cpu-baseline > $OUT/bench_joint_d64.json 2> $OUT/bench_joint_d64.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cut -c1-400 $OUT/bench.json
+python bench.py --full --workload joint --no-cpu-baseline > $OUT/bench_joint.json 2> $OUT/bench_joint.err
+python bench.py --full --workload joint --d 64 --batch 8 --no-cpu-baseline > $OUT/bench_joint_d64.json 2> $OUT/bench_joint_d64.err
 # round 5: the inference configurations and the d = 64 grid, each engine on its own (a joint run shares the chip between two
 # streams: its per-kernel brackets time contention)
-python bench.py --workload predict --no-cpu-baseline > $OUT/bench_predict.json 2> $OUT/bench_predict.err
-python bench.py --workload generate --no-cpu-baseline > $OUT/bench_generate.json 2> $OUT/bench_generate.err
-python bench.py --workload unet --d 64 --batch 8 --no-cpu-baseline --no-secondary --no-inference > $OUT/bench_unet_d64.json 2> $OUT/bench_unet_d64.err
-python bench.py --workload vae --d 64 --batch 8 --no-cpu-baseline > $OUT/bench_vae_d64.json 2> $OUT/bench_vae_d64.err
+python bench.py --full --workload predict --no-cpu-baseline > $OUT/bench_predict.json 2> $OUT/bench_predict.err
+python bench.py --full --workload generate --no-cpu-baseline > $OUT/bench_generate.json 2> $OUT/bench_generate.err
+python bench.py --full --workload unet --d 64 --batch 8 --no-cpu-baseline --no-secondary --no-inference > $OUT/bench_unet_d64.json 2> $OUT/bench_unet_d64.err
+python bench.py --full --workload vae --d 64 --batch 8 --no-cpu-baseline > $OUT/bench_vae_d64.json 2> $OUT/bench_vae_d64.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_unet -o prof -- python3 $ROOT/bench.py --steps 8 --warmup 2 --soak-seconds 0 --no-cpu-baseline --no-secondary --no-inference > $OUT/prof_unet.log 2>&1
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_vae -o prof -- python3 $ROOT/bench.py --steps 8 --warmup 2 --workload vae > $OUT/prof_vae.log 2>&1

@@ -13,8 +13,8 @@ echo "visible GPUs: $NG" | tee $OUT/info.txt
 python -m pytest tests/test_gpu_dp2.py -m gpu -q > $OUT/dp2_test.log 2>&1; tail -2 $OUT/dp2_test.log
 for N in 1 2 4 8; do
   if [ $N -le $NG ]; then
-    python bench.py --gpus $N --no-cpu-baseline --no-inference > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
-    python bench.py --gpus $N --no-cpu-baseline --no-inference --sync-bn --no-secondary > $OUT/bench_syncbn_n$N.json 2> $OUT/bench_syncbn_n$N.err
+    python bench.py --gpus $N --full --no-cpu-baseline --no-inference > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
+    python bench.py --gpus $N --full --no-cpu-baseline --no-inference --sync-bn --no-secondary > $OUT/bench_syncbn_n$N.json 2> $OUT/bench_syncbn_n$N.err
   fi
 done
 python - "$OUT" <<'PY'

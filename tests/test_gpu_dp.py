@@ -107,7 +107,7 @@ def test_bench_through_torchrun_single_rank():
     env = dict(os.environ, ICSG3D_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--soak-seconds", "1"]
+           "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--soak-seconds", "1"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=850)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
