@@ -2842,9 +2842,7 @@ int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, con
 }
 int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
                        int32_t* labels, int32_t* nlabels, int32_t* stats) {
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return segment_label_boxes(st, vols, dims, nbox, connectivity, max_labels, labels, nlabels, stats);
+  return segment_label_boxes(op_stream, vols, dims, nbox, connectivity, max_labels, labels, nlabels, stats);
 }
 int ics_op_region_stats(const int32_t* R, const uint8_t* species, int D, int H, int W, int num_labels, int num_species,
                         int32_t* stats) {
@@ -2860,7 +2858,8 @@ int ics_op_component_bounds(const int32_t* labels, const int32_t* dims, int nbox
 }
 int ics_op_watershed_split(const int32_t* boxes, const int32_t* dims, const int32_t* cls, int nbox, int tie, int32_t* wss) {
   // Round 6: the boxes of a level go to host threads (segment_watershed_split_host: the flood is sequential per box and a
-  // CPU core walks it ~30x faster than one GPU lane); ICSG3D_WS_DEVICE=1 keeps the kernel (A/B, tests run both).
+  // CPU core walks it ~30x faster than one GPU lane); ICSG3D_WS_DEVICE=1 keeps the kernel (A/B, tests run both) for the
+  // boxes it takes (extents <= 64), the others still go to the host flood.
   const char* env = getenv("ICSG3D_WS_DEVICE");       // read per call: tests flip it inside one process
   const bool on_device = env != nullptr && atoi(env) != 0;
   if (!on_device) return segment_watershed_split_host(boxes, dims, cls, nbox, tie, wss);

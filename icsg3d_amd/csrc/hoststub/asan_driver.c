@@ -370,7 +370,7 @@ int main(void) {
     OK(ics_op_watershed_split(vols, dims, cls, 2, 0, wss));
     OK(ics_op_watershed_split(vols, dims, cls, 2, 1, wss));
     OK(ics_op_region_stats(vols, sp, 3, 4, 5, 4, 95, rstats));
-    dims[0] = 65;
+    dims[0] = 257;
     if (ics_op_label_boxes(vols, dims, 2, 1, 8, labels, nlab, bstats) == 0) { fprintf(stderr, "box extent check missing\n"); return 1; }
     if (ics_op_label_boxes(vols, dims + 3, 1, 2, 8, labels, nlab, bstats) == 0) { fprintf(stderr, "connectivity check missing\n"); return 1; }
     OK(ics_release_caches());     /* the per-thread stream and scratch of the box-level entry points (LeakSanitizer sees the rest) */
@@ -436,6 +436,39 @@ int main(void) {
     OK(ics_op_watershed_split(boxes, bd, bc, nb, 1, out));
     printf("asan driver: %d components, %d exact hull counts, %d boxes split on host threads\n", n, exact, nb);
     free(vol); free(lab); free(stack); free(st7); free(bnd); free(boxes); free(out); free(bd); free(bc);
+  }
+  {  /* boxes with an extent above 64 (whole grids at d >= 128): the host labeller next to a kernel box in one call, the
+        host flood for the device form of the split, component bounds over the large box, and a refused stats row */
+    enum { D = 70, H = 9, W = 11, V = D * H * W, ML = 64 };
+    int32_t dims[6] = {D, H, W, 3, 4, 5};
+    int32_t* vol = (int32_t*)calloc(V + 60, 4);
+    int32_t* lab = (int32_t*)calloc(V + 60, 4);
+    int32_t* wss = (int32_t*)calloc(V + 60, 4);
+    int32_t* st = (int32_t*)calloc(2 * ML * 7, 4);
+    int32_t nl[2], cls[2] = {1, 1};
+    int64_t* bnd = (int64_t*)calloc(2 * ML * 5, 8);
+    for (int z = 2; z < 68; ++z) for (int y = 1; y < 8; ++y) for (int x = 1; x < 10; ++x)      /* a bar with a notch */
+      vol[(z * H + y) * W + x] = !(z > 30 && z < 40 && y < 5);
+    vol[(0 * H + 0) * W + 0] = 1;
+    vol[V + 7] = 1; vol[V + 8] = 1;
+    OK(ics_op_label_boxes(vol, dims, 2, 1, ML, lab, nl, st));      /* (the kernel box's outputs are the stub's) */
+    if (nl[0] != 2 || st[7] != 66 * 7 * 9 - 9 * 4 * 9 || st[8] != 2 || st[11] != 68) { fprintf(stderr, "large-box labels wrong\n"); return 1; }
+    OK(ics_op_label_boxes(vol, dims, 2, 3, ML, lab, nl, NULL));
+    setenv("ICSG3D_WS_DEVICE", "1", 1);
+    OK(ics_op_watershed_split(vol, dims, cls, 2, 0, wss));
+    unsetenv("ICSG3D_WS_DEVICE");
+    OK(ics_op_watershed_split(vol, dims, cls, 2, 1, wss));
+    setenv("ICSG3D_LABEL_HOST", "1", 1);      /* every box on the host labeller */
+    OK(ics_op_label_boxes(vol, dims, 2, 1, ML, lab, nl, st));
+    unsetenv("ICSG3D_LABEL_HOST");
+    if (nl[0] != 2 || nl[1] != 1 || st[ML * 7] != 2) { fprintf(stderr, "host labeller wrong\n"); return 1; }
+    OK(ics_op_component_bounds(lab, dims, 2, nl, st, ML, 3, 0.8, bnd));
+    if (bnd[5 + 0] != st[7] || bnd[5 + 1] < bnd[5 + 2] || bnd[5 + 2] < bnd[5 + 0]) { fprintf(stderr, "large-box bounds wrong\n"); return 1; }
+    st[7 + 4] = st[7 + 1];     /* an empty (inverted) z range for label 2 of box 0 */
+    bnd[0] = -7;
+    if (ics_op_component_bounds(lab, dims, 2, nl, st, ML, 3, 0.8, bnd) == 0 || bnd[0] != -7) { fprintf(stderr, "stats box check missing\n"); return 1; }
+    printf("asan driver: large box labelled and bounded on host threads; %s\n", ics_last_error());
+    free(vol); free(lab); free(wss); free(st); free(bnd);
   }
   printf("asan driver: all entry points walked, no sanitizer report\n");
   return 0;

@@ -245,8 +245,9 @@ __global__ void seg_vote_kernel(const unsigned* __restrict__ hist, int nbins, si
 // segment_nuclei's non-convex branch and its recursion (watershed.py:40-150), one workgroup per box
 // ======================================================================================================================
 // A "box" is a small dense int32 volume [D][H][W] (a component cropped to its bounding box, or a watershed result that is
-// segmented again): D, H, W <= 64.  The scikit-image 0.17.2 routines the reference calls on it are restated in
-// oracle/watershed_ref.py (PARITY UNPINNED: skimage absent); these kernels are held to that file bit for bit.
+// segmented again): D, H, W <= 64 for these kernels (larger boxes take the host forms below).  The scikit-image 0.17.2
+// routines the reference calls on it are restated in oracle/watershed_ref.py (PARITY UNPINNED: skimage absent); these
+// kernels are held to that file bit for bit.
 struct BoxDesc {
   long long off;         // element offset of the box in the flat input / output arrays
   int D, H, W, cl;       // extents; cl: the component's label value (split kernel)
@@ -565,18 +566,31 @@ int launch_segment_atoms(hipStream_t st, const unsigned char* mask, const unsign
 
 namespace ics {
 
-// Host-side batching for the two box kernels: `dims` [nbox][3] (D, H, W), boxes laid out back to back in `vols`.
-static int box_descs(const int* dims, const int* cls, int nbox, std::vector<BoxDesc>* out, size_t* total) {
+// Box extents: the two box kernels run one workgroup per box and propagate labels by sweeps over the whole box, which is
+// only sensible up to 64 per axis; the host forms (label, split, component bounds) take whole d^3 grids up to 256.
+constexpr int kBoxDeviceMax = 64;
+constexpr int kBoxHostMax = 256;
+
+// Host-side batching: `dims` [nbox][3] (D, H, W), boxes laid out back to back in `vols`; every extent in [1, max_ext].
+static int box_descs(const int* dims, const int* cls, int nbox, int max_ext, std::vector<BoxDesc>* out, size_t* total) {
   out->resize(nbox);
   size_t off = 0;
   for (int b = 0; b < nbox; ++b) {
     const int D = dims[3 * b], H = dims[3 * b + 1], W = dims[3 * b + 2];
-    ICS_CHECK(D >= 1 && H >= 1 && W >= 1 && D <= 64 && H <= 64 && W <= 64, "box extents must be in [1, 64]");
+    ICS_CHECK(D >= 1 && H >= 1 && W >= 1 && D <= max_ext && H <= max_ext && W <= max_ext,
+              "box " + std::to_string(b) + ": extents must be in [1, " + std::to_string(max_ext) + "]");
     (*out)[b] = BoxDesc{(long long)off, D, H, W, cls ? cls[b] : 0, (long long)off};
     off += (size_t)D * H * W;
   }
+  ICS_CHECK(off < (1ull << 31), "boxes too large for 32-bit voxel offsets");
   *total = off;
   return 0;
+}
+static bool box_fits_device(const BoxDesc& d) { return d.D <= kBoxDeviceMax && d.H <= kBoxDeviceMax && d.W <= kBoxDeviceMax; }
+// ICSG3D_LABEL_HOST=1: every box of ics_op_label_boxes goes to the host labeller (read per call: tests flip it)
+static bool label_host_forced() {
+  const char* e = getenv("ICSG3D_LABEL_HOST");
+  return e != nullptr && atoi(e) != 0;
 }
 
 // The box-level entry points are called once per recursion level of segment_nuclei -- tens of times per sample, a few tens of
@@ -625,38 +639,6 @@ void segment_release_scratch() {
   reap_orphans();
 }
 #undef tl_scratch
-
-int segment_label_boxes(hipStream_t st, const int* h_vols, const int* h_dims, int nbox, int connectivity, int max_labels,
-                        int* h_labels, int* h_nlabels, int* h_stats) {
-  ICS_CHECK(h_vols && h_dims && h_labels && h_nlabels && nbox >= 1 && max_labels >= 1, "bad label_boxes arguments");
-  ICS_CHECK(connectivity == 1 || connectivity == 3, "connectivity must be 1 (6 neighbours) or 3 (26)");
-  std::vector<BoxDesc> desc;
-  size_t total = 0;
-  ICS_TRY(box_descs(h_dims, nullptr, nbox, &desc, &total));
-  unsigned char* buf = nullptr;
-  const size_t b_vol = total * 4, b_desc = (size_t)nbox * sizeof(BoxDesc), b_n = (size_t)nbox * 4,
-               b_st = (size_t)nbox * max_labels * 7 * 4;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  ICS_TRY(scratch_get(up(b_vol) * 2 + up(b_desc) + up(b_n) + up(b_st), &buf));
-  int* d_vol = reinterpret_cast<int*>(buf);
-  int* d_lab = reinterpret_cast<int*>(buf + up(b_vol));
-  BoxDesc* d_desc = reinterpret_cast<BoxDesc*>(buf + 2 * up(b_vol));
-  int* d_n = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc));
-  int* d_st = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc) + up(b_n));
-  hipError_t e = hipMemcpyAsync(d_vol, h_vols, b_vol, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, desc.data(), b_desc, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    ICS_LAUNCH(label_boxes_kernel, dim3(nbox), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
-               d_lab, d_n, d_st);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_labels, d_lab, b_vol, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h_nlabels, d_n, b_n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && h_stats) e = hipMemcpyAsync(h_stats, d_st, b_st, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_error(std::string("label_boxes: ") + hipGetErrorString(e)); return -1; }
-  return 0;
-}
 
 int segment_region_stats(hipStream_t st, const int* h_R, const unsigned char* h_species, int D, int H, int W, int nlab,
                          int nbins, int* h_stats) {
@@ -860,29 +842,180 @@ void host_split_box(const int* val, int D, int H, int W, int tie, int* out) {
   }
   for (int i = 0; i < V; ++i) if (out[i] == 1) out[i] = 0;     // wss[wss == 1] = 0
 }
+
+// measure.label(box, connectivity) on the host, for boxes the label kernel does not take (an extent above 64: whole d^3
+// grids of segment_nuclei's first level at d >= 128).  Union-find over the already-visited neighbours in raster order,
+// always hanging the larger root under the smaller, so that a root is the smallest index of its set; numbering the roots
+// in raster order is then label_boxes_kernel's numbering.  Same 7-int stats; rows past min(n, max_labels) stay as they are.
+void host_label_box(const int* val, int D, int H, int W, bool conn26, int max_labels, int* lab, int* n_out, int* st) {
+  const int V = D * H * W;
+  std::vector<int> parent(V);
+  auto find = [&](int i) {
+    while (parent[i] != i) { parent[i] = parent[parent[i]]; i = parent[i]; }      // path halving
+    return i;
+  };
+  auto unite = [&](int a, int b) {
+    a = find(a); b = find(b);
+    if (a == b) return;
+    if (a < b) parent[b] = a; else parent[a] = b;
+  };
+  for (int z = 0, i = 0; z < D; ++z)
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x, ++i) {
+        const int v = val[i];
+        if (v == 0) continue;
+        parent[i] = i;
+        // the neighbours that precede i in raster order: -x, -y, -z (6), or the 13 with (dz, dy, dx) < (0, 0, 0) (26)
+        for (int dz = -1; dz <= 0; ++dz)
+          for (int dy = -1; dy <= (dz < 0 ? 1 : 0); ++dy)
+            for (int dx = -1; dx <= ((dz < 0 || dy < 0) ? 1 : -1); ++dx) {
+              if (!conn26 && (dz != 0) + (dy != 0) + (dx != 0) != 1) continue;
+              const int zz = z + dz, yy = y + dy, xx = x + dx;
+              if (zz < 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+              const int j = (zz * H + yy) * W + xx;
+              if (val[j] == v) unite(i, j);
+            }
+      }
+  int n = 0;
+  for (int i = 0; i < V; ++i) {
+    if (val[i] == 0) { lab[i] = 0; continue; }
+    const int r = find(i);
+    lab[i] = r == i ? ++n : lab[r];                    // r < i: already numbered
+  }
+  *n_out = n;
+  if (st == nullptr) return;
+  const int nst = n < max_labels ? n : max_labels;
+  for (int a = 0; a < nst; ++a) {
+    int* s = st + (size_t)a * 7;
+    s[0] = 0; s[1] = D; s[2] = H; s[3] = W; s[4] = 0; s[5] = 0; s[6] = 0;
+  }
+  for (int z = 0, i = 0; z < D; ++z)
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x, ++i) {
+        const int l = lab[i];
+        if (l <= 0 || l > nst) continue;
+        int* s = st + (size_t)(l - 1) * 7;
+        ++s[0];
+        s[1] = std::min(s[1], z); s[2] = std::min(s[2], y); s[3] = std::min(s[3], x);
+        s[4] = std::max(s[4], z + 1); s[5] = std::max(s[5], y + 1); s[6] = std::max(s[6], x + 1);
+      }
+}
+
+// fn(b) for the boxes `which` on host threads: largest boxes first (a level lasts as long as its slowest box), one box at a
+// time per thread, one thread per ~16 k voxels of boxes, at most one per box
+void host_boxes_run(const std::vector<BoxDesc>& desc, std::vector<int> which, const std::function<void(int)>& fn) {
+  if (which.empty()) return;
+  std::sort(which.begin(), which.end(), [&](int a, int b) {
+    return (long long)desc[a].D * desc[a].H * desc[a].W > (long long)desc[b].D * desc[b].H * desc[b].W;
+  });
+  size_t vox = 0;
+  for (int b : which) vox += (size_t)desc[b].D * desc[b].H * desc[b].W;
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (size_t k = next.fetch_add(1); k < which.size(); k = next.fetch_add(1)) fn(which[k]);
+  };
+  HostPool::get().run((int)std::min<size_t>(which.size(), vox / 16384 + 1), work);
+}
+
+// the boxes the kernels take (box_fits_device) packed back to back, and their descriptors re-based onto the packing;
+// `pos` = their indices in the caller's list.  Used when a call mixes them with boxes that go to the host.
+size_t pack_device_boxes(const int* h_vols, const std::vector<BoxDesc>& desc, const std::vector<int>& pos,
+                         std::vector<int>* vols, std::vector<BoxDesc>* ddesc) {
+  size_t off = 0;
+  ddesc->clear();
+  for (int b : pos) {
+    BoxDesc d = desc[b];
+    d.off = d.heap_off = (long long)off;
+    ddesc->push_back(d);
+    off += (size_t)d.D * d.H * d.W;
+  }
+  vols->resize(off);
+  for (size_t k = 0; k < pos.size(); ++k)
+    std::memcpy(vols->data() + (*ddesc)[k].off, h_vols + desc[pos[k]].off,
+                (size_t)desc[pos[k]].D * desc[pos[k]].H * desc[pos[k]].W * sizeof(int));
+  return off;
+}
 }  // namespace
 
 int segment_watershed_split_host(const int* h_boxes, const int* h_dims, const int* h_cls, int nbox, int tie, int* h_wss) {
   ICS_CHECK(h_boxes && h_dims && h_cls && h_wss && nbox >= 1 && (tie == 0 || tie == 1), "bad watershed_split arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
-  ICS_TRY(box_descs(h_dims, h_cls, nbox, &desc, &total));
-  // largest boxes first (a level lasts as long as its slowest box), one box at a time per thread
-  std::vector<int> order(nbox);
-  for (int b = 0; b < nbox; ++b) order[b] = b;
-  std::sort(order.begin(), order.end(), [&](int a, int b) {
-    return (long long)desc[a].D * desc[a].H * desc[a].W > (long long)desc[b].D * desc[b].H * desc[b].W;
+  ICS_TRY(box_descs(h_dims, h_cls, nbox, kBoxHostMax, &desc, &total));
+  std::vector<int> all(nbox);
+  for (int b = 0; b < nbox; ++b) all[b] = b;
+  host_boxes_run(desc, all, [&](int b) {
+    const BoxDesc& d = desc[b];
+    host_split_box(h_boxes + d.off, d.D, d.H, d.W, tie, h_wss + d.off);
   });
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (int k = next.fetch_add(1); k < nbox; k = next.fetch_add(1)) {
-      const BoxDesc& d = desc[order[k]];
-      host_split_box(h_boxes + d.off, d.D, d.H, d.W, tie, h_wss + d.off);
+  return 0;
+}
+
+// Boxes with an extent above 64 (or every box, ICSG3D_LABEL_HOST=1) go to host_label_box on host threads, the others to
+// label_boxes_kernel; the stream is only asked for when a box goes to the device.
+int segment_label_boxes(int (*get_stream)(hipStream_t*), const int* h_vols, const int* h_dims, int nbox, int connectivity,
+                        int max_labels, int* h_labels, int* h_nlabels, int* h_stats) {
+  ICS_CHECK(h_vols && h_dims && h_labels && h_nlabels && nbox >= 1 && max_labels >= 1, "bad label_boxes arguments");
+  ICS_CHECK(connectivity == 1 || connectivity == 3, "connectivity must be 1 (6 neighbours) or 3 (26)");
+  std::vector<BoxDesc> desc;
+  size_t total = 0;
+  ICS_TRY(box_descs(h_dims, nullptr, nbox, kBoxHostMax, &desc, &total));
+  const bool host_all = label_host_forced();
+  std::vector<int> on_host, on_dev;
+  for (int b = 0; b < nbox; ++b) (host_all || !box_fits_device(desc[b]) ? on_host : on_dev).push_back(b);
+  const size_t row = (size_t)max_labels * 7;
+  host_boxes_run(desc, on_host, [&](int b) {
+    const BoxDesc& d = desc[b];
+    host_label_box(h_vols + d.off, d.D, d.H, d.W, connectivity == 3, max_labels, h_labels + d.off, h_nlabels + b,
+                   h_stats ? h_stats + b * row : nullptr);
+  });
+  if (on_dev.empty()) return 0;
+  // a mixed call: the device boxes are packed, and their results dealt back afterwards
+  const bool mixed = (int)on_dev.size() != nbox;
+  std::vector<int> pvol, plab, pn, pst;
+  std::vector<BoxDesc> pdesc;
+  const int* vols = h_vols;
+  int *labels = h_labels, *nlabels = h_nlabels, *stats = h_stats;
+  const std::vector<BoxDesc>* dd = &desc;
+  size_t dtotal = total;
+  if (mixed) {
+    dtotal = pack_device_boxes(h_vols, desc, on_dev, &pvol, &pdesc);
+    plab.resize(dtotal); pn.resize(on_dev.size());
+    if (h_stats) pst.resize(on_dev.size() * row);
+    vols = pvol.data(); labels = plab.data(); nlabels = pn.data(); stats = h_stats ? pst.data() : nullptr; dd = &pdesc;
+  }
+  const int ndev = (int)on_dev.size();
+  hipStream_t st;
+  ICS_TRY(get_stream(&st));
+  unsigned char* buf = nullptr;
+  const size_t b_vol = dtotal * 4, b_desc = (size_t)ndev * sizeof(BoxDesc), b_n = (size_t)ndev * 4, b_st = (size_t)ndev * row * 4;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ICS_TRY(scratch_get(up(b_vol) * 2 + up(b_desc) + up(b_n) + up(b_st), &buf));
+  int* d_vol = reinterpret_cast<int*>(buf);
+  int* d_lab = reinterpret_cast<int*>(buf + up(b_vol));
+  BoxDesc* d_desc = reinterpret_cast<BoxDesc*>(buf + 2 * up(b_vol));
+  int* d_n = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc));
+  int* d_st = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc) + up(b_n));
+  hipError_t e = hipMemcpyAsync(d_vol, vols, b_vol, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, dd->data(), b_desc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    ICS_LAUNCH(label_boxes_kernel, dim3(ndev), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
+               d_lab, d_n, d_st);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(labels, d_lab, b_vol, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(nlabels, d_n, b_n, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_st, b_st, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { set_error(std::string("label_boxes: ") + hipGetErrorString(e)); return -1; }
+  if (mixed)
+    for (int k = 0; k < ndev; ++k) {
+      const int b = on_dev[k];
+      const BoxDesc &d = desc[b], &p = pdesc[k];
+      std::memcpy(h_labels + d.off, plab.data() + p.off, (size_t)d.D * d.H * d.W * sizeof(int));
+      h_nlabels[b] = pn[k];
+      if (h_stats) std::memcpy(h_stats + b * row, pst.data() + k * row, row * sizeof(int));
     }
-  };
-  // threads by the work at hand: one per ~16 k voxels of boxes, at most one per box
-  const int nthreads = (int)std::min<size_t>((size_t)nbox, total / 16384 + 1);
-  HostPool::get().run(nthreads, work);
   return 0;
 }
 
@@ -899,11 +1032,15 @@ int segment_watershed_split_host(const int* h_boxes, const int* h_dims, const in
 namespace {
 // ---- exact grid-point count of convex_hull_image(component) (round 6).  skimage offsets every voxel centre by +-0.5 along one
 // axis at a time and counts the grid points inside the hull of those points; on doubled coordinates everything is an integer:
-// S' = {2p +- e_k}.  The facet planes of conv(S') are found by gift wrapping with exact predicates (coordinates < 2^8, triple
-// products < 2^27) and -- lattice sets being as degenerate as point sets get -- with whole coplanar groups per facet: a
+// S' = {2p +- e_k}.  The facet planes of conv(S') are found by gift wrapping with exact predicates and -- lattice sets being
+// as degenerate as point sets get -- with whole coplanar groups per facet: a
 // supporting plane's points are hulled in 2-D, its polygon's edges are pivoted across to the neighbouring planes.  A grid point
 // is inside iff no plane excludes it; a point ON a plane is inside (Qhull evaluates those to ~1e-16 < the reference's 1e-10
 // tolerance, watershed.py:80-81 / convex_hull_image).  Only the points between the two integer bounds need the test.
+// Magnitudes, for box extents up to kBoxHostMax = 256: doubled coordinates lie in [-1, 511], so a coordinate difference is
+// at most 512 = 2^9; a 2 x 2 minor (h_collinear, h_face_edges' cross, a plane normal in h_plane / h_planes) is at most 2^19;
+// a triple product (h_triple) and a plane offset or evaluation n . p (h_plane, h_face_edges, the count below) are at most
+// 3 * 2^9 * 2^19 < 2^31.  Every product is taken in long long: exact with 2^32 to spare.
 struct HP { int x, y, z; };
 inline long long h_triple(const HP& a, const HP& b, const HP& c, const HP& d) {
   const long long ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z,
@@ -966,8 +1103,9 @@ void h_face_edges(const std::vector<HP>& pts, const HPlane& pl, std::vector<std:
   --k;
   for (int i = 0; i < k; ++i) edges->push_back({h[i], h[(i + 1) % k]});
 }
-// both supporting planes through the hull edge (a, b): the extreme directions of the set seen along the edge
-void h_pivot(const std::vector<HP>& pts, int ia, int ib, std::vector<HPlane>* out) {
+// both supporting planes through the hull edge (a, b): the extreme directions of the set seen along the edge.  false if
+// every point is collinear with the edge or a candidate's plane does not support the set (then the search cannot be trusted)
+bool h_pivot(const std::vector<HP>& pts, int ia, int ib, HPlane out[2]) {
   const HP &a = pts[ia], &b = pts[ib];
   int c1 = -1, c2 = -1;
   for (int i = 0; i < (int)pts.size(); ++i) {
@@ -976,11 +1114,11 @@ void h_pivot(const std::vector<HP>& pts, int ia, int ib, std::vector<HPlane>* ou
     if (h_triple(a, b, pts[c1], pts[i]) < 0) c1 = i;
     if (h_triple(a, b, pts[c2], pts[i]) > 0) c2 = i;
   }
-  HPlane pl;
-  if (c1 >= 0 && h_plane(pts, a, b, pts[c1], &pl)) out->push_back(pl);
-  if (c2 >= 0 && h_plane(pts, a, b, pts[c2], &pl)) out->push_back(pl);
+  return c1 >= 0 && h_plane(pts, a, b, pts[c1], &out[0]) && h_plane(pts, a, b, pts[c2], &out[1]);
 }
-// all facet planes of conv(pts); false if the search did not close (never observed; the caller then falls back to "undecided")
+// all facet planes of conv(pts); false if the search did not close -- a hull edge without two distinct supporting planes,
+// a pivot candidate without a supporting plane, or the step guard (never observed; the caller then leaves the component to
+// Qhull)
 bool h_planes(const std::vector<HP>& pts, std::set<HPlane>* planes) {
   if (pts.size() < 4) return false;
   // a first supporting plane: the points of minimal x lie on x = xmin; tilt it around its extreme points until it is a facet
@@ -1036,8 +1174,9 @@ bool h_planes(const std::vector<HP>& pts, std::set<HPlane>* planes) {
     const std::pair<int, int> key = e.first < e.second ? e : std::make_pair(e.second, e.first);
     if (!seen.insert(key).second) continue;
     if (++guard > 200000) return false;
-    std::vector<HPlane> two;
-    h_pivot(pts, e.first, e.second, &two);
+    HPlane two[2];
+    if (!h_pivot(pts, e.first, e.second, two)) return false;
+    if (!(two[0] < two[1]) && !(two[1] < two[0])) return false;            // one plane where a hull edge has two
     for (const HPlane& pl : two)
       if (planes->insert(pl).second) h_face_edges(pts, pl, &todo);
   }
@@ -1170,6 +1309,7 @@ void component_bounds_one(const int* lab, int H, int W, int cl, const int* st, d
           if (pl.nx * (2 * x) + pl.ny * (2 * y) + pl.nz * (2 * z) > pl.d) { in = false; break; }
         Hc += in;
       }
+  if (Hc < cnt || Hc > P) return;                  // outside F <= H <= P: a plane is missing; out[4] stays 0 (Qhull)
   out[4] = Hc;
 }
 }  // namespace
@@ -1179,15 +1319,26 @@ int segment_component_bounds(const int* h_labels, const int* h_dims, int nbox, c
   ICS_CHECK(h_labels && h_dims && h_nlabels && h_stats && h_bounds && nbox >= 1 && max_labels >= 1, "bad component_bounds arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
-  ICS_TRY(box_descs(h_dims, nullptr, nbox, &desc, &total));
-  std::memset(h_bounds, 0, (size_t)nbox * max_labels * 5 * sizeof(long long));
+  ICS_TRY(box_descs(h_dims, nullptr, nbox, kBoxHostMax, &desc, &total));
   struct Job { int box, cl; };
   std::vector<Job> jobs;
   for (int b = 0; b < nbox; ++b) {
     ICS_CHECK(h_nlabels[b] >= 0 && h_nlabels[b] <= max_labels, "component_bounds: nlabels exceeds max_labels");
-    for (int c = 0; c < h_nlabels[b]; ++c)
-      if (h_stats[((size_t)b * max_labels + c) * 7] > min_voxels) jobs.push_back(Job{b, c + 1});
+    const BoxDesc& d = desc[b];
+    for (int c = 0; c < h_nlabels[b]; ++c) {
+      const int* s = h_stats + ((size_t)b * max_labels + c) * 7;
+      if (s[0] <= min_voxels) continue;
+      // component_bounds_one reads the label volume inside this box: a stale or inverted row must not reach it
+      ICS_CHECK(0 <= s[1] && s[1] < s[4] && s[4] <= d.D && 0 <= s[2] && s[2] < s[5] && s[5] <= d.H && 0 <= s[3] &&
+                    s[3] < s[6] && s[6] <= d.W,
+                "component_bounds: box " + std::to_string(b) + " label " + std::to_string(c + 1) + ": stats box [" +
+                    std::to_string(s[1]) + "," + std::to_string(s[4]) + ")x[" + std::to_string(s[2]) + "," +
+                    std::to_string(s[5]) + ")x[" + std::to_string(s[3]) + "," + std::to_string(s[6]) + ") must be non-empty and inside " +
+                    std::to_string(d.D) + "x" + std::to_string(d.H) + "x" + std::to_string(d.W));
+      jobs.push_back(Job{b, c + 1});
+    }
   }
+  std::memset(h_bounds, 0, (size_t)nbox * max_labels * 5 * sizeof(long long));
   std::atomic<size_t> next{0};
   auto work = [&]() {
     for (size_t k = next.fetch_add(1); k < jobs.size(); k = next.fetch_add(1)) {
@@ -1201,15 +1352,37 @@ int segment_component_bounds(const int* h_labels, const int* h_dims, int nbox, c
   return 0;
 }
 
+// ICSG3D_WS_DEVICE=1: ws_split_kernel for the boxes it takes; boxes with an extent above 64 go to the host flood
+// (host_split_box, the same arithmetic) instead of being refused.
 int segment_watershed_split(hipStream_t st, const int* h_boxes, const int* h_dims, const int* h_cls, int nbox, int tie,
                             int* h_wss) {
   ICS_CHECK(h_boxes && h_dims && h_cls && h_wss && nbox >= 1 && (tie == 0 || tie == 1), "bad watershed_split arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
-  ICS_TRY(box_descs(h_dims, h_cls, nbox, &desc, &total));
+  ICS_TRY(box_descs(h_dims, h_cls, nbox, kBoxHostMax, &desc, &total));
+  std::vector<int> on_host, on_dev;
+  for (int b = 0; b < nbox; ++b) (box_fits_device(desc[b]) ? on_dev : on_host).push_back(b);
+  host_boxes_run(desc, on_host, [&](int b) {
+    const BoxDesc& d = desc[b];
+    host_split_box(h_boxes + d.off, d.D, d.H, d.W, tie, h_wss + d.off);
+  });
+  if (on_dev.empty()) return 0;
+  const bool mixed = (int)on_dev.size() != nbox;
+  std::vector<int> pvol, pout;
+  std::vector<BoxDesc> pdesc;
+  const int* boxes = h_boxes;
+  int* wss = h_wss;
+  const std::vector<BoxDesc>* dd = &desc;
+  size_t dtotal = total;
+  if (mixed) {
+    dtotal = pack_device_boxes(h_boxes, desc, on_dev, &pvol, &pdesc);
+    pout.resize(dtotal);
+    boxes = pvol.data(); wss = pout.data(); dd = &pdesc;
+  }
+  const int ndev = (int)on_dev.size();
   unsigned char* buf = nullptr;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_vol = total * 4, b_desc = (size_t)nbox * sizeof(BoxDesc);
+  const size_t b_vol = dtotal * 4, b_desc = (size_t)ndev * sizeof(BoxDesc);
   // work: 4 ints per voxel (BoxDesc::heap_off * 2 with room to spare), heap: 2 unsigned per voxel
   ICS_TRY(scratch_get(up(b_vol) * 2 + up(b_desc) + up(b_vol * 4) + up(b_vol * 2), &buf));
   int* d_box = reinterpret_cast<int*>(buf);
@@ -1217,15 +1390,20 @@ int segment_watershed_split(hipStream_t st, const int* h_boxes, const int* h_dim
   BoxDesc* d_desc = reinterpret_cast<BoxDesc*>(buf + 2 * up(b_vol));
   int* d_work = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc));
   unsigned* d_heap = reinterpret_cast<unsigned*>(buf + 2 * up(b_vol) + up(b_desc) + up(b_vol * 4));
-  hipError_t e = hipMemcpyAsync(d_box, h_boxes, b_vol, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, desc.data(), b_desc, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(d_box, boxes, b_vol, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, dd->data(), b_desc, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    ICS_LAUNCH(ws_split_kernel, dim3(nbox), dim3(1024), 0, st, d_box, d_desc, tie, d_work, d_heap, d_out);
+    ICS_LAUNCH(ws_split_kernel, dim3(ndev), dim3(1024), 0, st, d_box, d_desc, tie, d_work, d_heap, d_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_wss, d_out, b_vol, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(wss, d_out, b_vol, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { set_error(std::string("watershed_split: ") + hipGetErrorString(e)); return -1; }
+  if (mixed)
+    for (int k = 0; k < ndev; ++k) {
+      const BoxDesc &d = desc[on_dev[k]], &p = pdesc[k];
+      std::memcpy(h_wss + d.off, pout.data() + p.off, (size_t)d.D * d.H * d.W * sizeof(int));
+    }
   return 0;
 }
 

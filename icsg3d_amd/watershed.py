@@ -100,8 +100,9 @@ def component_bounds(labels, stats_rows, min_voxels=3, hull_threshold=0.0):
 
 
 def label_boxes(vols, connectivity=1, max_labels=1024, want_bounds=False, min_voxels=3, hull_threshold=0.0):
-    """skimage.measure.label(vol, connectivity=...) for each int volume in `vols` (extents <= 64): components of equal
-    non-zero value, raster-order numbering.  Returns [(labels int32, n, stats (n,7) = {voxels, z0, y0, x0, z1, y1, x1})];
+    """skimage.measure.label(vol, connectivity=...) for each int volume in `vols` (extents 1..256; boxes up to 64 per axis
+    run on the device, larger ones -- whole grids at d >= 128 -- on the library's host threads, ICSG3D_LABEL_HOST=1 sends
+    every box there): components of equal non-zero value, raster-order numbering.  Returns [(labels int32, n, stats (n,7) = {voxels, z0, y0, x0, z1, y1, x1})];
     with want_bounds a fourth entry, int64 (n,5) = {voxels, P, F, flat, H} per component with more than min_voxels voxels
     (zeros otherwise): the exact-integer bounds P >= count_nonzero(convex_hull_image(component)) >= F, the flatness flag, and
     the exact count H where hull_threshold > 0 and the bounds leave the decision open (ics_op_component_bounds, host threads)."""
@@ -133,8 +134,9 @@ def label_boxes(vols, connectivity=1, max_labels=1024, want_bounds=False, min_vo
 
 
 def watershed_split(boxes, cls, tie="heap"):
-    """watershed.py:95-110 for each box (values {0, cls[b]}): eroded cores -> markers -> priority flood -> `wss[wss == 1]
-    = 0`; labels 2.. or 0, before the reference's max_class shift."""
+    """watershed.py:95-110 for each box (values {0, cls[b]}, extents 1..256): eroded cores -> markers -> priority flood ->
+    `wss[wss == 1] = 0`; labels 2.. or 0, before the reference's max_class shift.  Host threads; under ICSG3D_WS_DEVICE=1
+    the kernel for boxes up to 64 per axis, the host flood for the others."""
     boxes = [np.ascontiguousarray(v, dtype=np.int32) for v in boxes]
     if not boxes:
         return []

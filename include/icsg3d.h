@@ -162,9 +162,11 @@ int ics_vae_decode_to_unet_labels(ics_net* vae, ics_net* unet, const float* z, c
 int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch, int d, int min_voxels, int max_atoms,
                          int num_species, int32_t* regions, int32_t* counts, int32_t* atom_stats,
                          int64_t* convexity_bounds);
-/* ---- segment_nuclei's non-convex branch and recursion (watershed.py:40-150) on small boxes.  A box is a dense int32
- * volume [D][H][W] (extents 1..64) -- a component cropped to its bounding box, or a watershed result that is segmented
- * again; `nbox` boxes lie back to back in `vols` / `boxes`, dims = [nbox][3].  HOST pointers; one workgroup per box.
+/* ---- segment_nuclei's non-convex branch and recursion (watershed.py:40-150) on boxes.  A box is a dense int32 volume
+ * [D][H][W] (extents 1..256) -- a whole d^3 grid, a component cropped to its bounding box, or a watershed result that is
+ * segmented again; `nbox` boxes lie back to back in `vols` / `boxes`, dims = [nbox][3].  HOST pointers.  Boxes up to 64
+ * per axis run one workgroup per box; larger ones run on host threads (same results), and so does every box of
+ * ics_op_label_boxes under ICSG3D_LABEL_HOST=1.
  * The scikit-image 0.17.2 routines these replace (requirements.txt:95) are absent from the image: PARITY UNPINNED, the
  * algorithms are restated in oracle/watershed_ref.py and the kernels are held to that restatement bit for bit.
  *   ics_op_label_boxes   = skimage.measure.label(box, connectivity) (watershed.py:52, :103): maximal sets of voxels of
@@ -188,7 +190,9 @@ int ics_op_watershed_split(const int32_t* boxes, const int32_t* dims, const int3
  * component closed under axis-parallel line fills -- flat = 1 for coplanar / collinear components (the reference stack's
  * Qhull call fails there), and H = that count itself, computed exactly (integer gift wrapping over the +-0.5 offset voxel
  * set on doubled coordinates; a grid point on a facet counts as inside, as under the reference's 1e-10 tolerance) only where
- * hull_threshold > 0 and voxels / P < hull_threshold <= voxels / F, else 0.  Host threads; no device work. */
+ * hull_threshold > 0 and voxels / P < hull_threshold <= voxels / F, else 0 (also 0 where the hull search does not close:
+ * the caller then uses Qhull).  Every stats row it reads (more than min_voxels voxels) must hold a non-empty box inside its
+ * volume: the call is refused, naming the box, before anything is written.  Host threads; no device work. */
 int ics_op_component_bounds(const int32_t* labels, const int32_t* dims, int nbox, const int32_t* nlabels, const int32_t* stats,
                             int max_labels, int min_voxels, double hull_threshold, int64_t* bounds);
 /* The three box-level entry points below keep one stream and one grow-only device scratch buffer per host thread (they are

@@ -97,8 +97,12 @@ def label_equal(vol, connectivity=1):
         np.minimum.at(first, flat, np.arange(flat.size))
         firsts += [(int(first[k]), v, k) for k in range(1, n + 1)]
     firsts.sort()
+    remap = {v: np.zeros(per_value[v].max() + 1, np.int32) for v in per_value}
     for new, (_, v, k) in enumerate(firsts, start=1):
-        out[per_value[v] == k] = new
+        remap[v][k] = new
+    for v, lab in per_value.items():                     # one gather per value, not one pass over the volume per label
+        fg = lab != 0
+        out[fg] = remap[v][lab[fg]]
     return out, len(firsts)
 
 
@@ -276,11 +280,12 @@ def segment_nuclei(binary, wmin=8, it=1, max_iters=5, min_convexity=0.8, tie="he
     seg_classes, seg_counts = np.unique(labels, return_counts=True)
     seg_classes = np.array([seg_classes[i] for i in range(len(seg_classes)) if seg_counts[i] > 3])
     seg_classes = seg_classes[seg_classes != 0]
+    boxes = ndimage.find_objects(labels)
     for cl in seg_classes:
-        binary_cl = np.where(labels == cl, labels, 0)
-        bb = bbox_of(binary_cl != 0)
-        sl = (slice(bb[0], bb[3]), slice(bb[1], bb[4]), slice(bb[2], bb[5]))
-        binary_bbox = binary_cl[sl]
+        # binary_cl = np.where(labels == cl, labels, 0) cropped to bbox_of(binary_cl != 0); cropped first (the same
+        # values), so that a d = 128 volume is not swept once per component
+        sl = boxes[cl - 1]
+        binary_bbox = np.where(labels[sl] == cl, labels[sl], 0)
         chull = convex_hull_image(binary_bbox, degenerate=degenerate)
         convexity = np.count_nonzero(binary_bbox) / np.count_nonzero(chull)
         if convexity >= min_convexity:

@@ -341,3 +341,122 @@ def test_component_bounds_op_equals_the_numpy_definitions():
                 boxes.append(lab[z0:z1, y0:y1, x0:x1] == cl); rows.append(B[cl - 1])
         got = P.convexity_many(boxes, 0.8, degenerate="solid", bounds=rows)
         assert [g[0] for g in got] == [P.convexity_at_least(b, 0.8, degenerate="solid")[0] for b in boxes]
+
+
+def _labelled_with_stats(v):
+    """6-connected components of a binary volume in raster order (W.label_equal's numbering) and their 7-int stats rows
+    {voxels, z0, y0, x0, z1, y1, x1}, vectorised (bincount / find_objects)."""
+    from scipy import ndimage
+    lab, n = ndimage.label(np.asarray(v) != 0)
+    st = np.zeros((n, 7), np.int32)
+    st[:, 0] = np.bincount(lab.ravel(), minlength=n + 1)[1:]
+    for i, sl in enumerate(ndimage.find_objects(lab)):
+        st[i, 1:4] = [s.start for s in sl]
+        st[i, 4:7] = [s.stop for s in sl]
+    return lab.astype(np.int32), st
+
+
+def test_component_bounds_op_on_label_volumes_larger_than_64():
+    """ics_op_component_bounds on whole label volumes with extents 65..128 (what refine_atoms hands it at d >= 128): the
+    same {voxels, P, F, flat} as the numpy definitions, and on every component the bounds leave undecided the exact hull
+    count H equal to Qhull's (convex_hull_volume) -- thresholded smooth noise and unions of balls with holes."""
+    import icsg3d_amd.watershed as P
+    from scipy import ndimage
+    rng = np.random.default_rng(12)
+    vols = []
+    for shape, sigma, q in (((96, 72, 80), 1.6, 0.9), ((70, 128, 66), 2.0, 0.88)):
+        f = ndimage.gaussian_filter(rng.standard_normal(shape), sigma)
+        vols.append((f >= np.quantile(f, q)).astype(np.int32))
+    zz, yy, xx = np.mgrid[:128, :70, :66]
+    balls = np.zeros((128, 70, 66), bool)
+    for c, r in (((20, 30, 30), 12), ((38, 30, 36), 11), ((60, 40, 30), 9), ((100, 20, 50), 10), ((110, 50, 20), 8)):
+        balls |= (zz - c[0]) ** 2 + (yy - c[1]) ** 2 + (xx - c[2]) ** 2 <= r * r
+    vols.append((balls & (rng.uniform(size=balls.shape) > 0.05)).astype(np.int32))
+    labs, stats = zip(*[_labelled_with_stats(v) for v in vols])
+    assert max(max(s[:, 4:7].max(0) - s[:, 1:4].min(0)) for s in stats) > 64        # components wider than 64 are there too
+    bounds = P.component_bounds(list(labs), list(stats), min_voxels=3, hull_threshold=0.8)
+    checked = exact = 0
+    for lab, st, B in zip(labs, stats, bounds):
+        for cl in np.nonzero(st[:, 0] > 3)[0] + 1:
+            z0, y0, x0, z1, y1, x1 = st[cl - 1, 1:7]
+            m = lab[z0:z1, y0:y1, x0:x1] == cl
+            n_, P_, F_ = int(m.sum()), P.dop_count(m), P.fill_count(m)
+            assert list(B[cl - 1][:4]) == [n_, P_, F_, int(P.is_flat(np.argwhere(m)))], (cl, list(B[cl - 1]))
+            checked += 1
+            if n_ / P_ < 0.8 <= n_ / F_:                   # undecided: the exact count is there, and it is Qhull's
+                assert B[cl - 1][4] == P.convex_hull_volume(m, degenerate="solid"), (cl, list(B[cl - 1]))
+                exact += 1
+            else:
+                assert B[cl - 1][4] == 0
+        assert (B[st[:, 0] <= 3] == 0).all()
+    print("component_bounds at extents > 64: %d components checked, %d exact hull counts" % (checked, exact))
+    assert checked > 100 and exact > 20, (checked, exact)
+
+
+def test_component_bounds_refuses_bad_stats_rows_and_stays_usable():
+    """A stats row whose box is inverted, reaches past the volume or starts below 0 is refused, naming the box and the
+    label, before anything is written; rows of components at or under min_voxels are never read."""
+    from icsg3d_amd import _lib as L
+    lib = L.load()
+    vols = [_balls(12, [((5, 5, 5), 3)]), np.zeros((70, 6, 5), np.int32)]
+    vols[1][2:68, 1:4, 1:4] = 1
+    vols[1][0, 0, 0] = 1
+    ls = [_labelled_with_stats(v) for v in vols]
+    ML = 4
+    lab = np.concatenate([l.ravel() for l, _ in ls]).astype(np.int32)
+    dims = np.array([v.shape for v in vols], np.int32)
+    n = np.array([len(s) for _, s in ls], np.int32)
+    good = np.zeros((2, ML, 7), np.int32)
+    for b, (_, s) in enumerate(ls):
+        good[b, :len(s)] = s
+    assert list(n) == [1, 2] and good[1, 1, 0] == 66 * 9
+
+    def call(st, out, min_voxels=3):
+        return lib.ics_op_component_bounds(L.i32ptr(lab), L.i32ptr(dims), 2, L.i32ptr(n), L.i32ptr(st), ML, min_voxels, 0.8,
+                                           L.i64ptr(out))
+    cases = []
+    st = good.copy(); st[1, 1, 4] = st[1, 1, 1]; cases.append((st, "box 1 label 2"))           # empty z range
+    st = good.copy(); st[1, 1, 1], st[1, 1, 4] = 40, 10; cases.append((st, "box 1 label 2"))    # inverted
+    st = good.copy(); st[1, 1, 4] = 71; cases.append((st, "box 1 label 2"))                     # past D = 70
+    st = good.copy(); st[0, 0, 6] = 13; cases.append((st, "box 0 label 1"))                     # past W = 12
+    st = good.copy(); st[0, 0, 2] = -1; cases.append((st, "box 0 label 1"))                     # negative origin
+    st = good.copy(); st[1, 0, 1:7] = (-5, -5, -5, 99, 99, 99); st[1, 1, 1:4] = -2; cases.append((st, "box 1 label 2"))
+    for st, msg in cases:
+        out = np.full((2, ML, 5), -7, np.int64)
+        assert call(st, out) != 0, msg
+        err = lib.ics_last_error().decode()
+        assert msg in err and "stats box" in err, (msg, err)
+        assert (out == -7).all(), msg                        # nothing written
+    # label 1 of box 1 (one voxel) is not a job at min_voxels = 3: its row is not read, whatever it holds
+    st = good.copy(); st[1, 0, 1:7] = (-5, -5, -5, 99, 99, 99)
+    out = np.full((2, ML, 5), -7, np.int64)
+    assert call(st, out) == 0
+    assert out[1, 1, 0] == 66 * 9 and out[0, 0, 0] == good[0, 0, 0] and (out[1, 0] == 0).all()
+    out2 = np.full((2, ML, 5), -7, np.int64)
+    assert call(good, out2) == 0 and np.array_equal(out, out2)
+
+
+@pytest.mark.parametrize("conn", [1, 3])
+def test_host_labeller_matches_oracle_on_boxes_up_to_256(conn, monkeypatch):
+    """ics_op_label_boxes' host labeller (boxes with an extent above 64; every box under ICSG3D_LABEL_HOST=1, which keeps
+    this test off the device) against W.label_equal: components of equal value, raster-order numbering, 7-int stats, in a
+    batch that interleaves small and large boxes."""
+    from icsg3d_amd.watershed import label_boxes
+    monkeypatch.setenv("ICSG3D_LABEL_HOST", "1")
+    rng = np.random.default_rng(60 + conn)
+    vols = [(rng.uniform(size=(65, 20, 9)) < 0.4).astype(np.int32) * rng.integers(1, 4, size=(65, 20, 9)).astype(np.int32),
+            rng.integers(0, 3, size=(5, 7, 4)).astype(np.int32),
+            (rng.uniform(size=(9, 256, 7)) < 0.5).astype(np.int32) * 7,
+            np.zeros((3, 3, 3), np.int32),
+            (rng.uniform(size=(128, 40, 33)) < 0.3).astype(np.int32),
+            rng.integers(0, 2, size=(1, 1, 256)).astype(np.int32),
+            _balls(24, [((8, 8, 8), 6)])[:, :, :] * 3]
+    res = label_boxes(vols, connectivity=conn, max_labels=64)          # grows max_labels by itself
+    for v, (lab, n, st) in zip(vols, res):
+        ref, nref = W.label_equal(v, connectivity=conn)
+        assert n == nref and np.array_equal(lab, ref), v.shape
+        assert np.array_equal(st[:, 0], np.bincount(ref.ravel(), minlength=n + 1)[1:])
+        if n:
+            from scipy import ndimage
+            box = np.array([[s.start for s in sl] + [s.stop for s in sl] for sl in ndimage.find_objects(ref)])
+            assert np.array_equal(st[:, 1:7], box), v.shape

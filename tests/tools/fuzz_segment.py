@@ -2,7 +2,8 @@
 marker-watershed splits on the library's host threads, recursion) against oracle/watershed_ref.py's
 restatement of watershed_clustering (/root/reference/watershed.py:40-203; skimage restated: parity unpinned).  Volumes: unions
 of random balls / ellipsoids that touch and overlap (non-convex components, splits, recursion levels), thin bridges, salt
-noise; batches of 1..8 grids at 16^3 / 32^3 / 64^3.  Integer work: region volumes, species votes and centroids must be EQUAL.
+noise; batches of 1..8 grids at 16^3 / 32^3 / 64^3 and of 1..2 at 128^3 (whole-grid boxes above 64 per axis: host
+labeller, host component bounds, split boxes wider than 64).  Integer work: region volumes, species votes and centroids must be EQUAL.
 
     python tests/tools/fuzz_segment.py [trials=40] [seed=0]"""
 import os
@@ -47,8 +48,8 @@ def main():
     nbad = ngrid = nsplit = 0
     t0 = time.time()
     for t in range(trials):
-        d = int(rng.choice([16, 32, 32, 32, 64]))
-        B = int(rng.integers(1, 9 if d < 64 else 4))
+        d = int(rng.choice([16, 32, 32, 32, 64, 128]))
+        B = int(rng.integers(1, 9 if d < 64 else 4 if d == 64 else 3))
         masks = np.stack([volume(rng, d) for _ in range(B)])
         species = np.where(masks != 0, rng.integers(1, 95, size=masks.shape), 0).astype(np.uint8)
         out = refine_atoms(segment_atoms(masks, species, max_atoms=1024), degenerate="solid")
