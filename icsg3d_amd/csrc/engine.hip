@@ -9,6 +9,7 @@
 #include "segment.h"
 #include "voxelise.h"
 #include "match.h"
+#include "latent.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -294,6 +295,7 @@ struct Net {
   float *cond_in = nullptr, *eps_in = nullptr, *z_buf = nullptr, *zc = nullptr, *recon = nullptr,
         *drecon = nullptr, *dmulv = nullptr;
   ConvLayer *enc_dense = nullptr, *zmulv = nullptr, *dec_dense = nullptr;
+  double* lat_alpha = nullptr;        // [maxB] the steps of an interpolation (ics_vae_interpolate*)
 
   ~Net() {
     if (canary_on && !canaries.empty()) {      // ICSG3D_DEBUG_CANARY=1: every handle -- the temporary ones of the single-op entry
@@ -870,7 +872,9 @@ __global__ void axpy_strided_kernel(float* __restrict__ y, const float* __restri
 }
 // route a padded layer through its materialised input buffer
 static void use_padded_input(ConvLayer& L) {
-  if (L.CinG == L.Cin) return;
+  // a condition-folded layer reads its virtual sources whatever its padding: at cond_shape 3 / 7 / 15 (C = 1) the logical
+  // Cin needs none (CinG == Cin) and vsrc was left empty -- the first forward was refused ("thin-C conv: unsupported shape")
+  if (L.CinG == L.Cin && !L.cond_fold) return;
   L.vsrc[0] = L.src[0]; L.vsrc[1] = L.src[1]; L.nvsrc = L.nsrc;
   L.src[0] = ConvSrc{L.pad_in, nullptr, nullptr, L.CinG, 0, ACT_NONE, 0};
   L.nsrc = 1;
@@ -1801,6 +1805,7 @@ static int vae_build(Net& n, const ics_vae_config& cfg, Net* pm) {
   for (auto& Lp : n.layers) ICS_TRY(enable_winog(n, *Lp, true));      // e3 at d = 32 (4^3 x 64 -> 128)
   ICS_TRY(alloc_workspaces(n, true));
   ICS_TRY(init_bn_defaults(n));
+  ICS_TRY(n.alloc(&n.lat_alpha, (size_t)n.maxB));
   if (pm) {
     // perceptual tap copies / gradients live with the U-Net (sized for ITS max batch)
     UnetRefs u = unet_refs(*pm);
@@ -2767,6 +2772,107 @@ int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, floa
   return 0;
 }
 
+// interpolate.py:47-64 as one chain per group of pairs: the group's 2g endpoints (a0, b0, a1, b1, ...) through ONE encoder
+// pass, latent_path_kernel from z_buf into zc = [z | cond] for g*steps frames, the decoder -- and for the atoms variant
+// the U-Net, labels and components exactly as ics_vae_decode_to_unet_atoms.  Only the requested outputs reach the host.
+struct InterpArgs {
+  const float *a, *b, *cond, *eps_a, *eps_b;
+  int pairs;
+  const double* alpha;
+  int steps, mode;
+};
+struct InterpAtomsOut {
+  float thresh; int min_voxels, max_atoms;
+  uint8_t *species, *mask; float *density, *coord_minmax; int32_t *regions, *counts, *atom_stats; int64_t* bounds;
+};
+static int interp_check(const char* who, const Net& n, const Net* u, const InterpArgs& A, const InterpAtomsOut* T, int* group) {
+  const std::string p = std::string(who) + ": ";
+  ICS_TRY(latent_path_check(who, A.pairs, n.latent, A.alpha, A.steps, A.mode));
+  ICS_CHECK(A.a && A.b && A.cond && A.eps_a && A.eps_b, p + "null argument (a, b, cond, eps_a, eps_b are required)");
+  int lim = n.maxB;                 // frames per group: the decoder's batch, and the U-Net's where one follows
+  if (u) {
+    ICS_CHECK(u->d == n.d && u->C == n.C && u->device == n.device, p + "U-Net / VAE engines do not match (grid, channels, device)");
+    ICS_CHECK(T->counts && T->atom_stats && T->max_atoms >= 1, p + "null argument (counts, atom_stats are required; max_atoms >= 1)");
+    lim = std::min(lim, u->maxB);
+  }
+  ICS_CHECK(n.maxB >= 2, p + "max_batch must be >= 2 (a pair's two endpoints share one encoder pass)");
+  ICS_CHECK(A.steps <= lim, p + "steps exceeds max_batch (" + std::to_string(lim) + ")");
+  *group = std::min(n.maxB / 2, lim / A.steps);
+  return 0;
+}
+static int interp_run(Net& n, Net* u, const InterpArgs& A, int group, const InterpAtomsOut* T, float* z_ends,
+                      float* z_path, float* recon) {
+  const size_t lat = n.latent, nc = n.ncond, W = lat + nc, vox = (size_t)n.d * n.d * n.d, xrow = vox * n.C;
+  n.resident_batch = 0;             // the endpoints overwrite the input batch: no resident step may run on them
+  if (u) ICS_HIP(hipStreamSynchronize(u->st));
+  ICS_HIP(hipMemcpyAsync(n.lat_alpha, A.alpha, (size_t)A.steps * sizeof(double), hipMemcpyHostToDevice, n.st));
+  for (int p0 = 0; p0 < A.pairs; p0 += group) {
+    const int g = std::min(group, A.pairs - p0), frames = g * A.steps;
+    // what x_in / cond_in / eps_in / z_buf (2g rows) and zc / recon (frames rows) hold is max_batch rows each
+    ICS_CHECK(2 * g <= n.maxB && frames <= n.maxB && (!u || frames <= u->maxB), "interpolation group exceeds a buffer sized for max_batch");
+    for (int i = 0; i < g; ++i) {
+      ICS_HIP(hipMemcpyAsync(n.x_in + (size_t)(2 * i) * xrow, A.a + (size_t)(p0 + i) * xrow, xrow * 4, hipMemcpyHostToDevice, n.st));
+      ICS_HIP(hipMemcpyAsync(n.x_in + (size_t)(2 * i + 1) * xrow, A.b + (size_t)(p0 + i) * xrow, xrow * 4, hipMemcpyHostToDevice, n.st));
+    }
+    for (int e = 0; e < 2; ++e) {   // row 2i + e: the pair's condition twice, eps_a / eps_b
+      ICS_HIP(hipMemcpy2DAsync(n.cond_in + e * nc, 2 * nc * 4, A.cond + (size_t)p0 * nc, nc * 4, nc * 4, g, hipMemcpyHostToDevice, n.st));
+      ICS_HIP(hipMemcpy2DAsync(n.eps_in + e * lat, 2 * lat * 4, (e ? A.eps_b : A.eps_a) + (size_t)p0 * lat, lat * 4, lat * 4, g,
+                               hipMemcpyHostToDevice, n.st));
+    }
+    ICS_TRY(vae_encode_fwd(n, 2 * g, false));
+    n.prof.begin(n.st, "latent_path", 0, 4.0 * (2.0 * g * lat + (double)frames * W));
+    ICS_TRY(launch_latent_path(n.st, n.z_buf, n.z_buf + lat, 2 * lat, n.cond_in, 2 * nc, (int)nc, g, (int)lat, n.lat_alpha,
+                               A.steps, A.mode, n.zc, nullptr));
+    n.prof.end(n.st);
+    if (z_ends) ICS_HIP(hipMemcpyAsync(z_ends + (size_t)p0 * 2 * lat, n.z_buf, (size_t)g * 2 * lat * 4, hipMemcpyDeviceToHost, n.st));
+    if (z_path)
+      ICS_HIP(hipMemcpy2DAsync(z_path + (size_t)p0 * A.steps * lat, lat * 4, n.zc, W * 4, lat * 4, frames, hipMemcpyDeviceToHost, n.st));
+    const size_t f0 = (size_t)p0 * A.steps;
+    if (!u) {
+      ICS_TRY(vae_decode_fwd(n, frames, false));
+      if (recon) ICS_HIP(hipMemcpyAsync(recon + f0 * xrow, n.recon, (size_t)frames * xrow * 4, hipMemcpyDeviceToHost, n.st));
+      ICS_HIP(hipStreamSynchronize(n.st));
+      continue;
+    }
+    unsigned char *d_species, *d_mask;
+    float* d_aux;
+    ICS_TRY(decode_to_labels_compute(n, *u, frames, T->thresh, T->density != nullptr, T->coord_minmax != nullptr, &d_species,
+                                     &d_mask, &d_aux));
+    ICS_TRY(tail_copy_out(n, frames, d_species, d_mask, d_aux, T->species ? T->species + f0 * vox : nullptr,
+                          T->mask ? T->mask + f0 * vox : nullptr, T->density ? T->density + f0 * vox : nullptr,
+                          T->coord_minmax ? T->coord_minmax + f0 * 6 : nullptr));
+    ICS_TRY(segment_to_host(n, d_mask, d_species, frames, n.d, T->min_voxels, T->max_atoms, u->ncls,
+                            T->regions ? T->regions + f0 * vox : nullptr, T->counts + f0 * 2,
+                            T->atom_stats + f0 * T->max_atoms * kSegStatInts,
+                            T->bounds ? T->bounds + f0 * T->max_atoms * kSegBoundInts : nullptr));
+  }
+  return 0;
+}
+
+int ics_vae_interpolate(ics_net* vae, const float* a, const float* b, const float* cond, const float* eps_a,
+                        const float* eps_b, int pairs, const double* alpha, int steps, int mode, float* z_ends,
+                        float* z_path, float* recon) {
+  ICS_TRY(require_kind(vae, 1));
+  const InterpArgs A{a, b, cond, eps_a, eps_b, pairs, alpha, steps, mode};
+  int group = 0;
+  ICS_TRY(interp_check("ics_vae_interpolate", vae->n, nullptr, A, nullptr, &group));
+  return interp_run(vae->n, nullptr, A, group, nullptr, z_ends, z_path, recon);
+}
+int ics_vae_interpolate_to_unet_atoms(ics_net* vae, ics_net* unet, const float* a, const float* b, const float* cond,
+                                      const float* eps_a, const float* eps_b, int pairs, const double* alpha, int steps,
+                                      int mode, float thresh, int min_voxels, int max_atoms, float* z_ends, float* z_path,
+                                      uint8_t* species, uint8_t* mask, float* density, float* coord_minmax,
+                                      int32_t* regions, int32_t* counts, int32_t* atom_stats, int64_t* convexity_bounds) {
+  ICS_TRY(require_kind(vae, 1));
+  ICS_TRY(require_kind(unet, 0));
+  const InterpArgs A{a, b, cond, eps_a, eps_b, pairs, alpha, steps, mode};
+  const InterpAtomsOut T{thresh, min_voxels, max_atoms, species, mask, density, coord_minmax, regions, counts, atom_stats,
+                         convexity_bounds};
+  int group = 0;
+  ICS_TRY(interp_check("ics_vae_interpolate_to_unet_atoms", vae->n, &unet->n, A, &T, &group));
+  return interp_run(vae->n, &unet->n, A, group, &T, z_ends, z_path, nullptr);
+}
+
 int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch, int d, int min_voxels, int max_atoms,
                          int num_species, int32_t* regions, int32_t* counts, int32_t* atom_stats, int64_t* convexity_bounds) {
   ICS_CHECK(mask && species && batch >= 1 && max_atoms >= 1 && min_voxels >= 0, "bad segmentation arguments");
@@ -2839,6 +2945,14 @@ int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, con
   hipStream_t st;
   ICS_TRY(op_stream(&st));
   return match_emd_op(st, a, a_off, b, b_off, batch, emd, match);
+}
+int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps, int mode,
+                       float* path) {
+  ICS_TRY(latent_path_check("ics_op_latent_path", pairs, latent, alpha, steps, mode));
+  ICS_CHECK(za && zb && path, "ics_op_latent_path: null argument (za, zb, path are required)");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return latent_path_op(st, za, zb, pairs, latent, alpha, steps, mode, path);
 }
 int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
                        int32_t* labels, int32_t* nlabels, int32_t* stats) {

@@ -202,6 +202,112 @@ static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const i
   return 0;
 }
 
+/* interpolate.py's walk: the kernel's op and the two chains (valid calls over several groups, then every refusal; the
+ * handle stays usable and a resident step is refused afterwards). */
+static int latent_walk(void) {
+  enum { P = 3, LAT = 70, S = 4 };
+  float za[P * LAT], zb[P * LAT];
+  static float path[P * S * LAT];
+  double alpha[S] = {0.0, 0.5, 1.0, 1.5};
+  int bad = 0;
+  for (int i = 0; i < P * LAT; ++i) { za[i] = 0.01f * i; zb[i] = 1.f - 0.02f * i; }
+  OK(ics_op_latent_path(za, zb, P, LAT, alpha, S, 0, path));
+  OK(ics_op_latent_path(za, zb, P, LAT, alpha, S, 1, path));
+  OK(ics_op_latent_path(za, zb, 1, 1, alpha, 1, 0, path));
+  bad += ics_op_latent_path(za, zb, 0, LAT, alpha, S, 0, path) == 0;
+  bad += ics_op_latent_path(za, zb, P, 0, alpha, S, 0, path) == 0;
+  bad += ics_op_latent_path(za, zb, P, LAT, alpha, 0, 0, path) == 0;
+  bad += ics_op_latent_path(za, zb, P, LAT, alpha, S, 2, path) == 0;
+  bad += ics_op_latent_path(NULL, zb, P, LAT, alpha, S, 0, path) == 0;
+  bad += ics_op_latent_path(za, NULL, P, LAT, alpha, S, 0, path) == 0;
+  bad += ics_op_latent_path(za, zb, P, LAT, NULL, S, 0, path) == 0;
+  bad += ics_op_latent_path(za, zb, P, LAT, alpha, S, 0, NULL) == 0;
+  alpha[2] = NAN; bad += ics_op_latent_path(za, zb, P, LAT, alpha, S, 0, path) == 0;
+  alpha[2] = INFINITY; bad += ics_op_latent_path(za, zb, P, LAT, alpha, S, 1, path) == 0; alpha[2] = 1.0;
+  if (bad) { fprintf(stderr, "latent path: %d invalid calls accepted\n", bad); return 1; }
+  OK(ics_op_latent_path(za, zb, P, LAT, alpha, S, 0, path));
+  return 0;
+}
+
+static int interp_walk(ics_net* unet, ics_net* vae, const ics_unet_config* uc, const float* x, const float* cond,
+                       const float* eps, int B, int d, int C) {
+  const int pairs = B, steps = 2, frames = pairs * steps;      /* max_batch B: groups of B / 2 pairs */
+  const size_t vox = (size_t)d * d * d;
+  double alpha[2] = {0.0, 1.25};
+  float* z_ends = (float*)malloc((size_t)pairs * 2 * 256 * sizeof(float));
+  float* z_path = (float*)malloc((size_t)frames * 256 * sizeof(float));
+  float* rec = (float*)malloc(frames * vox * C * sizeof(float));
+  uint8_t* sp = (uint8_t*)malloc(frames * vox);
+  uint8_t* mk = (uint8_t*)malloc(frames * vox);
+  float* dens = (float*)malloc(frames * vox * sizeof(float));
+  float* minmax = (float*)malloc((size_t)frames * 6 * sizeof(float));
+  int32_t* regions = (int32_t*)malloc(frames * vox * sizeof(int32_t));
+  int32_t* counts = (int32_t*)malloc((size_t)frames * 2 * sizeof(int32_t));
+  int32_t* stats = (int32_t*)malloc((size_t)frames * 16 * 11 * sizeof(int32_t));
+  int64_t* bnd = (int64_t*)calloc((size_t)frames * 16 * 8, 8);
+  float mv[4];
+  int bad = 0;
+  for (int mode = 0; mode < 2; ++mode) {
+    OK(ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, alpha, steps, mode, z_ends, z_path, rec));
+    OK(ics_vae_interpolate(vae, x, x, cond, eps, eps, 1, alpha, 1, mode, NULL, NULL, NULL));
+    OK(ics_vae_interpolate_to_unet_atoms(vae, unet, x, x, cond, eps, eps, pairs, alpha, steps, mode, 0.8f, 3, 16, z_ends,
+                                         z_path, sp, mk, dens, minmax, regions, counts, stats, bnd));
+    OK(ics_vae_interpolate_to_unet_atoms(vae, unet, x, x, cond, eps, eps, pairs, alpha, steps, mode, 0.8f, 3, 16, NULL,
+                                         NULL, NULL, NULL, NULL, NULL, NULL, counts, stats, NULL));
+  }
+  /* the chain cleared the resident batch */
+  bad += ics_vae_train_step_resident(vae, mv) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, 0, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, alpha, 0, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, alpha, steps, 7, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, NULL, x, cond, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, NULL, cond, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, NULL, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, NULL, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, NULL, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, NULL, steps, 0, z_ends, z_path, rec) == 0;
+  bad += ics_vae_interpolate(unet, x, x, cond, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  alpha[1] = NAN;
+  bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec) == 0;
+  alpha[1] = 1.25;
+  {   /* steps above max_batch */
+    double* many = (double*)calloc((size_t)B + 1, sizeof(double));
+    bad += ics_vae_interpolate(vae, x, x, cond, eps, eps, 1, many, B + 1, 0, NULL, NULL, NULL) == 0;
+    free(many);
+  }
+  bad += ics_vae_interpolate_to_unet_atoms(vae, unet, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 16, NULL, NULL,
+                                           NULL, NULL, NULL, NULL, NULL, NULL, stats, NULL) == 0;
+  bad += ics_vae_interpolate_to_unet_atoms(vae, unet, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 16, NULL, NULL,
+                                           NULL, NULL, NULL, NULL, NULL, counts, NULL, NULL) == 0;
+  bad += ics_vae_interpolate_to_unet_atoms(vae, unet, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 0, NULL, NULL,
+                                           NULL, NULL, NULL, NULL, NULL, counts, stats, NULL) == 0;
+  bad += ics_vae_interpolate_to_unet_atoms(vae, vae, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 16, NULL, NULL,
+                                           NULL, NULL, NULL, NULL, NULL, counts, stats, NULL) == 0;
+  {   /* a U-Net of other channels is refused; a smaller one only shortens the groups (steps above ITS max_batch: refused) */
+    ics_unet_config u2 = *uc;
+    ics_net* un2 = NULL;
+    u2.in_channels = uc->in_channels == 1 ? 4 : 1;
+    OK(ics_unet_create(&u2, &un2));
+    bad += ics_vae_interpolate_to_unet_atoms(vae, un2, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 16, NULL, NULL,
+                                             NULL, NULL, NULL, NULL, NULL, counts, stats, NULL) == 0;
+    OK(ics_net_destroy(un2));
+    u2 = *uc; u2.max_batch = 1;
+    OK(ics_unet_create(&u2, &un2));
+    bad += ics_vae_interpolate_to_unet_atoms(vae, un2, x, x, cond, eps, eps, pairs, alpha, steps, 0, 0.8f, 3, 16, NULL, NULL,
+                                             NULL, NULL, NULL, NULL, NULL, counts, stats, NULL) == 0;
+    OK(ics_vae_interpolate_to_unet_atoms(vae, un2, x, x, cond, eps, eps, pairs, alpha, 1, 0, 0.8f, 3, 16, NULL, NULL, NULL,
+                                         NULL, NULL, NULL, NULL, counts, stats, NULL));
+    OK(ics_net_destroy(un2));
+  }
+  if (bad) { fprintf(stderr, "interpolate: %d invalid calls accepted\n", bad); return 1; }
+  OK(ics_vae_interpolate(vae, x, x, cond, eps, eps, pairs, alpha, steps, 0, z_ends, z_path, rec));   /* still usable */
+  OK(ics_vae_upload_batch(vae, x, cond, eps, B));          /* a resident batch again for what follows */
+  OK(ics_vae_train_step_resident(vae, mv));
+  free(z_ends); free(z_path); free(rec); free(sp); free(mk); free(dens); free(minmax); free(regions); free(counts);
+  free(stats); free(bnd);
+  return 0;
+}
+
 static int run(int d, int C, int B, int with_comm) {
   const size_t M = (size_t)B * d * d * d;
   ics_unet_config uc = {C, 95, d, B, 1e-3f, 0.f, 1, 1, with_comm == 2};
@@ -269,6 +375,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_upload_batch(vae, x, cond, eps, B));
   OK(ics_vae_train_step_resident(vae, mv));
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
+  if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
   if (reconstruct_refusals(unet, &vc, &uc, x, cond, eps, B)) return 1;
   if (ics_unet_train_step(unet, x, lab, B + 1, mm) == 0) { fprintf(stderr, "max_batch check missing\n"); return 1; }
   int rows = 0;
@@ -328,6 +435,7 @@ int main(void) {
                                           BatchNorm-backward blocks than 5 do (the engine's capacity checks fire if a
                                           workspace was sized for max_batch alone, round 6) */
   if (match_walk()) return 1;
+  if (latent_walk()) return 1;
   {   /* single-op entry points */
     const int B = 1, S = 8, Cin = 32, Cout = 64;
     size_t nx = (size_t)B * S * S * S * Cin, ny = (size_t)B * S * S * S * Cout, nw = (size_t)27 * Cin * Cout;

@@ -419,6 +419,61 @@ class VaeEngine(_Net):
                 "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
                 "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed}
 
+    def _interp_args(self, a, b, cond, eps_a, eps_b, alpha, mode):
+        a, b, cond, eps_a, eps_b = _f32(a), _f32(b), _f32(cond), _f32(eps_a), _f32(eps_b)
+        P, d = a.shape[0], self.d
+        if a.shape != (P, d, d, d, self.in_channels) or b.shape != a.shape:
+            raise ValueError("bad endpoint shapes %s / %s" % (a.shape, b.shape))
+        if cond.shape != (P, self.cond_shape):
+            raise ValueError("bad cond shape %s" % (cond.shape,))
+        if eps_a.shape != (P, self.latent_dim) or eps_b.shape != eps_a.shape:
+            raise ValueError("bad eps shapes %s / %s" % (eps_a.shape, eps_b.shape))
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        return a, b, cond, eps_a, eps_b, alpha, P, latent_mode(mode)
+
+    def interpolate(self, a, b, cond, eps_a, eps_b, alpha, mode="lerp", want_recon=True):
+        """interpolate.py:50-59 for P pairs as device-resident chains (ics_vae_interpolate): a, b (P,d,d,d,C), cond
+        (P,cond_shape), eps_a / eps_b (P,latent) the two sampling draws, alpha (S,) float64 = np.linspace(0, max_alpha, S).
+        Returns (z_ends (P,2,latent), z_path (P,S,latent), recon (P,S,d,d,d,C) | None).  Overwrites the resident batch."""
+        a, b, cond, eps_a, eps_b, alpha, P, mode = self._interp_args(a, b, cond, eps_a, eps_b, alpha, mode)
+        S, d = len(alpha), self.d
+        z_ends = np.empty((P, 2, self.latent_dim), np.float32)
+        z_path = np.empty((P, S, self.latent_dim), np.float32)
+        recon = np.empty((P, S, d, d, d, self.in_channels), np.float32) if want_recon else None
+        self._resident = 0
+        L.check(self._lib.ics_vae_interpolate(self._h, L.fptr(a), L.fptr(b), L.fptr(cond), L.fptr(eps_a), L.fptr(eps_b), P,
+                                              L.f64ptr(alpha), S, mode, L.fptr(z_ends), L.fptr(z_path), L.fptr(recon)))
+        return z_ends, z_path, recon
+
+    def interpolate_to_atoms(self, unet, a, b, cond, eps_a, eps_b, alpha, mode="lerp", thresh=0.8, min_voxels=3,
+                             max_atoms=512, want_density=True, want_regions=False):
+        """interpolate continued for every frame as decode_to_atoms (ics_vae_interpolate_to_unet_atoms): decode_to_atoms'
+        dict for the P*S frames, frame p*S + k, plus z_ends (P,2,latent) and z_path (P,S,latent)."""
+        from .watershed import STAT_FIELDS, _atoms_from_stats
+        a, b, cond, eps_a, eps_b, alpha, P, mode = self._interp_args(a, b, cond, eps_a, eps_b, alpha, mode)
+        S, d = len(alpha), self.d
+        B = P * S
+        z_ends = np.empty((P, 2, self.latent_dim), np.float32)
+        z_path = np.empty((P, S, self.latent_dim), np.float32)
+        sp = np.empty((B, d, d, d), np.uint8)
+        mk = np.empty((B, d, d, d), np.uint8)
+        dens = np.empty((B, d, d, d), np.float32) if want_density else None
+        reg = np.empty((B, d, d, d), np.int32) if want_regions else None
+        mm = np.zeros((B, 3, 2), np.float32)
+        counts = np.zeros((B, 2), np.int32)
+        stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
+        bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None
+        self._resident = 0
+        L.check(self._lib.ics_vae_interpolate_to_unet_atoms(
+            self._h, unet._h, L.fptr(a), L.fptr(b), L.fptr(cond), L.fptr(eps_a), L.fptr(eps_b), P, L.f64ptr(alpha), S, mode,
+            float(thresh), int(min_voxels), int(max_atoms), L.fptr(z_ends), L.fptr(z_path), L.u8ptr(sp), L.u8ptr(mk),
+            L.fptr(dens), L.fptr(mm), L.i32ptr(reg), L.i32ptr(counts), L.i32ptr(stats), L.i64ptr(bounds)))
+        failed = counts[:, 1] > max_atoms
+        counts[failed, 1] = 0
+        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm, "regions": reg,
+                "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
+                "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed, "z_ends": z_ends, "z_path": z_path}
+
     def train_step(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)
         m = np.zeros(4, np.float32)
@@ -460,6 +515,33 @@ class VaeEngine(_Net):
             return m
         L.check(self._lib.ics_vae_train_step_resident(self._h, None))
         return None
+
+
+LATENT_MODES = {"lerp": 0, "slerp": 1}
+
+
+def latent_mode(mode):
+    if mode in LATENT_MODES:
+        return LATENT_MODES[mode]
+    if mode in (0, 1) and not isinstance(mode, bool):
+        return int(mode)
+    raise ValueError("mode must be 'lerp' or 'slerp', not %r" % (mode,))
+
+
+def latent_path(za, zb, alpha, mode="lerp"):
+    """Single-op entry (ics_op_latent_path): the walk of interpolate.py:54-56 between latent codes za, zb (P,latent)
+    float32 at the float64 steps alpha (S,); returns (P,S,latent) float32.  lerp is the reference's arithmetic bit for
+    bit; slerp falls back to it for (anti)parallel or zero codes -- see include/icsg3d.h."""
+    lib = L.load()
+    za, zb = _f32(za), _f32(zb)
+    if za.ndim != 2 or zb.shape != za.shape:
+        raise ValueError("bad code shapes %s / %s" % (za.shape, zb.shape))
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    P, lat = za.shape
+    out = np.empty((P, len(alpha), lat), np.float32)
+    L.check(lib.ics_op_latent_path(L.fptr(za), L.fptr(zb), P, lat, L.f64ptr(alpha), len(alpha), latent_mode(mode),
+                                   L.fptr(out)))
+    return out
 
 
 def conv3d_forward(x, w, bias=None, pre_act=0):

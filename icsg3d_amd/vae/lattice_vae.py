@@ -294,6 +294,30 @@ class LatticeDFCVAE(DataParallelMixin):
             refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
         return out
 
+    def interpolate_segment_atoms(self, A, B, conds, unet, num_interps=8, max_alpha=1, mode="lerp", eps=None,
+                                  thresh=0.8, min_voxels=3, max_atoms=512, want_regions=False, split=True, max_iters=5):
+        """interpolate.py:47-59 for P pairs continued per frame as decode_segment_atoms: encode A[p], B[p] under conds[p],
+        walk num_interps points (alpha = linspace(0, max_alpha, num_interps), mode "lerp" | "slerp") between the sampled
+        codes, decode, U-Net, argmax / threshold, components -- one device-resident chain per group of pairs
+        (VaeEngine.interpolate_to_atoms) -- then the same host refinement (split=True: refine_atoms).  eps: None (fresh
+        draws) or (P, 2, latent).  Returns decode_segment_atoms' dict for the P * num_interps frames, frame
+        p * num_interps + k, plus z_ends (P, 2, latent) and z_path (P, num_interps, latent).  Sets batch_size = num_interps
+        as the reference's interpolate does."""
+        A = np.asarray(A)
+        P = len(A)
+        if eps is None:
+            eps = np.random.normal(size=(P, 2, self.latent_dim))
+        eps = np.asarray(eps, np.float32).reshape(P, 2, self.latent_dim)
+        self.batch_size = num_interps = int(num_interps)
+        eng = self._engine(max(2, num_interps), grow=True)
+        ueng = unet._engine(max(2, num_interps), grow=True)
+        out = eng.interpolate_to_atoms(ueng, A, B, conds, eps[:, 0], eps[:, 1], np.linspace(0, max_alpha, num_interps),
+                                       mode, thresh, min_voxels, max_atoms, want_regions=want_regions or split)
+        if split:
+            from ..watershed import refine_atoms
+            refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
+        return out
+
     def save_(self, weights, model="saved_models/vae.h5"):
         self.model.load_weights(weights)
         self.model.save(model)

@@ -270,6 +270,51 @@ int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, floa
 int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
                      double* emd, int32_t* match);
 
+/* ---------------------------------------------------------------- interpolation (interpolate.py)
+ * interpolate(a, b, cond, vae, num_interps, return_zs, max_alpha) (interpolate.py:47-64): encode both crystals under one
+ * condition, walk a straight line between their SAMPLED codes (the encoder's third output, F8), decode every point.
+ * alpha = np.linspace(0, max_alpha, num_interps) (interpolate.py:55) is passed in as `steps` doubles, any finite values.
+ * mode 0, lerp -- the reference's arithmetic bit for bit (interpolate.py:54-56: a float32 difference, a float64 product
+ * and sum, one rounding to float32 when Keras feeds the decoder):
+ *     path[k][j] = fl32( fl64(za[j]) + alpha[k] * fl64( fl32(zb[j] - za[j]) ) ),   product and sum rounded separately;
+ * mode 1, slerp (new, opt-in), in float64 from the float32 codes: c = a.b / (|a||b|), w = acos(clamp(c, -1, 1)),
+ * s = sqrt(1 - c c), path[k] = fl32( sin((1 - t) w)/s a + sin(t w)/s b ), t = alpha[k]; a pair with |a| == 0, |b| == 0 or
+ * s < 1e-3 takes the lerp for all its steps.  The dot products are summed in a fixed order: same bits run to run.
+ *
+ * ics_op_latent_path: the kernel alone (interpolate.py:54-56).  HOST pointers: za, zb [pairs][latent], path
+ * [pairs][steps][latent]; any pairs (chunked internally), latent >= 1, steps >= 1; synchronous, the calling thread's op
+ * stream and scratch. */
+int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps,
+                       int mode, float* path);
+/* The whole of interpolate() for `pairs` pairs (interpolate.py:50-59): a, b [pairs][d^3][C], cond [pairs][cond_shape]
+ * (tiled to every step, interpolate.py:58), eps_a, eps_b [pairs][latent] the sampling draws of the two encoder calls.
+ * Outputs, each optional (NULL to skip): z_ends [pairs][2][latent] = (z_a, z_b); z_path [pairs][steps][latent];
+ * recon [pairs*steps][d^3][C], frame p*steps + k.
+ * One device-resident chain per group of g = min(max_batch / 2, max_batch / steps, pairs left) pairs: the 2g endpoints
+ * (a0, b0, a1, b1, ...) in one encoder pass (learning phase 0), the path from the encoder's z into the decoder's
+ * [z | cond] input, the decoder on g*steps frames.  Within one group the results are bit-identical to ics_vae_encode of
+ * those 2g grids, ics_op_latent_path of its z and ics_vae_decode of the path at batch g*steps.
+ * Refused, naming the argument, with nothing written and the handle usable afterwards: pairs < 1, steps < 1,
+ * steps > max_batch, max_batch < 2, a non-finite alpha, an unknown mode, a null a / b / cond / eps_a / eps_b / alpha.
+ * The chain OVERWRITES the engine's input batch with the endpoints and clears the resident-batch mark: a later
+ * ics_vae_train_step_resident / ics_vae_reconstruct_resident_to_unet_atoms is refused ("no resident batch") until a
+ * batch is uploaded again. */
+int ics_vae_interpolate(ics_net* vae, const float* a, const float* b, const float* cond, const float* eps_a,
+                        const float* eps_b, int pairs, const double* alpha, int steps, int mode, float* z_ends,
+                        float* z_path, float* recon);
+/* The same chain continued per group exactly as ics_vae_decode_to_unet_atoms (generate.py:204-236 for every frame of
+ * interpolate.py:57-59): outputs as there for pairs*steps frames, frame p*steps + k, each optional except counts /
+ * atom_stats; bit-identical to ics_vae_decode_to_unet_atoms of z_path at the group's batch.  A group's frames must fit
+ * both engines: the chain GROUPS by the smaller limit, g = min(vae max_batch / 2, min(vae, unet max_batch) / steps),
+ * and refuses only steps above that smaller max_batch -- and a U-Net of another d / C / device, a null counts /
+ * atom_stats, max_atoms < 1, and everything ics_vae_interpolate refuses. */
+int ics_vae_interpolate_to_unet_atoms(ics_net* vae, ics_net* unet, const float* a, const float* b, const float* cond,
+                                      const float* eps_a, const float* eps_b, int pairs, const double* alpha, int steps,
+                                      int mode, float thresh, int min_voxels, int max_atoms, float* z_ends,
+                                      float* z_path, uint8_t* species, uint8_t* mask, float* density,
+                                      float* coord_minmax, int32_t* regions, int32_t* counts, int32_t* atom_stats,
+                                      int64_t* convexity_bounds);
+
 /* ---------------------------------------------------------------- common to both engines */
 int ics_net_destroy(ics_net* net);
 int ics_net_sync(ics_net* net);
