@@ -42,6 +42,13 @@ class Structures(C.Structure):
                 ("abc", C.POINTER(C.c_double))]
 
 
+class TsneConfig(C.Structure):
+    _fields_ = [("dim", C.c_int), ("capacity", C.c_int), ("n_components", C.c_int), ("perplexity", C.c_double),
+                ("early_exaggeration", C.c_double), ("exaggeration_iter", C.c_int), ("max_iter", C.c_int),
+                ("n_iter_check", C.c_int), ("n_iter_without_progress", C.c_int), ("min_grad_norm", C.c_double),
+                ("learning_rate", C.c_double)]
+
+
 _F = C.POINTER(C.c_float)
 _U8 = C.POINTER(C.c_uint8)
 _I32 = C.POINTER(C.c_int32)
@@ -95,6 +102,19 @@ SIGNATURES = {
     "ics_vae_interpolate": (C.c_int, [_H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, _F, _F, _F]),
     "ics_vae_interpolate_to_unet_atoms": (C.c_int, [_H, _H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, C.c_float,
                                                     C.c_int, C.c_int, _F, _F, _U8, _U8, _F, _F, _I32, _I32, _I32, _I64]),
+    "ics_op_tsne_knn": (C.c_int, [_F, C.c_int, C.c_int, C.c_int, _I32, _D]),
+    "ics_op_tsne_affinities": (C.c_int, [_D, C.c_int, C.c_int, C.c_double, _D]),
+    "ics_op_tsne_create": (C.c_int, [C.POINTER(TsneConfig), C.POINTER(_H)]),
+    "ics_op_tsne_destroy": (C.c_int, [_H]),
+    "ics_op_tsne_append": (C.c_int, [_H, _F, C.c_int]),
+    "ics_op_tsne_append_vae": (C.c_int, [_H, _H, C.c_int]),
+    "ics_op_tsne_get_codes": (C.c_int, [_H, _F, C.c_int]),
+    "ics_op_tsne_prepare": (C.c_int, [_H, _F, C.c_int, C.c_int, _D]),
+    "ics_op_tsne_set_graph": (C.c_int, [_H, C.c_int, _I64, _I32, _D, _F, C.c_int, C.c_int]),
+    "ics_op_tsne_get_graph": (C.c_int, [_H, _I64, _I32, _D, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ics_op_tsne_gradient": (C.c_int, [_H, _F, C.c_double, _F, _D]),
+    "ics_op_tsne_run": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
+    "ics_op_tsne_read": (C.c_int, [_H, _F, _D, _D, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ics_op_region_stats": (C.c_int, [_I32, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _I32]),
     "ics_net_destroy": (C.c_int, [_H]),
     "ics_net_sync": (C.c_int, [_H]),

@@ -10,6 +10,7 @@
 #include "voxelise.h"
 #include "match.h"
 #include "latent.h"
+#include "tsne.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -2953,6 +2954,52 @@ int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, 
   hipStream_t st;
   ICS_TRY(op_stream(&st));
   return latent_path_op(st, za, zb, pairs, latent, alpha, steps, mode, path);
+}
+int ics_op_tsne_knn(const float* x, int n, int dim, int k, int32_t* idx, double* dist2) {
+  ICS_TRY(tsne_knn_check(x, n, dim, k, idx, dist2));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return tsne_knn_op(st, x, n, dim, k, idx, dist2);
+}
+int ics_op_tsne_affinities(const double* dist2, int n, int k, double perplexity, double* cond_p) {
+  ICS_TRY(tsne_affinities_check(dist2, n, k, perplexity, cond_p));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return tsne_affinities_op(st, dist2, n, k, perplexity, cond_p);
+}
+int ics_op_tsne_create(const ics_tsne_config* cfg, ics_tsne** out) { return tsne_create(cfg, out); }
+int ics_op_tsne_destroy(ics_tsne* h) { return tsne_destroy(h); }
+int ics_op_tsne_append(ics_tsne* h, const float* codes, int rows) { return tsne_append_host(h, codes, rows); }
+// encode -> append with nothing to the host: z_mean is the first half of each row of the zml layer's stored output,
+// read in place as ics_vae_reconstruct_resident_to_unet_atoms reads zc
+int ics_op_tsne_append_vae(ics_tsne* h, ics_net* vae, int batch) {
+  ICS_CHECK(h != nullptr, "ics_op_tsne_append_vae: null t-SNE handle");
+  ICS_TRY(require_kind(vae, 1));
+  Net& n = vae->n;
+  ICS_CHECK(n.device == tsne_device(h), "ics_op_tsne_append_vae: the engine and the t-SNE handle are on different devices");
+  ICS_CHECK((int)n.latent == tsne_dim(h), "ics_op_tsne_append_vae: latent_dim differs from the handle's dim");
+  ICS_CHECK(n.resident_batch > 0, "ics_op_tsne_append_vae: no encoder pass yet: call ics_vae_encode first");
+  ICS_CHECK(batch >= 1 && batch <= n.resident_batch, "ics_op_tsne_append_vae: batch exceeds the engine's resident batch");
+  VaeRefs r = vae_refs(n);
+  return tsne_append_device(h, r.zml->s, 2 * (size_t)n.latent, batch, n.st);
+}
+int ics_op_tsne_get_codes(ics_tsne* h, float* out, int rows) { return tsne_get_codes(h, out, rows); }
+int ics_op_tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, double seconds[3]) {
+  return tsne_prepare(h, init, init_rows, init_cols, seconds);
+}
+int ics_op_tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* indices, const double* vals,
+                          const float* init, int init_rows, int init_cols) {
+  return tsne_set_graph(h, n, indptr, indices, vals, init, init_rows, init_cols);
+}
+int ics_op_tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals, size_t capacity, size_t* nnz) {
+  return tsne_get_graph(h, indptr, indices, vals, capacity, nnz);
+}
+int ics_op_tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad, double* kl) {
+  return tsne_gradient(h, y, exaggeration, grad, kl);
+}
+int ics_op_tsne_run(ics_tsne* h, int iters, int* done) { return tsne_run(h, iters, done); }
+int ics_op_tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count) {
+  return tsne_read(h, embedding, kl, grad_norm, n_iter, count);
 }
 int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
                        int32_t* labels, int32_t* nlabels, int32_t* stats) {

@@ -229,6 +229,102 @@ static int latent_walk(void) {
   return 0;
 }
 
+/* The t-SNE map: the two ops, the handle from host codes and from a VAE engine's encoder output, every refusal (outputs
+ * untouched), and the handle still usable afterwards. */
+static int tsne_walk(ics_net* vae, ics_net* unet, const float* x, const float* cond, const float* eps, int B) {
+  enum { N = 70, D = 5, K = 16 };
+  static float codes[N * D];
+  static int32_t idx[N * K];
+  static double d2[N * K], cp[N * K], sec[3];
+  static float init[N * 2], emb[N * 2], grad[N * 2];
+  int bad = 0, done = 0, n_iter = 0, count = 0;
+  double kl = 0, gn = 0;
+  for (int i = 0; i < N * D; ++i) codes[i] = (float)((i * 37) % 101) * 0.01f;
+  for (int i = 0; i < N * 2; ++i) init[i] = 1e-4f * (float)(i % 13);
+  OK(ics_op_tsne_knn(codes, N, D, K, idx, d2));
+  OK(ics_op_tsne_knn(codes, 2, 1, 1, idx, d2));
+  for (int i = 0; i < N * K; ++i) d2[i] = 0.5 + 0.01 * i;
+  OK(ics_op_tsne_affinities(d2, N, K, 5.0, cp));
+  bad += ics_op_tsne_knn(NULL, N, D, K, idx, d2) == 0;
+  bad += ics_op_tsne_knn(codes, 1, D, 1, idx, d2) == 0;
+  bad += ics_op_tsne_knn(codes, N, 0, K, idx, d2) == 0;
+  bad += ics_op_tsne_knn(codes, N, 4097, K, idx, d2) == 0;
+  bad += ics_op_tsne_knn(codes, N, D, N, idx, d2) == 0;
+  bad += ics_op_tsne_knn(codes, N, D, 0, idx, d2) == 0;
+  codes[3] = NAN; bad += ics_op_tsne_knn(codes, N, D, K, idx, d2) == 0; codes[3] = 0.5f;
+  bad += ics_op_tsne_affinities(d2, N, K, 0.0, cp) == 0;
+  bad += ics_op_tsne_affinities(NULL, N, K, 5.0, cp) == 0;
+  bad += ics_op_tsne_affinities(d2, N, 0, 5.0, cp) == 0;
+  d2[5] = -1.0; bad += ics_op_tsne_affinities(d2, N, K, 5.0, cp) == 0; d2[5] = 1.0;
+
+  ics_tsne_config c = {D, N, 2, 5.0, 12.0, 4, 12, 2, 300, 1e-7, -1.0};
+  ics_tsne* h = NULL;
+  { ics_tsne_config b2 = c; b2.n_components = 3; bad += ics_op_tsne_create(&b2, &h) == 0; }
+  { ics_tsne_config b2 = c; b2.capacity = 1; bad += ics_op_tsne_create(&b2, &h) == 0; }
+  { ics_tsne_config b2 = c; b2.dim = 0; bad += ics_op_tsne_create(&b2, &h) == 0; }
+  { ics_tsne_config b2 = c; b2.exaggeration_iter = 13; bad += ics_op_tsne_create(&b2, &h) == 0; }
+  bad += ics_op_tsne_create(NULL, &h) == 0;
+  OK(ics_op_tsne_create(&c, &h));
+  bad += ics_op_tsne_prepare(h, init, 0, 2, sec) == 0;                 /* no codes */
+  bad += ics_op_tsne_run(h, 1, &done) == 0;                           /* no graph */
+  OK(ics_op_tsne_append(h, codes, 1));
+  bad += ics_op_tsne_prepare(h, init, 1, 2, sec) == 0;                 /* N < 2 */
+  OK(ics_op_tsne_append(h, codes + D, 3));
+  bad += ics_op_tsne_prepare(h, init, 4, 2, sec) == 0;                 /* perplexity 5 >= N = 4 */
+  OK(ics_op_tsne_append(h, codes + 4 * D, N - 4));
+  bad += ics_op_tsne_append(h, codes, 1) == 0;                        /* over capacity */
+  codes[7] = INFINITY; bad += ics_op_tsne_append(h, codes, 1) == 0; codes[7] = 0.5f;
+  bad += ics_op_tsne_prepare(h, init, N - 1, 2, sec) == 0;             /* init of the wrong shape */
+  bad += ics_op_tsne_prepare(h, init, N, 3, sec) == 0;
+  bad += ics_op_tsne_prepare(h, NULL, N, 2, sec) == 0;
+  OK(ics_op_tsne_get_codes(h, codes, N));
+  OK(ics_op_tsne_prepare(h, init, N, 2, sec));
+  OK(ics_op_tsne_prepare(h, init, N, 2, NULL));                        /* again: the state is rebuilt */
+  for (int r = 0; r < 8 && !done; ++r) OK(ics_op_tsne_run(h, 3, &done));
+  OK(ics_op_tsne_read(h, emb, &kl, &gn, &n_iter, &count));
+  OK(ics_op_tsne_read(h, NULL, NULL, NULL, NULL, NULL));
+  OK(ics_op_tsne_gradient(h, init, 12.0, grad, &kl));
+  bad += ics_op_tsne_gradient(h, init, 0.0, grad, &kl) == 0;
+  {
+    size_t nnz = 0;
+    OK(ics_op_tsne_get_graph(h, NULL, NULL, NULL, 0, &nnz));
+    int64_t* ip = (int64_t*)malloc((N + 1) * sizeof(int64_t));
+    int32_t* ix = (int32_t*)malloc((nnz + 1) * sizeof(int32_t));
+    double* vv = (double*)malloc((nnz + 1) * sizeof(double));
+    OK(ics_op_tsne_get_graph(h, ip, ix, vv, nnz, &nnz));
+    if (nnz > 0) bad += ics_op_tsne_get_graph(h, ip, ix, vv, nnz - 1, &nnz) == 0;
+    for (size_t e = 0; e < nnz; ++e) vv[e] = 1.0 / (double)(nnz ? nnz : 1);
+    OK(ics_op_tsne_set_graph(h, N, ip, ix, vv, init, N, 2));
+    OK(ics_op_tsne_run(h, 5, &done));
+    ip[0] = 1; bad += ics_op_tsne_set_graph(h, N, ip, ix, vv, init, N, 2) == 0; ip[0] = 0;
+    if (nnz > 0) { ix[0] = N; bad += ics_op_tsne_set_graph(h, N, ip, ix, vv, init, N, 2) == 0; ix[0] = 0; }
+    bad += ics_op_tsne_set_graph(h, N + 1, ip, ix, vv, init, N + 1, 2) == 0;
+    bad += ics_op_tsne_set_graph(h, N, ip, ix, vv, init, N, 1) == 0;
+    free(ip); free(ix); free(vv);
+  }
+  OK(ics_op_tsne_destroy(h));
+  OK(ics_op_tsne_destroy(NULL));
+  if (vae) {   /* encode -> append, device to device */
+    static float z[3 * 8 * 256];
+    ics_tsne_config cv = {256, 2 * 8, 2, 1.5, 12.0, 2, 4, 2, 300, 1e-7, 50.0};
+    ics_tsne* hv = NULL;
+    OK(ics_op_tsne_create(&cv, &hv));
+    OK(ics_vae_encode(vae, x, cond, eps, B, z, z + 8 * 256, z + 16 * 256));
+    OK(ics_op_tsne_append_vae(hv, vae, B));
+    OK(ics_op_tsne_append_vae(hv, vae, 1));
+    bad += ics_op_tsne_append_vae(hv, vae, B + 1) == 0;
+    bad += ics_op_tsne_append_vae(hv, unet, 1) == 0;
+    bad += ics_op_tsne_append_vae(NULL, vae, 1) == 0;
+    bad += ics_op_tsne_append_vae(hv, NULL, 1) == 0;
+    OK(ics_op_tsne_prepare(hv, init, B + 1, 2, sec));
+    OK(ics_op_tsne_run(hv, 4, &done));
+    OK(ics_op_tsne_destroy(hv));
+    { ics_tsne_config c7 = cv; c7.dim = 7; OK(ics_op_tsne_create(&c7, &hv)); bad += ics_op_tsne_append_vae(hv, vae, 1) == 0; OK(ics_op_tsne_destroy(hv)); }
+  }
+  if (bad) { fprintf(stderr, "tsne: %d invalid calls accepted\n", bad); return 1; }
+  return 0;
+}
+
 static int interp_walk(ics_net* unet, ics_net* vae, const ics_unet_config* uc, const float* x, const float* cond,
                        const float* eps, int B, int d, int C) {
   const int pairs = B, steps = 2, frames = pairs * steps;      /* max_batch B: groups of B / 2 pairs */
@@ -376,6 +472,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_train_step_resident(vae, mv));
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
+  if (B >= 2 && B <= 8 && tsne_walk(vae, unet, x, cond, eps, B)) return 1;
   if (reconstruct_refusals(unet, &vc, &uc, x, cond, eps, B)) return 1;
   if (ics_unet_train_step(unet, x, lab, B + 1, mm) == 0) { fprintf(stderr, "max_batch check missing\n"); return 1; }
   int rows = 0;
@@ -436,6 +533,7 @@ int main(void) {
                                           workspace was sized for max_batch alone, round 6) */
   if (match_walk()) return 1;
   if (latent_walk()) return 1;
+  if (tsne_walk(NULL, NULL, NULL, NULL, NULL, 0)) return 1;
   {   /* single-op entry points */
     const int B = 1, S = 8, Cin = 32, Cout = 64;
     size_t nx = (size_t)B * S * S * S * Cin, ny = (size_t)B * S * S * S * Cout, nw = (size_t)27 * Cin * Cout;

@@ -412,6 +412,63 @@ int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, con
 int ics_op_conv3d_bench(int B, int S, int Cin, int Cout, int taps, int mode, int ablate, int iters,
                         float* ms_per_launch);
 
+/* ---------------------------------------------------------------- t-SNE map of the latent space
+ * viz.tsne_latent (viz.py: sklearn.manifold.TSNE(n_components=2).fit_transform(Zs)) with the repulsion summed exactly
+ * over all pairs, which is scikit-learn's objective at angle = 0.  Results are bit-identical
+ * run to run.  Every call checks its arguments before it writes anything. */
+/* The k nearest other rows of each row of x [n][dim] (1 <= dim <= 4096, 1 <= k <= n - 1) under the squared euclidean
+ * distance, differences and squares accumulated in fp64 in dimension order: idx [n][k], dist2 [n][k], each row sorted
+ * by (distance, index).  Host pointers, synchronous. */
+int ics_op_tsne_knn(const float* x, int n, int dim, int k, int32_t* idx, double* dist2);
+/* sklearn.manifold._utils._binary_search_perplexity on float32(dist2 [n][k]): cond_p [n][k] float64 conditional
+ * probabilities (beta from 1, doubled / halved until bracketed, then bisected; at most 100 steps; stops at
+ * |H - log(perplexity)| <= 1e-5).  0 < perplexity; host pointers, synchronous. */
+int ics_op_tsne_affinities(const double* dist2, int n, int k, double perplexity, double* cond_p);
+
+typedef struct ics_tsne ics_tsne; /* opaque: codes, affinities and the state of one gradient descent */
+typedef struct ics_tsne_config {
+  int dim;                    /* width of a code, 1..4096                                              */
+  int capacity;               /* most codes the handle will hold, 2..2^20                              */
+  int n_components;           /* 2 (anything else is refused)                                          */
+  double perplexity;          /* TSNE(perplexity=30.0); must stay below the number of codes            */
+  double early_exaggeration;  /* 12.0                                                                  */
+  int exaggeration_iter;      /* 250 iterations at momentum 0.5 with P * early_exaggeration, <= max_iter */
+  int max_iter;               /* 1000                                                                  */
+  int n_iter_check;           /* 50: KL divergence and gradient norm every so many iterations          */
+  int n_iter_without_progress;/* 300                                                                   */
+  double min_grad_norm;       /* 1e-7                                                                  */
+  double learning_rate;       /* <= 0: scikit-learn's "auto", max(n / early_exaggeration / 4, 50)      */
+} ics_tsne_config;
+int ics_op_tsne_create(const ics_tsne_config* cfg, ics_tsne** out);
+int ics_op_tsne_destroy(ics_tsne* h);
+/* rows more codes [rows][dim] from the host (finite values only) */
+int ics_op_tsne_append(ics_tsne* h, const float* codes, int rows);
+/* The device-resident path: the z_mean rows of the first `batch` samples of the VAE engine's most recent encoder
+ * pass (ics_vae_encode, ics_vae_reconstruct_*) are copied device to device behind the handle's codes; nothing reaches
+ * the host.  latent_dim must equal dim.  Non-finite codes are refused by ics_op_tsne_prepare. */
+int ics_op_tsne_append_vae(ics_tsne* h, ics_net* vae, int batch);
+/* the first `rows` codes back on the host (tests) */
+int ics_op_tsne_get_codes(ics_tsne* h, float* out, int rows);
+/* Neighbour search (k = min(n - 1, int(3 perplexity + 1))), affinities and P = (C + C^T) / sum in CSR form over the
+ * codes appended so far, then the embedding is set to init [init_rows][init_cols] (init_rows = the number of codes,
+ * init_cols = 2, finite) and the descent is rewound to iteration 0.  seconds (optional): wall time of the three stages.
+ * Refused: fewer than 2 codes, perplexity >= the number of codes, non-finite codes, an init of another shape. */
+int ics_op_tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, double seconds[3]);
+/* The same with P given: CSR over n <= capacity points, indptr [n + 1], column indices in [0, n), values >= 0. */
+int ics_op_tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* indices, const double* vals,
+                          const float* init, int init_rows, int init_cols);
+/* P of the handle: indptr [n + 1]; indices / vals hold `capacity` entries (NULL, 0: only *nnz is returned). */
+int ics_op_tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals, size_t capacity, size_t* nnz);
+/* sklearn.manifold._t_sne._kl_divergence_bh(angle=0) of the embedding y [n][2] on float32(P * exaggeration):
+ * grad [n][2] and the KL divergence.  Leaves the descent's state alone. */
+int ics_op_tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad, double* kl);
+/* Up to `iters` more iterations of sklearn.manifold._t_sne._gradient_descent under TSNE._tsne's schedule;
+ * *done (optional) = 1 once max_iter is reached or one of the two stopping rules fired.  Synchronous. */
+int ics_op_tsne_run(ics_tsne* h, int iters, int* done);
+/* embedding [n][2] (optional), the KL divergence and gradient norm of the latest check, TSNE.n_iter_ (the index of
+ * the last iteration run, -1 before the first) and the number of points; every pointer is optional. */
+int ics_op_tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count);
+
 #ifdef __cplusplus
 }
 #endif
