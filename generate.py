@@ -5,12 +5,17 @@ components + majority vote + centroids -- one device-resident chain per batch (g
 ics_vae_decode_to_unet_atoms) -- and watershed_clustering's convexity test + recursive marker watershed for the
 non-convex components (icsg3d_amd/watershed.py; the scikit-image routines behind it are restated, parity unpinned).
 Written under output/results/<formula>__v=<var>/: densities, species, binary masks, voxel parameters and per-sample
-atom coordinates (.npy).  The steps after that in the reference (CIF writing with pymatgen, CGCNN property
-prediction, generate.py:247-300) are out of scope.
+atom coordinates (.npy).  Then the reference's structure stage (generate.py:250-318, utils.py:225-239) without pymatgen:
+every batch is screened in one device call (icsg3d_amd.structures.screen -> ics_op_structure_screen: the periodic
+structure in the --alpha/--beta/--gamma cell, exact shortest periodic distances, is_valid's 0.5 A rule), and per valid
+sample cifs/<formula_count>.cif, a row of results.csv (sorted by id) and a results.json record are written; a sample with
+no atoms, a species outside 1..94 or no usable cell is counted invalid, not raised.  pymatgen's semantics are restated,
+parity with it is unpinned.  CGCNN property prediction and the oxidation-state guess ("charge
+balanced") stay out of scope.
 
 Flags: the reference's, same names and defaults (generate.py:52-102): --name --base --batch_size --nsamples --var
---eps_frac --clus_iters --alpha --beta --gamma --target --ncond --d.  --alpha/--beta/--gamma only feed
-to_pymatgen_structure (not built): accepted, recorded in run.json; --clus_iters is watershed_clustering's max_iters.
+--eps_frac --clus_iters --alpha --beta --gamma --target --ncond --d.  --alpha/--beta/--gamma are the angles of the cell
+the structures are screened and written in (to_pymatgen_structure); --clus_iters is watershed_clustering's max_iters.
 --eps_frac goes where the reference puts it: the shift of the atom coordinates (generate.py:237-241); like the
 reference, to_lattice_params / to_voxel_params keep their default 0.25 (generate.py:211,214).
 Added: --channels (the reference hard-codes 4) and --synthetic (a Gaussian-blob base compound, condition bin
@@ -22,6 +27,7 @@ import os
 
 import numpy as np
 
+from icsg3d_amd.structures import ResultsWriter
 from icsg3d_amd.synthetic import synthetic_batch
 from icsg3d_amd.utils import to_lattice_params_from_minmax, to_voxel_params
 from icsg3d_amd.unet.unet import AtomUnet
@@ -41,6 +47,12 @@ def base_compound_from_csv(csv_path, base, target, ncond):
         task_id = df[df["pretty_formula"] == base]["task_id"].values[0]
     row = df[df["task_id"] == task_id]
     return task_id, formula, float(row[target].values[0]), int(row["interval"].values[0])
+
+
+def training_formulas(csv_path):
+    """generate.py:139: the pretty_formula column of the dataset's CSV (the `training` flag of a generated formula)."""
+    import pandas as pd
+    return set(pd.read_csv(csv_path)["pretty_formula"].values)
 
 
 if __name__ == "__main__":
@@ -95,6 +107,9 @@ if __name__ == "__main__":
 
     z_mu_base, z_logvar_base, z_base = vae.encoder.predict([M_base, cond])
     n_atoms = []
+    training_names = set() if a.synthetic else training_formulas(os.path.join("data", mode, mode + ".csv"))
+    results = ResultsWriter(out_dir, a.alpha, a.beta, a.gamma, training_names=training_names,
+                            target_value=base_target_value)
     for batch in range(int(a.nsamples / bs)):
         print("Batch", batch)
         z_samples = np.random.normal(z_mu_base, a.var, size=(bs, vae.latent_dim))
@@ -109,6 +124,7 @@ if __name__ == "__main__":
                                        split=True, max_iters=a.clus_iters)
         l_prime = to_lattice_params_from_minmax(out["coord_minmax"], d=d)
         dv_pred = to_voxel_params(l_prime, d=d)
+        batch_atoms = [None] * bs
         for i in range(bs):
             k = batch * bs + i
             if out["failed"][i]:
@@ -124,4 +140,9 @@ if __name__ == "__main__":
             np.save(os.path.join(out_dir, "binary", "%d.npy" % k), out["mask"][i])
             np.save(os.path.join(out_dir, "voxel_params", "%d.npy" % k), dv_pred[i])
             np.save(os.path.join(out_dir, "coords", "%d.npy" % k), coords)
+            batch_atoms[i] = (species_sample, mu)
+        # generate.py:250-318: structure, formula, is_valid, CIF and results row -- the batch screened in one device call
+        results.add_batch(range(batch * bs, batch * bs + bs), l_prime, batch_atoms)
+    counts = results.finish()
+    print("structures: generated %(generated)d / failed %(failed)d / invalid %(invalid)d / written %(written)d" % counts)
     print("wrote", out_dir, "- atoms per sample: mean %.1f" % (np.mean(n_atoms) if n_atoms else 0.0))

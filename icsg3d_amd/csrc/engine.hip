@@ -9,6 +9,7 @@
 #include "segment.h"
 #include "voxelise.h"
 #include "match.h"
+#include "structure.h"
 #include "latent.h"
 #include "tsne.h"
 #include "../../include/icsg3d.h"
@@ -2946,6 +2947,19 @@ int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, con
   hipStream_t st;
   ICS_TRY(op_stream(&st));
   return match_emd_op(st, a, a_off, b, b_off, batch, emd, match);
+}
+int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, const double* xyz, const double* abc,
+                            const double* angles, int batch, double tol, double* lattice, double* volume, double* frac,
+                            double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid, int32_t* reason,
+                            double* nearest, int32_t* hist) {
+  ICS_TRY(structure_screen_check(offsets, species, xyz, abc, angles, batch, tol));
+  ICS_CHECK(lattice && volume && min_dist && min_pair && n_close && valid && reason && hist,
+            "ics_op_structure_screen: null output");
+  ICS_CHECK((frac && nearest) || offsets[batch] == 0, "ics_op_structure_screen: null frac or nearest");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return structure_screen_op(st, offsets, species, xyz, abc, angles, batch, tol, lattice, volume, frac, min_dist, min_pair,
+                             n_close, valid, reason, nearest, hist);
 }
 int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps, int mode,
                        float* path) {

@@ -159,6 +159,73 @@ static int match_walk(void) {
   return 0;
 }
 
+/* Batched structure screening: a ragged batch with empty, one-wave and whole-workgroup structures, more atoms than one
+ * chunk holds, and every refused argument, after which the op still works. */
+static int structure_walk(void) {
+  enum { NB = 5, NA = 2 + 0 + 1 + 70 + 40 };
+  int32_t off[NB + 1] = {0, 2, 2, 3, 73, 113}, sp[NA];
+  double xyz[NA * 3], abc[NB * 3], ang[NB * 3];
+  for (int i = 0; i < NA; ++i) { sp[i] = i % 97; xyz[3 * i] = 0.31 * i; xyz[3 * i + 1] = 7.0 - 0.17 * i; xyz[3 * i + 2] = 0.05 * i; }
+  for (int i = 0; i < NB; ++i) {
+    abc[3 * i] = 4.0 + i; abc[3 * i + 1] = 5.0; abc[3 * i + 2] = 6.5;
+    ang[3 * i] = 90.0; ang[3 * i + 1] = i % 2 ? 100.0 : 90.0; ang[3 * i + 2] = i % 2 ? 120.0 : 90.0;
+  }
+  double lat[NB * 9], vol[NB], frac[NA * 3], dmin[NB], nearest[NA];
+  int32_t pair[NB * 2], nclose[NB], valid[NB], reason[NB], hist[NB * 95];
+#define SCREEN(o, s, x, l, g, n, t) ics_op_structure_screen(o, s, x, l, g, n, t, lat, vol, frac, dmin, pair, nclose, valid, reason, nearest, hist)
+  OK(SCREEN(off, sp, xyz, abc, ang, NB, 0.5));
+  OK(SCREEN(off, sp, xyz, abc, ang, 2, 0.0));
+  {   /* 600 structures of 2048 atoms: more than one chunk's atom budget */
+    const int ns = 600, np = 2048;
+    double* bx = (double*)calloc((size_t)ns * np * 3, sizeof(double));
+    int32_t* bs = (int32_t*)calloc((size_t)ns * np, sizeof(int32_t));
+    int32_t* bo = (int32_t*)malloc((ns + 1) * sizeof(int32_t));
+    double* bl = (double*)malloc((size_t)ns * 3 * sizeof(double));
+    double* bg = (double*)malloc((size_t)ns * 3 * sizeof(double));
+    double* o_lat = (double*)malloc((size_t)ns * 9 * 8);
+    double* o_vol = (double*)malloc((size_t)ns * 8);
+    double* o_frac = (double*)malloc((size_t)ns * np * 24);
+    double* o_dmin = (double*)malloc((size_t)ns * 8);
+    double* o_near = (double*)malloc((size_t)ns * np * 8);
+    int32_t* o_int = (int32_t*)malloc((size_t)ns * (2 + 1 + 1 + 1 + 95) * 4);
+    for (int k = 0; k <= ns; ++k) bo[k] = k * np;
+    for (int k = 0; k < 3 * ns; ++k) { bl[k] = 9.0; bg[k] = 90.0; }
+    OK(ics_op_structure_screen(bo, bs, bx, bl, bg, ns, 0.5, o_lat, o_vol, o_frac, o_dmin, o_int, o_int + 2 * ns, o_int + 3 * ns,
+                               o_int + 4 * ns, o_near, o_int + 5 * ns));
+    bo[1] = np + 1;   /* a structure above the limit */
+    if (ics_op_structure_screen(bo, bs, bx, bl, bg, 1, 0.5, o_lat, o_vol, o_frac, o_dmin, o_int, o_int + 2 * ns, o_int + 3 * ns,
+                                o_int + 4 * ns, o_near, o_int + 5 * ns) == 0) {
+      fprintf(stderr, "structure: 2049 atoms accepted\n"); return 1;
+    }
+    free(bx); free(bs); free(bo); free(bl); free(bg); free(o_lat); free(o_vol); free(o_frac); free(o_dmin); free(o_near); free(o_int);
+  }
+  int bad = 0;
+  bad += SCREEN(off, sp, xyz, abc, ang, 0, 0.5) == 0;
+  bad += SCREEN(NULL, sp, xyz, abc, ang, NB, 0.5) == 0;
+  bad += SCREEN(off, NULL, xyz, abc, ang, NB, 0.5) == 0;
+  bad += SCREEN(off, sp, NULL, abc, ang, NB, 0.5) == 0;
+  bad += SCREEN(off, sp, xyz, NULL, ang, NB, 0.5) == 0;
+  bad += SCREEN(off, sp, xyz, abc, NULL, NB, 0.5) == 0;
+  bad += SCREEN(off, sp, xyz, abc, ang, NB, NAN) == 0;
+  bad += SCREEN(off, sp, xyz, abc, ang, NB, -0.5) == 0;
+  bad += ics_op_structure_screen(off, sp, xyz, abc, ang, NB, 0.5, lat, vol, frac, NULL, pair, nclose, valid, reason, nearest, hist) == 0;
+  off[0] = 1; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; off[0] = 0;
+  off[2] = 1; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; off[2] = 2;
+  xyz[7] = NAN; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; xyz[7] = 0.5;
+  xyz[7] = 1e200; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; xyz[7] = 0.5;
+  abc[4] = 0.0; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; abc[4] = 5.0;
+  abc[4] = INFINITY; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; abc[4] = 5.0;
+  abc[3] = 0.01; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; abc[3] = 5.0;                 /* image range */
+  ang[5] = 180.0; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; ang[5] = 120.0;
+  ang[3] = 60.0; ang[4] = 60.0; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; ang[3] = 90.0; ang[4] = 100.0;   /* no cell */
+  ang[5] = NAN; bad += SCREEN(off, sp, xyz, abc, ang, NB, 0.5) == 0; ang[5] = 120.0;
+  if (bad) { fprintf(stderr, "structure: %d invalid argument sets accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "structure: no error message\n"); return 1; }
+  OK(SCREEN(off, sp, xyz, abc, ang, NB, 0.5));     /* still usable */
+#undef SCREEN
+  return 0;
+}
+
 /* The reconstruction chain's refusals: no resident batch, a U-Net of other channels, a resident batch above the U-Net's
  * max_batch. */
 static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const ics_unet_config* uc, const float* x,
@@ -532,6 +599,7 @@ int main(void) {
                                           BatchNorm-backward blocks than 5 do (the engine's capacity checks fire if a
                                           workspace was sized for max_batch alone, round 6) */
   if (match_walk()) return 1;
+  if (structure_walk()) return 1;
   if (latent_walk()) return 1;
   if (tsne_walk(NULL, NULL, NULL, NULL, NULL, 0)) return 1;
   {   /* single-op entry points */

@@ -1,0 +1,339 @@
+"""The last stage of the reference's generate.py (generate.py:250-318, utils.py:225-239): the periodic
+structure of every generated sample, its formula, the validity screen and the CIF file.
+
+The reference builds a pymatgen Structure per sample; pymatgen is not a dependency here.  Its semantics are restated
+(parity with pymatgen is UNPINNED: no fixture can be recorded from it -- DESIGN section 16):
+
+- screen            to_pymatgen_structure + structure.is_valid() for a whole batch in one device call
+                    (ics_op_structure_screen: exact fp64 shortest periodic distances over all lattice translations).
+                    No host fallback: a missing library is an error.
+- formula, reduced_formula, anonymized_formula, average_electroneg
+                    Composition's, from the species histogram the op returns.
+- write_cif / read_cif
+                    a P1 CIF 1.1 file as CifWriter lays it out, and a reader for that subset.
+- numbered          the duplicate-formula numbering of generate.py:257-260.
+- ResultsWriter     generate.py:250-318 around them: per batch one screen, then per valid sample the CIF, the results
+                    row and the results.json record; results.csv at the end.
+"""
+from __future__ import annotations
+
+import csv
+import json
+import math
+import os
+import string
+from functools import reduce
+
+import numpy as np
+
+from . import _lib as L
+
+MAX_ATOMS = 2048        # atoms per structure ics_op_structure_screen accepts
+HIST = 95               # histogram row: atomic numbers 0..94
+MAX_IMAGE = 32          # lattice translations per axis its image search covers
+REASON_CLOSE, REASON_SPECIES, REASON_EMPTY = 1, 2, 4     # the op's reason bits
+REASON_CELL = 8         # set here: the sample's own cell lengths or coordinates are not finite and positive
+REASONS = {REASON_CLOSE: "atoms closer than tol", REASON_SPECIES: "species outside 1..94", REASON_EMPTY: "no atoms",
+           REASON_CELL: "no cell"}
+
+# Element symbols by atomic number 1..94 and Pauling electronegativities (public tables; None = no value).
+SYMBOLS = ("X H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
+           "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir "
+           "Pt Au Hg Tl Pb Bi Po At Rn Fr Ra Ac Th Pa U Np Pu").split()
+ELECTRONEG = (None, 2.20, None, 0.98, 1.57, 2.04, 2.55, 3.04, 3.44, 3.98, None, 0.93, 1.31, 1.61, 1.90, 2.19, 2.58, 3.16,
+              None, 0.82, 1.00, 1.36, 1.54, 1.63, 1.66, 1.55, 1.83, 1.88, 1.91, 1.90, 1.65, 1.81, 2.01, 2.18, 2.55, 2.96,
+              3.00, 0.82, 0.95, 1.22, 1.33, 1.60, 2.16, 1.90, 2.20, 2.28, 2.20, 1.93, 1.69, 1.78, 1.96, 2.05, 2.10, 2.66,
+              2.60, 0.79, 0.89, 1.10, 1.12, 1.13, 1.14, 1.13, 1.17, 1.20, 1.20, 1.10, 1.22, 1.23, 1.24, 1.25, 1.10, 1.27,
+              1.30, 1.50, 2.36, 1.90, 2.20, 2.20, 2.28, 2.54, 2.00, 1.62, 2.33, 2.02, 2.00, 2.20, 2.20, 0.70, 0.90, 1.10,
+              1.30, 1.50, 1.38, 1.36, 1.28)
+assert len(SYMBOLS) == HIST and len(ELECTRONEG) == HIST
+
+
+# ---------------------------------------------------------------- composition
+def _ordered(hist):
+    """[(Z, amount)] of the elements present, ordered as Composition.formula: by electronegativity, elements without a
+    value last, ties by Z."""
+    hist = np.asarray(hist).reshape(-1)
+    zs = [z for z in range(1, min(len(hist), HIST)) if hist[z] > 0]
+    return [(z, int(hist[z])) for z in sorted(zs, key=lambda z: (ELECTRONEG[z] is None, ELECTRONEG[z] or 0.0, z))]
+
+
+def formula(hist):
+    """Composition.formula: "La1 Fe1 O3"."""
+    return " ".join("%s%d" % (SYMBOLS[z], n) for z, n in _ordered(hist))
+
+
+def reduced_formula(hist):
+    """The amounts divided by their gcd, 1s dropped: "LaFeO3"."""
+    el = _ordered(hist)
+    if not el:
+        return ""
+    g = reduce(math.gcd, [n for _, n in el])
+    return "".join(SYMBOLS[z] + (str(n // g) if n // g != 1 else "") for z, n in el)
+
+
+def anonymized_formula(hist):
+    """Composition.anonymized_formula: reduced amounts ascending, letters A, B, C...: "ABC3"."""
+    el = _ordered(hist)
+    if not el:
+        return ""
+    g = reduce(math.gcd, [n for _, n in el])
+    return "".join(c + (str(n) if n != 1 else "") for c, n in zip(string.ascii_uppercase, sorted(n // g for _, n in el)))
+
+
+def average_electroneg(hist):
+    """Composition.average_electroneg: the amount-weighted mean; NaN when an element has no value or there is no atom."""
+    el = _ordered(hist)
+    if not el or any(ELECTRONEG[z] is None for z, _ in el):
+        return float("nan")
+    return sum(ELECTRONEG[z] * n for z, n in el) / sum(n for _, n in el)
+
+
+def numbered(name, seen):
+    """generate.py:257-260: name + "_" + str(count) when `name` occurs `count` > 0 times in `seen`."""
+    c = list(seen).count(name)
+    return name + "_" + str(c) if c else name
+
+
+# ---------------------------------------------------------------- the device screen
+def cell(abc, angles):
+    """Lattice.from_parameters as ics_op_structure_screen builds it: (lattice (3, 3) with rows va, vb, vc, volume, norms
+    of the columns of its inverse).  Sine and cosine of exactly 90 degrees are 1 and 0.  ValueError for angles that
+    make no cell."""
+    a, b, c = (float(v) for v in abc)
+    ang = [float(t) for t in angles]
+    if not all(0.0 < t < 180.0 for t in ang):
+        raise ValueError("angles %s make no cell" % (ang,))
+    sn = [1.0 if t == 90.0 else math.sin(math.radians(t)) for t in ang]
+    cs = [0.0 if t == 90.0 else math.cos(math.radians(t)) for t in ang]
+    val = (cs[0] * cs[1] - cs[2]) / (sn[0] * sn[1])
+    if not abs(val) < 1.0:
+        raise ValueError("angles %s make no cell" % (ang,))
+    gs = math.acos(val)
+    M = np.array([[a * sn[1], 0.0, a * cs[1]], [-b * sn[0] * math.cos(gs), b * sn[0] * math.sin(gs), b * cs[0]],
+                  [0.0, 0.0, c]])
+    vol = float(np.dot(M[0], np.cross(M[1], M[2])))
+    if not vol > 0.0:
+        raise ValueError("angles %s make no cell" % (ang,))
+    g = np.array([np.linalg.norm(np.cross(M[1], M[2])), np.linalg.norm(np.cross(M[2], M[0])),
+                  np.linalg.norm(np.cross(M[0], M[1]))]) / vol
+    return M, vol, g
+
+
+def screen_packed(offsets, species, xyz, abc, angles, tol=0.5):
+    """ics_op_structure_screen on packed arrays: offsets (B + 1,), species (N,), xyz (N, 3), abc and angles (B, 3).
+    Returns the op's outputs as a dict of arrays."""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    B = len(offsets) - 1
+    if B < 1:
+        raise ValueError("screen needs at least one structure")
+    species = np.ascontiguousarray(species, np.int32).reshape(-1)
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    abc = np.ascontiguousarray(abc, np.float64).reshape(-1, 3)
+    angles = np.ascontiguousarray(angles, np.float64).reshape(-1, 3)
+    N = len(species)
+    if len(xyz) != N or len(abc) != B or len(angles) != B or (B >= 1 and int(offsets[-1]) != N):
+        raise ValueError("screen: array lengths do not agree (atoms %d / %d / %d, structures %d / %d / %d)"
+                         % (N, len(xyz), int(offsets[-1]), B, len(abc), len(angles)))
+    out = {"lattice": np.zeros((B, 3, 3)), "volume": np.zeros(B), "frac": np.zeros((max(N, 1), 3)),
+           "min_dist": np.zeros(B), "min_pair": np.zeros((B, 2), np.int32), "n_close": np.zeros(B, np.int32),
+           "valid": np.zeros(B, np.int32), "reason": np.zeros(B, np.int32), "nearest": np.zeros(max(N, 1)),
+           "hist": np.zeros((B, HIST), np.int32)}
+    L.check(L.load().ics_op_structure_screen(
+        L.i32ptr(offsets), L.i32ptr(species), L.f64ptr(xyz), L.f64ptr(abc), L.f64ptr(angles), B, float(tol),
+        L.f64ptr(out["lattice"]), L.f64ptr(out["volume"]), L.f64ptr(out["frac"]), L.f64ptr(out["min_dist"]),
+        L.i32ptr(out["min_pair"]), L.i32ptr(out["n_close"]), L.i32ptr(out["valid"]), L.i32ptr(out["reason"]),
+        L.f64ptr(out["nearest"]), L.i32ptr(out["hist"])))
+    out["frac"], out["nearest"] = out["frac"][:N], out["nearest"][:N]
+    return out
+
+
+def screen(lattice_params, atoms, alpha=90, beta=90, gamma=90, tol=0.5):
+    """to_pymatgen_structure(l_prime[b], coords, alpha, beta, gamma) and is_valid(tol) for every sample of a batch.
+    lattice_params (B, 3); atoms[b] = (species (n,), xyz (n, 3) in Angstrom) or None for a sample to leave out (a failed
+    one).  One device call for the batch.  Returns a list of B entries: None where atoms[b] is None, else a dict
+    (species, frac (n, 3), abc, angles, lattice (3, 3), volume, min_dist, min_pair, n_close, nearest (n,), hist (95,),
+    valid, reason, formula).  A sample whose own numbers make no cell (non-finite or non-positive lengths, non-finite
+    coordinates, more than 2048 atoms) is returned invalid with reason REASON_CELL instead of failing the batch; angles
+    that make no cell are the caller's and raise."""
+    lp = np.asarray(lattice_params, np.float64).reshape(-1, 3)
+    if len(lp) != len(atoms):
+        raise ValueError("screen: %d lattice parameter rows for %d samples" % (len(lp), len(atoms)))
+    angles = np.array([alpha, beta, gamma], np.float64)
+    cell(np.ones(3), angles)      # raises for angles that make no cell
+    res = [None] * len(atoms)
+    keep, sp_l, xyz_l = [], [], []
+    for b, at in enumerate(atoms):
+        if at is None:
+            continue
+        sp = np.asarray(at[0], np.int64).reshape(-1)
+        xyz = np.asarray(at[1], np.float64).reshape(len(sp), 3)
+        ok = (np.all(np.isfinite(lp[b])) and np.all(lp[b] >= 1e-6) and np.all(lp[b] <= 1e6) and np.all(np.isfinite(xyz))
+              and np.all(np.abs(xyz) <= 1e12) and len(sp) <= MAX_ATOMS and np.all(np.abs(sp) < 2 ** 31))
+        # the op's image search covers 32 translations per axis (it refuses the whole call above that)
+        ok = ok and 0.5 * lp[b].sum() * cell(lp[b], angles)[2].max() + 0.5 <= MAX_IMAGE - 0.1
+        if not ok:
+            hist = np.bincount(sp[(sp >= 1) & (sp < HIST)], minlength=HIST).astype(np.int32)
+            res[b] = {"species": sp.astype(np.int32), "frac": np.full((len(sp), 3), np.nan), "abc": lp[b].copy(),
+                      "angles": angles.copy(), "lattice": np.full((3, 3), np.nan), "volume": float("nan"),
+                      "min_dist": float("nan"), "min_pair": (-1, -1), "n_close": 0, "nearest": np.full(len(sp), np.nan),
+                      "hist": hist, "valid": False, "reason": REASON_CELL, "formula": formula(hist)}
+            continue
+        keep.append(b)
+        sp_l.append(sp.astype(np.int32))
+        xyz_l.append(xyz)
+    if not keep:
+        return res
+    off = np.zeros(len(keep) + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in sp_l])
+    o = screen_packed(off, np.concatenate(sp_l), np.concatenate(xyz_l), lp[keep], np.tile(angles, (len(keep), 1)), tol)
+    for k, b in enumerate(keep):
+        a0, a1 = int(off[k]), int(off[k + 1])
+        res[b] = {"species": sp_l[k], "frac": o["frac"][a0:a1].copy(), "abc": lp[b].copy(), "angles": angles.copy(),
+                  "lattice": o["lattice"][k].copy(), "volume": float(o["volume"][k]), "min_dist": float(o["min_dist"][k]),
+                  "min_pair": (int(o["min_pair"][k, 0]), int(o["min_pair"][k, 1])), "n_close": int(o["n_close"][k]),
+                  "nearest": o["nearest"][a0:a1].copy(), "hist": o["hist"][k].copy(), "valid": bool(o["valid"][k]),
+                  "reason": int(o["reason"][k]), "formula": formula(o["hist"][k])}
+    return res
+
+
+def reason_text(reason):
+    return ", ".join(t for bit, t in REASONS.items() if reason & bit) or "valid"
+
+
+# ---------------------------------------------------------------- CIF
+def write_cif(path, abc, angles, species, frac, volume=None):
+    """A P1 CIF 1.1 file of one structure: cell lengths (Angstrom) and angles (degrees), atomic numbers, fractional
+    coordinates (written as they are, 8 decimals)."""
+    species = np.asarray(species, np.int64).reshape(-1)
+    frac = np.asarray(frac, np.float64).reshape(len(species), 3)
+    hist = np.bincount(species, minlength=HIST)
+    if len(hist) > HIST or (len(species) and species.min() < 1):
+        raise ValueError("write_cif: species outside 1..94")
+    if volume is None:
+        ca, cb, cg = (0.0 if t == 90 else math.cos(math.radians(t)) for t in angles)
+        volume = abc[0] * abc[1] * abc[2] * math.sqrt(max(0.0, 1 - ca * ca - cb * cb - cg * cg + 2 * ca * cb * cg))
+    f = formula(hist)
+    lines = ["data_" + reduced_formula(hist), "_symmetry_space_group_name_H-M   'P 1'"]
+    lines += ["_cell_length_%s   %.8f" % (n, v) for n, v in zip("abc", abc)]
+    lines += ["_cell_angle_%s   %.8f" % (n, v) for n, v in zip(("alpha", "beta", "gamma"), angles)]
+    lines += ["_symmetry_Int_Tables_number   1", "_chemical_formula_structural   " + reduced_formula(hist),
+              "_chemical_formula_sum   '%s'" % f, "_cell_volume   %.8f" % volume, "_cell_formula_units_Z   %d"
+              % (reduce(math.gcd, [int(n) for n in hist if n]) if len(species) else 0),
+              "loop_", " _symmetry_equiv_pos_site_id", " _symmetry_equiv_pos_as_xyz", "  1  'x, y, z'",
+              "loop_", " _atom_site_type_symbol", " _atom_site_label", " _atom_site_symmetry_multiplicity",
+              " _atom_site_fract_x", " _atom_site_fract_y", " _atom_site_fract_z", " _atom_site_occupancy"]
+    for k, (z, p) in enumerate(zip(species, frac)):
+        lines.append("  %s  %s%d  1  %.8f  %.8f  %.8f  1" % (SYMBOLS[z], SYMBOLS[z], k, p[0], p[1], p[2]))
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_cif(path):
+    """The subset write_cif writes: dict(name, abc (3,), angles (3,), volume, formula_sum, species (n,) atomic numbers,
+    labels [n], frac (n, 3))."""
+    tags, loops, cols, rows = {}, [], None, None
+    for raw in open(path):
+        ln = raw.strip()
+        if not ln or ln.startswith("#"):
+            continue
+        if ln.startswith("data_"):
+            tags["name"] = ln[5:]
+        elif ln == "loop_":
+            cols, rows = [], []
+            loops.append((cols, rows))
+        elif ln.startswith("_"):
+            if cols is not None and not rows:
+                if len(ln.split()) == 1:
+                    cols.append(ln)
+                    continue
+            cols = None
+            k, _, v = ln.partition(" ")
+            tags[k] = v.strip().strip("'")
+        elif cols is not None:
+            rows.append(ln)
+    site = [(c, r) for c, r in loops if "_atom_site_fract_x" in c]
+    if not site:
+        raise ValueError("%s: no atom-site loop" % path)
+    c, r = site[0]
+    rec = [x.split() for x in r]
+    sym = [x[c.index("_atom_site_type_symbol")] for x in rec]
+    return {"name": tags.get("name", ""),
+            "abc": np.array([float(tags["_cell_length_" + n]) for n in "abc"]),
+            "angles": np.array([float(tags["_cell_angle_" + n]) for n in ("alpha", "beta", "gamma")]),
+            "volume": float(tags["_cell_volume"]), "formula_sum": tags.get("_chemical_formula_sum", ""),
+            "species": np.array([SYMBOLS.index(s) for s in sym], np.int32),
+            "labels": [x[c.index("_atom_site_label")] for x in rec],
+            "frac": np.array([[float(x[c.index("_atom_site_fract_" + a)]) for a in "xyz"] for x in rec],
+                             np.float64).reshape(len(rec), 3)}
+
+
+# ---------------------------------------------------------------- generate.py:250-318
+class ResultsWriter:
+    """The tail of generate.py's sample loop.  add_batch screens one batch on the device and, per sample in order:
+    builds the formula, numbers a formula seen before (formula_count), SKIPS an invalid structure, writes
+    cifs/<formula_count>.cif, appends the row and its results.json record.  finish() writes results.csv sorted by id (the
+    reference sorts by the CGCNN target, which is not predicted here) and returns the counts."""
+    COLUMNS = ("formula", "id", "training", "target", "anon_formula", "electronegativity", "cif", "sample", "natoms",
+               "min_distance", "volume")
+
+    def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None):
+        self.out_dir, self.angles, self.tol = out_dir, (alpha, beta, gamma), tol
+        self.training_names, self.target_value = set(training_names), target_value
+        self.formulae, self.rows = [], []
+        self.counts = {"generated": 0, "failed": 0, "invalid": 0, "written": 0}
+        self.invalid_reasons = {}
+        os.makedirs(os.path.join(out_dir, "cifs"), exist_ok=True)
+        open(os.path.join(out_dir, "results.json"), "w").close()      # the records of THIS run (appended per row below)
+
+    def add_batch(self, ks, lattice_params, atoms):
+        """ks: the sample indices; atoms[b] = (species, xyz in Angstrom), or None for a failed sample."""
+        res = screen(lattice_params, atoms, *self.angles, tol=self.tol)
+        for k, r in zip(ks, res):
+            self.counts["generated"] += 1
+            if r is None:
+                self.counts["failed"] += 1
+                continue
+            if not r["valid"]:
+                self.counts["invalid"] += 1
+                self.invalid_reasons[int(k)] = reason_text(r["reason"])
+                continue
+            f = r["formula"]
+            fid = numbered(f, self.formulae)
+            path = os.path.join(self.out_dir, "cifs", fid + ".cif")
+            write_cif(path, r["abc"], r["angles"], r["species"], r["frac"], r["volume"])
+            rd = {"formula": f, "id": fid, "training": int(reduced_formula(r["hist"]) in self.training_names),
+                  "target": self.target_value, "anon_formula": anonymized_formula(r["hist"]),
+                  "electronegativity": average_electroneg(r["hist"]), "cif": path, "sample": int(k),
+                  "natoms": int(len(r["species"])), "min_distance": r["min_dist"], "volume": r["volume"]}
+            self.rows.append(rd)
+            self.formulae.append(f)
+            self.counts["written"] += 1
+            with open(os.path.join(self.out_dir, "results.json"), "a+") as wf:      # generate.py:313-314
+                json.dump(str(rd), wf)
+        return res
+
+    def finish(self):
+        order = sorted(range(len(self.rows)), key=lambda i: self.rows[i]["id"])
+        with open(os.path.join(self.out_dir, "results.csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(("",) + self.COLUMNS)                          # the index column DataFrame.to_csv writes
+            for i in order:
+                w.writerow([i] + ["" if self.rows[i][c] is None else repr(self.rows[i][c]) if isinstance(self.rows[i][c], float)
+                                  else self.rows[i][c] for c in self.COLUMNS])
+        return dict(self.counts)
+
+
+def read_results_csv(path):
+    """results.csv back as a list of dicts (numbers converted)."""
+    out = []
+    with open(path, newline="") as fh:
+        for row in csv.DictReader(fh):
+            row.pop("", None)
+            for c in ("training", "sample", "natoms"):
+                row[c] = int(row[c])
+            for c in ("electronegativity", "min_distance", "volume"):
+                row[c] = float(row[c])
+            row["target"] = float(row["target"]) if row["target"] != "" else None
+            out.append(row)
+    return out

@@ -270,6 +270,35 @@ int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, floa
 int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
                      double* emd, int32_t* match);
 
+/* ---------------------------------------------------------------- structures (generate.py's CIF stage)
+ * to_pymatgen_structure (utils.py:225-239) and structure.is_valid() (generate.py:251-263) for a ragged batch: structure
+ * b holds atoms offsets[b] .. offsets[b+1]) with species (atomic numbers) and cartesian xyz (float64, Angstrom, the
+ * orthogonal frame in which generate.py computes mu), lattice lengths abc [batch][3] and angles [batch][3] in degrees.
+ *   lattice [batch][9]  rows va = [a sin(beta), 0, a cos(beta)], vb = [-b sin(alpha) cos(g), b sin(alpha) sin(g),
+ *                       b cos(alpha)], vc = [0, 0, c], g = acos((cos(alpha) cos(beta) - cos(gamma)) / (sin(alpha)
+ *                       sin(beta))) (Lattice.from_parameters; sine and cosine of exactly 90 degrees are 1 and 0)
+ *   volume  [batch]     its determinant
+ *   frac    [atoms][3]  xyz / abc: the atoms are placed in the 90-degree lattice and keep their fractional coordinates
+ *                       when the lattice is swapped (utils.py:231-238); not wrapped into the cell
+ *   min_dist [batch], min_pair [batch][2]  the smallest shortest-periodic distance over pairs i < j and that pair, ties
+ *                       to the lexicographically smallest pair; +inf and (-1, -1) below two atoms
+ *   n_close [batch]     pairs with distance <= tol
+ *   valid, reason [batch]  valid = 1 where reason = 0; reason bits: 1 a pair at or under tol (is_valid's rule; a one-site
+ *                       structure passes), 2 a species outside 1..94, 4 no atoms
+ *   nearest [atoms]     each atom's distance to its nearest other atom (+inf for a lone atom)
+ *   hist    [batch][95] atoms per atomic number (species outside 1..94 are not counted)
+ * The shortest periodic distance is the exact minimum over ALL lattice translations of the wrapped fractional
+ * difference (the image range per axis is derived from the cell), in fp64; results are the same bits run to run.
+ * Refused, naming the structure, with nothing written: batch < 1, a null argument, a non-finite or negative tol, offsets
+ * that do not start at 0 or decrease, more than 2048 atoms in a structure, a non-finite input, a cell length <= 0, angles
+ * that make no cell (volume <= 0), a cell so skewed that the search would exceed 32 translations per axis, a coordinate
+ * above 1e150 in magnitude.
+ * HOST pointers, all outputs required, any batch (chunked internally), synchronous, the calling thread's op stream. */
+int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, const double* xyz, const double* abc,
+                            const double* angles, int batch, double tol, double* lattice, double* volume, double* frac,
+                            double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid, int32_t* reason,
+                            double* nearest, int32_t* hist);
+
 /* ---------------------------------------------------------------- interpolation (interpolate.py)
  * interpolate(a, b, cond, vae, num_interps, return_zs, max_alpha) (interpolate.py:47-64): encode both crystals under one
  * condition, walk a straight line between their SAMPLED codes (the encoder's third output, F8), decode every point.
