@@ -21,6 +21,7 @@ import sys
 import numpy as np
 
 from icsg3d_amd import matrices
+from icsg3d_amd.matrices import accept, load_sites
 
 KINDS = ("density_matrices", "species_matrices", "lattice_vectors", "coordinate_grids")
 
@@ -38,27 +39,6 @@ def parse_args(argv=None):
     p.add_argument("--batch", type=int, default=8, help="Structures per device call")
     p.add_argument("--root", type=str, default="data", help="Directory holding <name>/")
     return p.parse_args(argv)
-
-
-def load_sites(path):
-    f = np.load(path)
-    frac = np.asarray(f["frac_coords"], np.float64).reshape(-1, 3)
-    return frac, np.asarray(f["Z"], np.float64), np.asarray(f["radii"], np.float64), np.asarray(f["lattice"], np.float64)
-
-
-def accept(fname, frac, radii, max_sites):
-    """The reference's per-structure rules (create_matrices.py:117-145): False = skip; an out-of-cell coordinate
-    raises SystemExit naming the file."""
-    if len(frac) > max_sites:
-        return False
-    N = frac - np.min(frac, axis=0)
-    if not np.all((N <= 1.0) & (N >= 0)):
-        print(fname, N)
-        sys.stdout.flush()
-        raise SystemExit("%s: fractional coordinates outside [0, 1] after the min-shift" % fname)
-    if any(np.isnan(radii)):
-        return False
-    return True
 
 
 def write_batch(sdir, ids, sites, rots, a):

@@ -60,43 +60,34 @@ def build_parser():
 
 def load_true(sites_dir, ids, sigma_frac):
     """Structures of the ids' site files (stem of "<id>.npy") and their (frac, Z, radii, lattice) tuples."""
-    from icsg3d_amd.matrices import Structures
-    sites = []
-    for i in ids:
-        f = np.load(os.path.join(sites_dir, os.path.splitext(i)[0] + ".npz"))
-        sites.append((np.asarray(f["frac_coords"], np.float64).reshape(-1, 3), np.asarray(f["Z"], np.float64),
-                      np.asarray(f["radii"], np.float64), np.asarray(f["lattice"], np.float64)))
+    from icsg3d_amd.matrices import Structures, load_sites
+    sites = [load_sites(os.path.join(sites_dir, os.path.splitext(i)[0] + ".npz")) for i in ids]
     return Structures.from_sites(sites, sigma_frac=sigma_frac), sites
 
 
 def site_listing(sites_dir, max_sites):
     """The "<id>.npy" names create_matrices.py would write for sites_dir (its skip rules), sorted."""
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import create_matrices as CM
+    from icsg3d_amd.matrices import accept, load_sites
     names = []
     for fname in sorted(f for f in os.listdir(sites_dir) if f.endswith(".npz")):
-        frac, _, radii, _ = CM.load_sites(os.path.join(sites_dir, fname))
-        if CM.accept(fname, frac, radii, max_sites):
+        frac, _, radii, _ = load_sites(os.path.join(sites_dir, fname))
+        if accept(fname, frac, radii, max_sites):
             names.append(os.path.splitext(fname)[0] + ".npy")
     return sorted(names)
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    from icsg3d_amd.cli import load_models
     from icsg3d_amd.evaluate import reconstruction_metrics
-    from icsg3d_amd.unet.unet import AtomUnet
     from icsg3d_amd.utils import data_split, data_split_names
     from icsg3d_amd.vae.data import VAEDataGenerator
-    from icsg3d_amd.vae.lattice_vae import LatticeDFCVAE
     from icsg3d_amd.watershed import refine_atoms
 
     mode, d, C, bs, eps = a.name, a.d, a.channels, a.batch_size, a.eps_frac
     data_path = os.path.join("data", mode, "matrices")
     sites_dir = os.path.join("data", mode, "sites")
     csv_path = os.path.join("data", mode, mode + ".csv")
-    vae_weights = os.path.join("saved_models", "vae", mode, "vae_weights_" + mode + ".best.hdf5")
-    unet_weights = os.path.join("saved_models", "unet", mode, "unet_weights_" + mode + ".best.hdf5")
-    perceptual_model = os.path.join("saved_models", "unet", mode, "unet_weights_" + mode + ".best.h5")
     out_dir = os.path.join("output", "eval", mode)
     os.makedirs(out_dir, exist_ok=True)
 
@@ -107,9 +98,7 @@ def main(argv=None):
     gen = VAEDataGenerator(validation_ids, data_path=data_path, property_csv=csv_path, batch_size=bs, dim=(d, d, d),
                            n_channels=C, shuffle=False, n_bins=a.ncond)
 
-    vae = LatticeDFCVAE(input_shape=(d, d, d, C), perceptual_model=perceptual_model, cond_shape=a.ncond)
-    vae._set_model(weights=vae_weights, batch_size=bs)
-    unet = AtomUnet(weights=unet_weights, input_shape=(d, d, d, C), max_batch=bs)
+    vae, unet = load_models(mode, d, C, a.ncond, bs, False, a.seed, True)
     rng = np.random.RandomState(a.seed)
 
     ids_out, failed_ids, emds, lt, lpred, nt, npred, species, coords = [], [], [], [], [], [], [], [], []

@@ -24,9 +24,12 @@ Added: --channels (the reference hard-codes 4) and --synthetic (a Gaussian-blob 
 import argparse
 import json
 import os
+import sys
 
 import numpy as np
 
+from icsg3d_amd.cli import checkpoint_paths
+from icsg3d_amd.evaluate import predicted_coordinates
 from icsg3d_amd.structures import ResultsWriter
 from icsg3d_amd.synthetic import synthetic_batch
 from icsg3d_amd.utils import to_lattice_params_from_minmax, to_voxel_params
@@ -55,7 +58,7 @@ def training_formulas(csv_path):
     return set(pd.read_csv(csv_path)["pretty_formula"].values)
 
 
-if __name__ == "__main__":
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--name", metavar="name", type=str, help="Name of data folder")
     p.add_argument("--base", metavar="base", type=str, help="Base Compound", default="LaFeO3")
@@ -73,13 +76,15 @@ if __name__ == "__main__":
     p.add_argument("--channels", type=int, default=4, help="input channels (density + 3 coordinate grids)")
     p.add_argument("--synthetic", action="store_true", help="Gaussian-blob base compound instead of data/<name>")
     p.add_argument("--cond_bin", type=int, default=0, help="--synthetic: condition bin of the base compound")
-    a = p.parse_args()
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
 
     mode, d, C, bs, eps = a.name, a.d, a.channels, a.batch_size, a.eps_frac
     path = os.path.join("data", mode, "matrices")
-    vae_weights = os.path.join("saved_models", "vae", mode, "vae_weights_" + mode + ".best.hdf5")
-    unet_weights = os.path.join("saved_models", "unet", mode, "unet_weights_" + mode + ".best.hdf5")
-    perceptual_model = os.path.join("saved_models", "unet", mode, "unet_weights_" + mode + ".best.h5")
+    vae_weights, unet_weights, perceptual_model = checkpoint_paths(mode)
 
     if a.synthetic:
         base_compound, base_formula, base_target_value, cond_bin = "synthetic", "synthetic", None, a.cond_bin
@@ -124,15 +129,14 @@ if __name__ == "__main__":
                                        split=True, max_iters=a.clus_iters)
         l_prime = to_lattice_params_from_minmax(out["coord_minmax"], d=d)
         dv_pred = to_voxel_params(l_prime, d=d)
+        xyz = predicted_coordinates(out["atoms"], out["coord_minmax"], eps, d)         # generate.py:237-241
         batch_atoms = [None] * bs
         for i in range(bs):
             k = batch * bs + i
             if out["failed"][i]:
                 print("Failed", k)
                 continue
-            species_sample, mu = out["atoms"][i]
-            mu = np.array(mu, np.float64).reshape(len(species_sample), 3)
-            mu = mu * dv_pred[i] - (eps * l_prime[i]) + (dv_pred[i] / 2.0)              # generate.py:237-241
+            species_sample, mu = out["atoms"][i][0], xyz[i]
             coords = np.concatenate([np.array(species_sample, np.float64).reshape(-1, 1), mu], axis=-1)
             n_atoms.append(len(species_sample))
             np.save(os.path.join(out_dir, "densities", "%d.npy" % k), out["density"][i])
@@ -146,3 +150,8 @@ if __name__ == "__main__":
     counts = results.finish()
     print("structures: generated %(generated)d / failed %(failed)d / invalid %(invalid)d / written %(written)d" % counts)
     print("wrote", out_dir, "- atoms per sample: mean %.1f" % (np.mean(n_atoms) if n_atoms else 0.0))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

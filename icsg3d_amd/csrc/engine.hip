@@ -2655,17 +2655,15 @@ static int decode_to_labels_compute(Net& n, Net& u, int batch, float thresh, boo
   *d_species_out = d_species; *d_mask_out = d_mask; *d_aux_out = d_aux;
   return 0;
 }
-// z / cond from the host into n.zc, then the compute
-static int decode_to_labels_device(Net& n, Net& u, const float* z, const float* cond, int batch, float thresh,
-                                   bool want_density, bool want_minmax, unsigned char** d_species_out,
-                                   unsigned char** d_mask_out, float** d_aux_out) {
+// z / cond from the host into n.zc = [z | cond], ahead of the compute
+static int upload_zc(Net& n, Net& u, const float* z, const float* cond, int batch) {
   ICS_CHECK(z && cond, "null argument");
   ICS_TRY(tail_check(n, u, batch));
   const size_t lat = n.latent, W = lat + n.ncond;
   ICS_HIP(hipStreamSynchronize(u.st));
   ICS_HIP(hipMemcpy2DAsync(n.zc, W * 4, z, lat * 4, lat * 4, batch, hipMemcpyHostToDevice, n.st));
   ICS_HIP(hipMemcpy2DAsync(n.zc + lat, W * 4, cond, n.ncond * 4, n.ncond * 4, batch, hipMemcpyHostToDevice, n.st));
-  return decode_to_labels_compute(n, u, batch, thresh, want_density, want_minmax, d_species_out, d_mask_out, d_aux_out);
+  return 0;
 }
 
 static int tail_copy_out(Net& n, int batch, const unsigned char* d_species, const unsigned char* d_mask,
@@ -2689,39 +2687,57 @@ int ics_vae_decode_to_unet_labels(ics_net* vae, ics_net* unet, const float* z, c
   Net& n = vae->n;
   unsigned char *d_species, *d_mask;
   float* d_aux;
-  ICS_TRY(decode_to_labels_device(n, unet->n, z, cond, batch, thresh, density != nullptr, coord_minmax != nullptr,
-                                  &d_species, &d_mask, &d_aux));
+  ICS_TRY(upload_zc(n, unet->n, z, cond, batch));
+  ICS_TRY(decode_to_labels_compute(n, unet->n, batch, thresh, density != nullptr, coord_minmax != nullptr, &d_species,
+                                   &d_mask, &d_aux));
   ICS_TRY(tail_copy_out(n, batch, d_species, d_mask, d_aux, species, mask, density, coord_minmax));
   ICS_HIP(hipStreamSynchronize(n.st));
   return 0;
 }
 
-// connected components + region statistics of device-resident mask / species volumes; results to the host
-static int segment_to_host(Net& n, const unsigned char* d_mask, const unsigned char* d_species, int batch, int d,
-                           int min_voxels, int max_atoms, int nbins, int32_t* regions, int32_t* counts,
-                           int32_t* atom_stats, int64_t* bounds) {
-  ICS_CHECK(counts && atom_stats && max_atoms >= 1, "null argument");
+// Where the tail's results go on the host, for the three *_to_unet_atoms chains and ics_op_segment_atoms: the thresholds
+// and the eight output pointers.  counts [B][2] and atom_stats [B][max_atoms][kSegStatInts] are required, the rest optional.
+struct AtomsOut {
+  float thresh; int min_voxels, max_atoms;
+  uint8_t *species, *mask; float *density, *coord_minmax; int32_t *regions, *counts, *atom_stats; int64_t* bounds;
+  // the same outputs f0 frames (of vox voxels) further on; an absent output stays absent
+  AtomsOut at(size_t f0, size_t vox) const {
+    auto off = [](auto* q, size_t k) { return q ? q + k : q; };
+    return {thresh, min_voxels, max_atoms, off(species, f0 * vox), off(mask, f0 * vox), off(density, f0 * vox),
+            off(coord_minmax, f0 * 6), off(regions, f0 * vox), off(counts, f0 * 2),
+            off(atom_stats, f0 * max_atoms * kSegStatInts), off(bounds, f0 * max_atoms * kSegBoundInts)};
+  }
+};
+// the one validation of the required outputs: every entry point calls it before its first launch
+static int atoms_out_check(const AtomsOut& T, const std::string& who = "") {
+  ICS_CHECK(T.counts && T.atom_stats && T.max_atoms >= 1, who + "null argument (counts, atom_stats are required; max_atoms >= 1)");
+  return 0;
+}
+
+// connected components + region statistics of device-resident mask / species volumes; results to the host (T checked)
+static int segment_to_host(Net& n, const unsigned char* d_mask, const unsigned char* d_species, int batch, int d, int nbins,
+                           const AtomsOut& T) {
   const size_t M = (size_t)batch * d * d * d;
-  const size_t wsb = segment_workspace_bytes(batch, d, max_atoms, nbins);
+  const size_t wsb = segment_workspace_bytes(batch, d, T.max_atoms, nbins);
   unsigned char* ws = nullptr;
   int* d_R = nullptr;
   const size_t wsb16 = (wsb + 15) & ~(size_t)15;
-  ICS_HIP(hipMalloc(reinterpret_cast<void**>(&ws), wsb16 + (regions ? M * 4 : 0)));
+  ICS_HIP(hipMalloc(reinterpret_cast<void**>(&ws), wsb16 + (T.regions ? M * 4 : 0)));
   int rc = 0;
   do {
-    if (regions) d_R = reinterpret_cast<int*>(ws + wsb16);
+    if (T.regions) d_R = reinterpret_cast<int*>(ws + wsb16);
     int *d_counts = nullptr, *d_stats = nullptr;
     long long* d_bounds = nullptr;
-    if ((rc = launch_segment_atoms(n.st, d_mask, d_species, batch, d, min_voxels, max_atoms, nbins, ws, wsb, d_R,
-                                   &d_counts, &d_stats, bounds ? &d_bounds : nullptr)))
+    if ((rc = launch_segment_atoms(n.st, d_mask, d_species, batch, d, T.min_voxels, T.max_atoms, nbins, ws, wsb, d_R,
+                                   &d_counts, &d_stats, T.bounds ? &d_bounds : nullptr)))
       break;
     hipError_t e = hipSuccess;
-    if (regions) e = hipMemcpyAsync(regions, d_R, M * 4, hipMemcpyDeviceToHost, n.st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, (size_t)batch * 2 * 4, hipMemcpyDeviceToHost, n.st);
+    if (T.regions) e = hipMemcpyAsync(T.regions, d_R, M * 4, hipMemcpyDeviceToHost, n.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(T.counts, d_counts, (size_t)batch * 2 * 4, hipMemcpyDeviceToHost, n.st);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(atom_stats, d_stats, (size_t)batch * max_atoms * kSegStatInts * 4, hipMemcpyDeviceToHost, n.st);
-    if (e == hipSuccess && bounds)
-      e = hipMemcpyAsync(bounds, d_bounds, (size_t)batch * max_atoms * kSegBoundInts * 8, hipMemcpyDeviceToHost, n.st);
+      e = hipMemcpyAsync(T.atom_stats, d_stats, (size_t)batch * T.max_atoms * kSegStatInts * 4, hipMemcpyDeviceToHost, n.st);
+    if (e == hipSuccess && T.bounds)
+      e = hipMemcpyAsync(T.bounds, d_bounds, (size_t)batch * T.max_atoms * kSegBoundInts * 8, hipMemcpyDeviceToHost, n.st);
     if (e == hipSuccess) e = hipStreamSynchronize(n.st);
     if (e != hipSuccess) { set_error(std::string("segmentation copy-out: ") + hipGetErrorString(e)); rc = -1; }
   } while (0);
@@ -2732,6 +2748,17 @@ static int segment_to_host(Net& n, const unsigned char* d_mask, const unsigned c
   return 0;
 }
 
+// the whole tail from [z | cond] in n.zc to the atoms of `frames` samples on the host (tail_check and atoms_out_check
+// passed, the U-Net's stream drained): compute, copy-out, components + statistics
+static int tail_to_atoms(Net& n, Net& u, int frames, const AtomsOut& T) {
+  unsigned char *d_species, *d_mask;
+  float* d_aux;
+  ICS_TRY(decode_to_labels_compute(n, u, frames, T.thresh, T.density != nullptr, T.coord_minmax != nullptr, &d_species,
+                                   &d_mask, &d_aux));
+  ICS_TRY(tail_copy_out(n, frames, d_species, d_mask, d_aux, T.species, T.mask, T.density, T.coord_minmax));
+  return segment_to_host(n, d_mask, d_species, frames, n.d, u.ncls, T);
+}
+
 int ics_vae_decode_to_unet_atoms(ics_net* vae, ics_net* unet, const float* z, const float* cond, int batch,
                                  float thresh, int min_voxels, int max_atoms, uint8_t* species, uint8_t* mask,
                                  float* density, float* coord_minmax, int32_t* regions, int32_t* counts,
@@ -2739,14 +2766,11 @@ int ics_vae_decode_to_unet_atoms(ics_net* vae, ics_net* unet, const float* z, co
   ICS_TRY(require_kind(vae, 1));
   ICS_TRY(require_kind(unet, 0));
   Net& n = vae->n;
-  unsigned char *d_species, *d_mask;
-  float* d_aux;
-  ICS_TRY(decode_to_labels_device(n, unet->n, z, cond, batch, thresh, density != nullptr, coord_minmax != nullptr,
-                                  &d_species, &d_mask, &d_aux));
-  ICS_TRY(tail_copy_out(n, batch, d_species, d_mask, d_aux, species, mask, density, coord_minmax));
-  ICS_TRY(segment_to_host(n, d_mask, d_species, batch, n.d, min_voxels, max_atoms, unet->n.ncls, regions, counts,
-                          atom_stats, convexity_bounds));
-  return 0;
+  const AtomsOut T{thresh, min_voxels, max_atoms, species, mask, density, coord_minmax, regions, counts, atom_stats,
+                   convexity_bounds};
+  ICS_TRY(atoms_out_check(T));
+  ICS_TRY(upload_zc(n, unet->n, z, cond, batch));
+  return tail_to_atoms(n, unet->n, batch, T);
 }
 
 // eval.py:163-175: the reconstruction chain on the resident batch.  The encoder's sampling leaves [z | cond] in zc
@@ -2760,18 +2784,13 @@ int ics_vae_reconstruct_resident_to_unet_atoms(ics_net* vae, ics_net* unet, floa
   Net& n = vae->n;
   const int batch = n.resident_batch;
   ICS_CHECK(batch > 0, "no resident batch: call ics_vae_upload_batch or ics_vae_voxelise_batch first");
-  ICS_CHECK(counts && atom_stats && max_atoms >= 1, "null argument");
+  const AtomsOut T{thresh, min_voxels, max_atoms, species, mask, density, coord_minmax, regions, counts, atom_stats,
+                   convexity_bounds};
+  ICS_TRY(atoms_out_check(T));
   ICS_TRY(tail_check(n, unet->n, batch));
   ICS_HIP(hipStreamSynchronize(unet->n.st));
   ICS_TRY(vae_encode_fwd(n, batch, false));
-  unsigned char *d_species, *d_mask;
-  float* d_aux;
-  ICS_TRY(decode_to_labels_compute(n, unet->n, batch, thresh, density != nullptr, coord_minmax != nullptr, &d_species,
-                                   &d_mask, &d_aux));
-  ICS_TRY(tail_copy_out(n, batch, d_species, d_mask, d_aux, species, mask, density, coord_minmax));
-  ICS_TRY(segment_to_host(n, d_mask, d_species, batch, n.d, min_voxels, max_atoms, unet->n.ncls, regions, counts,
-                          atom_stats, convexity_bounds));
-  return 0;
+  return tail_to_atoms(n, unet->n, batch, T);
 }
 
 // interpolate.py:47-64 as one chain per group of pairs: the group's 2g endpoints (a0, b0, a1, b1, ...) through ONE encoder
@@ -2783,18 +2802,14 @@ struct InterpArgs {
   const double* alpha;
   int steps, mode;
 };
-struct InterpAtomsOut {
-  float thresh; int min_voxels, max_atoms;
-  uint8_t *species, *mask; float *density, *coord_minmax; int32_t *regions, *counts, *atom_stats; int64_t* bounds;
-};
-static int interp_check(const char* who, const Net& n, const Net* u, const InterpArgs& A, const InterpAtomsOut* T, int* group) {
+static int interp_check(const char* who, const Net& n, const Net* u, const InterpArgs& A, const AtomsOut* T, int* group) {
   const std::string p = std::string(who) + ": ";
   ICS_TRY(latent_path_check(who, A.pairs, n.latent, A.alpha, A.steps, A.mode));
   ICS_CHECK(A.a && A.b && A.cond && A.eps_a && A.eps_b, p + "null argument (a, b, cond, eps_a, eps_b are required)");
   int lim = n.maxB;                 // frames per group: the decoder's batch, and the U-Net's where one follows
   if (u) {
     ICS_CHECK(u->d == n.d && u->C == n.C && u->device == n.device, p + "U-Net / VAE engines do not match (grid, channels, device)");
-    ICS_CHECK(T->counts && T->atom_stats && T->max_atoms >= 1, p + "null argument (counts, atom_stats are required; max_atoms >= 1)");
+    ICS_TRY(atoms_out_check(*T, p));
     lim = std::min(lim, u->maxB);
   }
   ICS_CHECK(n.maxB >= 2, p + "max_batch must be >= 2 (a pair's two endpoints share one encoder pass)");
@@ -2802,7 +2817,7 @@ static int interp_check(const char* who, const Net& n, const Net* u, const Inter
   *group = std::min(n.maxB / 2, lim / A.steps);
   return 0;
 }
-static int interp_run(Net& n, Net* u, const InterpArgs& A, int group, const InterpAtomsOut* T, float* z_ends,
+static int interp_run(Net& n, Net* u, const InterpArgs& A, int group, const AtomsOut* T, float* z_ends,
                       float* z_path, float* recon) {
   const size_t lat = n.latent, nc = n.ncond, W = lat + nc, vox = (size_t)n.d * n.d * n.d, xrow = vox * n.C;
   n.resident_batch = 0;             // the endpoints overwrite the input batch: no resident step may run on them
@@ -2830,23 +2845,13 @@ static int interp_run(Net& n, Net* u, const InterpArgs& A, int group, const Inte
     if (z_path)
       ICS_HIP(hipMemcpy2DAsync(z_path + (size_t)p0 * A.steps * lat, lat * 4, n.zc, W * 4, lat * 4, frames, hipMemcpyDeviceToHost, n.st));
     const size_t f0 = (size_t)p0 * A.steps;
-    if (!u) {
-      ICS_TRY(vae_decode_fwd(n, frames, false));
-      if (recon) ICS_HIP(hipMemcpyAsync(recon + f0 * xrow, n.recon, (size_t)frames * xrow * 4, hipMemcpyDeviceToHost, n.st));
-      ICS_HIP(hipStreamSynchronize(n.st));
+    if (u) {
+      ICS_TRY(tail_to_atoms(n, *u, frames, T->at(f0, vox)));
       continue;
     }
-    unsigned char *d_species, *d_mask;
-    float* d_aux;
-    ICS_TRY(decode_to_labels_compute(n, *u, frames, T->thresh, T->density != nullptr, T->coord_minmax != nullptr, &d_species,
-                                     &d_mask, &d_aux));
-    ICS_TRY(tail_copy_out(n, frames, d_species, d_mask, d_aux, T->species ? T->species + f0 * vox : nullptr,
-                          T->mask ? T->mask + f0 * vox : nullptr, T->density ? T->density + f0 * vox : nullptr,
-                          T->coord_minmax ? T->coord_minmax + f0 * 6 : nullptr));
-    ICS_TRY(segment_to_host(n, d_mask, d_species, frames, n.d, T->min_voxels, T->max_atoms, u->ncls,
-                            T->regions ? T->regions + f0 * vox : nullptr, T->counts + f0 * 2,
-                            T->atom_stats + f0 * T->max_atoms * kSegStatInts,
-                            T->bounds ? T->bounds + f0 * T->max_atoms * kSegBoundInts : nullptr));
+    ICS_TRY(vae_decode_fwd(n, frames, false));
+    if (recon) ICS_HIP(hipMemcpyAsync(recon + f0 * xrow, n.recon, (size_t)frames * xrow * 4, hipMemcpyDeviceToHost, n.st));
+    ICS_HIP(hipStreamSynchronize(n.st));
   }
   return 0;
 }
@@ -2868,8 +2873,8 @@ int ics_vae_interpolate_to_unet_atoms(ics_net* vae, ics_net* unet, const float* 
   ICS_TRY(require_kind(vae, 1));
   ICS_TRY(require_kind(unet, 0));
   const InterpArgs A{a, b, cond, eps_a, eps_b, pairs, alpha, steps, mode};
-  const InterpAtomsOut T{thresh, min_voxels, max_atoms, species, mask, density, coord_minmax, regions, counts, atom_stats,
-                         convexity_bounds};
+  const AtomsOut T{thresh, min_voxels, max_atoms, species, mask, density, coord_minmax, regions, counts, atom_stats,
+                   convexity_bounds};
   int group = 0;
   ICS_TRY(interp_check("ics_vae_interpolate_to_unet_atoms", vae->n, &unet->n, A, &T, &group));
   return interp_run(vae->n, &unet->n, A, group, &T, z_ends, z_path, nullptr);
@@ -2879,6 +2884,8 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
                          int num_species, int32_t* regions, int32_t* counts, int32_t* atom_stats, int64_t* convexity_bounds) {
   ICS_CHECK(mask && species && batch >= 1 && max_atoms >= 1 && min_voxels >= 0, "bad segmentation arguments");
   ICS_CHECK(d >= 16 && d <= 256 && (d & (d - 1)) == 0, "grid must be a power of two in [16, 256]");
+  const AtomsOut T{0.f, min_voxels, max_atoms, nullptr, nullptr, nullptr, nullptr, regions, counts, atom_stats, convexity_bounds};
+  ICS_TRY(atoms_out_check(T));
   Net n;
   n.arena_next = (size_t)1 << 22;      // a temporary Net: see op_prepare
   ICS_TRY(net_common_init(n));
@@ -2887,7 +2894,7 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
   ICS_TRY(n.alloc(&dm, M)); ICS_TRY(n.alloc(&ds, M));
   ICS_HIP(hipMemcpyAsync(dm, mask, M, hipMemcpyHostToDevice, n.st));
   ICS_HIP(hipMemcpyAsync(ds, species, M, hipMemcpyHostToDevice, n.st));
-  return segment_to_host(n, dm, ds, batch, d, min_voxels, max_atoms, num_species, regions, counts, atom_stats, convexity_bounds);
+  return segment_to_host(n, dm, ds, batch, d, num_species, T);
 }
 
 // The three box-level entry points run tens of times per sample from the host recursion of segment_nuclei

@@ -289,6 +289,44 @@ class UnetEngine(_Net):
         return None
 
 
+class _AtomsOut:
+    """The host arrays the decoder -> U-Net -> atoms tail fills for B samples, the ctypes arguments that point a C entry
+    at a slice of them, and the result dict the three *_to_atoms methods return."""
+
+    def __init__(self, B, d, max_atoms, want_density, want_regions):
+        from .watershed import STAT_FIELDS
+        self.B, self.d, self.max_atoms = B, d, max_atoms
+        self.species = np.empty((B, d, d, d), np.uint8)
+        self.mask = np.empty((B, d, d, d), np.uint8)
+        self.density = np.empty((B, d, d, d), np.float32) if want_density else None
+        self.coord_minmax = np.zeros((B, 3, 2), np.float32)
+        self.regions = np.empty((B, d, d, d), np.int32) if want_regions else None
+        self.counts = np.zeros((B, 2), np.int32)
+        self.stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
+        self.bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None   # refine_atoms' convexity shortcut
+
+    def label_args(self, s=slice(None)):
+        """species, mask, density, coord_minmax of samples s, as every entry point of the tail takes them"""
+        cut = lambda a: a[s] if a is not None else None
+        return (L.u8ptr(self.species[s]), L.u8ptr(self.mask[s]), L.fptr(cut(self.density)), L.fptr(self.coord_minmax[s]))
+
+    def args(self, s=slice(None)):
+        """the eight output pointers of the *_to_unet_atoms entry points for samples s"""
+        cut = lambda a: a[s] if a is not None else None
+        return self.label_args(s) + (L.i32ptr(cut(self.regions)), L.i32ptr(self.counts[s]), L.i32ptr(self.stats[s]),
+                                     L.i64ptr(cut(self.bounds)))
+
+    def result(self):
+        from .watershed import _atoms_from_stats
+        counts = self.counts
+        failed = counts[:, 1] > self.max_atoms            # more kept components than rows: sample skipped, not the batch
+        counts[failed, 1] = 0
+        return {"species": self.species, "mask": self.mask, "density": self.density, "coord_minmax": self.coord_minmax,
+                "regions": self.regions, "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(),
+                "stats": self.stats, "bounds": self.bounds, "atoms": _atoms_from_stats(counts, self.stats, self.d ** 3),
+                "failed": failed}
+
+
 class VaeEngine(_Net):
     def __init__(self, unet: UnetEngine, in_channels=1, cond_shape=10, latent_dim=256,
                  filters=(16, 32, 64, 128), d=32, max_batch=32, lr=5e-4, alpha=0.5, beta=3e-4,
@@ -340,18 +378,13 @@ class VaeEngine(_Net):
         """decoder.predict -> unet.model.predict -> argmax / threshold without leaving the device
         (generate.py:204-225).  Returns dict(species u8, mask u8, density f32 | None, coord_minmax (B,3,2))."""
         z, cond = _f32(z), _f32(cond)
-        B, d = z.shape[0], self.d
+        out = _AtomsOut(z.shape[0], self.d, 0, want_density, False)
         mb = min(self.max_batch, unet.max_batch)
-        sp = np.empty((B, d, d, d), np.uint8)
-        mk = np.empty((B, d, d, d), np.uint8)
-        dens = np.empty((B, d, d, d), np.float32) if want_density else None
-        mm = np.zeros((B, 3, 2), np.float32)
-        for i in range(0, B, mb):
+        for i in range(0, out.B, mb):
             s = slice(i, i + mb)
             L.check(self._lib.ics_vae_decode_to_unet_labels(
-                self._h, unet._h, L.fptr(z[s]), L.fptr(cond[s]), z[s].shape[0], float(thresh), L.u8ptr(sp[s]),
-                L.u8ptr(mk[s]), L.fptr(dens[s]) if want_density else None, L.fptr(mm[s])))
-        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm}
+                self._h, unet._h, L.fptr(z[s]), L.fptr(cond[s]), z[s].shape[0], float(thresh), *out.label_args(s)))
+        return {"species": out.species, "mask": out.mask, "density": out.density, "coord_minmax": out.coord_minmax}
 
     def decode_to_atoms(self, unet, z, cond, thresh=0.8, min_voxels=3, max_atoms=512, want_density=True,
                         want_regions=False):
@@ -360,64 +393,40 @@ class VaeEngine(_Net):
         n_components (B,), n_atoms (B,), stats int32 (B,max_atoms,11), atoms [(species list, mean list)], failed (B,)).
         Every kept component is taken as convex here; icsg3d_amd.watershed.refine_atoms continues with the convexity
         test and the recursive split (needs want_regions=True)."""
-        from .watershed import STAT_FIELDS, _atoms_from_stats
         z, cond = _f32(z), _f32(cond)
-        B, d = z.shape[0], self.d
+        out = _AtomsOut(z.shape[0], self.d, max_atoms, want_density, want_regions)
         mb = min(self.max_batch, unet.max_batch)
-        sp = np.empty((B, d, d, d), np.uint8)
-        mk = np.empty((B, d, d, d), np.uint8)
-        dens = np.empty((B, d, d, d), np.float32) if want_density else None
-        reg = np.empty((B, d, d, d), np.int32) if want_regions else None
-        mm = np.zeros((B, 3, 2), np.float32)
-        counts = np.zeros((B, 2), np.int32)
-        stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
-        bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None    # refine_atoms' convexity shortcut
-        for i in range(0, B, mb):
+        for i in range(0, out.B, mb):
             s = slice(i, i + mb)
             L.check(self._lib.ics_vae_decode_to_unet_atoms(
                 self._h, unet._h, L.fptr(z[s]), L.fptr(cond[s]), z[s].shape[0], float(thresh), int(min_voxels),
-                int(max_atoms), L.u8ptr(sp[s]), L.u8ptr(mk[s]), L.fptr(dens[s]) if want_density else None,
-                L.fptr(mm[s]), L.i32ptr(reg[s]) if want_regions else None, L.i32ptr(counts[s]), L.i32ptr(stats[s]),
-                L.i64ptr(bounds[s]) if bounds is not None else None))
-        failed = counts[:, 1] > max_atoms                 # more kept components than rows: sample skipped, not the batch
-        counts[failed, 1] = 0
-        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm, "regions": reg,
-                "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
-                "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed}
+                int(max_atoms), *out.args(s)))
+        return out.result()
 
     def reconstruct_to_atoms(self, unet, x=None, cond=None, eps=None, thresh=0.8, min_voxels=3, max_atoms=512,
                              want_density=True, want_regions=False):
         """vae.model.predict([M, cond]) -> unet.model.predict -> argmax / threshold -> components + statistics
         (eval.py:163-175) in one device-resident chain: encode, sample z with the batch's eps (F8), decode, segment.
-        With x (and cond, eps) the batch is uploaded first (upload_batch); without, the resident batch placed by
-        upload_batch / voxelise_batch is used and left unchanged.  Returns decode_to_atoms' dict, bit for bit what
-        decode_to_atoms(unet, encode(x, cond, eps)[2], cond) returns."""
-        from .watershed import STAT_FIELDS, _atoms_from_stats
-        if x is not None:
-            self.upload_batch(x, cond, eps)
-        elif cond is not None or eps is not None:
+        With x (and cond, eps) the batch is uploaded first (upload_batch), max_batch samples at a time; without, the
+        resident batch placed by upload_batch / voxelise_batch is used and left unchanged.  Returns decode_to_atoms'
+        dict, bit for bit what decode_to_atoms(unet, encode(x, cond, eps)[2], cond) returns."""
+        if x is None and (cond is not None or eps is not None):
             raise ValueError("cond / eps go with x; the resident batch carries its own")
-        B = self._resident
-        if not B:
-            raise RuntimeError("no resident batch: call upload_batch or voxelise_batch first")
-        d = self.d
-        sp = np.empty((B, d, d, d), np.uint8)
-        mk = np.empty((B, d, d, d), np.uint8)
-        dens = np.empty((B, d, d, d), np.float32) if want_density else None
-        reg = np.empty((B, d, d, d), np.int32) if want_regions else None
-        mm = np.zeros((B, 3, 2), np.float32)
-        counts = np.zeros((B, 2), np.int32)
-        stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
-        bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None
-        L.check(self._lib.ics_vae_reconstruct_resident_to_unet_atoms(
-            self._h, unet._h, float(thresh), int(min_voxels), int(max_atoms), L.u8ptr(sp), L.u8ptr(mk),
-            L.fptr(dens) if want_density else None, L.fptr(mm), L.i32ptr(reg) if want_regions else None,
-            L.i32ptr(counts), L.i32ptr(stats), L.i64ptr(bounds) if bounds is not None else None))
-        failed = counts[:, 1] > max_atoms
-        counts[failed, 1] = 0
-        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm, "regions": reg,
-                "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
-                "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed}
+        if x is not None:
+            x, cond, eps, B = self._args(x, cond, eps)
+        else:
+            B = self._resident
+            if not B:
+                raise RuntimeError("no resident batch: call upload_batch or voxelise_batch first")
+        out = _AtomsOut(B, self.d, max_atoms, want_density, want_regions)
+        mb = min(self.max_batch, unet.max_batch) if x is not None else B
+        for i in range(0, B, mb):
+            s = slice(i, i + mb)
+            if x is not None:
+                self.upload_batch(x[s], cond[s], eps[s])
+            L.check(self._lib.ics_vae_reconstruct_resident_to_unet_atoms(
+                self._h, unet._h, float(thresh), int(min_voxels), int(max_atoms), *out.args(s)))
+        return out.result()
 
     def _interp_args(self, a, b, cond, eps_a, eps_b, alpha, mode):
         a, b, cond, eps_a, eps_b = _f32(a), _f32(b), _f32(cond), _f32(eps_a), _f32(eps_b)
@@ -449,30 +458,16 @@ class VaeEngine(_Net):
                              max_atoms=512, want_density=True, want_regions=False):
         """interpolate continued for every frame as decode_to_atoms (ics_vae_interpolate_to_unet_atoms): decode_to_atoms'
         dict for the P*S frames, frame p*S + k, plus z_ends (P,2,latent) and z_path (P,S,latent)."""
-        from .watershed import STAT_FIELDS, _atoms_from_stats
         a, b, cond, eps_a, eps_b, alpha, P, mode = self._interp_args(a, b, cond, eps_a, eps_b, alpha, mode)
-        S, d = len(alpha), self.d
-        B = P * S
+        S = len(alpha)
         z_ends = np.empty((P, 2, self.latent_dim), np.float32)
         z_path = np.empty((P, S, self.latent_dim), np.float32)
-        sp = np.empty((B, d, d, d), np.uint8)
-        mk = np.empty((B, d, d, d), np.uint8)
-        dens = np.empty((B, d, d, d), np.float32) if want_density else None
-        reg = np.empty((B, d, d, d), np.int32) if want_regions else None
-        mm = np.zeros((B, 3, 2), np.float32)
-        counts = np.zeros((B, 2), np.int32)
-        stats = np.zeros((B, max_atoms, len(STAT_FIELDS)), np.int32)
-        bounds = np.zeros((B, max_atoms, 8), np.int64) if want_regions else None
+        out = _AtomsOut(P * S, self.d, max_atoms, want_density, want_regions)
         self._resident = 0
         L.check(self._lib.ics_vae_interpolate_to_unet_atoms(
             self._h, unet._h, L.fptr(a), L.fptr(b), L.fptr(cond), L.fptr(eps_a), L.fptr(eps_b), P, L.f64ptr(alpha), S, mode,
-            float(thresh), int(min_voxels), int(max_atoms), L.fptr(z_ends), L.fptr(z_path), L.u8ptr(sp), L.u8ptr(mk),
-            L.fptr(dens), L.fptr(mm), L.i32ptr(reg), L.i32ptr(counts), L.i32ptr(stats), L.i64ptr(bounds)))
-        failed = counts[:, 1] > max_atoms
-        counts[failed, 1] = 0
-        return {"species": sp, "mask": mk, "density": dens, "coord_minmax": mm, "regions": reg,
-                "n_components": counts[:, 0].copy(), "n_atoms": counts[:, 1].copy(), "stats": stats, "bounds": bounds,
-                "atoms": _atoms_from_stats(counts, stats, d ** 3), "failed": failed, "z_ends": z_ends, "z_path": z_path}
+            float(thresh), int(min_voxels), int(max_atoms), L.fptr(z_ends), L.fptr(z_path), *out.args()))
+        return dict(out.result(), z_ends=z_ends, z_path=z_path)
 
     def train_step(self, x, cond, eps):
         x, cond, eps, B = self._args(x, cond, eps)

@@ -10,6 +10,7 @@ grid comes from libicsg3d_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -133,3 +134,25 @@ def coordinate_grid(l, dim=32, eps_frac=0.25):
     s = Structures.from_cartesian([np.zeros((1, 3))], [0.0], [1.0], [l])
     _, _, p = voxelise(s, d=int(dim), eps_frac=eps_frac, want=("p",))
     return p[0]
+
+
+def load_sites(path):
+    """(frac (n,3), Z, radii, lattice (6,)) of one data/<name>/sites/<id>.npz, float64"""
+    f = np.load(path)
+    frac = np.asarray(f["frac_coords"], np.float64).reshape(-1, 3)
+    return frac, np.asarray(f["Z"], np.float64), np.asarray(f["radii"], np.float64), np.asarray(f["lattice"], np.float64)
+
+
+def accept(fname, frac, radii, max_sites):
+    """The reference's per-structure rules (create_matrices.py:117-145): False = skip; an out-of-cell coordinate
+    raises SystemExit naming the file."""
+    if len(frac) > max_sites:
+        return False
+    N = frac - np.min(frac, axis=0)
+    if not np.all((N <= 1.0) & (N >= 0)):
+        print(fname, N)
+        sys.stdout.flush()
+        raise SystemExit("%s: fractional coordinates outside [0, 1] after the min-shift" % fname)
+    if any(np.isnan(radii)):
+        return False
+    return True

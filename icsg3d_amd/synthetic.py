@@ -78,6 +78,29 @@ def glorot_params(shapes, seed):
     return out
 
 
+def random_weights(d, C, seed):
+    """(U-Net weights, VAE weights) of the reference's widths: Glorot kernels from `seed` / `seed + 1`, BN moving
+    statistics at their Keras defaults."""
+    us = unet_param_shapes(C, 95)
+    uw = glorot_params(us, seed=seed); uw.update(bn_state_defaults(us))
+    vs = vae_param_shapes(C, 10, (16, 32, 64, 128), 256, d)
+    vw = glorot_params(vs, seed=seed + 1); vw.update(bn_state_defaults(vs))
+    return uw, vw
+
+
+def random_engines(d, C, max_batch, seed=0, unet=True, weights=None):
+    """(VaeEngine on a perceptual UnetEngine of its own, a second UnetEngine of the same weights | None) on
+    random_weights(d, C, seed), or on `weights` = (uw, vw): what the benches and the GPU tests run the inference tail on."""
+    from .engine import UnetEngine, VaeEngine      # lazily: this module is imported on hosts without the library
+    uw, vw = weights or random_weights(d, C, seed)
+    pm = UnetEngine(in_channels=C, d=d, max_batch=max_batch); pm.set_weights(uw)
+    un = None
+    if unet:
+        un = UnetEngine(in_channels=C, d=d, max_batch=max_batch); un.set_weights(uw)
+    ve = VaeEngine(pm, in_channels=C, d=d, max_batch=max_batch); ve.set_weights(vw)
+    return ve, un
+
+
 def synthetic_batch(B, d=32, C=1, seed=0, noise=0.0):
     """Gaussian-blob densities (mimics utils.density_matrix, /root/reference/utils.py:135-143),
     uint8 species labels, one-hot condition (i mod 10).  Returns (X float32, labels uint8, cond)."""

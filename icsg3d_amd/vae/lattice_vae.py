@@ -101,6 +101,14 @@ class _VaeModel:
         _save_weight_file(path, self._o._get_weights(), "vae", full_model=True)
 
 
+def _refine(out, unet, split, max_iters):
+    """the host end of the three *_segment_atoms chains: the convexity test and recursive split of watershed.refine_atoms"""
+    if split:
+        from ..watershed import refine_atoms
+        refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
+    return out
+
+
 class LatticeDFCVAE(DataParallelMixin):
     """Conditional VAE with a deep-feature-consistent (perceptual U-Net) loss; parameters as
     lattice_vae.py:89-105.  `perceptual_model` is a U-Net checkpoint written by
@@ -262,10 +270,7 @@ class LatticeDFCVAE(DataParallelMixin):
         eng = self._engine(min(len(z), self.batch_size or 32))
         out = eng.decode_to_atoms(unet._engine(min(len(z), eng.max_batch)), z, cond, thresh, min_voxels, max_atoms,
                                   want_regions=want_regions or split)
-        if split:
-            from ..watershed import refine_atoms
-            refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
-        return out
+        return _refine(out, unet, split, max_iters)
 
     def reconstruct_segment_atoms(self, M, cond, unet, eps=None, thresh=0.8, min_voxels=3, max_atoms=512, split=True,
                                   max_iters=5, want_regions=False):
@@ -280,19 +285,8 @@ class LatticeDFCVAE(DataParallelMixin):
         cond, eps = np.asarray(cond), np.asarray(eps)
         eng = self._engine(min(n, self.batch_size or 32))
         ueng = unet._engine(min(n, eng.max_batch))
-        mb = min(eng.max_batch, ueng.max_batch)
-        parts = [eng.reconstruct_to_atoms(ueng, M[i:i + mb], cond[i:i + mb], eps[i:i + mb], thresh, min_voxels,
-                                          max_atoms, want_regions=want_regions or split) for i in range(0, n, mb)]
-        out = {}
-        for k, v in parts[0].items():
-            if k == "atoms":
-                out[k] = [a for p in parts for a in p[k]]
-            else:
-                out[k] = None if v is None else np.concatenate([p[k] for p in parts])
-        if split:
-            from ..watershed import refine_atoms
-            refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
-        return out
+        out = eng.reconstruct_to_atoms(ueng, M, cond, eps, thresh, min_voxels, max_atoms, want_regions=want_regions or split)
+        return _refine(out, unet, split, max_iters)
 
     def interpolate_segment_atoms(self, A, B, conds, unet, num_interps=8, max_alpha=1, mode="lerp", eps=None,
                                   thresh=0.8, min_voxels=3, max_atoms=512, want_regions=False, split=True, max_iters=5):
@@ -313,10 +307,7 @@ class LatticeDFCVAE(DataParallelMixin):
         ueng = unet._engine(max(2, num_interps), grow=True)
         out = eng.interpolate_to_atoms(ueng, A, B, conds, eps[:, 0], eps[:, 1], np.linspace(0, max_alpha, num_interps),
                                        mode, thresh, min_voxels, max_atoms, want_regions=want_regions or split)
-        if split:
-            from ..watershed import refine_atoms
-            refine_atoms(out, max_iters=max_iters, num_species=unet.num_classes if hasattr(unet, "num_classes") else 95)
-        return out
+        return _refine(out, unet, split, max_iters)
 
     def save_(self, weights, model="saved_models/vae.h5"):
         self.model.load_weights(weights)

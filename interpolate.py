@@ -81,27 +81,6 @@ def dataset_pairs(name, ncond, d, C):
     return np.stack(A).astype(np.float32), np.stack(B).astype(np.float32), ids, formulae
 
 
-def models(name, d, C, ncond, batch_size, synthetic, seed, want_unet):
-    """LatticeDFCVAE (+ AtomUnet) from saved_models/ as the reference loads them; with --synthetic and no checkpoint,
-    random weights drawn from np.random seeded with `seed`."""
-    from icsg3d_amd.unet.unet import AtomUnet
-    from icsg3d_amd.vae.lattice_vae import LatticeDFCVAE
-    vae_weights = os.path.join("saved_models", "vae", name, "vae_weights_" + name + ".best.hdf5")
-    unet_weights = os.path.join("saved_models", "unet", name, "unet_weights_" + name + ".best.hdf5")
-    unet_model = os.path.join("saved_models", "unet", name, "unet_weights_" + name + ".best.h5")
-    np.random.seed(seed)
-    unet = None
-    if synthetic and not os.path.exists(unet_model):
-        unet = AtomUnet(input_shape=(d, d, d, C), max_batch=batch_size)
-        vae = LatticeDFCVAE(input_shape=(d, d, d, C), perceptual_model=unet, cond_shape=ncond)
-    else:
-        vae = LatticeDFCVAE(input_shape=(d, d, d, C), perceptual_model=unet_model, cond_shape=ncond)
-        if want_unet:
-            unet = AtomUnet(weights=unet_weights, input_shape=(d, d, d, C), max_batch=batch_size)
-    vae._set_model(weights=vae_weights, batch_size=batch_size)
-    return vae, unet
-
-
 def draw_eps(seed, ncond, latent):
     return np.random.RandomState(seed).normal(size=(ncond, 2, latent)).astype(np.float32)
 
@@ -131,13 +110,14 @@ def plot_rows(rows, formulae, n_interps, d, path):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    from icsg3d_amd.cli import load_models
     from icsg3d_amd.interpolate import interpolate_pairs
     name, d, C, n = a.name, a.d, a.channels, a.ninterps
     projection = None if a.projection == "None" else a.projection
     out_dir = os.path.join("output", "interpolation")
     os.makedirs(out_dir, exist_ok=True)
 
-    vae, unet = models(name, d, C, a.ncond, a.batch_size, a.synthetic, a.seed, a.atoms)
+    vae, unet = load_models(name, d, C, a.ncond, a.batch_size, a.synthetic, a.seed, a.atoms)
     np.random.seed(a.seed)
     if a.synthetic:
         A, B, ids, formulae = synthetic_pairs(a.ncond, d, C, a.seed)
@@ -150,18 +130,13 @@ def main(argv=None):
     rows, zs = interpolate_pairs(A, B, conds, vae, num_interps=n, return_zs=True, mode=a.mode, eps=eps)
     extra = {}
     if a.atoms:
-        from icsg3d_amd.evaluate import emd
-        from icsg3d_amd.utils import to_lattice_params_from_minmax, to_voxel_params
+        from icsg3d_amd.evaluate import emd, predicted_coordinates
         out = vae.interpolate_segment_atoms(A, B, conds, unet, num_interps=n, mode=a.mode, eps=eps, thresh=0.8,
                                             min_voxels=3, max_atoms=2048, split=True)
-        l_prime = to_lattice_params_from_minmax(out["coord_minmax"], d=d)
-        dv_pred = to_voxel_params(l_prime, d=d)
         os.makedirs(os.path.join(out_dir, name + "_atoms"), exist_ok=True)
         xyz = []
-        for f in range(a.ncond * n):
-            species, mu = out["atoms"][f]
-            mu = np.array(mu, np.float64).reshape(len(species), 3)
-            mu = mu * dv_pred[f] - (0.25 * l_prime[f]) + (dv_pred[f] / 2.0)            # generate.py:237-241
+        for f, mu in enumerate(predicted_coordinates(out["atoms"], out["coord_minmax"], d=d)):    # generate.py:237-241
+            species = out["atoms"][f][0]
             if out["failed"][f]:
                 mu = mu[:0]
             else:

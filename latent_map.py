@@ -65,12 +65,11 @@ def plot_map(emb, bins, thumbs, thumb_idx, path):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    from icsg3d_amd.cli import load_models
     from icsg3d_amd.tsne import latent_map
     name, d, C, bs = a.name, a.d, a.channels, a.batch_size
     out_dir = os.path.join("output", "latent")
     os.makedirs(out_dir, exist_ok=True)
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import interpolate as I                                           # models(): checkpoints or seeded random weights
 
     target = None
     if a.synthetic:
@@ -88,7 +87,7 @@ def main(argv=None):
     n = len(gen) * bs
     if n < 2:
         raise SystemExit("fewer than 2 structures in whole batches of %d" % bs)
-    vae, _ = I.models(name, d, C, a.ncond, bs, a.synthetic, a.seed, False)
+    vae, _ = load_models(name, d, C, a.ncond, bs, a.synthetic, a.seed, False)   # checkpoints or seeded random weights
 
     ids, bins, thumbs, thumb_idx = [], [], [], []
     every = max(1, n // max(a.thumbnails, 1))

@@ -22,29 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timeit(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return {"median_ms": 1e3 * float(np.median(ts)), "min_ms": 1e3 * float(np.min(ts)), "reps": reps}
-
-
-def engines(d, C, mb, seed=0):
-    from icsg3d_amd.engine import UnetEngine, VaeEngine
-    from icsg3d_amd.synthetic import bn_state_defaults, glorot_params, unet_param_shapes, vae_param_shapes
-    us = unet_param_shapes(C, 95)
-    uw = glorot_params(us, seed=seed); uw.update(bn_state_defaults(us))
-    vs = vae_param_shapes(C, 10, (16, 32, 64, 128), 256, d)
-    vw = glorot_params(vs, seed=seed + 1); vw.update(bn_state_defaults(vs))
-    pm = UnetEngine(in_channels=C, d=d, max_batch=mb); pm.set_weights(uw)
-    un = UnetEngine(in_channels=C, d=d, max_batch=mb); un.set_weights(uw)
-    ve = VaeEngine(pm, in_channels=C, d=d, max_batch=mb); ve.set_weights(vw)
-    return ve, un
+from benchutil import timeit  # noqa: E402
 
 
 def structures(rng, n, max_sites=40):
@@ -67,13 +45,14 @@ def main():
     from icsg3d_amd import _lib as L
     from icsg3d_amd.evaluate import emd, reconstruction_metrics
     from icsg3d_amd.matrices import make_jobs, voxelise
+    from icsg3d_amd.synthetic import random_engines
     from icsg3d_amd.watershed import refine_atoms
     assert L.device_count() >= 1, "no HIP device visible"
     rng = np.random.default_rng(0)
     res = {"reps": a.reps, "warmup": a.warmup}
 
     B, d, C = 32, 32, 4
-    ve, un = engines(d, C, B)
+    ve, un = random_engines(d, C, B)
     s = structures(rng, B)
     jobs = make_jobs(B)
     M, _, p = voxelise(s, d=d, want=("M", "p"))

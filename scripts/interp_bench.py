@@ -16,36 +16,13 @@ import json
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timeit(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return {"median_ms": 1e3 * float(np.median(ts)), "min_ms": 1e3 * float(np.min(ts)), "reps": reps}
-
-
-def engines(d, C, mb, seed=0):
-    from icsg3d_amd.engine import UnetEngine, VaeEngine
-    from icsg3d_amd.synthetic import bn_state_defaults, glorot_params, unet_param_shapes, vae_param_shapes
-    us = unet_param_shapes(C, 95)
-    uw = glorot_params(us, seed=seed); uw.update(bn_state_defaults(us))
-    vs = vae_param_shapes(C, 10, (16, 32, 64, 128), 256, d)
-    vw = glorot_params(vs, seed=seed + 1); vw.update(bn_state_defaults(vs))
-    pm = UnetEngine(in_channels=C, d=d, max_batch=mb); pm.set_weights(uw)
-    un = UnetEngine(in_channels=C, d=d, max_batch=mb); un.set_weights(uw)
-    ve = VaeEngine(pm, in_channels=C, d=d, max_batch=mb); ve.set_weights(vw)
-    return ve, un
+from benchutil import timeit  # noqa: E402
 
 
 def main():
@@ -59,9 +36,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "interp_bench.json"))
     a = ap.parse_args()
     from icsg3d_amd.interpolate import lerp_path
-    from icsg3d_amd.synthetic import synthetic_batch
+    from icsg3d_amd.synthetic import random_engines, synthetic_batch
     P, S, d, C = a.pairs, a.steps, a.d, a.channels
-    ve, un = engines(d, C, P * S)
+    ve, un = random_engines(d, C, P * S)
     rng = np.random.default_rng(0)
     X = synthetic_batch(2 * P, d, C, seed=1, noise=1e-3)[0].astype(np.float32)
     A, B = np.ascontiguousarray(X[0::2]), np.ascontiguousarray(X[1::2])

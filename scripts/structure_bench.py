@@ -27,16 +27,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timeit(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return {"median_ms": 1e3 * float(np.median(ts)), "min_ms": 1e3 * float(np.min(ts)), "reps": reps}
+from benchutil import timeit  # noqa: E402
 
 
 def draw(rng, n, lo, hi, S):
@@ -111,6 +102,7 @@ def main():
     a = ap.parse_args()
     from icsg3d_amd import _lib as L
     from icsg3d_amd import structures as S
+    from icsg3d_amd.evaluate import predicted_coordinates
     assert L.device_count() >= 1, "no HIP device visible"
     rng = np.random.default_rng(0)
     res = {"reps": a.reps, "warmup": a.warmup}
@@ -142,6 +134,7 @@ def main():
     l_prime = np.array([s[2] for s in structs])
     dv = (l_prime + 2 * l_prime * 0.25) / d
     mus = [(s[1] + eps * s[2] - dv[i] / 2.0) / dv[i] for i, s in enumerate(structs)]          # voxel-frame centroids
+    minmax = np.stack([np.zeros_like(l_prime), 1.5 * l_prime], -1)           # coordinate channels that read back as l_prime
     vol = {"density": rng.random((B, d, d, d)).astype(np.float32), "species": rng.integers(0, 95, (B, d, d, d)).astype(np.uint8),
            "mask": rng.integers(0, 2, (B, d, d, d)).astype(np.uint8)}
     tmp = tempfile.mkdtemp(prefix="structure_bench_")
@@ -152,10 +145,9 @@ def main():
             os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
         writer = S.ResultsWriter(out_dir, 90, 90, 120) if stage else None
         atoms = [None] * B
+        xyz = predicted_coordinates([(s[0], mu) for s, mu in zip(structs, mus)], minmax, eps, d)
         for i in range(B):
-            species_sample = structs[i][0]
-            mu = np.array(mus[i], np.float64).reshape(len(species_sample), 3)
-            mu = mu * dv[i] - (eps * l_prime[i]) + (dv[i] / 2.0)
+            species_sample, mu = structs[i][0], xyz[i]
             coords = np.concatenate([np.array(species_sample, np.float64).reshape(-1, 1), mu], axis=-1)
             np.save(os.path.join(out_dir, "densities", "%d.npy" % i), vol["density"][i])
             np.save(os.path.join(out_dir, "species", "%d.npy" % i), vol["species"][i])

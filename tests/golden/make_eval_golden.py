@@ -38,7 +38,7 @@ def _functions(path, names, ns):
 
 
 def reference_shift():
-    """The statements `lpp = ...` and `mu = mu * dv_pred[i] - ...` of eval.py's scoring loop, as one callable."""
+    """The statements `lpp = ...` and `mu = ... - lpp + ...` of eval.py's scoring loop, as one callable."""
     tree = ast.parse(open(REF_EVAL).read())
     stmts = []
     for node in ast.walk(tree):

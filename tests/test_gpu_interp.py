@@ -157,12 +157,9 @@ def test_latent_path_slerp_bound_fallbacks_and_determinism():
 
 # ---------------------------------------------------------------- engines
 def _weights(C, d, seed):
-    from icsg3d_amd.synthetic import bn_state_defaults, glorot_params, unet_param_shapes, vae_param_shapes
+    from icsg3d_amd.synthetic import random_weights
     rng = np.random.default_rng(seed)
-    us = unet_param_shapes(C, 95)
-    uw = glorot_params(us, seed=seed); uw.update(bn_state_defaults(us))
-    vs = vae_param_shapes(C, 10, (16, 32, 64, 128), 256, d)
-    vw = glorot_params(vs, seed=seed + 1); vw.update(bn_state_defaults(vs))
+    uw, vw = random_weights(d, C, seed)
     for w in (uw, vw):                       # non-trivial moving statistics: eval-mode BatchNorm everywhere
         for k in list(w):
             if k.endswith("moving_var"):
@@ -174,11 +171,8 @@ def _weights(C, d, seed):
 
 
 def _vae(C, d, mb, seed):
-    from icsg3d_amd.engine import UnetEngine, VaeEngine
-    uw, vw = _weights(C, d, seed)
-    pm = UnetEngine(in_channels=C, d=d, max_batch=mb); pm.set_weights(uw)
-    ve = VaeEngine(pm, in_channels=C, d=d, max_batch=mb); ve.set_weights(vw)
-    return ve
+    from icsg3d_amd.synthetic import random_engines
+    return random_engines(d, C, mb, unet=False, weights=_weights(C, d, seed))[0]
 
 
 def _pairs(rng, P, d, C):
@@ -461,11 +455,12 @@ def test_script_end_to_end(tmp_path):
     spec = importlib.util.spec_from_file_location("interpolate_script", os.path.join(ROOT, "interpolate.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
+    from icsg3d_amd.cli import load_models
     from icsg3d_amd.interpolate import interpolate_pairs
     cwd = os.getcwd()
     os.chdir(tmp_path)
     try:
-        vae, _ = mod.models("t", 16, 1, 3, 20, True, 5, True)
+        vae, _ = load_models("t", 16, 1, 3, 20, True, 5, True)
     finally:
         os.chdir(cwd)
     A, B, ids, _ = mod.synthetic_pairs(3, 16, 1, 5)

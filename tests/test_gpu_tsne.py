@@ -233,15 +233,8 @@ def test_two_runs_give_the_same_bits():
 
 # ---------------------------------------------------------------- 7. the device-resident path
 def _vae(C, d, mb, seed=3):
-    from icsg3d_amd.engine import UnetEngine, VaeEngine
-    from icsg3d_amd.synthetic import bn_state_defaults, glorot_params, unet_param_shapes, vae_param_shapes
-    us = unet_param_shapes(C, 95)
-    uw = glorot_params(us, seed=seed); uw.update(bn_state_defaults(us))
-    vs = vae_param_shapes(C, 10, (16, 32, 64, 128), 256, d)
-    vw = glorot_params(vs, seed=seed + 1); vw.update(bn_state_defaults(vs))
-    pm = UnetEngine(in_channels=C, d=d, max_batch=mb); pm.set_weights(uw)
-    ve = VaeEngine(pm, in_channels=C, d=d, max_batch=mb); ve.set_weights(vw)
-    return ve
+    from icsg3d_amd.synthetic import random_engines
+    return random_engines(d, C, mb, seed, unet=False)[0]
 
 
 def test_device_resident_codes_and_latent_map_bit_for_bit():

@@ -148,3 +148,31 @@ def test_shard_ids_equal_whole_batches():
     assert m._dp_is_writer() and m._dp_barrier() is None and m._dp_attach(object()) is None
     m._dp = (None, 3, 8, False, False)
     assert not m._dp_is_writer()
+
+
+def test_checkpoint_paths_are_the_reference_layout():
+    from icsg3d_amd.cli import checkpoint_paths
+    assert checkpoint_paths("x") == (os.path.join("saved_models", "vae", "x", "vae_weights_x.best.hdf5"),
+                                     os.path.join("saved_models", "unet", "x", "unet_weights_x.best.hdf5"),
+                                     os.path.join("saved_models", "unet", "x", "unet_weights_x.best.h5"))
+
+
+def test_atoms_out_result_applies_the_failed_rule():
+    """_AtomsOut.result() on hand-filled counts / stats, no device: a sample with more kept components than rows is
+    marked failed and yields no atoms; the others' atoms come from their rows; the key set is the *_to_atoms one."""
+    from icsg3d_amd.engine import _AtomsOut
+    out = _AtomsOut(3, 4, 2, want_density=True, want_regions=False)
+    assert out.stats.shape == (3, 2, 11) and out.counts.shape == (3, 2) and out.regions is None and out.bounds is None
+    out.counts[:] = [[5, 2], [7, 3], [0, 0]]                 # sample 1: 3 kept components, 2 rows
+    out.stats[0, 0, :5] = (8, 4, 4, 8, 12)                   # species 8, 4 voxels, coordinate sums
+    out.stats[0, 1, :5] = (26, 2, 6, 6, 2)
+    out.stats[1, 0, :5] = (3, 5, 5, 5, 5)
+    r = out.result()
+    assert set(r) == {"species", "mask", "density", "coord_minmax", "regions", "n_components", "n_atoms", "stats", "bounds",
+                      "atoms", "failed"}
+    assert r["failed"].tolist() == [False, True, False]
+    assert r["n_components"].tolist() == [5, 7, 0] and r["n_atoms"].tolist() == [2, 0, 0]
+    assert r["atoms"][0][0] == [8, 26] and r["atoms"][1] == ([], []) and r["atoms"][2] == ([], [])
+    assert np.array_equal(np.array(r["atoms"][0][1]), [[1.0, 2.0, 3.0], [3.0, 3.0, 1.0]])
+    assert r["density"].shape == (3, 4, 4, 4) and r["regions"] is None and r["bounds"] is None
+    assert _AtomsOut(2, 4, 2, False, True).result()["bounds"].shape == (2, 2, 8)

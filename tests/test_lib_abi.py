@@ -40,7 +40,8 @@ def test_product_package_never_imports_the_oracle():
     """... nor do the entry scripts and the helpers under scripts/: the checkers that use the oracle live under tests/tools/.
     Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg touch oracle/."""
     trees = [os.path.join(ROOT, "icsg3d_amd"), os.path.join(ROOT, "scripts")]
-    files = [os.path.join(ROOT, f) for f in ("train_unet.py", "train_vae.py", "generate.py")]
+    files = [os.path.join(ROOT, f) for f in ("train_unet.py", "train_vae.py", "generate.py", "eval.py", "interpolate.py",
+                                               "latent_map.py", "create_matrices.py")]
     for tree in trees:
         for dirpath, _, names in os.walk(tree):
             files += [os.path.join(dirpath, f) for f in names if f.endswith(".py")]

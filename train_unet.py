@@ -22,6 +22,7 @@ import sys
 
 import numpy as np
 
+from icsg3d_amd.cli import checkpoint_paths
 from icsg3d_amd.dataparallel import from_env, shard_ids
 from icsg3d_amd.unet.data import SyntheticUnetGenerator, UnetDataGenerator
 from icsg3d_amd.unet.get_weights import get_weights
@@ -55,10 +56,10 @@ if __name__ == "__main__":
     mode, d = a.name, a.d
     path = os.path.join("data", mode, "matrices")
     input_shape = (d, d, d, a.channels)
-    weights_dir = os.path.join("saved_models", "unet", mode)
+    weights = checkpoint_paths(mode)[1]
+    weights_dir = os.path.dirname(weights)
     os.makedirs(weights_dir, exist_ok=True)
     os.makedirs(os.path.join("output/unet", mode), exist_ok=True)
-    weights = os.path.join(weights_dir, "unet_weights_" + mode + ".best.hdf5")
 
     if a.synthetic:
         n_train = int(a.synthetic * a.split)

@@ -13,6 +13,7 @@ import json
 import os
 import sys
 
+from icsg3d_amd.cli import checkpoint_paths
 from icsg3d_amd.dataparallel import from_env, shard_ids
 from icsg3d_amd.utils import data_split
 from icsg3d_amd.vae.data import SyntheticVAEGenerator, VAEDataGenerator
@@ -46,11 +47,9 @@ if __name__ == "__main__":
     path = os.path.join("data", mode, "matrices")
     csv_path = os.path.join("data", mode, mode + ".csv")
     input_shape = (d, d, d, a.channels)
-    weights_dir = os.path.join("saved_models", "vae", mode)
-    os.makedirs(weights_dir, exist_ok=True)
+    weights, _, perceptual_model = checkpoint_paths(mode)
+    os.makedirs(os.path.dirname(weights), exist_ok=True)
     os.makedirs(os.path.join("output", "vae", mode), exist_ok=True)
-    weights = os.path.join(weights_dir, "vae_weights_" + mode + ".best.hdf5")
-    perceptual_model = os.path.join("saved_models", "unet", mode, "unet_weights_" + mode + ".best.h5")
 
     if a.synthetic:
         n_train = int(a.synthetic * a.split) // (bs * world) * bs
