@@ -100,6 +100,11 @@ SIGNATURES = {
     "ics_op_match_emd": (C.c_int, [_D, _I32, _D, _I32, C.c_int, _D, _I32]),
     "ics_op_structure_screen": (C.c_int, [_I32, _I32, _D, _D, _D, C.c_int, C.c_double, _D, _D, _D, _D, _I32, _I32, _I32,
                                           _I32, _D, _I32]),
+    "ics_op_render_density": (C.c_int, [_F, C.c_int, C.c_int, C.c_int, C.c_int, _F, C.c_int, C.c_float, C.c_float, _D,
+                                        C.c_int, C.c_int, _F]),
+    "ics_op_render_labels": (C.c_int, [_I32, C.c_int, C.c_int, _F, C.c_int, C.c_float, _D, C.c_int, C.c_int, _F]),
+    "ics_op_render_atoms": (C.c_int, [_I32, _I32, _D, C.c_int, C.c_int, C.c_double, _F, C.c_int, _D, C.c_int, C.c_int, _F]),
+    "ics_vae_render_resident": (C.c_int, [_H, C.c_int, C.c_int, C.c_float, C.c_float, _F, _D, C.c_int, C.c_int, _F]),
     "ics_op_latent_path": (C.c_int, [_F, _F, C.c_int, C.c_int, _D, C.c_int, C.c_int, _F]),
     "ics_vae_interpolate": (C.c_int, [_H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, _F, _F, _F]),
     "ics_vae_interpolate_to_unet_atoms": (C.c_int, [_H, _H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, C.c_float,

@@ -12,6 +12,7 @@
 #include "structure.h"
 #include "latent.h"
 #include "tsne.h"
+#include "render.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -285,6 +286,7 @@ struct Net {
   float tap_coef[4] = {0, 0, 0, 0};
   double* tap_partial[4] = {nullptr, nullptr, nullptr, nullptr};
   int resident_batch = 0;
+  int recon_batch = 0;                // VAE: samples the last decoder pass left in recon (ics_vae_render_resident)
   hipEvent_t timer_ev[2] = {nullptr, nullptr};   // ics_net_timer_start / _stop
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
@@ -1859,6 +1861,7 @@ static int vae_decode_fwd(Net& n, int B, bool training) {
   ICS_TRY(conv_forward(n, *r.dout, B, training, training, n.tp(r.dout->t_b)));
   const size_t cnt = n.rows(*r.dout, B) * n.C;
   ICS_TRY(launch_bn_apply(n.st, r.dout->s, r.dout->scale, r.dout->shift, ACT_RELU, cnt, n.C, n.recon));
+  n.recon_batch = B;
   return 0;
 }
 
@@ -2967,6 +2970,71 @@ int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, cons
   ICS_TRY(op_stream(&st));
   return structure_screen_op(st, offsets, species, xyz, abc, angles, batch, tol, lattice, volume, frac, min_dist, min_pair,
                              n_close, valid, reason, nearest, hist);
+}
+// view_results.py's pictures (viz.py:43-66, 184-233; view_results.py:152-183): render.h has the camera and the compositing
+int ics_op_render_density(const float* vol, int batch, int d, int stride_c, int channel, const float* lut, int mode,
+                          float alpha, float floor, const double* camera, int width, int height, float* out) {
+  ICS_TRY(render_check("ics_op_render_density", batch, d, camera, width, height, out));
+  ICS_TRY(render_density_check("ics_op_render_density", stride_c, channel, lut, mode, alpha, floor));
+  ICS_CHECK(vol != nullptr, "ics_op_render_density: null vol");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return render_density_op(st, vol, batch, d, stride_c, channel, lut, mode, alpha, floor, camera, width, height, out);
+}
+int ics_op_render_labels(const int32_t* labels, int batch, int d, const float* palette, int npal, float alpha,
+                         const double* camera, int width, int height, float* out) {
+  ICS_TRY(render_check("ics_op_render_labels", batch, d, camera, width, height, out));
+  ICS_CHECK(labels && palette, "ics_op_render_labels: null argument (labels, palette)");
+  ICS_CHECK(npal >= 1, "ics_op_render_labels: npal must be >= 1");
+  ICS_CHECK(alpha >= 0.f && alpha <= 1.f, "ics_op_render_labels: alpha must be in [0, 1]");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return render_labels_op(st, labels, batch, d, palette, npal, alpha, camera, width, height, out);
+}
+int ics_op_render_atoms(const int32_t* offsets, const int32_t* species, const double* xyz, int batch, int d, double radius,
+                        const float* palette, int npal, const double* camera, int width, int height, float* out) {
+  const std::string op = "ics_op_render_atoms: ";
+  ICS_TRY(render_check("ics_op_render_atoms", batch, d, camera, width, height, out));
+  ICS_CHECK(offsets && palette, op + "null argument (offsets, palette)");
+  ICS_CHECK(npal >= 1, op + "npal must be >= 1");
+  ICS_CHECK(std::isfinite(radius) && radius > 0.0, op + "radius must be finite and > 0");
+  ICS_CHECK(offsets[0] == 0, op + "offsets[0] must be 0");
+  for (int b = 0; b < batch; ++b)
+    ICS_CHECK(offsets[b + 1] >= offsets[b], op + "offsets decrease at sample " + std::to_string(b));
+  ICS_CHECK((species && xyz) || offsets[batch] == 0, op + "null species or xyz");
+  for (long long k = 0; k < 3LL * offsets[batch]; ++k)
+    ICS_CHECK(std::isfinite(xyz[k]), op + "non-finite coordinate");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return render_atoms_op(st, offsets, species, xyz, batch, d, radius, palette, npal, camera, width, height, out);
+}
+// The density picture of what the engine already holds: the resident input (which = 0) or recon as the last decoder pass
+// left it (which = 1), channel 0, read where it lies.  Only the colour table goes up and the pictures come back.
+int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, float floor, const float* lut,
+                            const double* camera, int width, int height, float* out) {
+  ICS_TRY(require_kind(vae, 1));
+  Net& n = vae->n;
+  ICS_CHECK(which == 0 || which == 1, "ics_vae_render_resident: which must be 0 (input) or 1 (reconstruction)");
+  ICS_CHECK(n.resident_batch > 0, "ics_vae_render_resident: no resident batch: call ics_vae_upload_batch or ics_vae_voxelise_batch first");
+  ICS_CHECK(which == 0 || n.recon_batch >= n.resident_batch,
+            "ics_vae_render_resident: no reconstruction of the resident batch: run ics_vae_reconstruct_resident_to_unet_atoms first");
+  const int batch = n.resident_batch;
+  ICS_TRY(render_check("ics_vae_render_resident", batch, n.d, camera, width, height, out));
+  ICS_TRY(render_density_check("ics_vae_render_resident", n.C, 0, lut, mode, alpha, floor));
+  RenderView<double> view;
+  ICS_CHECK(render_view(camera, n.d, width, height, &view) == 0, "ics_vae_render_resident: camera must be finite");
+  ICS_HIP(hipSetDevice(n.device));
+  const size_t lut_b = 3 * kRenderLutRows * sizeof(float), img_b = (size_t)batch * width * height * 16;
+  unsigned char* base = nullptr;
+  ICS_TRY(scratch_get(4096 + img_b, &base));
+  float* d_lut = reinterpret_cast<float*>(base);
+  float* d_out = reinterpret_cast<float*>(base + 4096);
+  ICS_HIP(hipMemcpyAsync(d_lut, lut, lut_b, hipMemcpyHostToDevice, n.st));
+  ICS_TRY(render_density_device(n.st, which ? n.recon : n.x_in, batch, n.d, n.C, 0, d_lut, mode, alpha, floor, view, width,
+                                height, d_out));
+  ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  return 0;
 }
 int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps, int mode,
                        float* path) {

@@ -226,6 +226,59 @@ static int structure_walk(void) {
   return 0;
 }
 
+/* view_results.py's pictures: the three ops over more than one picture and an image that is no multiple of the tile, an
+ * empty atom set, every refusal, and the ops still usable afterwards. */
+static int render_walk(void) {
+  enum { B = 3, D = 8, C = 4, W = 50, H = 37, NA = 4 };
+  static float vol[B * D * D * D * C], lut[256 * 3], out[B * W * H * 4];
+  static int32_t lab[B * D * D * D];
+  float pal[2 * 3] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+  int32_t off[B + 1] = {0, 3, 3, 4}, sp[NA] = {1, 12, -5, 7};
+  double xyz[NA * 3] = {4, 4, 4, 5, 4.5, 3, 2, 3, 6, 1, 1, 1}, cam[2] = {30.0, -60.0}, top[2] = {90.0, 0.0};
+  int bad = 0;
+  for (int i = 0; i < B * D * D * D * C; ++i) vol[i] = (float)((i * 37) % 101) * 0.012f - 0.1f;
+  for (int i = 0; i < B * D * D * D; ++i) lab[i] = (i * 13) % 7 == 0 ? i % 40 : 0;
+  for (int i = 0; i < 256 * 3; ++i) lut[i] = (float)i / 768.f;
+#define DENS(v, b, d, sc, ch, l, m, a, c, w, h, o) ics_op_render_density(v, b, d, sc, ch, l, m, a, -1.f, c, w, h, o)
+  OK(DENS(vol, B, D, C, 0, lut, 0, 0.2f, cam, W, H, out));
+  OK(DENS(vol, B, D, C, 3, lut, 1, 1.f, top, W, H, out));
+  OK(DENS(vol, 1, 1, 1, 0, lut, 1, 0.5f, cam, 1, 1, out));
+  OK(ics_op_render_labels(lab, B, D, pal, 2, 0.5f, cam, W, H, out));
+  OK(ics_op_render_atoms(off, sp, xyz, B, D, 1.5, pal, 2, top, W, H, out));
+  bad += ics_op_render_atoms(off, NULL, NULL, 1, D, 1.5, pal, 2, cam, W, H, out) == 0;   /* atoms without arrays */
+  { int32_t none[2] = {0, 0}; OK(ics_op_render_atoms(none, NULL, NULL, 1, D, 1.5, pal, 2, cam, W, H, out)); }
+  bad += DENS(NULL, B, D, C, 0, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, 0, D, C, 0, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, 0, C, 0, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, 257, C, 0, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, C, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, 0, 0, lut, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, NULL, 0, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 2, 0.2f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, 1.5f, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, NAN, cam, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, 0.2f, NULL, W, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, 0.2f, cam, 0, H, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, 0.2f, cam, W, 4097, out) == 0;
+  bad += DENS(vol, B, D, C, 0, lut, 0, 0.2f, cam, W, H, NULL) == 0;
+  bad += ics_op_render_density(vol, B, D, C, 0, lut, 0, 0.2f, NAN, cam, W, H, out) == 0;
+  cam[1] = INFINITY; bad += DENS(vol, B, D, C, 0, lut, 0, 0.2f, cam, W, H, out) == 0; cam[1] = -60.0;
+#undef DENS
+  bad += ics_op_render_labels(NULL, B, D, pal, 2, 0.5f, cam, W, H, out) == 0;
+  bad += ics_op_render_labels(lab, B, D, NULL, 2, 0.5f, cam, W, H, out) == 0;
+  bad += ics_op_render_labels(lab, B, D, pal, 0, 0.5f, cam, W, H, out) == 0;
+  bad += ics_op_render_labels(lab, B, D, pal, 2, -0.5f, cam, W, H, out) == 0;
+  bad += ics_op_render_atoms(NULL, sp, xyz, B, D, 1.5, pal, 2, cam, W, H, out) == 0;
+  bad += ics_op_render_atoms(off, sp, xyz, B, D, 0.0, pal, 2, cam, W, H, out) == 0;
+  bad += ics_op_render_atoms(off, sp, xyz, B, D, 1.5, pal, 0, cam, W, H, out) == 0;
+  off[0] = 1; bad += ics_op_render_atoms(off, sp, xyz, B, D, 1.5, pal, 2, cam, W, H, out) == 0; off[0] = 0;
+  off[2] = 2; bad += ics_op_render_atoms(off, sp, xyz, B, D, 1.5, pal, 2, cam, W, H, out) == 0; off[2] = 3;
+  xyz[4] = NAN; bad += ics_op_render_atoms(off, sp, xyz, B, D, 1.5, pal, 2, cam, W, H, out) == 0; xyz[4] = 4.5;
+  if (bad) { fprintf(stderr, "render: %d invalid calls accepted\n", bad); return 1; }
+  OK(ics_op_render_labels(lab, B, D, pal, 2, 0.5f, cam, W, H, out));
+  return 0;
+}
+
 /* The reconstruction chain's refusals: no resident batch, a U-Net of other channels, a resident batch above the U-Net's
  * max_batch. */
 static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const ics_unet_config* uc, const float* x,
@@ -237,7 +290,21 @@ static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const i
   OK(ics_vae_create(vc, unet, &v2));
   bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, unet, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
                                                     NULL) == 0;
+  /* ics_vae_render_resident: refused without a resident batch, the reconstruction refused before a decoder pass */
+  static float lut[256 * 3];
+  const double cam[2] = {30.0, -60.0};
+  float* img = (float*)malloc((size_t)B * 20 * 13 * 4 * sizeof(float));
+  bad += ics_vae_render_resident(v2, 0, 1, 0.5f, -1.f, lut, cam, 20, 13, img) == 0;
   OK(ics_vae_upload_batch(v2, x, cond, eps, B));
+  OK(ics_vae_render_resident(v2, 0, 1, 0.5f, -1.f, lut, cam, 20, 13, img));
+  bad += ics_vae_render_resident(v2, 1, 1, 0.5f, -1.f, lut, cam, 20, 13, img) == 0;
+  bad += ics_vae_render_resident(v2, 2, 1, 0.5f, -1.f, lut, cam, 20, 13, img) == 0;
+  bad += ics_vae_render_resident(unet, 0, 1, 0.5f, -1.f, lut, cam, 20, 13, img) == 0;
+  bad += ics_vae_render_resident(v2, 0, 1, 0.5f, -1.f, NULL, cam, 20, 13, img) == 0;
+  bad += ics_vae_render_resident(v2, 0, 1, 0.5f, -1.f, lut, cam, 20, 13, NULL) == 0;
+  OK(ics_vae_reconstruct_resident_to_unet_atoms(v2, unet, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats, NULL));
+  OK(ics_vae_render_resident(v2, 1, 0, 0.2f, 0.1f, lut, cam, 20, 13, img));
+  free(img);
   bad += ics_vae_reconstruct_resident_to_unet_atoms(v2, unet, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, NULL, stats,
                                                     NULL) == 0;
   bad += ics_vae_reconstruct_resident_to_unet_atoms(unet, v2, 0.8f, 3, 16, NULL, NULL, NULL, NULL, NULL, counts, stats,
@@ -601,6 +668,7 @@ int main(void) {
   if (match_walk()) return 1;
   if (structure_walk()) return 1;
   if (latent_walk()) return 1;
+  if (render_walk()) return 1;
   if (tsne_walk(NULL, NULL, NULL, NULL, NULL, 0)) return 1;
   {   /* single-op entry points */
     const int B = 1, S = 8, Cin = 32, Cout = 64;

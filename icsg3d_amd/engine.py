@@ -428,6 +428,24 @@ class VaeEngine(_Net):
                 self._h, unet._h, float(thresh), int(min_voxels), int(max_atoms), *out.args(s)))
         return out.result()
 
+    def render_resident(self, which=0, cam=None, size=256, mode="value", alpha=0.2, floor=-1.0, lut=None):
+        """The density picture (icsg3d_amd.render.density) of channel 0 of what the engine holds, read where it lies:
+        which = 0 the resident input batch, 1 the reconstruction the last decoder pass left (view_results.py:152-183,
+        the M panels).  float32 premultiplied RGBA (resident batch, height, width, 4), the bits render.density gives
+        for the same values."""
+        from . import render as R
+        if not self._resident:
+            raise RuntimeError("no resident batch: call upload_batch or voxelise_batch first")
+        w, h = R._size(size)
+        cam = R._cam(cam)
+        lut = np.ascontiguousarray(R.VIRIDIS if lut is None else lut, np.float32)
+        if lut.shape != (256, 3):
+            raise ValueError("lut must be (256, 3)")
+        out = np.empty((self._resident, h, w, 4), np.float32)
+        L.check(self._lib.ics_vae_render_resident(self._h, int(which), R._mode(mode), float(alpha), float(floor),
+                                                  L.fptr(lut), L.f64ptr(cam), w, h, L.fptr(out)))
+        return out
+
     def _interp_args(self, a, b, cond, eps_a, eps_b, alpha, mode):
         a, b, cond, eps_a, eps_b = _f32(a), _f32(b), _f32(cond), _f32(eps_a), _f32(eps_b)
         P, d = a.shape[0], self.d

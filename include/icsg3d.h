@@ -299,6 +299,42 @@ int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, cons
                             double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid, int32_t* reason,
                             double* nearest, int32_t* hist);
 
+/* ---------------------------------------------------------------- pictures (view_results.py)
+ * The panels of view_results.py:152-183 -- viz.py:184-233 (the voxel panels of M, S and the watershed regions) and
+ * viz.py:43-66 (plot_points_3d, the atoms) -- as ray casts at full resolution; the reference shrinks every volume to 10^3
+ * because matplotlib draws one polygon set per voxel.  The picture is this library's own: no parity with matplotlib's
+ * polygon renderer is claimed.
+ * Camera: camera[2] = (elev, azim) in degrees as matplotlib's 3-D axes define them (defaults 30, -60); orthographic, width x
+ * height pixels, looking at the grid centre, array axis 0 = x, 1 = y, 2 = z (up); the pixel-to-ray formula and the
+ * compositing rule (path-length weighted front-to-back "over") are written down once, in icsg3d_amd/csrc/render.h.
+ * out: float32 premultiplied RGBA in [0, 1], [batch][height][width][4].
+ * All four refuse, with nothing written: batch outside [1, 65535], d outside [1, 256], an image side outside [1, 4096], a
+ * null argument, a camera that is not finite, alpha outside [0, 1], npal < 1.
+ * The three ics_op_* take HOST pointers, any batch (chunked internally), synchronous, the calling thread's op stream.
+ *
+ * ics_op_render_density (viz.py:184-233 on M): vol [batch][d][d][d][stride_c] float32, channel `channel`.  Colour is
+ * lut[idx] (lut [256][3] float32) with matplotlib's index rule for floats: idx = int(v * 256), v == 1 -> 255, v < 0 -> 0,
+ * v > 1 -> 255; NaN is empty.  mode 0: every voxel with v > floor has opacity alpha (floor < 0: the reference's picture,
+ * everything drawn at alpha = 0.2); mode 1: opacity alpha * clip(v, 0, 1). */
+int ics_op_render_density(const float* vol, int batch, int d, int stride_c, int channel, const float* lut, int mode,
+                          float alpha, float floor, const double* camera, int width, int height, float* out);
+/* viz.py:184-233 on S and on the watershed regions: labels [batch][d][d][d] int32; label 0 (or below) is empty, label k is
+ * drawn in palette[(k - 1) % npal] (palette [npal][3] float32) at opacity alpha (the reference: 0.5). */
+int ics_op_render_labels(const int32_t* labels, int batch, int d, const float* palette, int npal, float alpha,
+                         const double* camera, int width, int height, float* out);
+/* viz.py:43-66 (plot_points_3d): atoms in the packed layout of ics_op_structure_screen (sample b holds atoms offsets[b] ..
+ * offsets[b+1]), xyz in voxel units, each a sphere of `radius` voxels.  Analytic ray-sphere intersection in fp64, the
+ * nearest hit wins; colour palette[species mod npal] times max(0, n . eye), alpha 1; a miss is transparent.  Also refused:
+ * offsets that do not start at 0 or decrease, a non-finite coordinate, radius <= 0. */
+int ics_op_render_atoms(const int32_t* offsets, const int32_t* species, const double* xyz, int batch, int d, double radius,
+                        const float* palette, int npal, const double* camera, int width, int height, float* out);
+/* view_results.py:152-183, the M panels: the density picture of what the VAE engine holds, channel 0, read where it lies in
+ * device memory.  which = 0: the resident input batch; which = 1: the reconstruction as the last decoder pass left it.
+ * out [resident batch][height][width][4] is bit-identical to ics_op_render_density on the same values.  Refused: no
+ * resident batch (also after ics_vae_interpolate, which clears the mark), which = 1 before any decoder pass over it. */
+int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, float floor, const float* lut,
+                            const double* camera, int width, int height, float* out);
+
 /* ---------------------------------------------------------------- interpolation (interpolate.py)
  * interpolate(a, b, cond, vae, num_interps, return_zs, max_alpha) (interpolate.py:47-64): encode both crystals under one
  * condition, walk a straight line between their SAMPLED codes (the encoder's third output, F8), decode every point.
