@@ -395,8 +395,9 @@ __device__ __forceinline__ ElemCtx decode_elem(size_t row, int c, int S, int lg)
   return e;
 }
 
-// Thread layout for [M][C] tensors with power-of-two C: CB = min(C/VW, 256) column groups across
-// threads, RPP = 256/CB rows per pass; column groups of 256*VW looped when C/VW > 256.
+// Thread layout for [M][C] tensors: CB = min(C/VW, 256) column groups across threads, RPP = 256/CB rows per pass (when CB
+// does not divide 256 the threads past RPP*CB repeat rows of the next pass and their sums are never read); column groups
+// of 256*VW looped when C/VW > 256, the last one ragged unless C is a multiple of 256*VW (predicate cv).
 template <int VW>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(LayerBwd L, int rows_per_block,
                                                              float* __restrict__ partial) {
@@ -408,10 +409,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(LayerBwd L, int rows
   const size_t r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
   for (int cg = 0; cg < CV; cg += 256) {
     const int c = (cg + tc) * VW;
+    const bool cv = cg + tc < CV;          // the last group of a width that is no multiple of 256 * VW is ragged
     float a1[VW], a2[VW];
 #pragma unroll
     for (int j = 0; j < VW; ++j) a1[j] = a2[j] = 0.f;
-    for (size_t row = r0 + tr; row < r1; row += RPP) {
+    for (size_t row = r0 + tr; cv && row < r1; row += RPP) {
       const ElemCtx e = decode_elem(row, c, L.S, L.lgS);
       Vec<VW> xh;
       const Vec<VW> d = elem_d<VW>(L, row, e, vload<VW>(L.s + row * C + c), &xh);
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(LayerBwd L, int rows
 #pragma unroll
     for (int j = 0; j < VW; ++j) { sh1[t * VW + j] = a1[j]; sh2[t * VW + j] = a2[j]; }
     __syncthreads();
-    for (int col = t; col < CB * VW; col += 256) {
+    for (int col = t; col < CB * VW && cg * VW + col < C; col += 256) {
       // column `col` of this group: thread (r, tc = col / VW) holds it at [.. * VW + col % VW]
       const int tcc = col / VW, jj = col % VW;
       float s1 = 0.f, s2 = 0.f;
@@ -488,14 +490,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(LayerBwd L, int rows_
   double tap_sq = 0.0;       // sum (s - tap_ref)^2 over this block's elements (perceptual loss term)
   for (int cg = 0; cg < CV; cg += 256) {
     const int c = (cg + tc) * VW;
+    const bool cv = cg + tc < CV;          // ragged last group: see bn_bwd_reduce_kernel
     Vec<VW> k1, k2, sg;
 #pragma unroll
     for (int j = 0; j < VW; ++j) { k1.v[j] = 0.f; k2.v[j] = 0.f; sg.v[j] = 1.f; }
-    if (L.has_bn) { k1 = vload<VW>(c1 + c); k2 = vload<VW>(c2 + c); sg = vload<VW>(L.scale + c); }
+    if (L.has_bn && cv) { k1 = vload<VW>(c1 + c); k2 = vload<VW>(c2 + c); sg = vload<VW>(L.scale + c); }
     float acc[VW];
 #pragma unroll
     for (int j = 0; j < VW; ++j) acc[j] = 0.f;
-    for (size_t row = r0 + tr; row < r1; row += RPP) {
+    for (size_t row = r0 + tr; cv && row < r1; row += RPP) {
       const ElemCtx e = decode_elem(row, c, L.S, L.lgS);
       const Vec<VW> sv = vload<VW>(L.s + row * C + c);
       Vec<VW> xh, g;
@@ -528,7 +531,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(LayerBwd L, int rows_
 #pragma unroll
       for (int j = 0; j < VW; ++j) sh1[t * VW + j] = acc[j];
       __syncthreads();
-      for (int col = t; col < CB * VW; col += 256) {
+      for (int col = t; col < CB * VW && cg * VW + col < C; col += 256) {
         const int tcc = col / VW, jj = col % VW;
         float sacc = 0.f;
         for (int r = 0; r < RPP; ++r) sacc += sh1[(r * CB + tcc) * VW + jj];

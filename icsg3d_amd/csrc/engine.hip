@@ -441,6 +441,8 @@ static int alloc_layer(Net& n, ConvLayer& L, bool need_bwd, bool pooled) {
     ICS_TRY(n.alloc(&L.dy, M * L.Cout));
     ICS_TRY(n.alloc(&L.dA, M * L.CinG));
     ICS_TRY(n.alloc(&L.c1c2, (size_t)2 * L.Cout));
+    // (layers whose width is neither -- VAE filters such as 6 or 34 -- keep db_partial == nullptr on purpose: conv_backward
+    // then does not defer their bias-gradient finalize, the scalar BatchNorm-backward kernels put the partials into ws_bwd)
     if ((L.Cout & (L.Cout - 1)) == 0 || L.Cout % 4 == 0) {
       // 512: the head's backward-data launch; M / 128: a Winograd backward-data launch (one row per tile block); the
       // BatchNorm-backward pass: its block count is NOT monotone in the batch (rows per block are rounded up to what one
@@ -535,8 +537,10 @@ static int enable_split_up(Net& n, ConvLayer& L) {
   if (n.flags & CF_NO_UPSPLIT) return 0;
   const ConvSrc& up = L.src[L.nsrc - 1];
   const int Cs = L.nsrc == 2 ? L.src[0].C : 0;
+  // Cout % 4: the per-tap pooling of dy (launch_pool27) moves four output channels per thread; other widths keep the
+  // direct kernels (filters such as (6, 10, 32, 64): d2 is 32 -> 10 over an upsampled source)
   if (!up.up || (L.nsrc == 2 && L.src[0].up) || L.taps != 27 || L.S < 2 || L.CinG != L.Cin || Cs % 32 || up.C % 32 ||
-      up.bcast)
+      up.bcast || L.Cout % 4)
     return 0;
   L.split_up = true;
   L.Cs = Cs; L.Cu = up.C;
@@ -639,8 +643,8 @@ static int alloc_workspaces(Net& n, bool need_bwd) {
       }
       LayerBwd lb{};
       lb.B = b; lb.S = L.S; lb.lgS = ilog2(L.S); lb.C = L.Cout;
-      // Cout may be a non power of two only for the head, which never goes through layer_bwd
-      if ((L.Cout & (L.Cout - 1)) == 0) bwd = std::max(bwd, layer_bwd_workspace_floats(lb));
+      // every layer but the U-Net head goes through layer_bwd, whatever its width (VAE filters need not be powers of two)
+      if (&L != n.head) bwd = std::max(bwd, layer_bwd_workspace_floats(lb));
       wg = std::max(wg, conv_wgrad_workspace_floats(g, L.src, L.nsrc));
       if (L.wino_w)
         wg = std::max(wg, conv_wino_wgrad_workspace_floats(L.split_up ? geom_skip_wgrad(L, b) : g));
@@ -2134,8 +2138,11 @@ static int net_common_init(Net& n) {
 int ics_unet_create(const ics_unet_config* cfg, ics_net** out) {
   ICS_CHECK(cfg && out, "null argument");
   ICS_CHECK(cfg->d >= 8 && (cfg->d & (cfg->d - 1)) == 0, "d must be a power of two >= 8");
-  ICS_CHECK(cfg->in_channels >= 1 && cfg->max_batch >= 1 && cfg->num_classes >= 2 && cfg->num_classes <= 127,
-            "bad U-Net config");
+  ICS_CHECK(cfg->in_channels >= 1, "bad U-Net config: in_channels must be >= 1");
+  ICS_CHECK(cfg->max_batch >= 1, "bad U-Net config: max_batch must be >= 1");
+  // 127: labels are uint8 class ids, the head's [soft | sig] logits are one row of at most 128 columns (head_kernel's
+  // column buffer, launch_head_bnfuse's one thread per column) -- the same range as ics_op_unet_head
+  ICS_CHECK(cfg->num_classes >= 2 && cfg->num_classes <= 127, "bad U-Net config: num_classes must be in [2, 127]");
   auto h = std::make_unique<ics_net>();
   ICS_TRY(net_common_init(h->n));
   ICS_TRY(unet_build(h->n, *cfg));
@@ -2147,6 +2154,21 @@ int ics_unet_create(const ics_unet_config* cfg, ics_net** out) {
 int ics_vae_create(const ics_vae_config* cfg, ics_net* pm, ics_net** out) {
   ICS_CHECK(cfg && out, "null argument");
   ICS_CHECK(pm == nullptr || pm->n.kind == 0, "perceptual model must be a U-Net engine");
+  // every size that becomes a buffer length or a GEMM dimension, before anything is allocated or launched
+  ICS_CHECK(cfg->in_channels >= 1, "bad VAE config: in_channels must be >= 1");
+  ICS_CHECK(cfg->max_batch >= 1, "bad VAE config: max_batch must be >= 1");
+  ICS_CHECK(cfg->cond_shape >= 1, "bad VAE config: cond_shape must be >= 1");
+  ICS_CHECK(cfg->latent_dim >= 1, "bad VAE config: latent_dim must be >= 1");
+  // 16384: a layer input without a BatchNorm in front of it (the pooled encoder stages, [z | cond] into dec_dense) is read
+  // through the identity-affine buffer of the convolution launchers (conv_igemm.hip fix_src), which is that wide; the
+  // bound also keeps every size product of add_conv / alloc_layer inside an int
+  ICS_CHECK(cfg->in_channels <= 16384 && cfg->cond_shape <= 16384 && cfg->in_channels * (1 + cfg->cond_shape) <= 16384,
+            "bad VAE config: in_channels * (1 + cond_shape) must be <= 16384");
+  ICS_CHECK(cfg->latent_dim <= 16384 && cfg->latent_dim + cfg->cond_shape <= 16384,
+            "bad VAE config: latent_dim + cond_shape must be <= 16384");
+  for (int i = 0; i < 4; ++i)
+    ICS_CHECK(cfg->filters[i] >= 1 && cfg->filters[i] <= 16384,
+              "bad VAE config: filters[" + std::to_string(i) + "] must be in [1, 16384]");
   auto h = std::make_unique<ics_net>();
   ICS_TRY(net_common_init(h->n));
   ICS_TRY(vae_build(h->n, *cfg, pm ? &pm->n : nullptr));
@@ -3284,8 +3306,8 @@ int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, con
                      float metrics[5], double sums[7]) {
   const int bce = ((mode >> 2) & 1) << 1;
   mode &= 3;
-  ICS_CHECK(x && wsoft && bsoft && wsig && bsig && labels && M >= 1 && ncls >= 2 && ncls <= 128 && mode >= 0 && mode <= 2,
-            "bad head arguments");
+  ICS_CHECK(x && wsoft && bsoft && wsig && bsig && labels && M >= 1 && mode >= 0 && mode <= 2, "bad head arguments");
+  ICS_CHECK(ncls >= 2 && ncls <= 127, "bad head arguments: ncls must be in [2, 127] (ics_unet_config.num_classes)");
   Net n;
   ICS_TRY(op_prepare(n));
   const int nz = ncls + 1, Kpad = 128, Npad = round_up(nz, 32);

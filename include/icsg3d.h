@@ -43,7 +43,8 @@ typedef struct ics_net ics_net; /* opaque: a U-Net or a DFC-VAE engine */
  *                                                   (unet/unet.py:245-259) */
 typedef struct ics_unet_config {
   int in_channels;   /* C of input_shape=(d,d,d,C): 1 or 4          (unet/unet.py:240) */
-  int num_classes;   /* 95                                          (unet/unet.py:237) */
+  int num_classes;   /* 95; accepted: 2 .. 127 (uint8 labels; the [soft | sig] logits are one row of <= 128 columns).
+                      * 95 takes the fused head kernels, every other count the 1x1x1 GEMM + head_kernel (unet/unet.py:237) */
   int d;             /* grid edge, power of two >= 8 (32; 64 is a build extension) */
   int max_batch;     /* largest batch a single call may carry                             */
   float lr;          /* Adam learning rate                          (unet/unet.py:241,245) */
@@ -107,6 +108,17 @@ typedef struct ics_vae_config {
   int bn_unbias;
 } ics_vae_config;
 
+/* Accepted ranges (anything else is refused here, with ics_last_error naming the option, before any allocation):
+ *   in_channels >= 1, max_batch >= 1, d a power of two >= 16;
+ *   cond_shape >= 1, latent_dim >= 1, filters[i] in [1, 16384], latent_dim + cond_shape <= 16384,
+ *   in_channels * (1 + cond_shape) <= 16384 (no layer input wider than 16384 channels: the width of the identity
+ *   affine the convolution launchers read a BatchNorm-less source through) -- any width inside these: multiples of 32
+ *   take the Winograd / vector kernels,
+ *   multiples of 4 the four-channel element-wise kernels, everything else the scalar paths (same results, slower);
+ *   widths past one block's 256 column groups (above 256, above 1024 for multiples of 4) loop over the columns;
+ *   the analytic fold of the tiled condition into e0 exists for in_channels == 1 with filters[0] == 16 or 32, other
+ *   widths run e0 as the (1 + cond_shape) * in_channels -channel convolution it is.
+ * alpha, beta and pm_layer_weights are plain scalars of the loss (0 allowed). */
 int ics_vae_create(const ics_vae_config* cfg, ics_net* perceptual_unet, ics_net** out);
 
 /* encoder.predict([M, cond]) -> (z_mean, z_log_var, z)  (generate.py:196, interpolate.py:50-59);
@@ -468,7 +480,8 @@ int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int 
  * weighted_categorical_crossentropy / binary_crossentropy / f1_m / wr_m (unet/unet.py:159-221,252-259).
  * x [M][128], wsoft [128][ncls], bsoft [ncls], wsig [128], bsig [1], labels uint8 [M]; loss_weight <= 0: the scalar ncls.
  * mode 0: out [M][ncls+1] = probabilities (soft | sig); 1: metrics[5] and sums[7] (ics_unet_metric_sums) only;
- * 2: also out = dLoss/dlogits; + 4: binary_crossentropy in the logits form (ics_unet_config.bce_from_logits).  fused != 0: the GEMM inside the loss kernel (M % 16 == 0, ncls == 95), else GEMM + loss kernel. */
+ * 2: also out = dLoss/dlogits; + 4: binary_crossentropy in the logits form (ics_unet_config.bce_from_logits).  fused != 0: the GEMM inside the loss kernel (M % 16 == 0, ncls == 95), else GEMM + loss kernel.
+ * ncls: 2 .. 127, the range of ics_unet_config.num_classes. */
 int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
                      const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
                      float metrics[5], double sums[7]);

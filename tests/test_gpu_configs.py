@@ -25,6 +25,9 @@ def _reset_bn(eng, w):
             eng.set_tensor(k, np.ones_like(w[k]))
 
 
+VAE_ALPHA, VAE_BETA = 0.5, 3e-4      # the loss constants the engines of this file are configured with (the defaults)
+
+
 def _vae_pair(B, d, lr=5e-4):
     from icsg3d_amd.engine import UnetEngine, VaeEngine
     from icsg3d_amd.synthetic import glorot_params, unet_param_shapes, vae_param_shapes
@@ -32,7 +35,7 @@ def _vae_pair(B, d, lr=5e-4):
     PV = glorot_params(vae_param_shapes(1, d=d), 3)
     ue = UnetEngine(in_channels=1, d=d, max_batch=B, lr=1e-4)
     ue.set_weights(PU)
-    ve = VaeEngine(ue, in_channels=1, d=d, max_batch=B, lr=lr)
+    ve = VaeEngine(ue, in_channels=1, d=d, max_batch=B, lr=lr, alpha=VAE_ALPHA, beta=VAE_BETA)
     ve.set_weights(PV)
     return ue, ve, PU, PV
 
@@ -49,7 +52,7 @@ def _vae_properties(B, d, steps=3, lr=5e-4):
     assert np.all(np.isfinite(ms))
     assert ms[-1][0] < ms[0][0]
     for m in ms:
-        assert abs(m[0] - (m[2] + 0.5 * m[1] + 3e-4 * m[3])) <= 2e-5 * abs(m[0])
+        assert abs(m[0] - (m[2] + VAE_ALPHA * m[1] + VAE_BETA * m[3])) <= 2e-5 * abs(m[0])
     w1 = ve.get_weights()
     pm_after = ue.get_weights()
     assert all(np.array_equal(pm_before[k], pm_after[k]) for k in pm_before)      # frozen, BN moving stats included
