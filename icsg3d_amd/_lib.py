@@ -105,6 +105,16 @@ SIGNATURES = {
     "ics_op_render_labels": (C.c_int, [_I32, C.c_int, C.c_int, _F, C.c_int, C.c_float, _D, C.c_int, C.c_int, _F]),
     "ics_op_render_atoms": (C.c_int, [_I32, _I32, _D, C.c_int, C.c_int, C.c_double, _F, C.c_int, _D, C.c_int, C.c_int, _F]),
     "ics_vae_render_resident": (C.c_int, [_H, C.c_int, C.c_int, C.c_float, C.c_float, _F, _D, C.c_int, C.c_int, _F]),
+    "ics_op_render_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F,
+                                      C.c_int, _F]),
+    "ics_vae_render_slice_resident": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F, C.c_int, _F]),
+    "ics_unet_render_slice_resident": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F, C.c_int, _F]),
+    "ics_op_kde_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_H)]),
+    "ics_op_kde_destroy": (C.c_int, [_H]),
+    "ics_op_kde_append": (C.c_int, [_H, _F, C.c_int]),
+    "ics_op_kde_append_vae": (C.c_int, [_H, _H, C.c_int, C.c_int]),
+    "ics_op_kde_evaluate": (C.c_int, [_H, _D, C.c_int, _D, _D, _I32, C.POINTER(C.c_int)]),
+    "ics_op_render_lines": (C.c_int, [_D, C.c_int, C.c_int, _D, _F, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, _F]),
     "ics_op_latent_path": (C.c_int, [_F, _F, C.c_int, C.c_int, _D, C.c_int, C.c_int, _F]),
     "ics_vae_interpolate": (C.c_int, [_H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, _F, _F, _F]),
     "ics_vae_interpolate_to_unet_atoms": (C.c_int, [_H, _H, _F, _F, _F, _F, _F, C.c_int, _D, C.c_int, C.c_int, C.c_float,

@@ -13,6 +13,7 @@
 #include "latent.h"
 #include "tsne.h"
 #include "render.h"
+#include "monitor.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -287,6 +288,13 @@ struct Net {
   double* tap_partial[4] = {nullptr, nullptr, nullptr, nullptr};
   int resident_batch = 0;
   int recon_batch = 0;                // VAE: samples the last decoder pass left in recon (ics_vae_render_resident)
+  int enc_batch = 0;                  // VAE: samples of the resident batch the last encoder pass left in zml / z_buf, and
+  int recon_fresh = 0;                // samples a decoder pass has left in recon since that batch came; a new resident
+                                      // batch clears both (ics_op_kde_append_vae, ics_vae_render_slice_resident)
+  int pred_kind = 0, pred_batch = 0;  // U-Net: what the last predict entry left in the head's buffers (1 probabilities in
+                                      // head->s, 2 uint8 labels in head->dy) and for how many samples; any other forward
+                                      // pass and a new resident batch clear it (ics_unet_render_slice_resident)
+  int labels_batch = 0;               // U-Net: samples of the resident batch whose true labels are in `labels`
   hipEvent_t timer_ev[2] = {nullptr, nullptr};   // ics_net_timer_start / _stop
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
@@ -1436,6 +1444,7 @@ static int unet_pack(Net& n) { return run_pack_table(n, unet_pack_jobs); }
 // trunk forward; upto_c10 for the perceptual sub-model (lattice_vae.py:257-270)
 static int unet_forward_trunk(Net& n, int B, bool training, bool update_moving, bool upto_c10, const float* input) {
   ICS_TRY(unet_pack(n));
+  n.pred_kind = 0;
   UnetRefs r = unet_refs(n);
   (r.c1->pad_in ? r.c1->vsrc[0] : r.c1->src[0]).p = input;
   const int last = upto_c10 ? 8 : 14;
@@ -1717,6 +1726,8 @@ static int unet_upload(Net& n, const float* x, const unsigned char* labels, int 
   ICS_HIP(hipMemcpyAsync(n.x_in, x, M * n.C * sizeof(float), hipMemcpyHostToDevice, n.st));
   if (labels) ICS_HIP(hipMemcpyAsync(n.labels, labels, M, hipMemcpyHostToDevice, n.st));
   n.resident_batch = B;
+  n.labels_batch = labels ? B : 0;
+  n.pred_kind = 0;                    // what the last predict left belongs to the batch this one replaces
   return 0;
 }
 
@@ -1854,6 +1865,7 @@ static int vae_encode_fwd(Net& n, int B, bool training) {
   ICS_TRY(conv_forward(n, *r.encd, B, training, training, n.tp(r.encd->t_b)));
   ICS_TRY(conv_forward(n, *r.zml, B, training, training, n.tp(r.zml->t_b)));
   ICS_TRY(launch_sampling(n.st, r.zml->s, 2 * n.latent, n.latent, n.eps_in, n.cond_in, n.ncond, B, n.z_buf, n.zc));
+  n.enc_batch = B;
   return 0;
 }
 
@@ -1866,6 +1878,7 @@ static int vae_decode_fwd(Net& n, int B, bool training) {
   const size_t cnt = n.rows(*r.dout, B) * n.C;
   ICS_TRY(launch_bn_apply(n.st, r.dout->s, r.dout->scale, r.dout->shift, ACT_RELU, cnt, n.C, n.recon));
   n.recon_batch = B;
+  n.recon_fresh = B;
   return 0;
 }
 
@@ -2033,6 +2046,7 @@ static int vae_upload(Net& n, const float* x, const float* cond, const float* ep
   if (cond) ICS_HIP(hipMemcpyAsync(n.cond_in, cond, (size_t)B * n.ncond * sizeof(float), hipMemcpyHostToDevice, n.st));
   if (eps) ICS_HIP(hipMemcpyAsync(n.eps_in, eps, (size_t)B * n.latent * sizeof(float), hipMemcpyHostToDevice, n.st));
   n.resident_batch = B;
+  n.enc_batch = 0; n.recon_fresh = 0;
   return 0;
 }
 
@@ -2393,6 +2407,7 @@ int ics_unet_predict(ics_net* net, const float* x, int batch, float* soft, float
   }
   ICS_HIP(hipStreamSynchronize(n.st));
   n.prof.resolve();
+  n.pred_kind = 1; n.pred_batch = batch;
   return 0;
 }
 
@@ -2408,6 +2423,7 @@ int ics_unet_predict_labels(ics_net* net, const float* x, int batch, float thres
   if (species) ICS_HIP(hipMemcpyAsync(species, d_species, M, hipMemcpyDeviceToHost, n.st));
   if (mask) ICS_HIP(hipMemcpyAsync(mask, d_mask, M, hipMemcpyDeviceToHost, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
+  n.pred_kind = 2; n.pred_batch = batch;
   return 0;
 }
 
@@ -2423,9 +2439,13 @@ int ics_unet_predict_resident(ics_net* net, int labels_only, float thresh) {
   if (labels_only) {
     const size_t M = n.rows(*n.head, batch);
     unsigned char* d_species = reinterpret_cast<unsigned char*>(n.head->dy);
-    return unet_head_labels(n, batch, thresh, d_species, d_species + M, n.st);
+    ICS_TRY(unet_head_labels(n, batch, thresh, d_species, d_species + M, n.st));
+    n.pred_kind = 2; n.pred_batch = batch;
+    return 0;
   }
-  return unet_head_loss(n, batch, 0, 0);
+  ICS_TRY(unet_head_loss(n, batch, 0, 0));
+  n.pred_kind = 1; n.pred_batch = batch;
+  return 0;
 }
 
 // Two engines of one process on ONE stream (joint U-Net + DFC-VAE training on one GPU): `net` gives up its own stream and
@@ -2567,6 +2587,8 @@ int ics_unet_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t
   ICS_TRY(voxelise_check(s, jobs, batch, n.d, eps_frac, label_frac, n.ncls));
   ICS_TRY(voxelise_engine(n.st, n.vox, s, jobs, batch, n.d, eps_frac, label_frac, n.x_in, n.C, n.labels, nullptr, 0));
   n.resident_batch = batch;
+  n.labels_batch = batch;
+  n.pred_kind = 0;
   return 0;
 }
 
@@ -2620,6 +2642,7 @@ int ics_vae_voxelise_batch(ics_net* net, const ics_structures* s, const int32_t*
                             {eps, n.eps_in, (size_t)batch * n.latent * sizeof(float)}};
   ICS_TRY(voxelise_engine(n.st, n.vox, s, jobs, batch, n.d, eps_frac, label_frac, n.x_in, n.C, nullptr, blobs, 2));
   n.resident_batch = batch;
+  n.enc_batch = 0; n.recon_fresh = 0;
   return 0;
 }
 int ics_vae_train_step_resident(ics_net* net, float* metrics) {
@@ -3057,6 +3080,103 @@ int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, floa
   ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
   return 0;
+}
+// ---------------------------------------------------------------- training monitors (monitor.h has the formulas)
+int ics_op_render_slice(const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
+                        const float* lut, const float* range_or_null, int zoom, float* out) {
+  ICS_TRY(slice_check("ics_op_render_slice", dtype, batch, d, stride_c, channel, axis, index, lut, range_or_null, zoom, out));
+  ICS_CHECK(vol != nullptr, "ics_op_render_slice: null vol");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return slice_op(st, vol, dtype, batch, d, stride_c, channel, axis, index, lut, range_or_null, zoom, out);
+}
+// the slice picture of `count` samples of a buffer the engine holds: only the colour table goes up, the pictures come back
+static int slice_resident(Net& n, const char* who, const void* src, int dtype, int stride_c, int channel, int count, int axis,
+                          int index, const float* lut, const float* range, int zoom, float* out) {
+  ICS_TRY(slice_check(who, dtype, count, n.d, stride_c, channel, axis, index, lut, range, zoom, out));
+  const size_t side = (size_t)n.d * zoom, img_b = (size_t)count * side * side * 16, rng_b = slice_range_bytes(count);
+  unsigned char* base = nullptr;
+  ICS_TRY(scratch_get(4096 + rng_b + img_b, &base));
+  float* d_lut = reinterpret_cast<float*>(base);
+  float* d_rng = reinterpret_cast<float*>(base + 4096);
+  float* d_out = reinterpret_cast<float*>(base + 4096 + rng_b);
+  ICS_HIP(hipMemcpyAsync(d_lut, lut, 3 * kMonitorLutRows * sizeof(float), hipMemcpyHostToDevice, n.st));
+  ICS_TRY(slice_device(n.st, src, dtype, slice_layout(n.d, stride_c, channel, axis, index), count, n.d, d_lut, range, d_rng,
+                       zoom, d_out));
+  ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  return 0;
+}
+int ics_vae_render_slice_resident(ics_net* vae, int which, int channel, int count, int axis, int index, const float* lut,
+                                  const float* range_or_null, int zoom, float* out) {
+  ICS_TRY(require_kind(vae, 1));
+  Net& n = vae->n;
+  const std::string op = "ics_vae_render_slice_resident: ";
+  ICS_CHECK(which == 0 || which == 1, op + "which must be 0 (input) or 1 (reconstruction)");
+  ICS_CHECK(n.resident_batch > 0, op + "no resident batch: call ics_vae_upload_batch or ics_vae_voxelise_batch first");
+  ICS_CHECK(count >= 1 && count <= n.resident_batch, op + "count exceeds the resident batch");
+  ICS_CHECK(which == 0 || n.recon_fresh >= count,
+            op + "no reconstruction of these samples: run a decoder pass on the resident batch first");
+  return slice_resident(n, "ics_vae_render_slice_resident", which ? n.recon : n.x_in, 0, n.C, channel, count, axis, index,
+                        lut, range_or_null, zoom, out);
+}
+int ics_unet_render_slice_resident(ics_net* unet, int which, int channel, int count, int axis, int index, const float* lut,
+                                   const float* range_or_null, int zoom, float* out) {
+  ICS_TRY(require_kind(unet, 0));
+  Net& n = unet->n;
+  const std::string op = "ics_unet_render_slice_resident: ";
+  ICS_CHECK(which >= 0 && which <= 3,
+            op + "which must be 0 (input), 1 (argmax species), 2 (sigmoid probability) or 3 (true labels)");
+  ICS_CHECK(n.resident_batch > 0, op + "no resident batch: call ics_unet_upload_batch or ics_unet_voxelise_batch first");
+  ICS_CHECK(count >= 1 && count <= n.resident_batch, op + "count exceeds the resident batch");
+  const char* who = "ics_unet_render_slice_resident";
+  if (which == 0)
+    return slice_resident(n, who, n.x_in, 0, n.C, channel, count, axis, index, lut, range_or_null, zoom, out);
+  ICS_CHECK(channel == 0, op + "channel must be 0 for the species, probability and label volumes");
+  if (which == 1) {
+    ICS_CHECK(n.pred_kind == 2 && n.pred_batch >= count,
+              op + "no argmax species of these samples: run a labels predict (ics_unet_predict_labels, or "
+                   "ics_unet_predict_resident with labels_only) first");
+    return slice_resident(n, who, n.head->dy, 1, 1, 0, count, axis, index, lut, range_or_null, zoom, out);
+  }
+  if (which == 2) {
+    ICS_CHECK(n.pred_kind == 1 && n.pred_batch >= count,
+              op + "no probabilities of these samples: run a probabilities predict (ics_unet_predict, or "
+                   "ics_unet_predict_resident without labels_only) first");
+    return slice_resident(n, who, n.head->s, 0, n.ncls + 1, n.ncls, count, axis, index, lut, range_or_null, zoom, out);
+  }
+  ICS_CHECK(n.labels_batch >= count, op + "no true labels of these samples in the resident batch");
+  return slice_resident(n, who, n.labels, 1, 1, 0, count, axis, index, lut, range_or_null, zoom, out);
+}
+int ics_op_kde_create(int dim, int capacity, ics_kde** out) { return kde_create(dim, capacity, out); }
+int ics_op_kde_destroy(ics_kde* h) { return kde_destroy(h); }
+int ics_op_kde_append(ics_kde* h, const float* codes, int rows) { return kde_append_host(h, codes, rows); }
+// encode -> append with nothing to the host: z_mean is the first half of each row of the zml layer's stored output (as
+// ics_op_tsne_append_vae reads it), the sampled z is z_buf as vae_encode_fwd's sampling kernel left it
+int ics_op_kde_append_vae(ics_kde* h, ics_net* vae, int batch, int which) {
+  ICS_CHECK(h != nullptr, "ics_op_kde_append_vae: null KDE handle");
+  ICS_TRY(require_kind(vae, 1));
+  Net& n = vae->n;
+  ICS_CHECK(which == 0 || which == 1, "ics_op_kde_append_vae: which must be 0 (z_mean) or 1 (the sampled z)");
+  ICS_CHECK(n.device == kde_device(h), "ics_op_kde_append_vae: the engine and the KDE handle are on different devices");
+  ICS_CHECK((int)n.latent == kde_dim(h), "ics_op_kde_append_vae: latent_dim differs from the handle's dim");
+  ICS_CHECK(n.resident_batch > 0 && n.enc_batch > 0,
+            "ics_op_kde_append_vae: no encoder pass on the resident batch yet: call ics_vae_encode first");
+  ICS_CHECK(batch >= 1 && batch <= n.enc_batch, "ics_op_kde_append_vae: batch exceeds the batch the encoder pass ran on");
+  if (which == 1) return kde_append_device(h, n.z_buf, (size_t)n.latent, batch, n.st);
+  VaeRefs r = vae_refs(n);
+  return kde_append_device(h, r.zml->s, 2 * (size_t)n.latent, batch, n.st);
+}
+int ics_op_kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status,
+                        int* count) {
+  return kde_evaluate(h, x, npts, density, bandwidth, status, count);
+}
+int ics_op_render_lines(const double* xy, int ncurves, int npts, const double window[4], const float* palette, int npal,
+                        double width_px, float alpha, int width, int height, float* out) {
+  ICS_TRY(lines_check(xy, ncurves, npts, window, palette, npal, width_px, alpha, width, height, out));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return lines_op(st, xy, ncurves, npts, window, palette, npal, width_px, alpha, width, height, out);
 }
 int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps, int mode,
                        float* path) {

@@ -279,6 +279,204 @@ static int render_walk(void) {
   return 0;
 }
 
+/* The training monitors: the three ops at sizes that are no multiple of a tile or a chunk, every refusal, the resident
+ * slices of both engines with each `which` refused until the pass that fills it has run, and the KDE handle fed from the
+ * host and from the VAE engine. */
+static int monitor_walk(ics_net* unet, ics_net* vae, const float* x, const uint8_t* lab, const float* cond, const float* eps,
+                        int B, int d) {
+  enum { NB = 3, D = 5, SC = 4, Z = 3, NC = 3, NP = 5, W = 37, H = 21, KD = 3, KN = 7, KP = 6 };
+  static float vol[NB * D * D * D * SC], lut[256 * 3], out[NB * D * Z * D * Z * 4], img[W * H * 4];
+  static uint8_t vol8[NB * D * D * D * SC];
+  static int32_t vol32[NB * D * D * D * SC];
+  float range[2] = {0.25f, 0.75f}, pal[2 * 3] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f}, codes[KN * KD];
+  double xy[NC * NP * 2], win[4] = {0.0, 4.0, -1.0, 1.0}, grid[KP], dens[KD * KP], bw[KD];
+  int32_t status[KD];
+  int bad = 0, cnt = 0;
+#define REFUSED(x) do { if ((x) == 0) { ++bad; fprintf(stderr, "monitor: accepted at line %d: %s\n", __LINE__, #x); } } while (0)
+  for (int i = 0; i < NB * D * D * D * SC; ++i) { vol[i] = (float)((i * 37) % 101) / 64.f; vol8[i] = (uint8_t)(i * 7); vol32[i] = i * 13 - 900; }
+  vol[11] = NAN;
+  for (int i = 0; i < 256 * 3; ++i) lut[i] = (float)i / 768.f;
+  for (int c = 0; c < NC; ++c)
+    for (int k = 0; k < NP; ++k) { xy[(c * NP + k) * 2] = (double)k; xy[(c * NP + k) * 2 + 1] = 0.3 * c - 0.1 * k; }
+  xy[(1 * NP + 2) * 2] = NAN;
+  for (int i = 0; i < KN * KD; ++i) codes[i] = i % KD == 2 ? 0.5f : 0.01f * (float)((i * 29) % 53) - 0.2f;
+  for (int k = 0; k < KP; ++k) grid[k] = -3.0 + 1.2 * k;
+#define SLICE(v, t, b, dd, sc, ch, ax, ix, l, r, z, o) ics_op_render_slice(v, t, b, dd, sc, ch, ax, ix, l, r, z, o)
+  for (int ax = 0; ax < 3; ++ax) {
+    OK(SLICE(vol, 0, NB, D, SC, 2, ax, ax + 1, lut, NULL, Z, out));
+    OK(SLICE(vol8, 1, NB, D, SC, 0, ax, 0, lut, range, 1, out));
+    OK(SLICE(vol32, 2, NB, D, SC, 3, ax, D - 1, lut, NULL, 2, out));
+  }
+  OK(SLICE(vol, 0, 1, 1, 1, 0, 0, 0, lut, NULL, 1, out));
+  REFUSED(SLICE(NULL, 0, NB, D, SC, 2, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, NULL, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, NULL, Z, NULL));
+  REFUSED(SLICE(vol, 3, NB, D, SC, 2, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, -1, NB, D, SC, 2, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, 0, D, SC, 2, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, 0, SC, 2, 2, 0, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, 257, SC, 2, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, SC, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, -1, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, 0, 0, 2, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 3, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, -1, 2, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, D, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, -1, lut, NULL, Z, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, NULL, 0, out));
+  REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, NULL, 65, out));
+  REFUSED(SLICE(vol, 0, NB, 256, SC, 2, 2, 2, lut, NULL, 17, out));          /* side 4352 */
+  range[0] = NAN; REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, range, Z, out)); range[0] = 0.25f;
+  range[1] = INFINITY; REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, range, Z, out)); range[1] = 0.75f;
+  range[1] = 0.f; REFUSED(SLICE(vol, 0, NB, D, SC, 2, 2, 2, lut, range, Z, out)); range[1] = 0.75f;
+#undef SLICE
+#define LINES(p, nc, np, w, pl, npl, wp, a, ww, hh, o) ics_op_render_lines(p, nc, np, w, pl, npl, wp, a, ww, hh, o)
+  OK(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, img));
+  OK(LINES(xy, 1, 2, win, pal, 1, 0.25, 1.f, 1, 1, img));
+  REFUSED(LINES(NULL, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, NULL, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, NULL, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, NULL));
+  REFUSED(LINES(xy, NC, 1, win, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, 4097, win, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, 0, NP, win, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, 65536, NP, win, pal, 2, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 0, 1.5, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 0.0, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, NAN, 0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 1.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, -0.5f, W, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, 0, H, img));
+  REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, 4097, img));
+  win[1] = 0.0; REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, img)); win[1] = 4.0;
+  win[3] = -1.0; REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, img)); win[3] = 1.0;
+  win[2] = NAN; REFUSED(LINES(xy, NC, NP, win, pal, 2, 1.5, 0.5f, W, H, img)); win[2] = -1.0;
+#undef LINES
+  {
+    ics_kde* h = NULL;
+    REFUSED(ics_op_kde_create(0, 8, &h));
+    REFUSED(ics_op_kde_create(4097, 8, &h));
+    REFUSED(ics_op_kde_create(KD, 1, &h));
+    REFUSED(ics_op_kde_create(KD, (1 << 20) + 1, &h));
+    REFUSED(ics_op_kde_create(KD, 8, NULL));
+    OK(ics_op_kde_create(KD, KN, &h));
+    OK(ics_op_kde_append(h, codes, 1));
+    REFUSED(ics_op_kde_evaluate(h, grid, KP, dens, bw, status, &cnt));        /* one code */
+    OK(ics_op_kde_append(h, codes + KD, KN - 1));
+    REFUSED(ics_op_kde_append(h, codes, 1));                                  /* over capacity */
+    REFUSED(ics_op_kde_append(NULL, codes, 1));
+    OK(ics_op_kde_evaluate(h, grid, KP, dens, bw, status, &cnt));
+    OK(ics_op_kde_evaluate(h, grid, 1, dens, NULL, NULL, NULL));
+    if (cnt != KN) { fprintf(stderr, "kde: count %d\n", cnt); return 1; }
+    REFUSED(ics_op_kde_evaluate(h, NULL, KP, dens, bw, status, &cnt));
+    REFUSED(ics_op_kde_evaluate(h, grid, KP, NULL, bw, status, &cnt));
+    REFUSED(ics_op_kde_evaluate(h, grid, 0, dens, bw, status, &cnt));
+    REFUSED(ics_op_kde_evaluate(h, grid, 4097, dens, bw, status, &cnt));
+    REFUSED(ics_op_kde_evaluate(NULL, grid, KP, dens, bw, status, &cnt));
+    OK(ics_op_kde_destroy(h));
+    OK(ics_op_kde_destroy(NULL));
+    OK(ics_op_kde_create(KD, KN, &h));
+    codes[4] = INFINITY; REFUSED(ics_op_kde_append(h, codes, 2)); codes[4] = 0.f;
+    REFUSED(ics_op_kde_append(h, NULL, 2));
+    REFUSED(ics_op_kde_append(h, codes, 0));
+    OK(ics_op_kde_destroy(h));
+  }
+  if (vae) {
+    const size_t side = (size_t)d * 2;
+    float* pic = (float*)malloc((size_t)B * side * side * 4 * sizeof(float));
+    static float z[3 * 8 * 256];
+    static double vd[256 * KP];
+    ics_net* v2 = NULL;
+    ics_vae_config vc = {1, 10, 256, {16, 32, 64, 128}, d, B, 5e-4f, 0.5f, 3e-4f, {1.f, 1.f, 1.f, 1.f}, 1};
+    ics_unet_config uc = {1, 95, d, B, 1e-3f, 0.f, 1, 1, 0};
+    ics_net* u2 = NULL;
+    ics_kde* hv = NULL;
+#define VS(n, wh, ch, c, ax, ix, l, r, zz, o) ics_vae_render_slice_resident(n, wh, ch, c, ax, ix, l, r, zz, o)
+#define US(n, wh, ch, c, ax, ix, l, r, zz, o) ics_unet_render_slice_resident(n, wh, ch, c, ax, ix, l, r, zz, o)
+    OK(ics_vae_create(&vc, unet, &v2));
+    REFUSED(VS(v2, 0, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* no resident batch */
+    OK(ics_vae_upload_batch(v2, x, cond, eps, B));
+    OK(VS(v2, 0, 0, B, 2, d / 2, lut, NULL, 2, pic));
+    OK(VS(v2, 0, 0, 1, 0, 0, lut, range, 1, pic));
+    REFUSED(VS(v2, 1, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* no decoder pass */
+    REFUSED(VS(v2, 2, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 1, 1, 2, d / 2, lut, NULL, 2, pic));                  /* channel */
+    REFUSED(VS(v2, 0, 0, B + 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 0, 0, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 0, 1, 3, d / 2, lut, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 0, 1, 2, d, lut, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 0, 1, 2, d / 2, NULL, NULL, 2, pic));
+    REFUSED(VS(v2, 0, 0, 1, 2, d / 2, lut, NULL, 2, NULL));
+    REFUSED(VS(v2, 0, 0, 1, 2, d / 2, lut, NULL, 65, pic));
+    REFUSED(VS(unet, 0, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(VS(NULL, 0, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    OK(ics_vae_encode(v2, x, cond, eps, B, z, z + 8 * 256, z + 16 * 256));
+    {
+      float* rec = (float*)malloc((size_t)B * d * d * d * sizeof(float));
+      OK(ics_vae_decode(v2, z + 16 * 256, cond, B, rec));
+      free(rec);
+    }
+    OK(VS(v2, 1, 0, B, 1, d - 1, lut, NULL, 2, pic));
+    OK(ics_op_kde_create(256, 2 * B + 1, &hv));
+    OK(ics_op_kde_append_vae(hv, v2, B, 1));
+    OK(ics_op_kde_append_vae(hv, v2, B, 0));
+    OK(ics_op_kde_append_vae(hv, v2, 1, 1));
+    REFUSED(ics_op_kde_append_vae(hv, v2, 1, 1));                           /* over capacity */
+    OK(ics_op_kde_evaluate(hv, grid, KP, vd, NULL, NULL, &cnt));
+    OK(ics_op_kde_destroy(hv));
+    OK(ics_op_kde_create(256, 4 * B, &hv));
+    REFUSED(ics_op_kde_append_vae(hv, v2, B + 1, 1));
+    REFUSED(ics_op_kde_append_vae(hv, v2, 0, 1));
+    REFUSED(ics_op_kde_append_vae(hv, v2, 1, 2));
+    REFUSED(ics_op_kde_append_vae(hv, unet, 1, 1));
+    REFUSED(ics_op_kde_append_vae(hv, NULL, 1, 1));
+    REFUSED(ics_op_kde_append_vae(NULL, v2, 1, 1));
+    OK(ics_op_kde_destroy(hv));
+    OK(ics_op_kde_create(7, 4, &hv)); REFUSED(ics_op_kde_append_vae(hv, v2, 1, 1)); OK(ics_op_kde_destroy(hv));
+    OK(ics_net_destroy(v2));
+    OK(ics_unet_create(&uc, &u2));
+    REFUSED(US(u2, 0, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* no resident batch */
+    {
+      float* soft = (float*)malloc((size_t)B * d * d * d * 95 * sizeof(float));
+      OK(ics_unet_predict(u2, x, B, soft, NULL));                              /* uploads without labels */
+      free(soft);
+    }
+    OK(US(u2, 0, 0, B, 2, d / 2, lut, NULL, 2, pic));
+    OK(US(u2, 2, 0, B, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, 1, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* probabilities only */
+    REFUSED(US(u2, 3, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* no labels uploaded */
+    OK(ics_unet_upload_batch(u2, x, lab, B));
+    OK(US(u2, 3, 0, B, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, 2, 0, B, 2, d / 2, lut, NULL, 2, pic));                  /* the predict was of the batch before */
+    OK(ics_unet_predict_resident(u2, 1, 0.8f));
+    OK(US(u2, 1, 0, B, 0, 1, lut, range, 1, pic));
+    REFUSED(US(u2, 2, 0, 1, 2, d / 2, lut, NULL, 2, pic));                  /* labels only */
+    OK(ics_unet_predict_resident(u2, 0, 0.8f));
+    OK(US(u2, 2, 0, 1, 1, 0, lut, NULL, 2, pic));
+    REFUSED(US(u2, 1, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, 4, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, -1, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, 2, 1, 1, 2, d / 2, lut, NULL, 2, pic));                  /* channel of a one-channel volume */
+    REFUSED(US(u2, 0, 1, 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(u2, 0, 0, B + 1, 2, d / 2, lut, NULL, 2, pic));
+    REFUSED(US(vae, 0, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+    {
+      float mm[5];
+      OK(ics_unet_test_step(u2, x, lab, B, mm));                               /* another forward pass discards the predict */
+      REFUSED(US(u2, 2, 0, 1, 2, d / 2, lut, NULL, 2, pic));
+      OK(US(u2, 3, 0, B, 2, d / 2, lut, NULL, 2, pic));
+    }
+    OK(ics_net_destroy(u2));
+#undef VS
+#undef US
+    free(pic);
+  }
+#undef REFUSED
+  if (bad) { fprintf(stderr, "monitor: %d invalid calls accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "monitor: no error message\n"); return 1; }
+  return 0;
+}
+
 /* The reconstruction chain's refusals: no resident batch, a U-Net of other channels, a resident batch above the U-Net's
  * max_batch. */
 static int reconstruct_refusals(ics_net* unet, const ics_vae_config* vc, const ics_unet_config* uc, const float* x,
@@ -608,6 +806,7 @@ static int run(int d, int C, int B, int with_comm) {
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
   if (B >= 2 && B <= 8 && tsne_walk(vae, unet, x, cond, eps, B)) return 1;
   if (reconstruct_refusals(unet, &vc, &uc, x, cond, eps, B)) return 1;
+  if (C == 1 && B >= 2 && B <= 8 && monitor_walk(unet, vae, x, lab, cond, eps, B, d)) return 1;
   if (ics_unet_train_step(unet, x, lab, B + 1, mm) == 0) { fprintf(stderr, "max_batch check missing\n"); return 1; }
   int rows = 0;
   OK(ics_net_profile_count(unet, &rows));
@@ -669,6 +868,7 @@ int main(void) {
   if (structure_walk()) return 1;
   if (latent_walk()) return 1;
   if (render_walk()) return 1;
+  if (monitor_walk(NULL, NULL, NULL, NULL, NULL, NULL, 0, 0)) return 1;
   if (tsne_walk(NULL, NULL, NULL, NULL, NULL, 0)) return 1;
   {   /* single-op entry points */
     const int B = 1, S = 8, Cin = 32, Cout = 64;

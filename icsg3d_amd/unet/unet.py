@@ -74,8 +74,8 @@ def _to_labels(y, num_classes):
 
 class TrainingPlot:
     """Loss-curve callback (unet/unet.py:39-157).  Records the per-epoch logs and writes
-    unet_loss.png when matplotlib is importable; the segmentation slice plots are plotting-only
-    and out of scope."""
+    unet_loss.png when matplotlib is importable; the segmentation slice plots are drawn on the GPU by
+    icsg3d_amd.monitor.UnetMonitor (train_generator(..., monitor=True))."""
 
     def __init__(self, val_gen, sdir):
         self.val_gen, self.sdir = val_gen, sdir
@@ -293,11 +293,17 @@ class AtomUnet(DataParallelMixin):
             self._host_weights.update({k: np.asarray(v, np.float32) for k, v in w.items()})
 
     # ---- reference methods
-    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/"):
+    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/", monitor=False):
+        """monitor=True: the writer rank also draws TrainingPlot's pictures on the GPU (icsg3d_amd.monitor.UnetMonitor):
+        the segmentation sheets on a new best val_loss and the loss curve every epoch, without matplotlib."""
         print("Training...")
         callbacks = [_BestCheckpoint(self.model, self.filepath)]
         if self._dp_is_writer():
             callbacks.append(TrainingPlot(val_gen, output_dir))
+            if monitor:
+                from ..monitor import UnetMonitor
+                callbacks.append(UnetMonitor(val_gen, output_dir))
+                callbacks[-1].set_model(self)
         self.model.fit_generator(generator=train_gen, validation_data=val_gen, use_multiprocessing=False,
                                  workers=4, epochs=epochs, callbacks=callbacks)
         self._dp_barrier()                               # rank 0 has finished writing the best checkpoint

@@ -347,6 +347,76 @@ int ics_op_render_atoms(const int32_t* offsets, const int32_t* species, const do
 int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, float floor, const float* lut,
                             const double* camera, int width, int height, float* out);
 
+/* ---------------------------------------------------------------- training monitors
+ * What the reference's two train loops draw when the validation loss improves: TrainingPlot.plot_segmentations,
+ * plot_binary and plot_losses (unet/unet.py:39-157) and LatticeDFCVAE.plot_reconstructions, plot_samples, plot_kde and
+ * plot_losses (vae/lattice_vae.py:327-337, 359-436), as three operations.  Their formulas are written down once, in
+ * icsg3d_amd/csrc/monitor.h; no text is drawn, and no parity with matplotlib's resampling, antialiasing or layout is
+ * claimed -- the colour index of a slice and the KDE are the parity claims.
+ *
+ * ics_op_render_slice: imshow(V[b, :, :, index, c]) with vmin / vmax the slice's own minimum and maximum.  vol
+ * [batch][d][d][d][stride_c] of float32 (dtype 0), uint8 (1) or int32 (2), HOST pointer; channel `channel`, plane `index`
+ * of array axis `axis`; row and column of the picture are the two remaining axes in array order, row 0 at the top; every
+ * voxel becomes zoom x zoom pixels.  range_or_null: (vmin, vmax), or NULL for each image's own minimum and maximum over its
+ * finite values.  Colour, in fp32: t = (v - vmin) / (vmax - vmin), index = min(255, (int)(t * 256)), t < 0 -> 0 (the rule
+ * of ics_op_render_density after the normalisation); vmax == vmin -> 0 (matplotlib's Normalize); a non-finite value is left
+ * out of the range and drawn transparent.  lut [256][3] float32.  out: float32 premultiplied RGBA, alpha 1,
+ * [batch][d zoom][d zoom][4].  Any batch (chunked internally), synchronous, the calling thread's op stream.
+ * Refused, with nothing written: a null argument, batch outside [1, 65535], d outside [1, 256], dtype, axis, index or
+ * channel out of range, zoom outside [1, 64], an image side d * zoom above 4096, a range that is not finite or has
+ * vmax < vmin. */
+int ics_op_render_slice(const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
+                        const float* lut, const float* range_or_null, int zoom, float* out);
+/* The same picture of the first `count` samples of what an engine holds, read where it lies in device memory and
+ * bit-identical to ics_op_render_slice on the same values.
+ * VAE, which = 0: the resident input batch; 1: the reconstruction a decoder pass has left since that batch came (a new
+ * resident batch discards it here, so a picture never pairs an input with the reconstruction of the batch before).
+ * U-Net, which = 0: the resident input batch; 1: the uint8 argmax species of the last labels predict
+ * (ics_unet_predict_labels, ics_unet_predict_resident with labels_only); 2: the sigmoid probability of the last
+ * probabilities predict (ics_unet_predict, ics_unet_predict_resident without labels_only); 3: the true labels uploaded with
+ * the resident batch.  channel must be 0 for which = 1, 2, 3.
+ * Also refused: no resident batch, count above it, VAE which = 1 before a decoder pass over `count` samples of this resident batch, U-Net
+ * which = 1 after a probabilities-only predict (or none), which = 2 after a labels-only predict (or none), which = 3 for a
+ * batch uploaded without labels.  Any other forward pass of the U-Net engine (a train or test step, a fused tail that
+ * drives it) and a new resident batch discard what the last predict left. */
+int ics_vae_render_slice_resident(ics_net* vae, int which, int channel, int count, int axis, int index, const float* lut,
+                                  const float* range_or_null, int zoom, float* out);
+int ics_unet_render_slice_resident(ics_net* unet, int which, int channel, int count, int axis, int index, const float* lut,
+                                   const float* range_or_null, int zoom, float* out);
+
+/* plot_kde (vae/lattice_vae.py:359-386): scipy.stats.gaussian_kde of every latent dimension, one launch for all of them,
+ * entirely in fp64 over float32 codes z [n][dim] kept on the device.  For dimension j: var_j the sample variance (ddof = 1,
+ * two passes), h2_j = var_j * n^(-2/5) (Scott's rule), density[j][k] = sum_i exp(-(x_k - z_ij)^2 / (2 h2_j)) /
+ * (n sqrt(2 pi h2_j)).  bandwidth [dim] = sqrt(h2_j) and status [dim] are optional: status 1 marks a dimension with h2_j == 0
+ * or not finite, whose density row is NaN (scipy raises LinAlgError there; here the call succeeds: a collapsed dimension is
+ * what the plot is for); *count (optional) = n.
+ * ics_op_kde_append takes HOST codes [rows][dim]; ics_op_kde_append_vae takes `batch` rows of what the VAE engine's last
+ * encoder pass left, device to device: which = 0 z_mean, 1 the sampled z.  A non-finite code on that path is not seen by
+ * the host and gives its dimension status 1.
+ * Refused: a null argument, dim outside [1, 4096], capacity outside [2, 2^20], appending past the capacity, a non-finite
+ * host code, evaluating with fewer than 2 codes, npts outside [1, 4096], a NaN grid point, an engine of another latent
+ * width or device, no encoder pass since the engine's resident batch came (an upload alone is not one), batch above the
+ * batch that pass ran on. */
+typedef struct ics_kde ics_kde; /* opaque: the codes appended so far */
+int ics_op_kde_create(int dim, int capacity, ics_kde** out);
+int ics_op_kde_destroy(ics_kde* h);
+int ics_op_kde_append(ics_kde* h, const float* codes, int rows);
+int ics_op_kde_append_vae(ics_kde* h, ics_net* vae, int batch, int which);
+int ics_op_kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status,
+                        int* count);
+
+/* plot_losses and the KDE curves: ncurves polylines of npts points, xy [ncurves][npts][2] float64 in data units, HOST
+ * pointer.  A point that is not finite breaks the line (frames, tick marks and shorter curves are NaN-padded polylines).
+ * window = (x0, x1, y0, y1) maps onto width x height pixels: px = (x - x0) / (x1 - x0) width, py = (1 - (y - y0) /
+ * (y1 - y0)) height.  A curve covers a pixel by max over its segments of clamp(width_px / 2 + 0.5 - dist, 0, 1), dist the
+ * distance from the pixel centre to the segment; curves are composited "over" in index order at opacity alpha * coverage in
+ * colour palette[curve % npal] (palette [npal][3] float32), in fp64, rounded to float32 once.  out: premultiplied RGBA
+ * [height][width][4].  Synchronous, the calling thread's op stream.
+ * Refused: a null argument, npts outside [2, 4096], ncurves outside [1, 65535], an image side outside [1, 4096], a window
+ * that is not finite or has x0 == x1 or y0 == y1, width_px <= 0, alpha outside [0, 1], npal < 1. */
+int ics_op_render_lines(const double* xy, int ncurves, int npts, const double window[4], const float* palette, int npal,
+                        double width_px, float alpha, int width, int height, float* out);
+
 /* ---------------------------------------------------------------- interpolation (interpolate.py)
  * interpolate(a, b, cond, vae, num_interps, return_zs, max_alpha) (interpolate.py:47-64): encode both crystals under one
  * condition, walk a straight line between their SAMPLED codes (the encoder's third output, F8), decode every point.

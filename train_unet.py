@@ -43,6 +43,8 @@ if __name__ == "__main__":
     p.add_argument("--channels", type=int, default=4, help="input channels (density + 3 coordinate grids)")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic grids instead of data/<name>")
     p.add_argument("--sync_bn", type=int, default=0, help="data parallel: BatchNorm statistics over all ranks")
+    p.add_argument("--monitor", action="store_true",
+                   help="draw the reference's training pictures on the GPU into the output folder (icsg3d_amd/monitor.py)")
     p.add_argument("--gpus", type=int, default=0,
                    help="data parallel over N GPUs of this node: without torch.distributed.run the script starts its N "
                         "ranks itself (icsg3d_amd/launcher.py); 0 = whatever the environment says (default)")
@@ -97,7 +99,7 @@ if __name__ == "__main__":
     if dp:
         unet.enable_data_parallel(dp[0], rank, world, sync_bn=bool(a.sync_bn), force=world == 1)
     unet.train_generator(training_generator, validation_generator, epochs=a.epochs,
-                         output_dir=os.path.join("output", "unet", mode))
+                         output_dir=os.path.join("output", "unet", mode), monitor=a.monitor)
     if rank == 0:
         unet.save_(weights, os.path.splitext(weights)[0] + ".h5")
     if dp:
