@@ -19,7 +19,12 @@ the structures are screened and written in (to_pymatgen_structure); --clus_iters
 --eps_frac goes where the reference puts it: the shift of the atom coordinates (generate.py:237-241); like the
 reference, to_lattice_params / to_voxel_params keep their default 0.25 (generate.py:211,214).
 Added: --channels (the reference hard-codes 4) and --synthetic (a Gaussian-blob base compound, condition bin
---cond_bin; no dataset exists offline).
+--cond_bin; no dataset exists offline).  --match (with --match_tol, --match_ltol, --match_ops {none,rot,all}): after the
+last batch all written samples are matched in one device call (icsg3d_amd.structures.match -> ics_op_structure_match,
+the project's own predicate): against each other for duplicates and against data/<name>/sites/*.npz
+for training hits; results.csv gains duplicate_of, duplicate_rms, training_match, training_rms, match_reason and run.json
+a `match` block with the parameters, the ineligible counts by reason and the validity / uniqueness / novelty rates.
+--synthetic runs have no site folder and report duplicates only.
 """
 import argparse
 import json
@@ -30,7 +35,7 @@ import numpy as np
 
 from icsg3d_amd.cli import checkpoint_paths
 from icsg3d_amd.evaluate import predicted_coordinates
-from icsg3d_amd.structures import ResultsWriter
+from icsg3d_amd.structures import OPS_MODES, Matcher, ReferenceSet, ResultsWriter
 from icsg3d_amd.synthetic import synthetic_batch
 from icsg3d_amd.utils import to_lattice_params_from_minmax, to_voxel_params
 from icsg3d_amd.unet.unet import AtomUnet
@@ -76,6 +81,11 @@ def build_parser():
     p.add_argument("--channels", type=int, default=4, help="input channels (density + 3 coordinate grids)")
     p.add_argument("--synthetic", action="store_true", help="Gaussian-blob base compound instead of data/<name>")
     p.add_argument("--cond_bin", type=int, default=0, help="--synthetic: condition bin of the base compound")
+    p.add_argument("--match", action="store_true", help="match the written samples: duplicates and training structures")
+    p.add_argument("--match_tol", type=float, default=0.1, help="--match: site tolerance in Angstrom")
+    p.add_argument("--match_ltol", type=float, default=0.05, help="--match: relative tolerance on the metric tensor")
+    p.add_argument("--match_ops", choices=sorted(OPS_MODES), default="rot",
+                   help="--match: cell operations tried (none, the 24 rotations, all 48 signed axis permutations)")
     return p
 
 
@@ -102,9 +112,11 @@ def main(argv=None):
     out_dir = os.path.join("output", "results", base_formula + "_" + "_v=" + str(a.var))
     for sub in ("densities", "species", "binary", "voxel_params", "coords"):
         os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+    shown = {k: v for k, v in vars(a).items() if a.match or not k.startswith("match")}     # without --match: today's keys
+    run_info = dict(shown, base_compound=base_compound, base_formula=base_formula, base_target=base_target_value,
+                    cond_bin=cond_bin)
     with open(os.path.join(out_dir, "run.json"), "w") as f:
-        json.dump(dict(vars(a), base_compound=base_compound, base_formula=base_formula, base_target=base_target_value,
-                       cond_bin=cond_bin), f)
+        json.dump(run_info, f)
 
     vae = LatticeDFCVAE(input_shape=(d, d, d, C), perceptual_model=perceptual_model, cond_shape=a.ncond)
     vae._set_model(vae_weights, batch_size=bs)
@@ -113,8 +125,13 @@ def main(argv=None):
     z_mu_base, z_logvar_base, z_base = vae.encoder.predict([M_base, cond])
     n_atoms = []
     training_names = set() if a.synthetic else training_formulas(os.path.join("data", mode, mode + ".csv"))
+    matcher = None
+    if a.match:
+        sites = os.path.join("data", mode, "sites")
+        reference = None if a.synthetic or not os.path.isdir(sites) else ReferenceSet.from_sites(sites)
+        matcher = Matcher(reference, a.match_tol, a.match_ltol, OPS_MODES[a.match_ops])
     results = ResultsWriter(out_dir, a.alpha, a.beta, a.gamma, training_names=training_names,
-                            target_value=base_target_value)
+                            target_value=base_target_value, matcher=matcher)
     for batch in range(int(a.nsamples / bs)):
         print("Batch", batch)
         z_samples = np.random.normal(z_mu_base, a.var, size=(bs, vae.latent_dim))
@@ -149,6 +166,19 @@ def main(argv=None):
         results.add_batch(range(batch * bs, batch * bs + bs), l_prime, batch_atoms)
     counts = results.finish()
     print("structures: generated %(generated)d / failed %(failed)d / invalid %(invalid)d / written %(written)d" % counts)
+    if matcher is not None:
+        compared = counts["written"] - counts["ineligible"]
+        run_info["match"] = dict(
+            tol=a.match_tol, ltol=a.match_ltol, ops=a.match_ops, references=len(matcher.reference) if matcher.reference else 0,
+            unique=counts["unique"], novel=counts["novel"] if matcher.reference else None, ineligible=counts["ineligible"],
+            ineligible_by_reason=results.match_summary["ineligible_by_reason"],
+            validity=counts["written"] / counts["generated"] if counts["generated"] else None,
+            uniqueness=counts["unique"] / compared if compared else None,
+            novelty=counts["novel"] / counts["unique"] if matcher.reference and counts["unique"] else None)
+        with open(os.path.join(out_dir, "run.json"), "w") as f:
+            json.dump(run_info, f)
+        print("match: unique %d / novel %s / ineligible %d of %d written" % (
+            counts["unique"], counts["novel"] if matcher.reference else "n/a", counts["ineligible"], counts["written"]))
     print("wrote", out_dir, "- atoms per sample: mean %.1f" % (np.mean(n_atoms) if n_atoms else 0.0))
     return 0
 

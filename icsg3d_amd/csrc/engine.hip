@@ -10,6 +10,7 @@
 #include "voxelise.h"
 #include "match.h"
 #include "structure.h"
+#include "structure_match.h"
 #include "latent.h"
 #include "tsne.h"
 #include "render.h"
@@ -3015,6 +3016,17 @@ int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, cons
   ICS_TRY(op_stream(&st));
   return structure_screen_op(st, offsets, species, xyz, abc, angles, batch, tol, lattice, volume, frac, min_dist, min_pair,
                              n_close, valid, reason, nearest, hist);
+}
+int ics_op_structure_match(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
+                           const int32_t* eligible, int nq, int nref, double tol, double ltol, int ops_mode,
+                           int32_t* dup_of, double* dup_rms, int32_t* dup_op, int32_t* ref_of, double* ref_rms,
+                           int32_t* ref_op, int32_t* n_cmp) {
+  ICS_TRY(structure_match_check(offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode));
+  ICS_CHECK(dup_of && dup_rms && dup_op && ref_of && ref_rms && ref_op && n_cmp, "ics_op_structure_match: null output");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return structure_match_op(st, offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode, dup_of, dup_rms,
+                            dup_op, ref_of, ref_rms, ref_op, n_cmp);
 }
 // view_results.py's pictures (viz.py:43-66, 184-233; view_results.py:152-183): render.h has the camera and the compositing
 int ics_op_render_density(const float* vol, int batch, int d, int stride_c, int channel, const float* lut, int mode,

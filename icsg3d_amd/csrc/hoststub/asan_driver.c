@@ -226,6 +226,74 @@ static int structure_walk(void) {
   return 0;
 }
 
+/* Structure matching: the argument checks, the bucket planner (several compositions, one-wave and whole-workgroup
+ * structures, ineligible entries, queries without partner, no references) and a pair count far above the chunk that
+ * ICSG3D_MATCH_CHUNK_PAIRS (set by main before the first call) leaves. */
+static int structure_match_walk(void) {
+  enum { NQ = 40, NR = 30, NS = NQ + NR };
+  static int32_t off[NS + 1], sp[NS * 70], el[NS];
+  static double fr[NS * 70 * 3], lat[NS * 9];
+  int32_t dup[NQ], ref[NQ], dop[NQ * 2], rop[NQ * 2], ncmp[NQ * 2];
+  double drms[NQ], rrms[NQ];
+  int at = 0;
+  for (int s = 0; s < NS; ++s) {
+    const int n = s % 7 == 0 ? 70 : (s % 3 == 0 ? 5 : 3);       /* three atom counts, two compositions of 3 */
+    off[s] = at;
+    for (int i = 0; i < n; ++i, ++at) {
+      sp[at] = n == 3 && s % 2 ? 8 + i : 1 + (i * 5) % 11;
+      fr[3 * at] = 0.013 * at - 3.0; fr[3 * at + 1] = 0.37 * i; fr[3 * at + 2] = 1.0 - 0.11 * i;
+    }
+    for (int k = 0; k < 9; ++k) lat[9 * s + k] = k % 4 == 0 ? 5.0 + k : (k == 3 ? -1.5 : 0.0);
+    el[s] = s % 11 != 10;
+  }
+  off[NS] = at;
+#define MATCH(o, z, f, l, e, nq, nr, t, lt, m) ics_op_structure_match(o, z, f, l, e, nq, nr, t, lt, m, dup, drms, dop, ref, rrms, rop, ncmp)
+  OK(MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1));
+  OK(MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 0));
+  OK(MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 2));
+  OK(MATCH(off, sp, fr, lat, el, NQ, 0, 0.1, 0.05, 1));            /* no references */
+  OK(MATCH(off, sp, fr, lat, el, 1, 0, 0.1, 0.05, 1));             /* no pair at all */
+  for (int q = 0; q < NQ; ++q)
+    if (dup[q] != -1 || ref[q] != -1) { fprintf(stderr, "structure match: a match without a kernel\n"); return 1; }
+  { int32_t none[NS]; memset(none, 0, sizeof none); OK(MATCH(off, sp, fr, lat, none, NQ, NR, 0.1, 0.05, 1)); }
+  int bad = 0;
+  bad += MATCH(off, sp, fr, lat, el, 0, NR, 0.1, 0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, -1, 0.1, 0.05, 1) == 0;
+  bad += MATCH(NULL, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0;
+  bad += MATCH(off, NULL, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0;
+  bad += MATCH(off, sp, NULL, lat, el, NQ, NR, 0.1, 0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, NULL, el, NQ, NR, 0.1, 0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, NULL, NQ, NR, 0.1, 0.05, 1) == 0;
+  bad += ics_op_structure_match(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1, dup, NULL, dop, ref, rrms, rop, ncmp) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.0, 0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, NAN, 0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, -0.05, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, INFINITY, 1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 3) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, -1) == 0;
+  bad += MATCH(off, sp, fr, lat, el, NQ, NR, 3.0, 0.05, 1) == 0;                                   /* too thin for tol */
+  off[0] = 1; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; off[0] = 0;
+  { const int32_t keep = off[2]; off[2] = off[1] - 1; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; off[2] = keep; }
+  fr[7] = NAN; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; fr[7] = 0.5;
+  lat[9 + 4] = INFINITY; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; lat[9 + 4] = 9.0;
+  lat[9 + 4] = -9.0; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; lat[9 + 4] = 9.0;  /* volume < 0 */
+  sp[1] = 95; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0;
+  sp[1] = 0; bad += MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1) == 0; sp[1] = 6;
+  {   /* 257 atoms, and an empty eligible structure */
+    static int32_t bo[3] = {0, 257, 257}, bs[257], be[2] = {1, 0};
+    static double bf[257 * 3], bl[18] = {20, 0, 0, 0, 20, 0, 0, 0, 20, 20, 0, 0, 0, 20, 0, 0, 0, 20};
+    for (int i = 0; i < 257; ++i) bs[i] = 8;
+    bad += MATCH(bo, bs, bf, bl, be, 2, 0, 0.1, 0.05, 1) == 0;
+    be[0] = 0; be[1] = 1; bad += MATCH(bo, bs, bf, bl, be, 2, 0, 0.1, 0.05, 1) == 0;
+    be[1] = 0; OK(MATCH(bo, bs, bf, bl, be, 2, 0, 0.1, 0.05, 1));                      /* ineligible: not looked at */
+  }
+  if (bad) { fprintf(stderr, "structure match: %d invalid argument sets accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "structure match: no error message\n"); return 1; }
+  OK(MATCH(off, sp, fr, lat, el, NQ, NR, 0.1, 0.05, 1));     /* still usable */
+#undef MATCH
+  return 0;
+}
+
 /* view_results.py's pictures: the three ops over more than one picture and an image that is no multiple of the tile, an
  * empty atom set, every refusal, and the ops still usable afterwards. */
 static int render_walk(void) {
@@ -857,6 +925,7 @@ int main(void) {
   OK(ics_set_device(0));
   OK(ics_device_info(name, &cus, &hbm));
   printf("asan driver on %s (%s)\n", name, ics_version());
+  setenv("ICSG3D_MATCH_CHUNK_PAIRS", "7", 1);   /* the match planner over many chunks (read at the first match call) */
   setenv("ICSG3D_DGRAD_BNFUSE_MIN", "0", 1);   /* walk the BatchNorm-backward-in-backward-data fusion at these small sizes too */
   if (run(16, 1, 3, 0)) return 1;
   if (run(16, 4, 2, 1)) return 1;      /* 4 channels (Cin 44 -> padded loaders), single-rank communicator */
@@ -866,6 +935,7 @@ int main(void) {
                                           workspace was sized for max_batch alone, round 6) */
   if (match_walk()) return 1;
   if (structure_walk()) return 1;
+  if (structure_match_walk()) return 1;
   if (latent_walk()) return 1;
   if (render_walk()) return 1;
   if (monitor_walk(NULL, NULL, NULL, NULL, NULL, NULL, 0, 0)) return 1;

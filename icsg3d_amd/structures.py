@@ -14,6 +14,10 @@ The reference builds a pymatgen Structure per sample; pymatgen is not a dependen
 - numbered          the duplicate-formula numbering of generate.py:257-260.
 - ResultsWriter     generate.py:250-318 around them: per batch one screen, then per valid sample the CIF, the results
                     row and the results.json record; results.csv at the end.
+- match, Matcher, ReferenceSet, eligibility, match_packed, signed_permutations
+                    which written samples are the same crystal as an earlier one and which are a training structure
+                    (ics_op_structure_match: the project's own predicate; no parity with pymatgen's
+                    StructureMatcher is claimed).  No host fallback either.
 """
 from __future__ import annotations
 
@@ -197,6 +201,205 @@ def screen(lattice_params, atoms, alpha=90, beta=90, gamma=90, tol=0.5):
     return res
 
 
+# ---------------------------------------------------------------- structure matching (ics_op_structure_match)
+MATCH_MAX_ATOMS = 256   # atoms per structure the match kernel takes
+OPS_MODES = {"none": 0, "rot": 1, "all": 2}
+# reason bits of a structure that is never compared (eligibility)
+INELIGIBLE_ATOMS, INELIGIBLE_CLOSE, INELIGIBLE_THIN, INELIGIBLE_INVALID = 1, 2, 4, 8
+INELIGIBLE = {INELIGIBLE_ATOMS: "more than 256 atoms", INELIGIBLE_CLOSE: "atoms within 4 tol",
+              INELIGIBLE_THIN: "cell too thin for tol", INELIGIBLE_INVALID: "invalid or failed"}
+
+
+def signed_permutations(ops_mode=1):
+    """The op table of ics_op_structure_match, (k, 3, 3) with f' = P f: lexicographic over (permutation, sign pattern),
+    + before -, identity first.  ops_mode 0: the identity; 1: the 24 of determinant +1 in that order; 2: all 48."""
+    if ops_mode not in (0, 1, 2):
+        raise ValueError("ops_mode must be 0, 1 or 2")
+    perms = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+    parity = (1, -1, -1, 1, 1, -1)
+    ops = []
+    for perm, par in zip(perms, parity):
+        for s in range(8):
+            sign = (-1 if s & 4 else 1, -1 if s & 2 else 1, -1 if s & 1 else 1)
+            if (ops_mode == 0 and ops) or (ops_mode == 1 and par * sign[0] * sign[1] * sign[2] != 1):
+                continue
+            P = np.zeros((3, 3))
+            for k in range(3):
+                P[k, perm[k]] = sign[k]
+            ops.append(P)
+    return np.array(ops)
+
+
+def eligibility(results, tol=0.1):
+    """The reason bits (0 = eligible) per entry of `results` (the dicts screen returns; None = a failed sample): more
+    than 256 atoms, screen min_dist <= 4 tol, 2 tol max(g) >= 0.5 for the inverse-column norms g of the cell, invalid or
+    failed.  With these the predicate means "the same crystal": only the wrapped image can lie within 2 tol, and the
+    nearest-atom map is forced to be a bijection."""
+    out = np.zeros(len(results), np.int32)
+    for k, r in enumerate(results):
+        if r is None or not r["valid"] or len(r["species"]) == 0 or not np.all(np.isfinite(r["lattice"])):
+            out[k] = INELIGIBLE_INVALID
+            continue
+        if len(r["species"]) > MATCH_MAX_ATOMS:
+            out[k] |= INELIGIBLE_ATOMS
+        if r["min_dist"] <= 4.0 * tol:
+            out[k] |= INELIGIBLE_CLOSE
+        g = np.linalg.norm(np.linalg.inv(np.asarray(r["lattice"], np.float64)), axis=0)
+        if not 2.0 * tol * g.max() < 0.5:
+            out[k] |= INELIGIBLE_THIN
+    return out
+
+
+def ineligible_text(bits):
+    return ", ".join(t for bit, t in INELIGIBLE.items() if bits & bit) or "eligible"
+
+
+def match_packed(offsets, species, frac, lattice, eligible, nq, nref, tol=0.1, ltol=0.05, ops_mode=1):
+    """ics_op_structure_match on packed arrays: nq queries then nref references; offsets (nq + nref + 1,), species (N,),
+    frac (N, 3), lattice (nq + nref, 3, 3) with rows va, vb, vc, eligible (nq + nref,).  Returns the op's outputs as a
+    dict of arrays (dup_of, dup_rms, dup_op (nq, 2) = (op, anchor), ref_of, ref_rms, ref_op, n_cmp (nq, 2))."""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    species = np.ascontiguousarray(species, np.int32).reshape(-1)
+    frac = np.ascontiguousarray(frac, np.float64).reshape(-1, 3)
+    lattice = np.ascontiguousarray(lattice, np.float64).reshape(-1, 9)
+    eligible = np.ascontiguousarray(eligible, np.int32).reshape(-1)
+    nq, nref = int(nq), int(nref)
+    ns = nq + nref
+    if nq >= 1 and nref >= 0 and (len(offsets) != ns + 1 or len(lattice) != ns or len(eligible) != ns
+                                  or len(frac) != len(species) or int(offsets[-1]) != len(species)):
+        raise ValueError("match: array lengths do not agree (structures %d / %d / %d / %d, atoms %d / %d / %d)"
+                         % (ns, len(offsets) - 1, len(lattice), len(eligible), len(species), len(frac), int(offsets[-1])))
+    n = max(nq, 1)
+    out = {"dup_of": np.full(n, -1, np.int32), "dup_rms": np.full(n, np.inf), "dup_op": np.full((n, 2), -1, np.int32),
+           "ref_of": np.full(n, -1, np.int32), "ref_rms": np.full(n, np.inf), "ref_op": np.full((n, 2), -1, np.int32),
+           "n_cmp": np.zeros((n, 2), np.int32)}
+    L.check(L.load().ics_op_structure_match(
+        L.i32ptr(offsets), L.i32ptr(species), L.f64ptr(frac), L.f64ptr(lattice), L.i32ptr(eligible), nq, nref, float(tol),
+        float(ltol), int(ops_mode), L.i32ptr(out["dup_of"]), L.f64ptr(out["dup_rms"]), L.i32ptr(out["dup_op"]),
+        L.i32ptr(out["ref_of"]), L.f64ptr(out["ref_rms"]), L.i32ptr(out["ref_op"]), L.i32ptr(out["n_cmp"])))
+    return out
+
+
+class ReferenceSet:
+    """The structures generated samples are held against: ids, species, fractional coordinates as stored, and the
+    lattice of the six parameters through cell().  from_sites reads data/<name>/sites/*.npz (matrices.load_sites),
+    sorted by file name.  screened() runs the device screen over the set once (tol 0: only coincident atoms, a species
+    outside 1..94 or no atoms make a reference invalid) and keeps its dicts -- min_dist is what eligibility needs."""
+
+    def __init__(self, ids, species, frac, lattice_params):
+        self.ids = [str(i) for i in ids]
+        self.species = [np.asarray(s, np.int32).reshape(-1) for s in species]
+        self.frac = [np.asarray(f, np.float64).reshape(len(s), 3) for f, s in zip(frac, self.species)]
+        self.lattice_params = np.asarray(lattice_params, np.float64).reshape(len(self.ids), 6)
+        if not len(self.ids) == len(self.species) == len(self.frac):
+            raise ValueError("ReferenceSet: ids, species and frac differ in length")
+        self._screened = None
+
+    @classmethod
+    def from_sites(cls, folder):
+        from .matrices import load_sites
+        names = sorted(f for f in os.listdir(folder) if f.endswith(".npz"))
+        ids, sp, fr, lp = [], [], [], []
+        for f in names:
+            frac, Z, _, lattice = load_sites(os.path.join(folder, f))
+            ids.append(f[:-4])
+            sp.append(np.rint(Z).astype(np.int32))
+            fr.append(frac)
+            lp.append(np.asarray(lattice, np.float64).reshape(-1)[:6])
+        return cls(ids, sp, fr, np.array(lp, np.float64).reshape(len(ids), 6))
+
+    def __len__(self):
+        return len(self.ids)
+
+    def screened(self):
+        """One dict per reference in screen()'s layout (frac: the stored coordinates), or None where the six parameters
+        make no usable cell."""
+        if self._screened is not None:
+            return self._screened
+        res, keep, cells = [None] * len(self), [], []
+        for k in range(len(self)):
+            abc, ang, sp, fr = self.lattice_params[k, :3], self.lattice_params[k, 3:], self.species[k], self.frac[k]
+            try:
+                ok = (np.all(np.isfinite(abc)) and np.all(abc >= 1e-6) and np.all(abc <= 1e6) and np.all(np.isfinite(fr))
+                      and np.all(np.abs(fr) <= 1e6) and len(sp) <= MAX_ATOMS)
+                M, vol, g = cell(abc, ang)
+                ok = ok and 0.5 * abc.sum() * g.max() + 0.5 <= MAX_IMAGE - 0.1
+            except ValueError:
+                ok = False
+            if ok:
+                keep.append(k)
+                cells.append((M, vol))
+        if keep:
+            off = np.zeros(len(keep) + 1, np.int32)
+            off[1:] = np.cumsum([len(self.species[k]) for k in keep])
+            o = screen_packed(off, np.concatenate([self.species[k] for k in keep]),
+                              np.concatenate([self.frac[k] * self.lattice_params[k, :3] for k in keep]),
+                              self.lattice_params[keep, :3], self.lattice_params[keep, 3:], 0.0)
+            for i, k in enumerate(keep):
+                res[k] = {"species": self.species[k], "frac": self.frac[k], "abc": self.lattice_params[k, :3].copy(),
+                          "angles": self.lattice_params[k, 3:].copy(), "lattice": cells[i][0], "volume": cells[i][1],
+                          "min_dist": float(o["min_dist"][i]), "hist": o["hist"][i].copy(), "valid": bool(o["valid"][i]),
+                          "reason": int(o["reason"][i])}
+        self._screened = res
+        return res
+
+
+def match(results, reference=None, tol=0.1, ltol=0.05, ops_mode=1):
+    """Duplicates and training hits of a run.  results: the dicts screen returns, in sample order (None = failed);
+    reference: a ReferenceSet or None.  One device call.  Returns one dict per sample: duplicate_of (index into results
+    of the first earlier sample that is the same structure, -1 if none), duplicate_rms, duplicate_op (op, anchor),
+    training_match (the reference's id, None if none), training_rms, training_op, match_reason (eligibility bits: a
+    sample with a bit set was not compared), n_compared (earlier samples, references)."""
+    nq = len(results)
+    qbits = eligibility(results, tol)
+    out = [{"duplicate_of": -1, "duplicate_rms": None, "duplicate_op": (-1, -1), "training_match": None,
+            "training_rms": None, "training_op": (-1, -1), "match_reason": int(qbits[k]), "n_compared": (0, 0)}
+           for k in range(nq)]
+    if nq == 0 or not np.any(qbits == 0):
+        return out
+    refs = reference.screened() if reference is not None and len(reference) else []
+    allr = list(results) + list(refs)
+    bits = np.concatenate([qbits, eligibility(refs, tol)])
+    sp_l, fr_l, lat = [], [], np.zeros((len(allr), 3, 3))
+    for k, r in enumerate(allr):
+        if bits[k] == 0:
+            sp_l.append(np.asarray(r["species"], np.int32))
+            fr_l.append(np.asarray(r["frac"], np.float64).reshape(-1, 3))
+            lat[k] = r["lattice"]
+        else:                                   # not compared: passed as an empty, ineligible entry
+            sp_l.append(np.zeros(0, np.int32))
+            fr_l.append(np.zeros((0, 3)))
+    off = np.zeros(len(allr) + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in sp_l])
+    o = match_packed(off, np.concatenate(sp_l), np.concatenate(fr_l), lat, (bits == 0).astype(np.int32), nq, len(refs),
+                     tol, ltol, ops_mode)
+    for k in range(nq):
+        d = out[k]
+        d["n_compared"] = (int(o["n_cmp"][k, 0]), int(o["n_cmp"][k, 1]))
+        if o["dup_of"][k] >= 0:
+            d["duplicate_of"], d["duplicate_rms"] = int(o["dup_of"][k]), float(o["dup_rms"][k])
+            d["duplicate_op"] = (int(o["dup_op"][k, 0]), int(o["dup_op"][k, 1]))
+        if o["ref_of"][k] >= 0:
+            d["training_match"], d["training_rms"] = reference.ids[int(o["ref_of"][k])], float(o["ref_rms"][k])
+            d["training_op"] = (int(o["ref_op"][k, 0]), int(o["ref_op"][k, 1]))
+    return out
+
+
+class Matcher:
+    """The matching parameters ResultsWriter(matcher=...) runs with: reference (a ReferenceSet or None: duplicates
+    only), tol (Angstrom), ltol (relative, on the metric tensor), ops_mode (0 identity, 1 the 24 rotations, 2 all 48)."""
+
+    def __init__(self, reference=None, tol=0.1, ltol=0.05, ops_mode=1):
+        if not (tol > 0 and ltol > 0 and math.isfinite(tol) and math.isfinite(ltol)):
+            raise ValueError("Matcher: tol and ltol must be finite and > 0")
+        if ops_mode not in (0, 1, 2):
+            raise ValueError("Matcher: ops_mode must be 0, 1 or 2")
+        self.reference, self.tol, self.ltol, self.ops_mode = reference, float(tol), float(ltol), int(ops_mode)
+
+    def __call__(self, results):
+        return match(results, self.reference, self.tol, self.ltol, self.ops_mode)
+
+
 def reason_text(reason):
     return ", ".join(t for bit, t in REASONS.items() if reason & bit) or "valid"
 
@@ -273,11 +476,19 @@ class ResultsWriter:
     """The tail of generate.py's sample loop.  add_batch screens one batch on the device and, per sample in order:
     builds the formula, numbers a formula seen before (formula_count), SKIPS an invalid structure, writes
     cifs/<formula_count>.cif, appends the row and its results.json record.  finish() writes results.csv sorted by id (the
-    reference sorts by the CGCNN target, which is not predicted here) and returns the counts."""
+    reference sorts by the CGCNN target, which is not predicted here) and returns the counts.
+    With matcher= (a Matcher), finish() first matches ALL written samples in one device call -- a duplicate may lie in
+    any earlier batch -- and every row carries MATCH_COLUMNS after COLUMNS: duplicate_of (the id of the first earlier
+    row that is the same structure), duplicate_rms, training_match (the reference's id), training_rms, match_reason (""
+    or why the sample was not compared); the counts gain unique (compared, no earlier duplicate), novel (unique and no
+    training match) and ineligible, and match_summary holds them with the ineligible counts by reason.  results.json is
+    written per batch and keeps today's records.  Without matcher= nothing changes."""
     COLUMNS = ("formula", "id", "training", "target", "anon_formula", "electronegativity", "cif", "sample", "natoms",
                "min_distance", "volume")
+    MATCH_COLUMNS = ("duplicate_of", "duplicate_rms", "training_match", "training_rms", "match_reason")
 
-    def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None):
+    def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None, matcher=None):
+        self.matcher, self.structs, self.match_summary = matcher, [], None
         self.out_dir, self.angles, self.tol = out_dir, (alpha, beta, gamma), tol
         self.training_names, self.target_value = set(training_names), target_value
         self.formulae, self.rows = [], []
@@ -307,20 +518,46 @@ class ResultsWriter:
                   "electronegativity": average_electroneg(r["hist"]), "cif": path, "sample": int(k),
                   "natoms": int(len(r["species"])), "min_distance": r["min_dist"], "volume": r["volume"]}
             self.rows.append(rd)
+            if self.matcher is not None:
+                self.structs.append(r)
             self.formulae.append(f)
             self.counts["written"] += 1
             with open(os.path.join(self.out_dir, "results.json"), "a+") as wf:      # generate.py:313-314
                 json.dump(str(rd), wf)
         return res
 
+    def _match_rows(self):
+        """The matcher over all written samples: the extra columns into the rows, the summary into match_summary."""
+        m = self.matcher(self.structs)
+        by_reason = {}
+        unique = novel = ineligible = 0
+        for rd, d in zip(self.rows, m):
+            rd["duplicate_of"] = self.rows[d["duplicate_of"]]["id"] if d["duplicate_of"] >= 0 else None
+            rd["duplicate_rms"], rd["training_match"], rd["training_rms"] = d["duplicate_rms"], d["training_match"], d["training_rms"]
+            rd["match_reason"] = ineligible_text(d["match_reason"]) if d["match_reason"] else None
+            if d["match_reason"]:
+                ineligible += 1
+                for bit, text in INELIGIBLE.items():
+                    if d["match_reason"] & bit:
+                        by_reason[text] = by_reason.get(text, 0) + 1
+            elif d["duplicate_of"] < 0:
+                unique += 1
+                novel += d["training_match"] is None
+        self.match_summary = {"unique": unique, "novel": novel, "ineligible": ineligible, "ineligible_by_reason": by_reason}
+        self.counts.update(unique=unique, novel=novel, ineligible=ineligible)
+
     def finish(self):
+        columns = self.COLUMNS
+        if self.matcher is not None:
+            self._match_rows()
+            columns = self.COLUMNS + self.MATCH_COLUMNS
         order = sorted(range(len(self.rows)), key=lambda i: self.rows[i]["id"])
         with open(os.path.join(self.out_dir, "results.csv"), "w", newline="") as fh:
             w = csv.writer(fh)
-            w.writerow(("",) + self.COLUMNS)                          # the index column DataFrame.to_csv writes
+            w.writerow(("",) + columns)                               # the index column DataFrame.to_csv writes
             for i in order:
                 w.writerow([i] + ["" if self.rows[i][c] is None else repr(self.rows[i][c]) if isinstance(self.rows[i][c], float)
-                                  else self.rows[i][c] for c in self.COLUMNS])
+                                  else self.rows[i][c] for c in columns])
         return dict(self.counts)
 
 

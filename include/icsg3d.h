@@ -310,6 +310,52 @@ int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, cons
                             const double* angles, int batch, double tol, double* lattice, double* volume, double* frac,
                             double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid, int32_t* reason,
                             double* nearest, int32_t* hist);
+/* Which structures are the same crystal: duplicates among `nq` queries and hits in `nref` references.  The predicate is
+ * this library's own -- exact, deterministic, no assignment solver; NO parity with pymatgen's StructureMatcher is
+ * claimed (it is not a dependency and no fixture was recorded from it).
+ * The packed table holds the nq queries followed by the nref references: structure s holds atoms offsets[s] ..
+ * offsets[s+1]) with species (atomic numbers Z_i), fractional coordinates frac [atoms][3] (any real values, wrapped
+ * internally: f - floor(f)) and lattice [nq+nref][9] = M, rows va, vb, vc as ics_op_structure_screen returns it;
+ * G = M M^T.  eligible [nq+nref]: 0 = the structure is never compared (see below).
+ *   Candidates.  (A, B) is compared only if both are eligible, n_A == n_B and the species histograms are equal.
+ *   Operations.  Signed axis permutations P (3x3, entries 0/+-1) acting as f' = P f, f'_k = sign_k f[perm_k].  Their
+ *     order is lexicographic over (permutation, sign pattern): permutations (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1)
+ *     (2,1,0), and per permutation the signs (+,+,+) (+,+,-) (+,-,+) (+,-,-) (-,+,+) (-,+,-) (-,-,+) (-,-,-); index 0 is
+ *     the identity.  ops_mode 0: the identity; 1: the 24 of determinant +1 (what np.rot90 produces on the grids), in
+ *     that order; 2: all 48.  A reported op indexes the list of the call's ops_mode.
+ *     P is admissible for (A, B) when, with G' = P G_A P^T, |G'_kl - G_B,kl| <= ltol sqrt(G_B,kk G_B,ll) for all k, l.
+ *   Anchor.  a0 = the lowest-index atom of A whose species has the smallest count in A (ties between species to the
+ *     lower Z); anchor candidates are the atoms j of B of that species, in index order.
+ *   One combination (P, j).  t = g_j - P f_a0; for every atom i of A, p_i = P f_i + t; among the atoms of B with
+ *     Z == Z_i the one with the smallest wrapped-image distance (D = g - p_i, D -= rint(D), u = M_B^T D; ties to the
+ *     lower index) is nb(i) with vector u_i.  The combination passes if (a) |u_i| <= 2 tol for all i, (b) nb is
+ *     injective, (c) with ubar = mean_i u_i and r_i = u_i - ubar, max_i |r_i| <= tol.  Its score is
+ *     rms = sqrt(mean_i |r_i|^2).
+ *   Pair.  A and B match if some admissible P and some anchor j pass; the pair's rms is the minimum over the passing
+ *     combinations and (op, anchor) its argmin, ties to the lower (op, anchor).
+ * Outputs, per query q:
+ *   dup_of [nq]      the smallest q' < q that matches q (A = q', B = q), -1 if none
+ *   dup_rms [nq], dup_op [nq][2]   that pair's rms and (op, anchor = atom index in B); +inf and (-1, -1) if none
+ *   ref_of [nq]      the reference (0 .. nref-1) with the smallest rms among the matching ones (A = q, B = reference),
+ *                    ties to the lower index; -1 if none.  ref_rms [nq], ref_op [nq][2] as above
+ *   n_cmp [nq][2]    candidate pairs compared against earlier queries and against references
+ * An ineligible query comes back -1 / +inf / n_cmp 0 and is nobody's partner.
+ * What makes "match" mean "the same crystal" is the caller's eligibility rule (icsg3d_amd.structures.eligibility): the
+ * wrapped image is the only one that can lie within 2 tol when 2 tol g_k < 0.5 for the norms g of the columns of
+ * inv(M) (enforced here, see the refusals), and nb is forced to be a bijection when every interatomic distance of both
+ * structures exceeds 4 tol (the caller's: the screen's min_dist).
+ * All arithmetic is fp64 with a fixed summation order and no floating-point atomics: the same bits run to run, for any
+ * chunking.  ICSG3D_MATCH_CHUNK_PAIRS (read once per process) shrinks the number of pair results held at a time.
+ * Refused, naming the structure, with nothing written: a null argument, nq < 1, nref < 0, a tolerance that is not
+ * finite and > 0, ops_mode outside 0..2, offsets that do not start at 0 or decrease, and an ELIGIBLE structure with no
+ * atoms or more than 256, a non-finite lattice entry or coordinate (or one above 1e15), a species outside 1..94, a
+ * lattice volume <= 0, or a cell too thin for tol (2 tol g_k >= 0.5).
+ * HOST pointers, all outputs required, any nq / nref (pairs are enumerated on the device from composition buckets and
+ * chunked internally), synchronous, the calling thread's op stream. */
+int ics_op_structure_match(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
+                           const int32_t* eligible, int nq, int nref, double tol, double ltol, int ops_mode,
+                           int32_t* dup_of, double* dup_rms, int32_t* dup_op, int32_t* ref_of, double* ref_rms,
+                           int32_t* ref_op, int32_t* n_cmp);
 
 /* ---------------------------------------------------------------- pictures (view_results.py)
  * The panels of view_results.py:152-183 -- viz.py:184-233 (the voxel panels of M, S and the watershed regions) and
