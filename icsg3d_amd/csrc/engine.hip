@@ -7,6 +7,7 @@
 #include "common.h"
 #include "elementwise.h"
 #include "segment.h"
+#include "scratch.h"
 #include "voxelise.h"
 #include "match.h"
 #include "structure.h"
@@ -2946,50 +2947,11 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
   return segment_to_host(n, dm, ds, batch, d, num_species, T);
 }
 
-// The three box-level entry points run tens of times per sample from the host recursion of segment_nuclei
-// (icsg3d_amd/watershed.py): one stream per host thread, created on first use and kept (a handle with two streams, two
-// events and its own allocations per call cost 10 - 16 ms against kernels of tens of microseconds).
-namespace {
-struct OpStream { hipStream_t st = nullptr; int device = -1; };
-// as segment.hip's scratch: a thread that exits hands its stream to a list of orphans instead of leaking it (or calling into
-// a runtime that may be shutting down); the next op_stream() creation and ics_release_caches destroy them
-std::mutex g_stream_orphan_mu;
-std::vector<hipStream_t> g_stream_orphans;
-void reap_stream_orphans() {
-  std::vector<hipStream_t> take;
-  { std::lock_guard<std::mutex> lk(g_stream_orphan_mu); take.swap(g_stream_orphans); }
-  for (hipStream_t s : take) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-}
-struct OpStreamTL {
-  OpStream o;
-  ~OpStreamTL() {
-    if (o.st) { std::lock_guard<std::mutex> lk(g_stream_orphan_mu); g_stream_orphans.push_back(o.st); }
-  }
-};
-thread_local OpStreamTL tl_op_stream_holder;
-#define tl_op_stream (tl_op_stream_holder.o)
-int op_stream(hipStream_t* out) {
-  int dev = 0;
-  ICS_HIP(hipGetDevice(&dev));
-  if (tl_op_stream.st == nullptr || tl_op_stream.device != dev) {
-    reap_stream_orphans();
-    if (tl_op_stream.st) (void)hipStreamDestroy(tl_op_stream.st);
-    tl_op_stream.st = nullptr;
-    ICS_HIP(hipStreamCreateWithFlags(&tl_op_stream.st, hipStreamNonBlocking));
-    tl_op_stream.device = dev;
-  }
-  *out = tl_op_stream.st;
-  return 0;
-}
-}  // namespace
+// The host-pointer ops below run on the calling thread's stream and scratch (scratch.h).
 int ics_release_caches() {
-  if (tl_op_stream.st) { (void)hipStreamSynchronize(tl_op_stream.st); (void)hipStreamDestroy(tl_op_stream.st); }
-  tl_op_stream = OpStream{};
-  reap_stream_orphans();
-  segment_release_scratch();
+  release_thread_caches();
   return 0;
 }
-#undef tl_op_stream
 
 int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac, double label_frac,
                     double* M, double* S, double* p) {
@@ -3081,15 +3043,15 @@ int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, floa
   RenderView<double> view;
   ICS_CHECK(render_view(camera, n.d, width, height, &view) == 0, "ics_vae_render_resident: camera must be finite");
   ICS_HIP(hipSetDevice(n.device));
-  const size_t lut_b = 3 * kRenderLutRows * sizeof(float), img_b = (size_t)batch * width * height * 16;
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(4096 + img_b, &base));
-  float* d_lut = reinterpret_cast<float*>(base);
-  float* d_out = reinterpret_cast<float*>(base + 4096);
-  ICS_HIP(hipMemcpyAsync(d_lut, lut, lut_b, hipMemcpyHostToDevice, n.st));
+  Layout L;
+  const auto s_lut = L.add<float>(3 * kRenderLutRows);
+  const auto s_out = L.add<float>((size_t)batch * width * height * 4);
+  float *d_lut, *d_out;
+  ICS_TRY(L.reserve(s_lut, &d_lut, s_out, &d_out));
+  ICS_TRY(L.upload(s_lut, lut, s_lut.count, n.st));
   ICS_TRY(render_density_device(n.st, which ? n.recon : n.x_in, batch, n.d, n.C, 0, d_lut, mode, alpha, floor, view, width,
                                 height, d_out));
-  ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, n.st));
+  ICS_TRY(L.download(out, s_out, s_out.count, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
   return 0;
 }
@@ -3106,16 +3068,18 @@ int ics_op_render_slice(const void* vol, int dtype, int batch, int d, int stride
 static int slice_resident(Net& n, const char* who, const void* src, int dtype, int stride_c, int channel, int count, int axis,
                           int index, const float* lut, const float* range, int zoom, float* out) {
   ICS_TRY(slice_check(who, dtype, count, n.d, stride_c, channel, axis, index, lut, range, zoom, out));
-  const size_t side = (size_t)n.d * zoom, img_b = (size_t)count * side * side * 16, rng_b = slice_range_bytes(count);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(4096 + rng_b + img_b, &base));
-  float* d_lut = reinterpret_cast<float*>(base);
-  float* d_rng = reinterpret_cast<float*>(base + 4096);
-  float* d_out = reinterpret_cast<float*>(base + 4096 + rng_b);
-  ICS_HIP(hipMemcpyAsync(d_lut, lut, 3 * kMonitorLutRows * sizeof(float), hipMemcpyHostToDevice, n.st));
-  ICS_TRY(slice_device(n.st, src, dtype, slice_layout(n.d, stride_c, channel, axis, index), count, n.d, d_lut, range, d_rng,
-                       zoom, d_out));
-  ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, n.st));
+  const size_t side = (size_t)n.d * zoom;
+  Layout L;
+  const auto s_lut = L.add<float>(3 * kMonitorLutRows);
+  const auto s_rng = L.add<float>(2 * (size_t)count);
+  const auto s_out = L.add<float>((size_t)count * side * side * 4);
+  float *d_lut, *d_rng, *d_out;
+  ICS_TRY(L.reserve(s_lut, &d_lut, s_rng, &d_rng, s_out, &d_out));
+  ICS_TRY(L.upload(s_lut, lut, s_lut.count, n.st));
+  if (range) ICS_TRY(L.upload(s_rng, range, 2, n.st));
+  ICS_TRY(slice_device(n.st, src, dtype, slice_layout(n.d, stride_c, channel, axis, index), count, n.d, d_lut,
+                       range == nullptr, d_rng, zoom, d_out));
+  ICS_TRY(L.download(out, s_out, s_out.count, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
   return 0;
 }

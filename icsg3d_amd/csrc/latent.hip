@@ -11,7 +11,7 @@
 // wave64 butterfly, then the wave sums from LDS in wave order -- so results are the same run to run.  Latency-sized
 // (256 x 8 values per pair at the defaults): the only care taken is that a row is written by consecutive threads.
 #include "latent.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -124,21 +124,20 @@ int latent_path_op(hipStream_t st, const float* za, const float* zb, int pairs, 
                    int steps, int mode, float* path) {
   const size_t per_pair = (size_t)steps * latent;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)pairs, kLatentChunkFloats / per_pair));
-  const size_t b_alpha = ((size_t)steps * 8 + 255) & ~(size_t)255;
-  const size_t b_z = ((size_t)chunk * latent * 4 + 255) & ~(size_t)255;
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(b_alpha + 2 * b_z + (size_t)chunk * per_pair * 4, &base));
-  double* d_alpha = reinterpret_cast<double*>(base);
-  float* da = reinterpret_cast<float*>(base + b_alpha);
-  float* db = reinterpret_cast<float*>(base + b_alpha + b_z);
-  float* dp = reinterpret_cast<float*>(base + b_alpha + 2 * b_z);
-  ICS_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)steps * 8, hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_alpha = L.add<double>(steps);
+  const auto s_a = L.add<float>((size_t)chunk * latent), s_b = L.add<float>((size_t)chunk * latent);
+  const auto s_path = L.add<float>((size_t)chunk * per_pair);
+  double* d_alpha;
+  float *da, *db, *dp;
+  ICS_TRY(L.reserve(s_alpha, &d_alpha, s_a, &da, s_b, &db, s_path, &dp));
+  ICS_TRY(L.upload(s_alpha, alpha, steps, st));
   for (int p0 = 0; p0 < pairs; p0 += chunk) {
     const int n = std::min(chunk, pairs - p0);
-    ICS_HIP(hipMemcpyAsync(da, za + (size_t)p0 * latent, (size_t)n * latent * 4, hipMemcpyHostToDevice, st));
-    ICS_HIP(hipMemcpyAsync(db, zb + (size_t)p0 * latent, (size_t)n * latent * 4, hipMemcpyHostToDevice, st));
+    ICS_TRY(L.upload(s_a, za + (size_t)p0 * latent, (size_t)n * latent, st));
+    ICS_TRY(L.upload(s_b, zb + (size_t)p0 * latent, (size_t)n * latent, st));
     ICS_TRY(launch_latent_path(st, da, db, (size_t)latent, nullptr, 0, 0, n, latent, d_alpha, steps, mode, nullptr, dp));
-    ICS_HIP(hipMemcpyAsync(path + (size_t)p0 * per_pair, dp, (size_t)n * per_pair * 4, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.download(path + (size_t)p0 * per_pair, s_path, (size_t)n * per_pair, st));
     ICS_HIP(hipStreamSynchronize(st));
   }
   return 0;

@@ -9,7 +9,7 @@
 // combined in wave order.  Ties go to an unassigned column, then to the lowest column index, so results are the same
 // run to run.  Only the augmentation walk along the predecessors is serial (thread 0).
 #include "match.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,7 +24,6 @@ constexpr double kMatchMaxCoord = 1e150;           // |coordinate| bound: every 
 constexpr int kKeyAssigned = 4096;                 // argmin key = (assigned ? 4096 : 0) + column, column < 2048
 constexpr int kKeyNone = 0x7fffffff;
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ double dist3(double ax, double ay, double az, double bx, double by, double bz) {
   const double dx = ax - bx, dy = ay - by, dz = az - bz;
@@ -231,26 +230,23 @@ int match_emd_op(hipStream_t st, const double* a, const int32_t* a_off, const do
     const int A0 = a_off[s0], NA = a_off[s1] - A0, B0 = b_off[s0], NB = b_off[s1] - B0;
     ao.resize(n + 1); bo.resize(n + 1);
     for (int k = 0; k <= n; ++k) { ao[k] = a_off[s0 + k] - A0; bo[k] = b_off[s0 + k] - B0; }
-    const size_t ba = align256((size_t)NA * 24 + 8), bb = align256((size_t)NB * 24 + 8);
-    const size_t bao = align256((size_t)(n + 1) * 4), be = align256((size_t)n * 8);
-    const size_t bm = match ? align256((size_t)NA * 4 + 4) : 0;
-    unsigned char* base = nullptr;
-    ICS_TRY(scratch_get(ba + bb + 2 * bao + be + bm, &base));
-    double* da = reinterpret_cast<double*>(base);
-    double* db = reinterpret_cast<double*>(base + ba);
-    int* dao = reinterpret_cast<int*>(base + ba + bb);
-    int* dbo = reinterpret_cast<int*>(base + ba + bb + bao);
-    double* demd = reinterpret_cast<double*>(base + ba + bb + 2 * bao);
-    int* dmatch = match ? reinterpret_cast<int*>(base + ba + bb + 2 * bao + be) : nullptr;
-    if (NA) ICS_HIP(hipMemcpyAsync(da, a + 3 * (size_t)A0, (size_t)NA * 24, hipMemcpyHostToDevice, st));
-    if (NB) ICS_HIP(hipMemcpyAsync(db, b + 3 * (size_t)B0, (size_t)NB * 24, hipMemcpyHostToDevice, st));
-    ICS_HIP(hipMemcpyAsync(dao, ao.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
-    ICS_HIP(hipMemcpyAsync(dbo, bo.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    Layout L;
+    const auto s_a = L.add<double>(3 * (size_t)NA + 1), s_b = L.add<double>(3 * (size_t)NB + 1);   // one spare: never empty
+    const auto s_ao = L.add<int>(n + 1), s_bo = L.add<int>(n + 1);
+    const auto s_emd = L.add<double>(n);
+    const auto s_match = L.add<int>(match ? (size_t)NA + 1 : 0);
+    double *da, *db, *demd;
+    int *dao, *dbo, *dmatch;
+    ICS_TRY(L.reserve(s_a, &da, s_b, &db, s_ao, &dao, s_bo, &dbo, s_emd, &demd, s_match, &dmatch));
+    ICS_TRY(L.upload(s_a, a + 3 * (size_t)A0, 3 * (size_t)NA, st));
+    ICS_TRY(L.upload(s_b, b + 3 * (size_t)B0, 3 * (size_t)NB, st));
+    ICS_TRY(L.upload(s_ao, ao.data(), n + 1, st));
+    ICS_TRY(L.upload(s_bo, bo.data(), n + 1, st));
     // one wave per sample while every sample's columns fit in two passes of it; four waves above that
     if (mc <= 128) ICS_TRY(launch_chunk<64>(st, da, dao, db, dbo, n, mc, mr, demd, dmatch));
     else ICS_TRY(launch_chunk<256>(st, da, dao, db, dbo, n, mc, mr, demd, dmatch));
-    ICS_HIP(hipMemcpyAsync(emd + s0, demd, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (match && NA) ICS_HIP(hipMemcpyAsync(match + A0, dmatch, (size_t)NA * 4, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.download(emd + s0, s_emd, n, st));
+    if (match) ICS_TRY(L.download(match + A0, s_match, NA, st));
     ICS_HIP(hipStreamSynchronize(st));
     s0 = s1;
   }

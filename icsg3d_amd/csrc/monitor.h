@@ -91,15 +91,13 @@ int slice_check(const char* op, int dtype, int count, int d, int stride_c, int c
                 const float* lut, const float* range_or_null, int zoom, const float* out);
 
 // The slice picture of DEVICE values (dtype 0 float32, 1 uint8, 2 int32) under `lay` and a DEVICE lut into DEVICE out
-// [count][d zoom][d zoom][4].  d_range: DEVICE [count][2] scratch; with h_range the given (vmin, vmax) is written to every
-// row of it, without, the range kernel fills it.  Asynchronous on st.  The one launch site of the slice kernels: the
+// [count][d zoom][d zoom][4].  d_range: DEVICE [count][2] scratch; with own_range the range kernel fills it, without, the
+// caller has uploaded the given (vmin, vmax) to its first row.  Asynchronous on st.  The one launch site of the slice kernels: the
 // host-pointer op and the two resident entries all come here, which is why their images are the same bits.
 int slice_device(hipStream_t st, const void* src, int dtype, const SliceLayout& lay, int count, int d, const float* d_lut,
-                 const float* h_range, float* d_range, int zoom, float* d_out);
-// bytes of device scratch slice_device's callers set aside for d_range
-inline size_t slice_range_bytes(int count) { return (((size_t)count * 2 * sizeof(float)) + 255) & ~(size_t)255; }
+                 bool own_range, float* d_range, int zoom, float* d_out);
 // Host-pointer op on checked arguments: the planes are gathered on the host, uploaded, drawn and downloaded in chunks
-// under a device-memory budget through the calling thread's scratch (segment.h); synchronous on st.
+// under a device-memory budget through the calling thread's scratch (scratch.h); synchronous on st.
 int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
              const float* lut, const float* range_or_null, int zoom, float* out);
 

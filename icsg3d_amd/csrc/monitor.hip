@@ -13,7 +13,7 @@
 #pragma clang fp contract(off)
 
 #include "monitor.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -33,7 +33,6 @@ constexpr size_t kMonitorBudget = (size_t)256 << 20;   // device bytes per chunk
 constexpr int kKdeThreads = 256, kKdeChunk = 2048;
 constexpr int kLineThreads = 256, kLineTile = 16;
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 template <typename V>
 __device__ __forceinline__ V wave_min(V v) {
@@ -282,27 +281,26 @@ int slice_check(const char* who, int dtype, int count, int d, int stride_c, int 
 }
 
 int slice_device(hipStream_t st, const void* src, int dtype, const SliceLayout& lay, int count, int d, const float* d_lut,
-                 const float* h_range, float* d_range, int zoom, float* d_out) {
-  if (h_range) ICS_HIP(hipMemcpyAsync(d_range, h_range, 2 * sizeof(float), hipMemcpyHostToDevice, st));
-  const bool own = h_range == nullptr;
-  if (dtype == 0) return slice_launch<float>(st, src, lay, count, d, d_lut, own, d_range, zoom, d_out);
-  if (dtype == 1) return slice_launch<unsigned char>(st, src, lay, count, d, d_lut, own, d_range, zoom, d_out);
-  return slice_launch<int32_t>(st, src, lay, count, d, d_lut, own, d_range, zoom, d_out);
+                 bool own_range, float* d_range, int zoom, float* d_out) {
+  if (dtype == 0) return slice_launch<float>(st, src, lay, count, d, d_lut, own_range, d_range, zoom, d_out);
+  if (dtype == 1) return slice_launch<unsigned char>(st, src, lay, count, d, d_lut, own_range, d_range, zoom, d_out);
+  return slice_launch<int32_t>(st, src, lay, count, d, d_lut, own_range, d_range, zoom, d_out);
 }
 
 int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
              const float* lut, const float* range, int zoom, float* out) {
   const size_t es = slice_elem_bytes(dtype), side = (size_t)d * zoom;
-  const size_t plane_b = (size_t)d * d * es, img_b = side * side * 16, lut_b = up256(3 * kMonitorLutRows * sizeof(float));
+  const size_t plane_b = (size_t)d * d * es, img_b = side * side * 16;
   const int nb = (int)std::min<size_t>((size_t)batch, std::max<size_t>(1, kMonitorBudget / (plane_b + img_b)));
-  const size_t rng_b = slice_range_bytes(nb);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(lut_b + rng_b + up256(plane_b * nb) + img_b * nb, &base));
-  float* d_lut = reinterpret_cast<float*>(base);
-  float* d_rng = reinterpret_cast<float*>(base + lut_b);
-  unsigned char* d_src = base + lut_b + rng_b;
-  float* d_out = reinterpret_cast<float*>(base + lut_b + rng_b + up256(plane_b * nb));
-  ICS_HIP(hipMemcpyAsync(d_lut, lut, 3 * kMonitorLutRows * sizeof(float), hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_lut = L.add<float>(3 * kMonitorLutRows);
+  const auto s_rng = L.add<float>(2 * (size_t)nb);
+  const auto s_src = L.add<unsigned char>(plane_b * nb);
+  const auto s_out = L.add<float>(img_b / 4 * nb);
+  float *d_lut, *d_rng, *d_out;
+  unsigned char* d_src;
+  ICS_TRY(L.reserve(s_lut, &d_lut, s_rng, &d_rng, s_src, &d_src, s_out, &d_out));
+  ICS_TRY(L.upload(s_lut, lut, s_lut.count, st));
   const SliceLayout src_l = slice_layout(d, stride_c, channel, axis, index);
   const SliceLayout dev_l = {(size_t)d * d, (size_t)d, 1, 0};
   std::vector<unsigned char> planes(plane_b * nb);
@@ -314,9 +312,10 @@ int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int s
         for (int c = 0; c < d; ++c)
           std::memcpy(&planes[(((size_t)b * d + r) * d + c) * es],
                       v + (src_l.offset + (size_t)(b0 + b) * src_l.img + (size_t)r * src_l.row + (size_t)c * src_l.col) * es, es);
-    ICS_HIP(hipMemcpyAsync(d_src, planes.data(), plane_b * n, hipMemcpyHostToDevice, st));
-    ICS_TRY(slice_device(st, d_src, dtype, dev_l, n, d, d_lut, range, d_rng, zoom, d_out));
-    ICS_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(out) + img_b * b0, d_out, img_b * n, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.upload(s_src, planes.data(), plane_b * n, st));
+    if (range) ICS_TRY(L.upload(s_rng, range, 2, st));
+    ICS_TRY(slice_device(st, d_src, dtype, dev_l, n, d, d_lut, range == nullptr, d_rng, zoom, d_out));
+    ICS_TRY(L.download(reinterpret_cast<unsigned char*>(out) + img_b * b0, s_out, img_b / 4 * n, st));
     ICS_HIP(hipStreamSynchronize(st));   // planes is refilled by the next chunk
   }
   return 0;
@@ -390,22 +389,22 @@ int kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double*
   ICS_CHECK(h->count >= 2, "ics_op_kde_evaluate: at least 2 codes are needed, the handle has " + std::to_string(h->count));
   for (int k = 0; k < npts; ++k) ICS_CHECK(!std::isnan(x[k]), "ics_op_kde_evaluate: x must not be NaN");
   const int n = h->count, dim = h->dim;
-  const size_t x_b = up256((size_t)npts * 8), dens_b = up256((size_t)dim * npts * 8), bw_b = up256((size_t)dim * 8),
-               st_b = up256((size_t)dim * 4);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(x_b + dens_b + bw_b + st_b, &base));
-  double* d_x = reinterpret_cast<double*>(base);
-  double* d_dens = reinterpret_cast<double*>(base + x_b);
-  double* d_bw = reinterpret_cast<double*>(base + x_b + dens_b);
-  int* d_st = reinterpret_cast<int*>(base + x_b + dens_b + bw_b);
-  ICS_HIP(hipMemcpyAsync(d_x, x, (size_t)npts * 8, hipMemcpyHostToDevice, h->st));
+  Layout L;
+  const auto s_x = L.add<double>(npts);
+  const auto s_dens = L.add<double>((size_t)dim * npts);
+  const auto s_bw = L.add<double>(dim);
+  const auto s_st = L.add<int>(dim);
+  double *d_x, *d_dens, *d_bw;
+  int* d_st;
+  ICS_TRY(L.reserve(s_x, &d_x, s_dens, &d_dens, s_bw, &d_bw, s_st, &d_st));
+  ICS_TRY(L.upload(s_x, x, npts, h->st));
   const double fac = std::pow((double)n, -1.0 / 5.0);
   ICS_LAUNCH(kde_kernel, dim3((unsigned)dim), dim3(kKdeThreads), 0, h->st, (const float*)h->codes, n, dim,
              (const double*)d_x, npts, fac * fac, d_dens, d_bw, d_st);
   ICS_HIP(hipGetLastError());
-  ICS_HIP(hipMemcpyAsync(density, d_dens, (size_t)dim * npts * 8, hipMemcpyDeviceToHost, h->st));
-  if (bandwidth) ICS_HIP(hipMemcpyAsync(bandwidth, d_bw, (size_t)dim * 8, hipMemcpyDeviceToHost, h->st));
-  if (status) ICS_HIP(hipMemcpyAsync(status, d_st, (size_t)dim * 4, hipMemcpyDeviceToHost, h->st));
+  ICS_TRY(L.download(density, s_dens, s_dens.count, h->st));
+  if (bandwidth) ICS_TRY(L.download(bandwidth, s_bw, dim, h->st));
+  if (status) ICS_TRY(L.download(status, s_st, dim, h->st));
   ICS_HIP(hipStreamSynchronize(h->st));
   if (count) *count = n;
   return 0;
@@ -432,14 +431,15 @@ int lines_check(const double* xy, int ncurves, int npts, const double* window, c
 
 int lines_op(hipStream_t st, const double* xy, int ncurves, int npts, const double* window, const float* palette, int npal,
              double width_px, float alpha, int width, int height, float* out) {
-  const size_t xy_n = (size_t)ncurves * npts * 2 * 8, pal_n = (size_t)npal * 3 * 4, img_b = (size_t)width * height * 16;
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(up256(xy_n) + up256(pal_n) + img_b, &base));
-  double* d_xy = reinterpret_cast<double*>(base);
-  float* d_pal = reinterpret_cast<float*>(base + up256(xy_n));
-  float* d_out = reinterpret_cast<float*>(base + up256(xy_n) + up256(pal_n));
-  ICS_HIP(hipMemcpyAsync(d_xy, xy, xy_n, hipMemcpyHostToDevice, st));
-  ICS_HIP(hipMemcpyAsync(d_pal, palette, pal_n, hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_xy = L.add<double>((size_t)ncurves * npts * 2);
+  const auto s_pal = L.add<float>((size_t)npal * 3);
+  const auto s_out = L.add<float>((size_t)width * height * 4);
+  double* d_xy;
+  float *d_pal, *d_out;
+  ICS_TRY(L.reserve(s_xy, &d_xy, s_pal, &d_pal, s_out, &d_out));
+  ICS_TRY(L.upload(s_xy, xy, s_xy.count, st));
+  ICS_TRY(L.upload(s_pal, palette, s_pal.count, st));
   LineArgs a;
   a.x0 = window[0]; a.x1 = window[1]; a.y0 = window[2]; a.y1 = window[3];
   a.reach = width_px / 2.0 + 0.5; a.alpha = (double)alpha;
@@ -447,7 +447,7 @@ int lines_op(hipStream_t st, const double* xy, int ncurves, int npts, const doub
   ICS_LAUNCH(lines_kernel, dim3((unsigned)((width + kLineTile - 1) / kLineTile), (unsigned)((height + kLineTile - 1) / kLineTile)),
              dim3(kLineThreads), 0, st, (const double*)d_xy, a, (const float*)d_pal, d_out);
   ICS_HIP(hipGetLastError());
-  ICS_HIP(hipMemcpyAsync(out, d_out, img_b, hipMemcpyDeviceToHost, st));
+  ICS_TRY(L.download(out, s_out, s_out.count, st));
   ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }

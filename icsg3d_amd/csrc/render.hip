@@ -9,7 +9,7 @@
 // Staging the whole volume in LDS instead (128 KiB at d = 32, 32x32 pixels per 1024-thread workgroup) was built and measured:
 // 1.4 - 1.6x slower than these global reads, so it is not kept.
 #include "render.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -20,7 +20,6 @@ namespace {
 
 constexpr size_t kRenderBudget = (size_t)256 << 20;   // device bytes per chunk (volumes + pictures)
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 RenderView<float> view_f32(const RenderView<double>& v) {
   RenderView<float> f;
@@ -163,19 +162,19 @@ int render_density_op(hipStream_t st, const float* vol, int B, int d, int stride
   RenderView<double> view;
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_density: camera must be finite");
   const size_t vol_b = (size_t)d * d * d * stride_c * sizeof(float), img_b = (size_t)W * H * 16;
-  const size_t lut_b = up256(3 * kRenderLutRows * sizeof(float));
   const int nb = chunk_images(vol_b + img_b, B);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(lut_b + up256(vol_b * nb) + img_b * nb, &base));
-  float* d_lut = reinterpret_cast<float*>(base);
-  float* d_vol = reinterpret_cast<float*>(base + lut_b);
-  float* d_out = reinterpret_cast<float*>(base + lut_b + up256(vol_b * nb));
-  ICS_HIP(hipMemcpyAsync(d_lut, lut, 3 * kRenderLutRows * sizeof(float), hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_lut = L.add<float>(3 * kRenderLutRows);
+  const auto s_vol = L.add<float>(vol_b / 4 * nb);
+  const auto s_out = L.add<float>(img_b / 4 * nb);
+  float *d_lut, *d_vol, *d_out;
+  ICS_TRY(L.reserve(s_lut, &d_lut, s_vol, &d_vol, s_out, &d_out));
+  ICS_TRY(L.upload(s_lut, lut, s_lut.count, st));
   for (int b0 = 0; b0 < B; b0 += nb) {
     const int n = std::min(nb, B - b0);
-    ICS_HIP(hipMemcpyAsync(d_vol, reinterpret_cast<const unsigned char*>(vol) + vol_b * b0, vol_b * n, hipMemcpyHostToDevice, st));
+    ICS_TRY(L.upload(s_vol, reinterpret_cast<const unsigned char*>(vol) + vol_b * b0, vol_b / 4 * n, st));
     ICS_TRY(render_density_device(st, d_vol, n, d, stride_c, channel, d_lut, mode, alpha, floor_v, view, W, H, d_out));
-    ICS_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(out) + img_b * b0, d_out, img_b * n, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.download(reinterpret_cast<unsigned char*>(out) + img_b * b0, s_out, img_b / 4 * n, st));
     ICS_HIP(hipStreamSynchronize(st));
   }
   return 0;
@@ -187,20 +186,21 @@ int render_labels_op(hipStream_t st, const int32_t* labels, int B, int d, const 
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_labels: camera must be finite");
   const RenderView<float> V = view_f32(view);
   const size_t vol_b = (size_t)d * d * d * sizeof(int32_t), img_b = (size_t)W * H * 16;
-  const size_t pal_b = up256((size_t)npal * 3 * sizeof(float));
   const int nb = chunk_images(vol_b + img_b, B);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(pal_b + up256(vol_b * nb) + img_b * nb, &base));
-  float* d_pal = reinterpret_cast<float*>(base);
-  int* d_lab = reinterpret_cast<int*>(base + pal_b);
-  float* d_out = reinterpret_cast<float*>(base + pal_b + up256(vol_b * nb));
-  ICS_HIP(hipMemcpyAsync(d_pal, palette, (size_t)npal * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_pal = L.add<float>((size_t)npal * 3);
+  const auto s_lab = L.add<int>(vol_b / 4 * nb);
+  const auto s_out = L.add<float>(img_b / 4 * nb);
+  float *d_pal, *d_out;
+  int* d_lab;
+  ICS_TRY(L.reserve(s_pal, &d_pal, s_lab, &d_lab, s_out, &d_out));
+  ICS_TRY(L.upload(s_pal, palette, s_pal.count, st));
   for (int b0 = 0; b0 < B; b0 += nb) {
     const int n = std::min(nb, B - b0);
-    ICS_HIP(hipMemcpyAsync(d_lab, reinterpret_cast<const unsigned char*>(labels) + vol_b * b0, vol_b * n, hipMemcpyHostToDevice, st));
+    ICS_TRY(L.upload(s_lab, reinterpret_cast<const unsigned char*>(labels) + vol_b * b0, vol_b / 4 * n, st));
     ICS_LAUNCH(render_labels_kernel, tile_grid(W, H, n), dim3(256), 0, st, d_lab, d, d_pal, npal, alpha, V, W, H, d_out);
     ICS_HIP(hipGetLastError());
-    ICS_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(out) + img_b * b0, d_out, img_b * n, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.download(reinterpret_cast<unsigned char*>(out) + img_b * b0, s_out, img_b / 4 * n, st));
     ICS_HIP(hipStreamSynchronize(st));
   }
   return 0;
@@ -210,7 +210,7 @@ int render_atoms_op(hipStream_t st, const int32_t* offsets, const int32_t* speci
                     double radius, const float* palette, int npal, const double* camera, int W, int H, float* out) {
   RenderView<double> view;
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_atoms: camera must be finite");
-  const size_t img_b = (size_t)W * H * 16, pal_b = up256((size_t)npal * 3 * sizeof(float));
+  const size_t img_b = (size_t)W * H * 16;
   const int nb = chunk_images(img_b, B);
   std::vector<int32_t> off(nb + 1);
   for (int b0 = 0; b0 < B; b0 += nb) {
@@ -218,24 +218,26 @@ int render_atoms_op(hipStream_t st, const int32_t* offsets, const int32_t* speci
     const int A0 = offsets[b0];
     const size_t N = (size_t)(offsets[b0 + n] - A0);
     for (int k = 0; k <= n; ++k) off[k] = offsets[b0 + k] - A0;
-    const size_t off_b = up256((size_t)(n + 1) * 4), sp_b = up256(N * 4 + 4), xyz_b = up256(N * 24 + 8);
-    unsigned char* base = nullptr;
-    ICS_TRY(scratch_get(pal_b + off_b + sp_b + xyz_b + img_b * n, &base));
-    float* d_pal = reinterpret_cast<float*>(base);
-    int* d_off = reinterpret_cast<int*>(base + pal_b);
-    int* d_sp = reinterpret_cast<int*>(base + pal_b + off_b);
-    double* d_xyz = reinterpret_cast<double*>(base + pal_b + off_b + sp_b);
-    float* d_out = reinterpret_cast<float*>(base + pal_b + off_b + sp_b + xyz_b);
-    ICS_HIP(hipMemcpyAsync(d_pal, palette, (size_t)npal * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-    ICS_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, st));
+    Layout L;
+    const auto s_pal = L.add<float>((size_t)npal * 3);
+    const auto s_off = L.add<int>(n + 1);
+    const auto s_sp = L.add<int>(N + 1);          // one spare element each: never empty
+    const auto s_xyz = L.add<double>(3 * N + 1);
+    const auto s_out = L.add<float>(img_b / 4 * n);
+    float *d_pal, *d_out;
+    int *d_off, *d_sp;
+    double* d_xyz;
+    ICS_TRY(L.reserve(s_pal, &d_pal, s_off, &d_off, s_sp, &d_sp, s_xyz, &d_xyz, s_out, &d_out));
+    ICS_TRY(L.upload(s_pal, palette, s_pal.count, st));
+    ICS_TRY(L.upload(s_off, off.data(), n + 1, st));
     if (N) {
-      ICS_HIP(hipMemcpyAsync(d_sp, species + A0, N * 4, hipMemcpyHostToDevice, st));
-      ICS_HIP(hipMemcpyAsync(d_xyz, xyz + 3 * (size_t)A0, N * 24, hipMemcpyHostToDevice, st));
+      ICS_TRY(L.upload(s_sp, species + A0, N, st));
+      ICS_TRY(L.upload(s_xyz, xyz + 3 * (size_t)A0, 3 * N, st));
     }
     ICS_LAUNCH(render_atoms_kernel, tile_grid(W, H, n), dim3(256), 0, st, d_off, d_sp, d_xyz, radius, d_pal, npal, view, W,
                H, d_out);
     ICS_HIP(hipGetLastError());
-    ICS_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(out) + img_b * b0, d_out, img_b * n, hipMemcpyDeviceToHost, st));
+    ICS_TRY(L.download(reinterpret_cast<unsigned char*>(out) + img_b * b0, s_out, img_b / 4 * n, st));
     ICS_HIP(hipStreamSynchronize(st));   // off is reused by the next chunk
   }
   return 0;

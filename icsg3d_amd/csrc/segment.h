@@ -49,10 +49,4 @@ int segment_watershed_split_host(const int* h_boxes, const int* h_dims, const in
 int segment_component_bounds(const int* h_labels, const int* h_dims, int nbox, const int* h_nlabels, const int* h_stats,
                              int max_labels, int min_voxels, double hull_threshold, long long* h_bounds);
 
-// The calling thread's grow-only device scratch (>= bytes; contents not kept across calls that grow it), shared by the
-// box-level entry points above and ics_op_voxelise; segment_release_scratch (ics_release_caches) frees it.
-int scratch_get(size_t bytes, unsigned char** out);
-// frees the calling thread's grow-only scratch of the three box-level entry points above
-void segment_release_scratch();
-
 }  // namespace ics

@@ -15,6 +15,7 @@
 // 1-2 M voxels per call).
 #include "common.h"
 #include "segment.h"
+#include "scratch.h"
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -593,81 +594,32 @@ static bool label_host_forced() {
   return e != nullptr && atoi(e) != 0;
 }
 
-// The box-level entry points are called once per recursion level of segment_nuclei -- tens of times per sample, a few tens of
-// KB each.  A hipMalloc / hipFree pair per call (the free synchronises the device) cost more than the kernels: the scratch
-// is a grow-only buffer per host thread, released by segment_release_scratch() (ics_release_caches) or with the process.
-namespace {
-struct Scratch { unsigned char* p = nullptr; size_t cap = 0; int device = -1; };
-// A host thread that used the box-level ops and then exits (a pool worker, a loader thread) must not leak its buffer until
-// the process ends -- and a thread_local destructor must not call into a HIP runtime that may already be
-// shutting down.  So the destructor only hands the buffer to a process-wide list of orphans; the next scratch allocation
-// of any thread, and ics_release_caches, free them.
-std::mutex g_orphan_mu;
-std::vector<unsigned char*> g_orphans;
-void reap_orphans() {
-  std::vector<unsigned char*> take;
-  { std::lock_guard<std::mutex> lk(g_orphan_mu); take.swap(g_orphans); }
-  for (unsigned char* p : take) (void)hipFree(p);
-}
-struct ScratchTL {
-  Scratch s;
-  ~ScratchTL() {
-    if (s.p) { std::lock_guard<std::mutex> lk(g_orphan_mu); g_orphans.push_back(s.p); }
-  }
-};
-thread_local ScratchTL tl_scratch_holder;
-#define tl_scratch (tl_scratch_holder.s)
-}  // namespace
-int scratch_get(size_t bytes, unsigned char** out) {
-  int dev = 0;
-  ICS_HIP(hipGetDevice(&dev));
-  Scratch& s = tl_scratch;
-  if (s.p == nullptr || s.cap < bytes || s.device != dev) {
-    reap_orphans();
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr; s.cap = 0;
-    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
-    ICS_HIP(hipMalloc(reinterpret_cast<void**>(&s.p), want));
-    s.cap = want; s.device = dev;
-  }
-  *out = s.p;
-  return 0;
-}
-void segment_release_scratch() {
-  if (tl_scratch.p) (void)hipFree(tl_scratch.p);
-  tl_scratch = Scratch{};
-  reap_orphans();
-}
-#undef tl_scratch
-
 int segment_region_stats(hipStream_t st, const int* h_R, const unsigned char* h_species, int D, int H, int W, int nlab,
                          int nbins, int* h_stats) {
   ICS_CHECK(h_R && h_species && h_stats && D >= 1 && H >= 1 && W >= 1 && nlab >= 1 && nbins >= 2 && nbins <= 256,
             "bad region_stats arguments");
   const size_t V = (size_t)D * H * W;
   ICS_CHECK(V < (1u << 30), "volume too large");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_R = V * 4, b_sp = V, b_st = (size_t)nlab * kSegStatInts * 4, b_h = (size_t)nlab * nbins * 4;
-  unsigned char* buf = nullptr;
-  ICS_TRY(scratch_get(up(b_R) + up(b_sp) + up(b_st) + up(b_h), &buf));
-  int* d_R = reinterpret_cast<int*>(buf);
-  unsigned char* d_sp = buf + up(b_R);
-  int* d_st = reinterpret_cast<int*>(buf + up(b_R) + up(b_sp));
-  unsigned* d_h = reinterpret_cast<unsigned*>(buf + up(b_R) + up(b_sp) + up(b_st));
-  hipError_t e = hipMemcpyAsync(d_R, h_R, b_R, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_sp, h_species, b_sp, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_h, 0, b_h, st);
-  if (e == hipSuccess) {
-    const int dmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
-    ICS_LAUNCH(seg_stats_init_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_st, (size_t)nlab, dmax);
-    ICS_LAUNCH(region_stats_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_R, d_sp, D, H, W, nlab, nbins,
-               d_st, d_h);
-    ICS_LAUNCH(seg_vote_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_h, nbins, (size_t)nlab, d_st);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d_st, b_st, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_error(std::string("region_stats: ") + hipGetErrorString(e)); return -1; }
+  Layout L;
+  const auto s_R = L.add<int>(V);
+  const auto s_sp = L.add<unsigned char>(V);
+  const auto s_st = L.add<int>((size_t)nlab * kSegStatInts);
+  const auto s_h = L.add<unsigned>((size_t)nlab * nbins);
+  int *d_R, *d_st;
+  unsigned char* d_sp;
+  unsigned* d_h;
+  ICS_TRY(L.reserve(s_R, &d_R, s_sp, &d_sp, s_st, &d_st, s_h, &d_h));
+  ICS_TRY(L.upload(s_R, h_R, V, st));
+  ICS_TRY(L.upload(s_sp, h_species, V, st));
+  ICS_TRY(L.fill(s_h, 0, s_h.count, st));
+  const int dmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
+  ICS_LAUNCH(seg_stats_init_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_st, (size_t)nlab, dmax);
+  ICS_LAUNCH(region_stats_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_R, d_sp, D, H, W, nlab, nbins,
+             d_st, d_h);
+  ICS_LAUNCH(seg_vote_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_h, nbins, (size_t)nlab, d_st);
+  ICS_HIP(hipGetLastError());
+  ICS_TRY(L.download(h_stats, s_st, s_st.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -987,27 +939,23 @@ int segment_label_boxes(int (*get_stream)(hipStream_t*), const int* h_vols, cons
   const int ndev = (int)on_dev.size();
   hipStream_t st;
   ICS_TRY(get_stream(&st));
-  unsigned char* buf = nullptr;
-  const size_t b_vol = dtotal * 4, b_desc = (size_t)ndev * sizeof(BoxDesc), b_n = (size_t)ndev * 4, b_st = (size_t)ndev * row * 4;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  ICS_TRY(scratch_get(up(b_vol) * 2 + up(b_desc) + up(b_n) + up(b_st), &buf));
-  int* d_vol = reinterpret_cast<int*>(buf);
-  int* d_lab = reinterpret_cast<int*>(buf + up(b_vol));
-  BoxDesc* d_desc = reinterpret_cast<BoxDesc*>(buf + 2 * up(b_vol));
-  int* d_n = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc));
-  int* d_st = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc) + up(b_n));
-  hipError_t e = hipMemcpyAsync(d_vol, vols, b_vol, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, dd->data(), b_desc, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    ICS_LAUNCH(label_boxes_kernel, dim3(ndev), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
-               d_lab, d_n, d_st);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(labels, d_lab, b_vol, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(nlabels, d_n, b_n, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_st, b_st, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_error(std::string("label_boxes: ") + hipGetErrorString(e)); return -1; }
+  Layout L;
+  const auto s_vol = L.add<int>(dtotal), s_lab = L.add<int>(dtotal);
+  const auto s_desc = L.add<BoxDesc>(ndev);
+  const auto s_n = L.add<int>(ndev);
+  const auto s_st = L.add<int>((size_t)ndev * row);
+  int *d_vol, *d_lab, *d_n, *d_st;
+  BoxDesc* d_desc;
+  ICS_TRY(L.reserve(s_vol, &d_vol, s_lab, &d_lab, s_desc, &d_desc, s_n, &d_n, s_st, &d_st));
+  ICS_TRY(L.upload(s_vol, vols, dtotal, st));
+  ICS_TRY(L.upload(s_desc, dd->data(), ndev, st));
+  ICS_LAUNCH(label_boxes_kernel, dim3(ndev), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
+             d_lab, d_n, d_st);
+  ICS_HIP(hipGetLastError());
+  ICS_TRY(L.download(labels, s_lab, dtotal, st));
+  ICS_TRY(L.download(nlabels, s_n, ndev, st));
+  if (stats) ICS_TRY(L.download(stats, s_st, s_st.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
   if (mixed)
     for (int k = 0; k < ndev; ++k) {
       const int b = on_dev[k];
@@ -1380,25 +1328,22 @@ int segment_watershed_split(hipStream_t st, const int* h_boxes, const int* h_dim
     boxes = pvol.data(); wss = pout.data(); dd = &pdesc;
   }
   const int ndev = (int)on_dev.size();
-  unsigned char* buf = nullptr;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_vol = dtotal * 4, b_desc = (size_t)ndev * sizeof(BoxDesc);
+  Layout L;
+  const auto s_box = L.add<int>(dtotal), s_out = L.add<int>(dtotal);
+  const auto s_desc = L.add<BoxDesc>(ndev);
   // work: 4 ints per voxel (BoxDesc::heap_off * 2 with room to spare), heap: 2 unsigned per voxel
-  ICS_TRY(scratch_get(up(b_vol) * 2 + up(b_desc) + up(b_vol * 4) + up(b_vol * 2), &buf));
-  int* d_box = reinterpret_cast<int*>(buf);
-  int* d_out = reinterpret_cast<int*>(buf + up(b_vol));
-  BoxDesc* d_desc = reinterpret_cast<BoxDesc*>(buf + 2 * up(b_vol));
-  int* d_work = reinterpret_cast<int*>(buf + 2 * up(b_vol) + up(b_desc));
-  unsigned* d_heap = reinterpret_cast<unsigned*>(buf + 2 * up(b_vol) + up(b_desc) + up(b_vol * 4));
-  hipError_t e = hipMemcpyAsync(d_box, boxes, b_vol, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, dd->data(), b_desc, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    ICS_LAUNCH(ws_split_kernel, dim3(ndev), dim3(1024), 0, st, d_box, d_desc, tie, d_work, d_heap, d_out);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(wss, d_out, b_vol, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { set_error(std::string("watershed_split: ") + hipGetErrorString(e)); return -1; }
+  const auto s_work = L.add<int>(dtotal * 4);
+  const auto s_heap = L.add<unsigned>(dtotal * 2);
+  int *d_box, *d_out, *d_work;
+  BoxDesc* d_desc;
+  unsigned* d_heap;
+  ICS_TRY(L.reserve(s_box, &d_box, s_out, &d_out, s_desc, &d_desc, s_work, &d_work, s_heap, &d_heap));
+  ICS_TRY(L.upload(s_box, boxes, dtotal, st));
+  ICS_TRY(L.upload(s_desc, dd->data(), ndev, st));
+  ICS_LAUNCH(ws_split_kernel, dim3(ndev), dim3(1024), 0, st, d_box, d_desc, tie, d_work, d_heap, d_out);
+  ICS_HIP(hipGetLastError());
+  ICS_TRY(L.download(wss, s_out, dtotal, st));
+  ICS_HIP(hipStreamSynchronize(st));
   if (mixed)
     for (int k = 0; k < ndev; ++k) {
       const BoxDesc &d = desc[on_dev[k]], &p = pdesc[k];

@@ -14,7 +14,7 @@
 // atomic min on the bit pattern of the (non-negative) distance and the histogram an integer LDS atomic add, so no result
 // depends on arrival order.
 #include "structure.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,8 +28,6 @@ constexpr int kStructMaxChunk = 1 << 16;            // structures per chunk
 constexpr int kStructSmall = 64;                    // atoms one wave takes
 constexpr double kRangeSlack = 1e-9;                // widens every image range: rounding never drops the minimiser
 constexpr int kCellStride = 16;                     // doubles per structure: M[9], abc[3], g[3], pad
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // dynamic LDS of one group of threads for `cap` atoms (cap even)
 __host__ __device__ inline size_t struct_lds_bytes(int cap) {
@@ -269,17 +267,16 @@ int structure_screen_op(hipStream_t st, const int32_t* offsets, const int32_t* s
     const int A0 = offsets[s0];
     const size_t N = atoms;
     // upload: cells | xyz | offsets | species | ids (small first)     download: frac | nearest | dmin | int rows
-    const size_t i_cell = 0, i_xyz = i_cell + align16((size_t)ns * kCellStride * 8), i_off = i_xyz + align16(N * 24 + 8),
-                 i_spec = i_off + align16((size_t)(ns + 1) * 4), i_ids = i_spec + align16(N * 4 + 4),
-                 in_bytes = i_ids + align16((size_t)ns * 4);
-    const size_t o_frac = 0, o_near = o_frac + align16(N * 24 + 8), o_dmin = o_near + align16(N * 8 + 8),
-                 o_pair = o_dmin + align16((size_t)ns * 8), o_close = o_pair + align16((size_t)ns * 8),
-                 o_valid = o_close + align16((size_t)ns * 4), o_reason = o_valid + align16((size_t)ns * 4),
-                 o_hist = o_reason + align16((size_t)ns * 4), out_bytes = o_hist + align16((size_t)ns * kStructHist * 4);
-    hin.assign(in_bytes, 0);
-    double* hc = reinterpret_cast<double*>(hin.data() + i_cell);
-    int* ho = reinterpret_cast<int*>(hin.data() + i_off);
-    int* hi = reinterpret_cast<int*>(hin.data() + i_ids);
+    Layout in(16), res(16);
+    const auto i_cell = in.add<double>((size_t)ns * kCellStride), i_xyz = in.add<double>(3 * N + 1);
+    const auto i_off = in.add<int>(ns + 1), i_spec = in.add<int>(N + 1), i_ids = in.add<int>(ns);
+    const auto o_frac = res.add<double>(3 * N + 1), o_near = res.add<double>(N + 1), o_dmin = res.add<double>(ns);
+    const auto o_pair = res.add<int>(2 * (size_t)ns), o_close = res.add<int>(ns), o_valid = res.add<int>(ns);
+    const auto o_reason = res.add<int>(ns), o_hist = res.add<int>((size_t)ns * kStructHist);
+    hin.assign(in.bytes(), 0);
+    double *hc, *hxyz;
+    int *ho, *hspec, *hi;
+    ICS_TRY(in.bind(hin.data(), hin.size(), i_cell, &hc, i_xyz, &hxyz, i_off, &ho, i_spec, &hspec, i_ids, &hi));
     int ks = 0, kb = nsmall;
     for (int k = 0; k < ns; ++k) {
       const int s = s0 + k;
@@ -295,46 +292,41 @@ int structure_screen_op(hipStream_t st, const int32_t* offsets, const int32_t* s
     }
     ho[ns] = offsets[s1] - A0;
     if (N) {
-      std::memcpy(hin.data() + i_xyz, xyz + 3 * (size_t)A0, N * 24);
-      std::memcpy(hin.data() + i_spec, species + A0, N * 4);
+      std::memcpy(hxyz, xyz + 3 * (size_t)A0, N * 24);
+      std::memcpy(hspec, species + A0, N * 4);
     }
-    unsigned char* base = nullptr;
-    ICS_TRY(scratch_get(align16(in_bytes) + out_bytes + 256, &base));
-    unsigned char* din = base;
-    unsigned char* dout = base + ((in_bytes + 255) & ~(size_t)255);
-    ICS_HIP(hipMemcpyAsync(din, hin.data(), in_bytes, hipMemcpyHostToDevice, st));
-    const double* dcell = reinterpret_cast<const double*>(din + i_cell);
-    const double* dxyz = reinterpret_cast<const double*>(din + i_xyz);
-    const int* doff = reinterpret_cast<const int*>(din + i_off);
-    const int* dspec = reinterpret_cast<const int*>(din + i_spec);
-    const int* dids = reinterpret_cast<const int*>(din + i_ids);
-    double* dfrac = reinterpret_cast<double*>(dout + o_frac);
-    double* dnear = reinterpret_cast<double*>(dout + o_near);
-    double* ddmin = reinterpret_cast<double*>(dout + o_dmin);
-    int* dpair = reinterpret_cast<int*>(dout + o_pair);
-    int* dclose = reinterpret_cast<int*>(dout + o_close);
-    int* dvalid = reinterpret_cast<int*>(dout + o_valid);
-    int* dreason = reinterpret_cast<int*>(dout + o_reason);
-    int* dhist = reinterpret_cast<int*>(dout + o_hist);
+    Layout L;
+    const auto s_in = L.add<unsigned char>(in.bytes()), s_res = L.add<unsigned char>(res.bytes());
+    unsigned char *din, *dres;
+    ICS_TRY(L.reserve(s_in, &din, s_res, &dres));
+    ICS_TRY(L.upload(s_in, hin.data(), in.bytes(), st));
+    double *dcell, *dxyz, *dfrac, *dnear, *ddmin;
+    int *doff, *dspec, *dids, *dpair, *dclose, *dvalid, *dreason, *dhist;
+    ICS_TRY(in.bind(din, s_in.count, i_cell, &dcell, i_xyz, &dxyz, i_off, &doff, i_spec, &dspec, i_ids, &dids));
+    ICS_TRY(res.bind(dres, s_res.count, o_frac, &dfrac, o_near, &dnear, o_dmin, &ddmin, o_pair, &dpair,
+                     o_close, &dclose, o_valid, &dvalid, o_reason, &dreason, o_hist, &dhist));
     if (nsmall)
       ICS_TRY((launch_screen<256, 64>(st, dids, nsmall, kStructSmall, doff, dspec, dxyz, dcell, tol, dfrac, dnear, ddmin,
                                       dpair, dclose, dvalid, dreason, dhist)));
     if (nbig)
       ICS_TRY((launch_screen<1024, 1024>(st, dids + nsmall, nbig, capbig, doff, dspec, dxyz, dcell, tol, dfrac, dnear,
                                          ddmin, dpair, dclose, dvalid, dreason, dhist)));
-    hout.resize(out_bytes);
-    ICS_HIP(hipMemcpyAsync(hout.data(), dout, out_bytes, hipMemcpyDeviceToHost, st));
+    hout.resize(res.bytes());
+    ICS_TRY(L.download(hout.data(), s_res, res.bytes(), st));
     ICS_HIP(hipStreamSynchronize(st));
+    // the same layout over the downloaded block
+    ICS_TRY(res.bind(hout.data(), hout.size(), o_frac, &dfrac, o_near, &dnear, o_dmin, &ddmin, o_pair, &dpair,
+                     o_close, &dclose, o_valid, &dvalid, o_reason, &dreason, o_hist, &dhist));
     if (N) {
-      std::memcpy(frac + 3 * (size_t)A0, hout.data() + o_frac, N * 24);
-      std::memcpy(nearest + A0, hout.data() + o_near, N * 8);
+      std::memcpy(frac + 3 * (size_t)A0, dfrac, N * 24);
+      std::memcpy(nearest + A0, dnear, N * 8);
     }
-    std::memcpy(min_dist + s0, hout.data() + o_dmin, (size_t)ns * 8);
-    std::memcpy(min_pair + 2 * (size_t)s0, hout.data() + o_pair, (size_t)ns * 8);
-    std::memcpy(n_close + s0, hout.data() + o_close, (size_t)ns * 4);
-    std::memcpy(valid + s0, hout.data() + o_valid, (size_t)ns * 4);
-    std::memcpy(reason + s0, hout.data() + o_reason, (size_t)ns * 4);
-    std::memcpy(hist + (size_t)kStructHist * s0, hout.data() + o_hist, (size_t)ns * kStructHist * 4);
+    std::memcpy(min_dist + s0, ddmin, (size_t)ns * 8);
+    std::memcpy(min_pair + 2 * (size_t)s0, dpair, (size_t)ns * 8);
+    std::memcpy(n_close + s0, dclose, (size_t)ns * 4);
+    std::memcpy(valid + s0, dvalid, (size_t)ns * 4);
+    std::memcpy(reason + s0, dreason, (size_t)ns * 4);
+    std::memcpy(hist + (size_t)kStructHist * s0, dhist, (size_t)ns * kStructHist * 4);
     s0 = s1;
   }
   return 0;

@@ -19,7 +19,7 @@
 // per-query state that is merged by key -- (partner) for duplicates, (rms, partner) for references -- so neither the
 // chunking nor any arrival order shows in the result.
 #include "structure_match.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <climits>
@@ -35,8 +35,6 @@ constexpr long long kMatchChunkPairs = 1 << 20;        // pair results per chunk
 constexpr size_t kMatchTableBudget = (size_t)1 << 31;  // resident structure tables
 constexpr int kCell = 16;                              // doubles per structure: M[9], G[6] (00 01 02 11 12 22), pad
 constexpr int kStateI = 6;                             // ints per query: dup k, op, anchor; ref k, op, anchor
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 long long chunk_pairs() {
   static const long long v = [] {
@@ -387,25 +385,23 @@ int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* sp
   int perm[kMatchOps][3], sign[kMatchOps][3];
   const int nops = structure_match_ops(ops_mode, perm, sign);
   const long long cp = std::min(chunk_pairs(), ptotal);
-  const size_t i_cell = 0, i_frac = i_cell + align16((size_t)ne * kCell * 8), i_std = i_frac + align16(N * 24),
-               i_pref = i_std + align16((size_t)nqs * 16), i_info = i_pref + align16((size_t)(nqs + 1) * 8),
-               i_qrec = i_info + align16((size_t)ne * 16), i_perm = i_qrec + align16((size_t)nqs * 16),
-               i_run = i_perm + align16(N * 4), i_ops = i_run + align16(N * 4), i_sti = i_ops + align16(kMatchOps * 4),
-               in_bytes = i_sti + align16((size_t)nqs * kStateI * 4);
-  const size_t o_rms = 0, o_oa = o_rms + align16((size_t)cp * 8), out_bytes = o_oa + align16((size_t)cp * 8);
-  if (in_bytes > kMatchTableBudget) {
-    set_error("ics_op_structure_match: the structure tables (" + std::to_string(in_bytes) + " bytes) exceed the device budget");
+  Layout in(16);
+  const auto i_cell = in.add<double>((size_t)ne * kCell), i_frac = in.add<double>(3 * N), i_std = in.add<double>(2 * (size_t)nqs);
+  const auto i_pref = in.add<long long>(nqs + 1);
+  const auto i_info = in.add<int4>(ne), i_qrec = in.add<int4>(nqs);
+  const auto i_perm = in.add<int>(N), i_run = in.add<int>(N), i_ops = in.add<int>(kMatchOps);
+  const auto i_sti = in.add<int>((size_t)nqs * kStateI);
+  if (in.bytes() > kMatchTableBudget) {
+    set_error("ics_op_structure_match: the structure tables (" + std::to_string(in.bytes()) + " bytes) exceed the device budget");
     return -1;
   }
-  std::vector<unsigned char> hin(in_bytes, 0);
-  double* hc = reinterpret_cast<double*>(hin.data() + i_cell);
-  double* hf = reinterpret_cast<double*>(hin.data() + i_frac);
-  double* hsd = reinterpret_cast<double*>(hin.data() + i_std);
-  int* hinfo = reinterpret_cast<int*>(hin.data() + i_info);
-  int* hperm = reinterpret_cast<int*>(hin.data() + i_perm);
-  int* hrun = reinterpret_cast<int*>(hin.data() + i_run);
-  int* hops = reinterpret_cast<int*>(hin.data() + i_ops);
-  int* hsti = reinterpret_cast<int*>(hin.data() + i_sti);
+  std::vector<unsigned char> hin(in.bytes(), 0);
+  double *hc, *hf, *hsd;
+  long long* hpref;
+  int4 *hinfo, *hqrec;
+  int *hperm, *hrun, *hops, *hsti;
+  ICS_TRY(in.bind(hin.data(), hin.size(), i_cell, &hc, i_frac, &hf, i_std, &hsd, i_pref, &hpref, i_info, &hinfo,
+                  i_qrec, &hqrec, i_perm, &hperm, i_run, &hrun, i_ops, &hops, i_sti, &hsti));
   size_t at = 0;
   for (int k = 0; k < ne; ++k) {
     const int s = order[k], a0 = offsets[s], n = offsets[s + 1] - a0;
@@ -429,11 +425,11 @@ int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* sp
       hperm[at + i] = a;
       std::memcpy(hf + 3 * (at + i), frac + 3 * (size_t)(a0 + a), 24);
     }
-    hinfo[4 * k] = (int)at; hinfo[4 * k + 1] = n; hinfo[4 * k + 2] = alo; hinfo[4 * k + 3] = ahi;
+    hinfo[k] = make_int4((int)at, n, alo, ahi);
     at += n;
   }
-  std::memcpy(hin.data() + i_pref, pref.data(), (size_t)(nqs + 1) * 8);
-  std::memcpy(hin.data() + i_qrec, qrec.data(), (size_t)nqs * 16);
+  std::memcpy(hpref, pref.data(), (size_t)(nqs + 1) * 8);
+  std::memcpy(hqrec, qrec.data(), (size_t)nqs * 16);
   for (int k = 0; k < nops; ++k)
     hops[k] = perm[k][0] | perm[k][1] << 2 | perm[k][2] << 4 | (sign[k][0] < 0) << 6 | (sign[k][1] < 0) << 7 |
               (sign[k][2] < 0) << 8;
@@ -442,24 +438,20 @@ int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* sp
     for (int i = 0; i < kStateI; ++i) hsti[kStateI * k + i] = i % 3 == 0 ? INT_MAX : -1;
   }
 
-  unsigned char* base = nullptr;
-  const size_t in_up = (in_bytes + 255) & ~(size_t)255;
-  ICS_TRY(scratch_get(in_up + out_bytes + 256, &base));
-  unsigned char* din = base;
-  unsigned char* dout = base + in_up;
-  ICS_HIP(hipMemcpyAsync(din, hin.data(), in_bytes, hipMemcpyHostToDevice, st));
-  const double* dcell = reinterpret_cast<const double*>(din + i_cell);
-  const double* dfrac = reinterpret_cast<const double*>(din + i_frac);
-  double* dstd = reinterpret_cast<double*>(din + i_std);
-  const long long* dpref = reinterpret_cast<const long long*>(din + i_pref);
-  const int4* dinfo = reinterpret_cast<const int4*>(din + i_info);
-  const int4* dqrec = reinterpret_cast<const int4*>(din + i_qrec);
-  const int* dperm = reinterpret_cast<const int*>(din + i_perm);
-  const int* drun = reinterpret_cast<const int*>(din + i_run);
-  const int* dops = reinterpret_cast<const int*>(din + i_ops);
-  int* dsti = reinterpret_cast<int*>(din + i_sti);
-  double* drms = reinterpret_cast<double*>(dout + o_rms);
-  int2* doa = reinterpret_cast<int2*>(dout + o_oa);
+  Layout L;
+  const auto s_in = L.add<unsigned char>(in.bytes());
+  const auto s_rms = L.add<double>(cp);
+  const auto s_oa = L.add<int2>(cp);
+  unsigned char* din;
+  double *dcell, *dfrac, *dstd, *drms;
+  long long* dpref;
+  int4 *dinfo, *dqrec;
+  int *dperm, *drun, *dops, *dsti;
+  int2* doa;
+  ICS_TRY(L.reserve(s_in, &din, s_rms, &drms, s_oa, &doa));
+  ICS_TRY(L.upload(s_in, hin.data(), in.bytes(), st));
+  ICS_TRY(in.bind(din, s_in.count, i_cell, &dcell, i_frac, &dfrac, i_std, &dstd, i_pref, &dpref, i_info, &dinfo,
+                  i_qrec, &dqrec, i_perm, &dperm, i_run, &drun, i_ops, &dops, i_sti, &dsti));
 
   for (long long c0 = 0; c0 < ptotal;) {
     // one chunk: pairs [c0, c1) of one kernel kind
@@ -483,8 +475,8 @@ int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* sp
   }
   std::vector<double> osd((size_t)nqs * 2);
   std::vector<int> osi((size_t)nqs * kStateI);
-  ICS_HIP(hipMemcpyAsync(osd.data(), dstd, osd.size() * 8, hipMemcpyDeviceToHost, st));
-  ICS_HIP(hipMemcpyAsync(osi.data(), dsti, osi.size() * 4, hipMemcpyDeviceToHost, st));
+  ICS_TRY(in.download(osd.data(), i_std, osd.size(), st));
+  ICS_TRY(in.download(osi.data(), i_sti, osi.size(), st));
   ICS_HIP(hipStreamSynchronize(st));
   for (int k = 0; k < nqs; ++k) {
     const int s = qrec[4 * k], b0 = qrec[4 * k + 1], r0 = qrec[4 * k + 2], r1 = qrec[4 * k + 3], q = order[s];

@@ -19,7 +19,7 @@
 // tsne_reduce2_kernel    KL divergence and squared gradient norm, one workgroup, fixed order (check iterations only).
 // No floating-point atomics; every sum has a fixed order, so results are the same run to run.
 #include "tsne.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <chrono>
@@ -63,7 +63,6 @@ constexpr int kRepThreads = 256, kRepTile = 1024, kRepChunk = 16, kRepMaxSlabs =
 constexpr int kRowThreads = 256;      // 4 waves = 4 rows per workgroup in the wave-per-row kernels
 constexpr float kFloatTiny = 1.17549435e-38f;   // np.finfo(np.float32).tiny
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __host__ __device__ inline size_t knn_lds_bytes(int k, bool lists) {
   size_t b = (size_t)2 * kKnnDk * kKnnTile * 8 + (size_t)kKnnTile * (kKnnTile + 1) * 8;
@@ -513,16 +512,18 @@ int tsne_knn_check(const float* x, int n, int dim, int k, const int32_t* idx, co
 }
 
 int tsne_knn_op(hipStream_t st, const float* x, int n, int dim, int k, int32_t* idx, double* dist2) {
-  const size_t bx = align256((size_t)n * dim * 4), bi = align256((size_t)n * k * 4);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(bx + bi + (size_t)n * k * 8, &base));
-  float* dx = reinterpret_cast<float*>(base);
-  int* di = reinterpret_cast<int*>(base + bx);
-  double* dd = reinterpret_cast<double*>(base + bx + bi);
-  ICS_HIP(hipMemcpyAsync(dx, x, (size_t)n * dim * 4, hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_x = L.add<float>((size_t)n * dim);
+  const auto s_i = L.add<int>((size_t)n * k);
+  const auto s_d = L.add<double>((size_t)n * k);
+  float* dx;
+  int* di;
+  double* dd;
+  ICS_TRY(L.reserve(s_x, &dx, s_i, &di, s_d, &dd));
+  ICS_TRY(L.upload(s_x, x, s_x.count, st));
   ICS_TRY(launch_knn(st, dx, n, dim, k, di, dd));
-  ICS_HIP(hipMemcpyAsync(idx, di, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
-  ICS_HIP(hipMemcpyAsync(dist2, dd, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
+  ICS_TRY(L.download(idx, s_i, s_i.count, st));
+  ICS_TRY(L.download(dist2, s_d, s_d.count, st));
   ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }
@@ -538,14 +539,13 @@ int tsne_affinities_check(const double* dist2, int n, int k, double perplexity, 
 }
 
 int tsne_affinities_op(hipStream_t st, const double* dist2, int n, int k, double perplexity, double* cond_p) {
-  const size_t b = align256((size_t)n * k * 8);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(2 * b, &base));
-  double* dd = reinterpret_cast<double*>(base);
-  double* dp = reinterpret_cast<double*>(base + b);
-  ICS_HIP(hipMemcpyAsync(dd, dist2, (size_t)n * k * 8, hipMemcpyHostToDevice, st));
+  Layout L;
+  const auto s_d = L.add<double>((size_t)n * k), s_p = L.add<double>((size_t)n * k);
+  double *dd, *dp;
+  ICS_TRY(L.reserve(s_d, &dd, s_p, &dp));
+  ICS_TRY(L.upload(s_d, dist2, s_d.count, st));
   ICS_TRY(launch_affinities(st, dd, n, k, perplexity, dp));
-  ICS_HIP(hipMemcpyAsync(cond_p, dp, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
+  ICS_TRY(L.download(cond_p, s_p, s_p.count, st));
   ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }
@@ -642,17 +642,17 @@ int tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, d
   const int k = std::min(n - 1, (int)(3.0 * h->cfg.perplexity + 1.0));
   ICS_CHECK(k >= 1 && (long long)n * k <= kTsneMaxEdges, "ics_op_tsne_prepare: n * k above the limit of 2^28");
   // non-finite codes (the device-resident path is not seen by the host)
-  const size_t bi = align256((size_t)n * k * 4), bd = align256((size_t)n * k * 8);
-  unsigned char* base = nullptr;
-  ICS_TRY(scratch_get(256 + bi + 2 * bd, &base));
-  int* d_flag = reinterpret_cast<int*>(base);
-  int* d_idx = reinterpret_cast<int*>(base + 256);
-  double* d_dist = reinterpret_cast<double*>(base + 256 + bi);
-  double* d_p = reinterpret_cast<double*>(base + 256 + bi + bd);
-  ICS_HIP(hipMemsetAsync(d_flag, 0, 4, h->st));
+  Layout L;
+  const auto s_flag = L.add<int>(1);
+  const auto s_idx = L.add<int>((size_t)n * k);
+  const auto s_dist = L.add<double>((size_t)n * k), s_p = L.add<double>((size_t)n * k);
+  int *d_flag, *d_idx;
+  double *d_dist, *d_p;
+  ICS_TRY(L.reserve(s_flag, &d_flag, s_idx, &d_idx, s_dist, &d_dist, s_p, &d_p));
+  ICS_TRY(L.fill(s_flag, 0, 1, h->st));
   ICS_LAUNCH(tsne_finite_kernel, dim3(1024), dim3(256), 0, h->st, h->codes, (size_t)n * dim, d_flag);
   int flag = 0;
-  ICS_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, h->st));
+  ICS_TRY(L.download(&flag, s_flag, 1, h->st));
   ICS_HIP(hipStreamSynchronize(h->st));
   ICS_CHECK(flag == 0, "ics_op_tsne_prepare: codes are not finite");
 
@@ -670,8 +670,8 @@ int tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, d
   t0 = std::chrono::steady_clock::now();
   std::vector<int> idx((size_t)n * k);
   std::vector<double> cp((size_t)n * k);
-  ICS_HIP(hipMemcpyAsync(idx.data(), d_idx, idx.size() * 4, hipMemcpyDeviceToHost, h->st));
-  ICS_HIP(hipMemcpyAsync(cp.data(), d_p, cp.size() * 8, hipMemcpyDeviceToHost, h->st));
+  ICS_TRY(L.download(idx.data(), s_idx, idx.size(), h->st));
+  ICS_TRY(L.download(cp.data(), s_p, cp.size(), h->st));
   ICS_HIP(hipStreamSynchronize(h->st));
   for (size_t e = 0; e < idx.size(); ++e)
     ICS_CHECK(idx[e] >= 0 && idx[e] < n, "ics_op_tsne_prepare: neighbour index out of range");

@@ -10,7 +10,7 @@
 // index (scipy.ndimage.rotate by 90 degrees with reshape=False is np.rot90: an index permutation), so writes stay in
 // output order and no second pass exists.  DESIGN.md section 12.
 #include "voxelise.h"
-#include "segment.h"
+#include "scratch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -134,8 +134,6 @@ __global__ __launch_bounds__(kVoxThreads) void voxelise_kernel(const double* __r
   }
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // Site table + job records of jobs[0..n): each structure a job names is packed once, rows < nsites only.  Per site
 // (create_matrices.py:140,150 done by the caller): x, y, z, sigma*label_frac, Z, Z/sigma**3, -1/(2*sigma**2), 0 -- the
 // per-site factors exactly as numpy forms them (utils.py:136-137: `z / (sigma ** 3)`, `2 * sigma ** 2`).
@@ -169,7 +167,7 @@ void vox_pack(const ics_structures* s, const int32_t* jobs, int n, double label_
     J.nsites = ns;
     for (int a = 0; a < 3; ++a) J.rot[a] = jobs[b * 4 + 1 + a];
   }
-  *job_off = align256(tab.size() * sizeof(double));
+  *job_off = align_up(tab.size() * sizeof(double), 256);
   buf->assign(*job_off + rec.size() * sizeof(VoxJob), 0);
   std::memcpy(buf->data(), tab.data(), tab.size() * sizeof(double));
   std::memcpy(buf->data() + *job_off, rec.data(), rec.size() * sizeof(VoxJob));
@@ -249,7 +247,7 @@ int voxelise_engine(hipStream_t st, VoxStage& stage, const ics_structures* s, co
   vox_pack(s, jobs, batch, label_frac, &buf, &job_off);
   std::vector<size_t> blob_off(nblob);
   for (int b = 0; b < nblob; ++b) {
-    blob_off[b] = align256(buf.size());
+    blob_off[b] = align_up(buf.size(), 256);
     buf.resize(blob_off[b] + blobs[b].bytes);
     std::memcpy(buf.data() + blob_off[b], blobs[b].host, blobs[b].bytes);
   }
@@ -285,19 +283,21 @@ int voxelise_op(hipStream_t st, const ics_structures* s, const int32_t* jobs, in
     const int n = std::min(chunk, njobs - j0);
     size_t job_off = 0;
     vox_pack(s, jobs + (size_t)j0 * 4, n, label_frac, &buf, &job_off);
-    const size_t in_b = align256(buf.size()), nV = (size_t)n * V;
-    const size_t bM = M ? align256(nV * 8) : 0, bS = S ? align256(nV * 8) : 0, bp = p ? nV * 24 : 0;
-    unsigned char* base = nullptr;
-    ICS_TRY(scratch_get(in_b + bM + bS + bp, &base));
-    ICS_HIP(hipMemcpyAsync(base, buf.data(), buf.size(), hipMemcpyHostToDevice, st));
-    double* dM = M ? reinterpret_cast<double*>(base + in_b) : nullptr;
-    double* dS = S ? reinterpret_cast<double*>(base + in_b + bM) : nullptr;
-    double* dp = p ? reinterpret_cast<double*>(base + in_b + bM + bS) : nullptr;
+    const size_t nV = (size_t)n * V;
+    Layout L;
+    const auto s_in = L.add<unsigned char>(buf.size());
+    const auto s_M = L.add<double>(M ? nV : 0);
+    const auto s_S = L.add<double>(S ? nV : 0);
+    const auto s_p = L.add<double>(p ? 3 * nV : 0);
+    unsigned char* din;
+    double *dM, *dS, *dp;
+    ICS_TRY(L.reserve(s_in, &din, s_M, &dM, s_S, &dS, s_p, &dp));
+    ICS_TRY(L.upload(s_in, buf.data(), buf.size(), st));
     VoxOut out{dM, dS, dp, nullptr, 0, nullptr};
-    ICS_TRY(vox_launch(st, false, base, job_off, n, d, eps_frac, out));
-    if (M) ICS_HIP(hipMemcpyAsync(M + (size_t)j0 * V, dM, nV * 8, hipMemcpyDeviceToHost, st));
-    if (S) ICS_HIP(hipMemcpyAsync(S + (size_t)j0 * V, dS, nV * 8, hipMemcpyDeviceToHost, st));
-    if (p) ICS_HIP(hipMemcpyAsync(p + (size_t)j0 * V * 3, dp, nV * 24, hipMemcpyDeviceToHost, st));
+    ICS_TRY(vox_launch(st, false, din, job_off, n, d, eps_frac, out));
+    if (M) ICS_TRY(L.download(M + (size_t)j0 * V, s_M, nV, st));
+    if (S) ICS_TRY(L.download(S + (size_t)j0 * V, s_S, nV, st));
+    if (p) ICS_TRY(L.download(p + (size_t)j0 * V * 3, s_p, 3 * nV, st));
     ICS_HIP(hipStreamSynchronize(st));
   }
   return 0;

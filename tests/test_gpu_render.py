@@ -154,3 +154,36 @@ def test_view_results_synthetic_run(tmp_path):
         assert row["n_atoms_true"] >= 1 and not row["failed_true"] and not row["failed_pred"]
         assert sid + ".png" in page and row["titles"][4] in page
     assert "samples: rendered 2" in p.stdout
+
+
+def test_ops_share_one_thread_scratch_and_stream():
+    """Ops of different families interleaved on one thread's scratch: a repeated call gives the same bits and the same
+    number of launches after another op used the scratch, after the scratch grew (three 160 x 160 pictures are 1.2 MB,
+    above its 1 MB floor), from a thread that exits, and after ics_release_caches."""
+    import threading
+    from icsg3d_amd import _lib as L, evaluate as E, render as P
+    lib = L.load()
+    rng = np.random.default_rng(5)
+    small = (rng.integers(1, 12, (1, 8, 8, 8)) * (rng.uniform(size=(1, 8, 8, 8)) < 0.4)).astype(np.int32)
+    big = (rng.integers(1, 12, (3, 8, 8, 8)) * (rng.uniform(size=(3, 8, 8, 8)) < 0.4)).astype(np.int32)
+    outs, launches = [], []
+
+    def first_call():
+        n0 = lib.ics_kernel_launches()
+        outs.append(P.labels(small, size=32))
+        launches.append(lib.ics_kernel_launches() - n0)
+
+    first_call()
+    pts = rng.uniform(0.0, 5.0, (2, 3, 3))
+    assert np.isfinite(E.emd([pts[0]], [pts[1]])).all()
+    assert P.labels(big, size=160)[..., 3].max() > 0
+    first_call()
+    t = threading.Thread(target=first_call)
+    t.start()
+    t.join()
+    assert lib.ics_release_caches() == 0
+    first_call()
+    assert len(outs) == 4 and outs[0][..., 3].max() > 0
+    for o in outs[1:]:
+        assert np.array_equal(o, outs[0])
+    assert launches[0] >= 1 and launches == [launches[0]] * 4
