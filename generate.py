@@ -25,6 +25,13 @@ the project's own predicate): against each other for duplicat
 for training hits; results.csv gains duplicate_of, duplicate_rms, training_match, training_rms, match_reason and run.json
 a `match` block with the parameters, the ineligible counts by reason and the validity / uniqueness / novelty rates.
 --synthetic runs have no site folder and report duplicates only.
+--symmetry (with --sym_tol, --sym_ltol, --sym_max_ops): after the last batch (and after --match, with which it
+composes) the symmetry of all written samples is found in one device call plus its retry rounds
+(icsg3d_amd.structures.symmetry -> ics_op_structure_symmetry, the project's own predicate): results.csv
+gains point_group, crystal_system, n_symops, n_centring, sym_shift, sym_tol, sym_reason; cifs_sym/<id>.cif holds the
+symmetrised structure with its operations and asymmetric unit; run.json gains a `symmetry` block with the parameters, the
+counts by point group and crystal system, the base compound's own point group when data/<name>/sites/<base id>.npz
+exists, and the share of symmetrised samples that keep it.  No space-group name or number is produced.
 """
 import argparse
 import json
@@ -35,7 +42,7 @@ import numpy as np
 
 from icsg3d_amd.cli import checkpoint_paths
 from icsg3d_amd.evaluate import predicted_coordinates
-from icsg3d_amd.structures import OPS_MODES, Matcher, ReferenceSet, ResultsWriter
+from icsg3d_amd.structures import OPS_MODES, Matcher, ReferenceSet, ResultsWriter, Symmetriser
 from icsg3d_amd.synthetic import synthetic_batch
 from icsg3d_amd.utils import to_lattice_params_from_minmax, to_voxel_params
 from icsg3d_amd.unet.unet import AtomUnet
@@ -86,7 +93,20 @@ def build_parser():
     p.add_argument("--match_ltol", type=float, default=0.05, help="--match: relative tolerance on the metric tensor")
     p.add_argument("--match_ops", choices=sorted(OPS_MODES), default="rot",
                    help="--match: cell operations tried (none, the 24 rotations, all 48 signed axis permutations)")
+    p.add_argument("--symmetry", action="store_true", help="find the symmetry of the written samples and write cifs_sym/")
+    p.add_argument("--sym_tol", type=float, default=0.1, help="--symmetry: site tolerance in Angstrom")
+    p.add_argument("--sym_ltol", type=float, default=0.05, help="--symmetry: relative tolerance on the metric tensor")
+    p.add_argument("--sym_max_ops", type=int, default=192, help="--symmetry: operations kept per structure")
     return p
+
+
+def base_point_group(sites_path, symmetriser):
+    """The point group the symmetriser finds for the structure stored in a sites file (None if it finds none)."""
+    from icsg3d_amd.matrices import load_sites
+    frac, Z, _, lattice = load_sites(sites_path)
+    ref = ReferenceSet(["base"], [np.rint(Z).astype(np.int32)], [frac], [np.asarray(lattice, np.float64).reshape(-1)[:6]])
+    res = symmetriser(ref.screened())[0]
+    return res["point_group"] if res["sym_reason"] == 0 else None
 
 
 def main(argv=None):
@@ -112,7 +132,8 @@ def main(argv=None):
     out_dir = os.path.join("output", "results", base_formula + "_" + "_v=" + str(a.var))
     for sub in ("densities", "species", "binary", "voxel_params", "coords"):
         os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
-    shown = {k: v for k, v in vars(a).items() if a.match or not k.startswith("match")}     # without --match: today's keys
+    shown = {k: v for k, v in vars(a).items() if (a.match or not k.startswith("match"))     # without the flags: today's keys
+             and (a.symmetry or not k.startswith("sym"))}
     run_info = dict(shown, base_compound=base_compound, base_formula=base_formula, base_target=base_target_value,
                     cond_bin=cond_bin)
     with open(os.path.join(out_dir, "run.json"), "w") as f:
@@ -130,8 +151,9 @@ def main(argv=None):
         sites = os.path.join("data", mode, "sites")
         reference = None if a.synthetic or not os.path.isdir(sites) else ReferenceSet.from_sites(sites)
         matcher = Matcher(reference, a.match_tol, a.match_ltol, OPS_MODES[a.match_ops])
+    symmetriser = Symmetriser(a.sym_tol, a.sym_ltol, a.sym_max_ops) if a.symmetry else None
     results = ResultsWriter(out_dir, a.alpha, a.beta, a.gamma, training_names=training_names,
-                            target_value=base_target_value, matcher=matcher)
+                            target_value=base_target_value, matcher=matcher, symmetriser=symmetriser)
     for batch in range(int(a.nsamples / bs)):
         print("Batch", batch)
         z_samples = np.random.normal(z_mu_base, a.var, size=(bs, vae.latent_dim))
@@ -179,6 +201,20 @@ def main(argv=None):
             json.dump(run_info, f)
         print("match: unique %d / novel %s / ineligible %d of %d written" % (
             counts["unique"], counts["novel"] if matcher.reference else "n/a", counts["ineligible"], counts["written"]))
+    if symmetriser is not None:
+        summary = results.symmetry_summary
+        base_sites = os.path.join("data", mode, "sites", base_compound + ".npz")
+        base_pg = base_point_group(base_sites, symmetriser) if not a.synthetic and os.path.isfile(base_sites) else None
+        kept = summary["by_point_group"].get(base_pg, 0) if base_pg is not None else None
+        run_info["symmetry"] = dict(
+            tol=a.sym_tol, ltol=a.sym_ltol, max_ops=a.sym_max_ops, symmetrised=summary["symmetrised"],
+            by_point_group=summary["by_point_group"], by_crystal_system=summary["by_crystal_system"],
+            base_point_group=base_pg, keep_base_point_group=kept,
+            keep_base_share=kept / summary["symmetrised"] if kept is not None and summary["symmetrised"] else None)
+        with open(os.path.join(out_dir, "run.json"), "w") as f:
+            json.dump(run_info, f)
+        print("symmetry: %d of %d written symmetrised; point groups %s" % (
+            summary["symmetrised"], counts["written"], summary["by_point_group"]))
     print("wrote", out_dir, "- atoms per sample: mean %.1f" % (np.mean(n_atoms) if n_atoms else 0.0))
     return 0
 

@@ -12,6 +12,7 @@
 #include "match.h"
 #include "structure.h"
 #include "structure_match.h"
+#include "structure_symmetry.h"
 #include "latent.h"
 #include "tsne.h"
 #include "render.h"
@@ -2989,6 +2990,22 @@ int ics_op_structure_match(const int32_t* offsets, const int32_t* species, const
   ICS_TRY(op_stream(&st));
   return structure_match_op(st, offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode, dup_of, dup_rms,
                             dup_op, ref_of, ref_rms, ref_op, n_cmp);
+}
+int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
+                              const int32_t* eligible, int ns, double tol, double ltol, int max_ops, int32_t* n_lat,
+                              int32_t* n_ops, int32_t* n_point, int32_t* n_trans, int32_t* types, int32_t* reason,
+                              int32_t* op_code, int32_t* op_anchor, double* op_t, double* op_rms, int32_t* orbit,
+                              int32_t* mult, double* sym_frac, double* sym_G, double* sym_shift, double* sym_resid) {
+  ICS_TRY(structure_symmetry_check(offsets, species, frac, lattice, eligible, ns, tol, ltol, max_ops));
+  ICS_CHECK(n_lat && n_ops && n_point && n_trans && types && reason && op_code && op_anchor && op_t && op_rms && sym_G &&
+                sym_shift && sym_resid,
+            "ics_op_structure_symmetry: null output");
+  ICS_CHECK((orbit && mult && sym_frac) || offsets[ns] == 0, "ics_op_structure_symmetry: null orbit, mult or sym_frac");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  return structure_symmetry_op(st, offsets, species, frac, lattice, eligible, ns, tol, ltol, max_ops, n_lat, n_ops, n_point,
+                               n_trans, types, reason, op_code, op_anchor, op_t, op_rms, orbit, mult, sym_frac, sym_G,
+                               sym_shift, sym_resid);
 }
 // view_results.py's pictures (viz.py:43-66, 184-233; view_results.py:152-183): render.h has the camera and the compositing
 int ics_op_render_density(const float* vol, int batch, int d, int stride_c, int channel, const float* lut, int mode,

@@ -294,6 +294,73 @@ static int structure_match_walk(void) {
   return 0;
 }
 
+/* Structure symmetry: the argument checks, the packing (two kernel kinds, an ineligible entry, several chunks under the
+ * ICSG3D_SYMMETRY_CHUNK_BYTES main sets) and one refusal of each kind; the kernels are no-ops here, so the counts the
+ * host reads back are whatever the stand-in memory holds and must be clamped before they index anything. */
+static int structure_symmetry_walk(void) {
+  enum { NS = 9, MO = 6, NA = NS * 70 };
+  static int32_t off[NS + 1], sp[NA], el[NS], orbit[NA], mult[NA];
+  static double fr[NA * 3], lat[NS * 9], sfrac[NA * 3];
+  int32_t nlat[NS], nops[NS], npoint[NS], ntrans[NS], types[NS * 10], reason[NS], ocode[NS * MO], oanc[NS * MO];
+  double ot[NS * MO * 3], orms[NS * MO], sg[NS * 9], sshift[NS], sresid[NS];
+  int at = 0;
+  for (int s = 0; s < NS; ++s) {
+    const int n = s % 4 == 0 ? 70 : (s % 3 == 0 ? 5 : 3);
+    off[s] = at;
+    for (int i = 0; i < n; ++i, ++at) {
+      sp[at] = 1 + (i * 5) % 11;
+      fr[3 * at] = 0.013 * at - 3.0; fr[3 * at + 1] = 0.37 * i; fr[3 * at + 2] = 1.0 - 0.11 * i;
+    }
+    for (int k = 0; k < 9; ++k) lat[9 * s + k] = k % 4 == 0 ? 5.0 + k : (k == 3 ? -1.5 : 0.0);
+    el[s] = s != 5;
+  }
+  off[NS] = at;
+#define SYMM(o, z, f, l, e, ns, t, lt, mo) ics_op_structure_symmetry(o, z, f, l, e, ns, t, lt, mo, nlat, nops, npoint, ntrans, types, reason, ocode, oanc, ot, orms, orbit, mult, sfrac, sg, sshift, sresid)
+  OK(SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO));
+  if (reason[5] != 1 || orbit[off[5] + 2] != 2 || mult[off[5]] != 1 || sg[9 * 5] != 25.0) {
+    fprintf(stderr, "structure symmetry: the ineligible entry is not neutral\n");
+    return 1;
+  }
+  OK(SYMM(off, sp, fr, lat, el, 1, 0.1, 0.05, 1));
+  { int32_t none[NS]; memset(none, 0, sizeof none); OK(SYMM(off, sp, fr, lat, none, NS, 0.1, 0.05, MO)); }
+  int bad = 0;
+  bad += SYMM(off, sp, fr, lat, el, 0, 0.1, 0.05, MO) == 0;
+  bad += SYMM(NULL, sp, fr, lat, el, NS, 0.1, 0.05, MO) == 0;
+  bad += SYMM(off, NULL, fr, lat, el, NS, 0.1, 0.05, MO) == 0;
+  bad += SYMM(off, sp, NULL, lat, el, NS, 0.1, 0.05, MO) == 0;
+  bad += SYMM(off, sp, fr, NULL, el, NS, 0.1, 0.05, MO) == 0;
+  bad += SYMM(off, sp, fr, lat, NULL, NS, 0.1, 0.05, MO) == 0;
+  bad += ics_op_structure_symmetry(off, sp, fr, lat, el, NS, 0.1, 0.05, MO, nlat, nops, npoint, ntrans, types, reason, ocode,
+                                   oanc, ot, NULL, orbit, mult, sfrac, sg, sshift, sresid) == 0;
+  bad += ics_op_structure_symmetry(off, sp, fr, lat, el, NS, 0.1, 0.05, MO, nlat, nops, npoint, ntrans, types, reason, ocode,
+                                   oanc, ot, orms, NULL, mult, sfrac, sg, sshift, sresid) == 0;
+  bad += SYMM(off, sp, fr, lat, el, NS, 0.0, 0.05, MO) == 0;
+  bad += SYMM(off, sp, fr, lat, el, NS, 0.1, NAN, MO) == 0;
+  bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, 0) == 0;
+  bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, 4097) == 0;
+  bad += SYMM(off, sp, fr, lat, el, NS, 3.0, 0.05, MO) == 0;                                       /* too thin for tol */
+  off[0] = 1; bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO) == 0; off[0] = 0;
+  fr[7] = NAN; bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO) == 0; fr[7] = 0.5;
+  lat[9 + 4] = -9.0; bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO) == 0; lat[9 + 4] = 9.0;   /* volume < 0 */
+  sp[1] = 95; bad += SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO) == 0; sp[1] = 6;
+  {   /* 257 atoms eligible: refused; ineligible: not looked at */
+    static int32_t bo[2] = {0, 257}, bs[257], be[1] = {1}, borb[257], bmul[257];
+    static double bf[257 * 3], bsf[257 * 3], bl[9] = {20, 0, 0, 0, 20, 0, 0, 0, 20};
+    for (int i = 0; i < 257; ++i) bs[i] = 8;
+    bad += ics_op_structure_symmetry(bo, bs, bf, bl, be, 1, 0.1, 0.05, MO, nlat, nops, npoint, ntrans, types, reason, ocode,
+                                     oanc, ot, orms, borb, bmul, bsf, sg, sshift, sresid) == 0;
+    be[0] = 0;
+    OK(ics_op_structure_symmetry(bo, bs, bf, bl, be, 1, 0.1, 0.05, MO, nlat, nops, npoint, ntrans, types, reason, ocode,
+                                 oanc, ot, orms, borb, bmul, bsf, sg, sshift, sresid));
+    if (reason[0] != 1 || borb[256] != 256) { fprintf(stderr, "structure symmetry: 257 ineligible atoms not neutral\n"); return 1; }
+  }
+  if (bad) { fprintf(stderr, "structure symmetry: %d invalid argument sets accepted\n", bad); return 1; }
+  if (!ics_last_error()[0]) { fprintf(stderr, "structure symmetry: no error message\n"); return 1; }
+  OK(SYMM(off, sp, fr, lat, el, NS, 0.1, 0.05, MO));     /* still usable */
+#undef SYMM
+  return 0;
+}
+
 /* view_results.py's pictures: the three ops over more than one picture and an image that is no multiple of the tile, an
  * empty atom set, every refusal, and the ops still usable afterwards. */
 static int render_walk(void) {
@@ -925,6 +992,7 @@ int main(void) {
   OK(ics_set_device(0));
   OK(ics_device_info(name, &cus, &hbm));
   printf("asan driver on %s (%s)\n", name, ics_version());
+  setenv("ICSG3D_SYMMETRY_CHUNK_BYTES", "300000", 1);   /* the symmetry op over several chunks */
   setenv("ICSG3D_MATCH_CHUNK_PAIRS", "7", 1);   /* the match planner over many chunks (read at the first match call) */
   setenv("ICSG3D_DGRAD_BNFUSE_MIN", "0", 1);   /* walk the BatchNorm-backward-in-backward-data fusion at these small sizes too */
   if (run(16, 1, 3, 0)) return 1;
@@ -936,6 +1004,7 @@ int main(void) {
   if (match_walk()) return 1;
   if (structure_walk()) return 1;
   if (structure_match_walk()) return 1;
+  if (structure_symmetry_walk()) return 1;
   if (latent_walk()) return 1;
   if (render_walk()) return 1;
   if (monitor_walk(NULL, NULL, NULL, NULL, NULL, NULL, 0, 0)) return 1;

@@ -18,6 +18,11 @@ The reference builds a pymatgen Structure per sample; pymatgen is not a dependen
                     which written samples are the same crystal as an earlier one and which are a training structure
                     (ics_op_structure_match: the project's own predicate; no parity with pymatgen's
                     StructureMatcher is claimed).  No host fallback either.
+- symmetry, Symmetriser, symmetry_packed, lattice_op, POINT_GROUPS, write_cif_symmetry, read_cif_symmetry, expand_symmetry
+                    which symmetry a written sample has: its operations (W, t), point group, crystal system, centring
+                    translations, orbits and the symmetrised structure (ics_op_structure_symmetry: the project's own
+                    predicate; no parity with spglib or pymatgen's SpacegroupAnalyzer is claimed, no
+                    space-group name or number is produced).
 """
 from __future__ import annotations
 
@@ -400,6 +405,173 @@ class Matcher:
         return match(results, self.reference, self.tol, self.ltol, self.ops_mode)
 
 
+# ---------------------------------------------------------------- symmetry (ics_op_structure_symmetry)
+SYM_MAX_OPS = 4096      # the largest max_ops the op accepts
+SYM_LAT_CAP = 64        # admissible lattice operations per structure
+SYM_NOT_ELIGIBLE, SYM_LATTICE_OVERFLOW, SYM_OPS_OVERFLOW, SYM_NOT_CLOSED = 1, 2, 4, 8     # the op's reason bits
+SYM_REASONS = {SYM_NOT_ELIGIBLE: "not eligible", SYM_LATTICE_OVERFLOW: "more than 64 lattice operations",
+               SYM_OPS_OVERFLOW: "more operations than max_ops", SYM_NOT_CLOSED: "operations not closed"}
+TYPE_ORDER = (-6, -4, -3, -2, -1, 1, 2, 3, 4, 6)      # the columns of the op's `types` histogram
+
+
+def _pg(rows):
+    return {tuple(int(c) for c in hist): (sym, system) for system, pairs in rows for sym, hist in pairs}
+
+
+# The 32 crystallographic point groups by their histogram of rotation types (TYPE_ORDER) -> (Hermann-Mauguin symbol,
+# crystal system).  The histograms are distinct; tests/test_structure_symmetry_host.py re-derives them by enumerating the
+# subgroups of the cubic and hexagonal holohedries.
+POINT_GROUPS = _pg((
+    ("triclinic", (("1", "0000010000"), ("-1", "0000110000"))),
+    ("monoclinic", (("2", "0000011000"), ("m", "0001010000"), ("2/m", "0001111000"))),
+    ("orthorhombic", (("222", "0000013000"), ("mm2", "0002011000"), ("mmm", "0003113000"))),
+    ("tetragonal", (("4", "0000011020"), ("-4", "0200011000"), ("4/m", "0201111020"), ("422", "0000015020"),
+                    ("4mm", "0004011020"), ("-42m", "0202013000"), ("4/mmm", "0205115020"))),
+    ("trigonal", (("3", "0000010200"), ("-3", "0020110200"), ("32", "0000013200"), ("3m", "0003010200"),
+                  ("-3m", "0023113200"))),
+    ("hexagonal", (("6", "0000011202"), ("-6", "2001010200"), ("6/m", "2021111202"), ("622", "0000017202"),
+                   ("6mm", "0006011202"), ("-6m2", "2004013200"), ("6/mmm", "2027117202"))),
+    ("cubic", (("23", "0000013800"), ("m-3", "0083113800"), ("432", "0000019860"), ("-43m", "0606013800"),
+               ("m-3m", "0689119860"))),
+))
+
+
+def lattice_op(code):
+    """The integer matrix W (3, 3) of a lattice-operation code: code = sum_k (W[k // 3][k % 3] + 1) 3^(8 - k); f' = W f + t."""
+    code = int(code)
+    if not 0 <= code < 3 ** 9:
+        raise ValueError("lattice_op: code outside 0..19682")
+    return np.array([(code // 3 ** (8 - k)) % 3 - 1 for k in range(9)], np.int64).reshape(3, 3)
+
+
+IDENTITY_CODE = 16484
+assert np.array_equal(lattice_op(IDENTITY_CODE), np.eye(3, dtype=np.int64))
+
+
+def symmetry_reason_text(bits):
+    return ", ".join(t for bit, t in SYM_REASONS.items() if bits & bit)
+
+
+def symmetry_packed(offsets, species, frac, lattice, eligible, tol=0.1, ltol=0.05, max_ops=192):
+    """ics_op_structure_symmetry on packed arrays: offsets (ns + 1,), species (N,), frac (N, 3), lattice (ns, 3, 3) with
+    rows va, vb, vc, eligible (ns,).  Returns the op's outputs as a dict of arrays: n_lat, n_ops, n_point, n_trans,
+    reason (ns,), types (ns, 10), op_code, op_anchor, op_rms (ns, max_ops), op_t (ns, max_ops, 3), orbit, mult (N,),
+    sym_frac (N, 3), sym_G (ns, 9), sym_shift, sym_resid (ns,)."""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    species = np.ascontiguousarray(species, np.int32).reshape(-1)
+    frac = np.ascontiguousarray(frac, np.float64).reshape(-1, 3)
+    lattice = np.ascontiguousarray(lattice, np.float64).reshape(-1, 9)
+    eligible = np.ascontiguousarray(eligible, np.int32).reshape(-1)
+    ns, N, max_ops = len(offsets) - 1, len(species), int(max_ops)
+    if ns < 1:
+        raise ValueError("symmetry needs at least one structure")
+    if len(lattice) != ns or len(eligible) != ns or len(frac) != N or int(offsets[-1]) != N:
+        raise ValueError("symmetry: array lengths do not agree (structures %d / %d / %d, atoms %d / %d / %d)"
+                         % (ns, len(lattice), len(eligible), N, len(frac), int(offsets[-1])))
+    if not 1 <= max_ops <= SYM_MAX_OPS:
+        raise ValueError("symmetry: max_ops must be in 1..%d" % SYM_MAX_OPS)
+    A = max(N, 1)
+    out = {"n_lat": np.zeros(ns, np.int32), "n_ops": np.zeros(ns, np.int32), "n_point": np.zeros(ns, np.int32),
+           "n_trans": np.zeros(ns, np.int32), "types": np.zeros((ns, 10), np.int32), "reason": np.zeros(ns, np.int32),
+           "op_code": np.full((ns, max_ops), -1, np.int32), "op_anchor": np.full((ns, max_ops), -1, np.int32),
+           "op_t": np.full((ns, max_ops, 3), np.nan), "op_rms": np.full((ns, max_ops), np.nan),
+           "orbit": np.zeros(A, np.int32), "mult": np.zeros(A, np.int32), "sym_frac": np.zeros((A, 3)),
+           "sym_G": np.zeros((ns, 9)), "sym_shift": np.zeros(ns), "sym_resid": np.zeros(ns)}
+    L.check(L.load().ics_op_structure_symmetry(
+        L.i32ptr(offsets), L.i32ptr(species), L.f64ptr(frac), L.f64ptr(lattice), L.i32ptr(eligible), ns, float(tol),
+        float(ltol), max_ops, L.i32ptr(out["n_lat"]), L.i32ptr(out["n_ops"]), L.i32ptr(out["n_point"]),
+        L.i32ptr(out["n_trans"]), L.i32ptr(out["types"]), L.i32ptr(out["reason"]), L.i32ptr(out["op_code"]),
+        L.i32ptr(out["op_anchor"]), L.f64ptr(out["op_t"]), L.f64ptr(out["op_rms"]), L.i32ptr(out["orbit"]),
+        L.i32ptr(out["mult"]), L.f64ptr(out["sym_frac"]), L.f64ptr(out["sym_G"]), L.f64ptr(out["sym_shift"]),
+        L.f64ptr(out["sym_resid"])))
+    out["orbit"], out["mult"], out["sym_frac"] = out["orbit"][:N], out["mult"][:N], out["sym_frac"][:N]
+    return out
+
+
+def metric_parameters(G):
+    """(abc (3,), angles (3,) in degrees) of a metric tensor G (9,) or (3, 3)."""
+    G = np.asarray(G, np.float64).reshape(3, 3)
+    abc = np.sqrt(np.diag(G))
+    cs = np.array([G[1, 2] / (abc[1] * abc[2]), G[0, 2] / (abc[0] * abc[2]), G[0, 1] / (abc[0] * abc[1])])
+    return abc, np.degrees(np.arccos(np.clip(cs, -1.0, 1.0)))
+
+
+def symmetry(results, tol=0.1, ltol=0.05, max_ops=192, retries=3, shrink=0.7, packed=None):
+    """The symmetry of every entry of `results` (the dicts screen returns, None = a failed sample).  One device call for
+    all structures; those that come back not closed (bit 8: a noisy structure near tol can pass some operations and miss
+    their products) are called again at tol * shrink, up to `retries` times, each round in one call over the remaining
+    subset -- at a small enough tol only the identity passes, and that is closed.  Eligibility is `eligibility(results,
+    tol)`, as for match.  packed: the callable that evaluates a packed table (symmetry_packed: the device op).
+    Returns one dict per sample: point_group and crystal_system (None when the histogram is in no row of POINT_GROUPS,
+    which only a result that is not closed can give, or when the sample was not analysed), n_ops, n_centring, n_lattice,
+    types, tol_used, sym_reason (the op's reason bits; 0 = symmetrised), ops [(W (3, 3) int, t (3,))], species, orbit, mult,
+    sym_frac, sym_abc, sym_angles, sym_shift, sym_resid."""
+    packed = symmetry_packed if packed is None else packed
+    if not (tol > 0 and ltol > 0 and math.isfinite(tol) and math.isfinite(ltol) and 0 < shrink < 1 and retries >= 0):
+        raise ValueError("symmetry: tol and ltol must be finite and > 0, shrink in (0, 1), retries >= 0")
+    ns = len(results)
+    bits = eligibility(results, tol)
+    out = [None] * ns
+    for k, r in enumerate(results):
+        n = 0 if r is None else len(r["species"])
+        out[k] = {"point_group": None, "crystal_system": None, "n_ops": 0, "n_centring": 0, "n_lattice": 0,
+                  "types": (0,) * 10, "tol_used": None, "sym_reason": SYM_NOT_ELIGIBLE, "ops": [],
+                  "species": None if r is None else np.asarray(r["species"], np.int32).copy(),
+                  "orbit": np.arange(n, dtype=np.int32), "mult": np.ones(n, np.int32),
+                  "sym_frac": None if r is None else np.asarray(r["frac"], np.float64).reshape(-1, 3).copy(),
+                  "sym_abc": None if r is None else np.asarray(r["abc"], np.float64).copy(),
+                  "sym_angles": None if r is None else np.asarray(r["angles"], np.float64).copy(), "sym_shift": 0.0,
+                  "sym_resid": 0.0, "eligibility": int(bits[k])}
+    todo = [k for k in range(ns) if bits[k] == 0]
+    t = float(tol)
+    for attempt in range(int(retries) + 1):
+        if not todo:
+            break
+        sp_l = [np.asarray(results[k]["species"], np.int32) for k in todo]
+        off = np.zeros(len(todo) + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in sp_l])
+        o = packed(off, np.concatenate(sp_l), np.concatenate([np.asarray(results[k]["frac"], np.float64).reshape(-1, 3)
+                                                              for k in todo]),
+                   np.array([results[k]["lattice"] for k in todo], np.float64), np.ones(len(todo), np.int32), t, ltol,
+                   max_ops)
+        again = []
+        for i, k in enumerate(todo):
+            a0, a1, d = int(off[i]), int(off[i + 1]), out[k]
+            types = tuple(int(v) for v in o["types"][i])
+            pg = POINT_GROUPS.get(types)
+            keep = min(int(o["n_ops"][i]), int(max_ops))
+            abc, ang = metric_parameters(o["sym_G"][i])
+            d.update(point_group=pg[0] if pg else None, crystal_system=pg[1] if pg else None, n_ops=int(o["n_ops"][i]),
+                     n_centring=int(o["n_trans"][i]), n_lattice=int(o["n_lat"][i]), types=types, tol_used=t,
+                     sym_reason=int(o["reason"][i]),
+                     ops=[(lattice_op(o["op_code"][i, g]), o["op_t"][i, g].copy()) for g in range(keep)],
+                     orbit=o["orbit"][a0:a1].copy(), mult=o["mult"][a0:a1].copy(), sym_frac=o["sym_frac"][a0:a1].copy(),
+                     sym_abc=abc, sym_angles=ang, sym_shift=float(o["sym_shift"][i]), sym_resid=float(o["sym_resid"][i]))
+            if int(o["reason"][i]) & SYM_NOT_CLOSED:
+                again.append(k)
+        todo, t = again, t * float(shrink)
+    return out
+
+
+class Symmetriser:
+    """The symmetry parameters ResultsWriter(symmetriser=...) runs with: tol (Angstrom), ltol (relative, on the metric
+    tensor), max_ops (operations kept per structure), retries and shrink (the rounds at a smaller tol for structures
+    whose operations are not closed)."""
+
+    def __init__(self, tol=0.1, ltol=0.05, max_ops=192, retries=3, shrink=0.7, packed=None):
+        if not (tol > 0 and ltol > 0 and math.isfinite(tol) and math.isfinite(ltol)):
+            raise ValueError("Symmetriser: tol and ltol must be finite and > 0")
+        if not 1 <= int(max_ops) <= SYM_MAX_OPS:
+            raise ValueError("Symmetriser: max_ops must be in 1..%d" % SYM_MAX_OPS)
+        if not (0 < shrink < 1 and retries >= 0):
+            raise ValueError("Symmetriser: shrink must be in (0, 1) and retries >= 0")
+        self.tol, self.ltol, self.max_ops = float(tol), float(ltol), int(max_ops)
+        self.retries, self.shrink, self.packed = int(retries), float(shrink), packed
+
+    def __call__(self, results):
+        return symmetry(results, self.tol, self.ltol, self.max_ops, self.retries, self.shrink, self.packed)
+
+
 def reason_text(reason):
     return ", ".join(t for bit, t in REASONS.items() if reason & bit) or "valid"
 
@@ -471,6 +643,132 @@ def read_cif(path):
                              np.float64).reshape(len(rec), 3)}
 
 
+def _xyz_row(W, t):
+    """One row of a _symmetry_equiv_pos_as_xyz loop: '-y+0.25000000, x, z+0.50000000'."""
+    parts = []
+    for r in range(3):
+        term = ""
+        for c, name in enumerate("xyz"):
+            w = int(W[r][c])
+            if w:
+                term += ("-" if w < 0 else ("+" if term else "")) + (name if abs(w) == 1 else "%d%s" % (abs(w), name))
+        v = float(t[r]) - math.floor(float(t[r]))
+        text = "%.8f" % v
+        if text.startswith("1."):
+            text = "0.00000000"
+        if text != "0.00000000" or not term:
+            term += ("+" if term else "") + text
+        parts.append(term)
+    return ", ".join(parts)
+
+
+def _parse_xyz_row(text):
+    """The inverse of _xyz_row: (W (3, 3) int, t (3,))."""
+    import re
+    W, t = np.zeros((3, 3), np.int64), np.zeros(3)
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise ValueError("not a symmetry operation: %r" % text)
+    for r, part in enumerate(parts):
+        part = part.replace(" ", "")
+        pos = 0
+        for m in re.finditer(r"([+-]?)(\d*)([xyz])|([+-]?)(\d+\.\d*|\d+/\d+|\d+)", part):
+            if m.start() != pos:
+                raise ValueError("not a symmetry operation: %r" % text)
+            pos = m.end()
+            if m.group(3):
+                W[r, "xyz".index(m.group(3))] += (-1 if m.group(1) == "-" else 1) * int(m.group(2) or 1)
+            else:
+                num = m.group(5)
+                v = float(num.split("/")[0]) / float(num.split("/")[1]) if "/" in num else float(num)
+                t[r] += -v if m.group(4) == "-" else v
+        if pos != len(part) or not part:
+            raise ValueError("not a symmetry operation: %r" % text)
+    return W, t
+
+
+def write_cif_symmetry(path, result, species=None):
+    """The symmetrised structure of one entry of symmetry()'s list (sym_reason 0; species: its atomic numbers, or others):
+    the symmetrised cell, the crystal system and point group, every operation as one row of the
+    _symmetry_equiv_pos_as_xyz loop (W and the fitted translation, 8 decimals), and the atom-site loop over the orbit
+    representatives only, with their multiplicities.  No space-group name is written: none is determined."""
+    if result["sym_reason"] != 0 or not result["ops"]:
+        raise ValueError("write_cif_symmetry: the structure was not symmetrised (%s)"
+                         % symmetry_reason_text(result["sym_reason"]))
+    species = np.asarray(result["species"] if species is None else species, np.int64).reshape(-1)
+    frac = np.asarray(result["sym_frac"], np.float64).reshape(len(species), 3)
+    orbit, mult = np.asarray(result["orbit"]), np.asarray(result["mult"])
+    hist = np.bincount(species, minlength=HIST)
+    if len(hist) > HIST or species.min() < 1:
+        raise ValueError("write_cif_symmetry: species outside 1..94")
+    abc, angles = result["sym_abc"], result["sym_angles"]
+    ca, cb, cg = (math.cos(math.radians(t)) for t in angles)
+    volume = abc[0] * abc[1] * abc[2] * math.sqrt(max(0.0, 1 - ca * ca - cb * cb - cg * cg + 2 * ca * cb * cg))
+    lines = ["data_" + reduced_formula(hist), "_symmetry_space_group_name_H-M   ?",
+             "_space_group_crystal_system   %s" % (result["crystal_system"] or "?"),
+             "_space_group_point_group_H-M   '%s'" % (result["point_group"] or "?")]
+    lines += ["_cell_length_%s   %.8f" % (n, v) for n, v in zip("abc", abc)]
+    lines += ["_cell_angle_%s   %.8f" % (n, v) for n, v in zip(("alpha", "beta", "gamma"), angles)]
+    lines += ["_chemical_formula_structural   " + reduced_formula(hist), "_chemical_formula_sum   '%s'" % formula(hist),
+              "_cell_volume   %.8f" % volume,
+              "_cell_formula_units_Z   %d" % reduce(math.gcd, [int(n) for n in hist if n]),
+              "loop_", " _symmetry_equiv_pos_site_id", " _symmetry_equiv_pos_as_xyz"]
+    lines += ["  %d  '%s'" % (k + 1, _xyz_row(W, t)) for k, (W, t) in enumerate(result["ops"])]
+    lines += ["loop_", " _atom_site_type_symbol", " _atom_site_label", " _atom_site_symmetry_multiplicity",
+              " _atom_site_fract_x", " _atom_site_fract_y", " _atom_site_fract_z", " _atom_site_occupancy"]
+    for k in range(len(species)):
+        if orbit[k] == k:
+            p, z = frac[k], species[k]
+            lines.append("  %s  %s%d  %d  %.8f  %.8f  %.8f  1" % (SYMBOLS[z], SYMBOLS[z], k, mult[k], p[0], p[1], p[2]))
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_cif_symmetry(path):
+    """The file write_cif_symmetry writes: read_cif's dict for the asymmetric unit, plus crystal_system, point_group,
+    ops [(W, t)] and mult (n,)."""
+    d = read_cif(path)
+    tags, rows, mult, state = {}, [], [], None
+    for raw in open(path):
+        ln = raw.strip()
+        if ln == "loop_":
+            state = "loop"
+        elif ln.startswith("_space_group_"):
+            k, _, v = ln.partition(" ")
+            tags[k] = v.strip().strip("'")
+        elif ln == "_symmetry_equiv_pos_as_xyz":
+            state = "ops"
+        elif ln == "_atom_site_occupancy":
+            state = "sites"
+        elif ln and not ln.startswith("_") and state == "ops":
+            rows.append(ln.split(None, 1)[1].strip().strip("'"))
+        elif ln and not ln.startswith("_") and state == "sites":
+            mult.append(int(ln.split()[2]))
+    d["crystal_system"], d["point_group"] = tags.get("_space_group_crystal_system"), tags.get("_space_group_point_group_H-M")
+    d["ops"] = [_parse_xyz_row(r) for r in rows]
+    d["mult"] = np.array(mult, np.int32)
+    return d
+
+
+def expand_symmetry(species, frac, ops, merge=1e-6):
+    """The full cell of an asymmetric unit: every operation applied to every site, wrapped into [0, 1), images of a site
+    within `merge` (fractional, periodic) of an earlier one dropped.  Returns (species (n,), frac (n, 3)), the sites of
+    one representative together, in operation order."""
+    species = np.asarray(species, np.int32).reshape(-1)
+    frac = np.asarray(frac, np.float64).reshape(len(species), 3)
+    out_z, out_f = [], []
+    for z, p in zip(species, frac):
+        mine = []
+        for W, t in ops:
+            q = np.asarray(W, np.float64) @ p + np.asarray(t, np.float64)
+            q -= np.floor(q)
+            if all(np.abs((q - m) - np.rint(q - m)).max() > merge for m in mine):
+                mine.append(q)
+        out_z += [int(z)] * len(mine)
+        out_f += mine
+    return np.array(out_z, np.int32), np.array(out_f, np.float64).reshape(len(out_z), 3)
+
+
 # ---------------------------------------------------------------- generate.py:250-318
 class ResultsWriter:
     """The tail of generate.py's sample loop.  add_batch screens one batch on the device and, per sample in order:
@@ -482,13 +780,22 @@ class ResultsWriter:
     row that is the same structure), duplicate_rms, training_match (the reference's id), training_rms, match_reason (""
     or why the sample was not compared); the counts gain unique (compared, no earlier duplicate), novel (unique and no
     training match) and ineligible, and match_summary holds them with the ineligible counts by reason.  results.json is
-    written per batch and keeps today's records.  Without matcher= nothing changes."""
+    written per batch and keeps today's records.  Without matcher= nothing changes.
+    With symmetriser= (a Symmetriser), finish() then finds the symmetry of ALL written samples in one device call (plus
+    the retry rounds) and every row carries SYMMETRY_COLUMNS after the others: point_group, crystal_system, n_symops,
+    n_centring, sym_shift, sym_tol (the tol the result was found at), sym_reason ("" or why the sample has no symmetrised
+    structure); cifs_sym/<id>.cif holds the symmetrised structure of every sample with an empty sym_reason, and
+    symmetry_summary the counts by point group and crystal system and the number symmetrised.  Without symmetriser=
+    every file, column and count is what it is without it."""
     COLUMNS = ("formula", "id", "training", "target", "anon_formula", "electronegativity", "cif", "sample", "natoms",
                "min_distance", "volume")
     MATCH_COLUMNS = ("duplicate_of", "duplicate_rms", "training_match", "training_rms", "match_reason")
+    SYMMETRY_COLUMNS = ("point_group", "crystal_system", "n_symops", "n_centring", "sym_shift", "sym_tol", "sym_reason")
 
-    def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None, matcher=None):
+    def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None, matcher=None,
+                 symmetriser=None):
         self.matcher, self.structs, self.match_summary = matcher, [], None
+        self.symmetriser, self.symmetry_summary, self.symmetry_results = symmetriser, None, None
         self.out_dir, self.angles, self.tol = out_dir, (alpha, beta, gamma), tol
         self.training_names, self.target_value = set(training_names), target_value
         self.formulae, self.rows = [], []
@@ -518,7 +825,7 @@ class ResultsWriter:
                   "electronegativity": average_electroneg(r["hist"]), "cif": path, "sample": int(k),
                   "natoms": int(len(r["species"])), "min_distance": r["min_dist"], "volume": r["volume"]}
             self.rows.append(rd)
-            if self.matcher is not None:
+            if self.matcher is not None or self.symmetriser is not None:
                 self.structs.append(r)
             self.formulae.append(f)
             self.counts["written"] += 1
@@ -546,11 +853,34 @@ class ResultsWriter:
         self.match_summary = {"unique": unique, "novel": novel, "ineligible": ineligible, "ineligible_by_reason": by_reason}
         self.counts.update(unique=unique, novel=novel, ineligible=ineligible)
 
+    def _symmetry_rows(self):
+        """The symmetriser over all written samples: the extra columns into the rows, cifs_sym/, symmetry_summary."""
+        res = self.symmetriser(self.structs)
+        os.makedirs(os.path.join(self.out_dir, "cifs_sym"), exist_ok=True)
+        by_group, by_system, done = {}, {}, 0
+        for rd, r, d in zip(self.rows, self.structs, res):
+            ok = d["sym_reason"] == 0
+            rd["point_group"], rd["crystal_system"] = d["point_group"], d["crystal_system"]
+            rd["n_symops"], rd["n_centring"] = int(d["n_ops"]), int(d["n_centring"])
+            rd["sym_shift"], rd["sym_tol"] = (float(d["sym_shift"]), d["tol_used"]) if ok else (None, d["tol_used"])
+            rd["sym_reason"] = None if ok else symmetry_reason_text(d["sym_reason"])
+            if ok:
+                done += 1
+                by_group[d["point_group"]] = by_group.get(d["point_group"], 0) + 1
+                by_system[d["crystal_system"]] = by_system.get(d["crystal_system"], 0) + 1
+                write_cif_symmetry(os.path.join(self.out_dir, "cifs_sym", rd["id"] + ".cif"), d, r["species"])
+        self.symmetry_results = res
+        self.symmetry_summary = {"symmetrised": done, "by_point_group": by_group, "by_crystal_system": by_system}
+        self.counts.update(symmetrised=done)
+
     def finish(self):
         columns = self.COLUMNS
         if self.matcher is not None:
             self._match_rows()
             columns = self.COLUMNS + self.MATCH_COLUMNS
+        if self.symmetriser is not None:
+            self._symmetry_rows()
+            columns = columns + self.SYMMETRY_COLUMNS
         order = sorted(range(len(self.rows)), key=lambda i: self.rows[i]["id"])
         with open(os.path.join(self.out_dir, "results.csv"), "w", newline="") as fh:
             w = csv.writer(fh)
