@@ -9,10 +9,6 @@
 #include "segment.h"
 #include "scratch.h"
 #include "voxelise.h"
-#include "match.h"
-#include "structure.h"
-#include "structure_match.h"
-#include "structure_symmetry.h"
 #include "latent.h"
 #include "tsne.h"
 #include "render.h"
@@ -2931,6 +2927,14 @@ int ics_vae_interpolate_to_unet_atoms(ics_net* vae, ics_net* unet, const float* 
   return interp_run(vae->n, &unet->n, A, group, &T, z_ends, z_path, nullptr);
 }
 
+// Short-lived Nets behind the single-op entry points: their buffers are a few KB to MB, so the arena starts at 4 MB (doubling
+// as usual) instead of the 128 MB first slab of a long-lived engine handle -- a 128 MB hipMalloc + a synchronising hipFree per
+// call was the very overhead the box-level ops got rid of in round 5 (ADVICE r5).
+static int op_prepare(Net& n) {
+  n.arena_next = (size_t)1 << 22;
+  return net_common_init(n);
+}
+
 int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch, int d, int min_voxels, int max_atoms,
                          int num_species, int32_t* regions, int32_t* counts, int32_t* atom_stats, int64_t* convexity_bounds) {
   ICS_CHECK(mask && species && batch >= 1 && max_atoms >= 1 && min_voxels >= 0, "bad segmentation arguments");
@@ -2938,8 +2942,7 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
   const AtomsOut T{0.f, min_voxels, max_atoms, nullptr, nullptr, nullptr, nullptr, regions, counts, atom_stats, convexity_bounds};
   ICS_TRY(atoms_out_check(T));
   Net n;
-  n.arena_next = (size_t)1 << 22;      // a temporary Net: see op_prepare
-  ICS_TRY(net_common_init(n));
+  ICS_TRY(op_prepare(n));
   const size_t M = (size_t)batch * d * d * d;
   unsigned char *dm, *ds;
   ICS_TRY(n.alloc(&dm, M)); ICS_TRY(n.alloc(&ds, M));
@@ -2948,102 +2951,8 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
   return segment_to_host(n, dm, ds, batch, d, num_species, T);
 }
 
-// The host-pointer ops below run on the calling thread's stream and scratch (scratch.h).
-int ics_release_caches() {
-  release_thread_caches();
-  return 0;
-}
-
-int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac, double label_frac,
-                    double* M, double* S, double* p) {
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return voxelise_op(st, s, jobs, njobs, d, eps_frac, label_frac, M, S, p);
-}
-int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
-                     double* emd, int32_t* match) {
-  ICS_TRY(match_emd_check(a, a_off, b, b_off, batch, emd));
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return match_emd_op(st, a, a_off, b, b_off, batch, emd, match);
-}
-int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, const double* xyz, const double* abc,
-                            const double* angles, int batch, double tol, double* lattice, double* volume, double* frac,
-                            double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid, int32_t* reason,
-                            double* nearest, int32_t* hist) {
-  ICS_TRY(structure_screen_check(offsets, species, xyz, abc, angles, batch, tol));
-  ICS_CHECK(lattice && volume && min_dist && min_pair && n_close && valid && reason && hist,
-            "ics_op_structure_screen: null output");
-  ICS_CHECK((frac && nearest) || offsets[batch] == 0, "ics_op_structure_screen: null frac or nearest");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return structure_screen_op(st, offsets, species, xyz, abc, angles, batch, tol, lattice, volume, frac, min_dist, min_pair,
-                             n_close, valid, reason, nearest, hist);
-}
-int ics_op_structure_match(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
-                           const int32_t* eligible, int nq, int nref, double tol, double ltol, int ops_mode,
-                           int32_t* dup_of, double* dup_rms, int32_t* dup_op, int32_t* ref_of, double* ref_rms,
-                           int32_t* ref_op, int32_t* n_cmp) {
-  ICS_TRY(structure_match_check(offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode));
-  ICS_CHECK(dup_of && dup_rms && dup_op && ref_of && ref_rms && ref_op && n_cmp, "ics_op_structure_match: null output");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return structure_match_op(st, offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode, dup_of, dup_rms,
-                            dup_op, ref_of, ref_rms, ref_op, n_cmp);
-}
-int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
-                              const int32_t* eligible, int ns, double tol, double ltol, int max_ops, int32_t* n_lat,
-                              int32_t* n_ops, int32_t* n_point, int32_t* n_trans, int32_t* types, int32_t* reason,
-                              int32_t* op_code, int32_t* op_anchor, double* op_t, double* op_rms, int32_t* orbit,
-                              int32_t* mult, double* sym_frac, double* sym_G, double* sym_shift, double* sym_resid) {
-  ICS_TRY(structure_symmetry_check(offsets, species, frac, lattice, eligible, ns, tol, ltol, max_ops));
-  ICS_CHECK(n_lat && n_ops && n_point && n_trans && types && reason && op_code && op_anchor && op_t && op_rms && sym_G &&
-                sym_shift && sym_resid,
-            "ics_op_structure_symmetry: null output");
-  ICS_CHECK((orbit && mult && sym_frac) || offsets[ns] == 0, "ics_op_structure_symmetry: null orbit, mult or sym_frac");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return structure_symmetry_op(st, offsets, species, frac, lattice, eligible, ns, tol, ltol, max_ops, n_lat, n_ops, n_point,
-                               n_trans, types, reason, op_code, op_anchor, op_t, op_rms, orbit, mult, sym_frac, sym_G,
-                               sym_shift, sym_resid);
-}
-// view_results.py's pictures (viz.py:43-66, 184-233; view_results.py:152-183): render.h has the camera and the compositing
-int ics_op_render_density(const float* vol, int batch, int d, int stride_c, int channel, const float* lut, int mode,
-                          float alpha, float floor, const double* camera, int width, int height, float* out) {
-  ICS_TRY(render_check("ics_op_render_density", batch, d, camera, width, height, out));
-  ICS_TRY(render_density_check("ics_op_render_density", stride_c, channel, lut, mode, alpha, floor));
-  ICS_CHECK(vol != nullptr, "ics_op_render_density: null vol");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return render_density_op(st, vol, batch, d, stride_c, channel, lut, mode, alpha, floor, camera, width, height, out);
-}
-int ics_op_render_labels(const int32_t* labels, int batch, int d, const float* palette, int npal, float alpha,
-                         const double* camera, int width, int height, float* out) {
-  ICS_TRY(render_check("ics_op_render_labels", batch, d, camera, width, height, out));
-  ICS_CHECK(labels && palette, "ics_op_render_labels: null argument (labels, palette)");
-  ICS_CHECK(npal >= 1, "ics_op_render_labels: npal must be >= 1");
-  ICS_CHECK(alpha >= 0.f && alpha <= 1.f, "ics_op_render_labels: alpha must be in [0, 1]");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return render_labels_op(st, labels, batch, d, palette, npal, alpha, camera, width, height, out);
-}
-int ics_op_render_atoms(const int32_t* offsets, const int32_t* species, const double* xyz, int batch, int d, double radius,
-                        const float* palette, int npal, const double* camera, int width, int height, float* out) {
-  const std::string op = "ics_op_render_atoms: ";
-  ICS_TRY(render_check("ics_op_render_atoms", batch, d, camera, width, height, out));
-  ICS_CHECK(offsets && palette, op + "null argument (offsets, palette)");
-  ICS_CHECK(npal >= 1, op + "npal must be >= 1");
-  ICS_CHECK(std::isfinite(radius) && radius > 0.0, op + "radius must be finite and > 0");
-  ICS_CHECK(offsets[0] == 0, op + "offsets[0] must be 0");
-  for (int b = 0; b < batch; ++b)
-    ICS_CHECK(offsets[b + 1] >= offsets[b], op + "offsets decrease at sample " + std::to_string(b));
-  ICS_CHECK((species && xyz) || offsets[batch] == 0, op + "null species or xyz");
-  for (long long k = 0; k < 3LL * offsets[batch]; ++k)
-    ICS_CHECK(std::isfinite(xyz[k]), op + "non-finite coordinate");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return render_atoms_op(st, offsets, species, xyz, batch, d, radius, palette, npal, camera, width, height, out);
-}
+// Every host-pointer op that reads no engine state is defined in its own module (voxelise.hip, match.hip, structure*.hip,
+// render.hip, monitor.hip, latent.hip, tsne.hip, segment.hip, scratch.hip); what follows needs a Net.
 // The density picture of what the engine already holds: the resident input (which = 0) or recon as the last decoder pass
 // left it (which = 1), channel 0, read where it lies.  Only the colour table goes up and the pictures come back.
 int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, float floor, const float* lut,
@@ -3073,14 +2982,6 @@ int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, floa
   return 0;
 }
 // ---------------------------------------------------------------- training monitors (monitor.h has the formulas)
-int ics_op_render_slice(const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
-                        const float* lut, const float* range_or_null, int zoom, float* out) {
-  ICS_TRY(slice_check("ics_op_render_slice", dtype, batch, d, stride_c, channel, axis, index, lut, range_or_null, zoom, out));
-  ICS_CHECK(vol != nullptr, "ics_op_render_slice: null vol");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return slice_op(st, vol, dtype, batch, d, stride_c, channel, axis, index, lut, range_or_null, zoom, out);
-}
 // the slice picture of `count` samples of a buffer the engine holds: only the colour table goes up, the pictures come back
 static int slice_resident(Net& n, const char* who, const void* src, int dtype, int stride_c, int channel, int count, int axis,
                           int index, const float* lut, const float* range, int zoom, float* out) {
@@ -3141,9 +3042,6 @@ int ics_unet_render_slice_resident(ics_net* unet, int which, int channel, int co
   ICS_CHECK(n.labels_batch >= count, op + "no true labels of these samples in the resident batch");
   return slice_resident(n, who, n.labels, 1, 1, 0, count, axis, index, lut, range_or_null, zoom, out);
 }
-int ics_op_kde_create(int dim, int capacity, ics_kde** out) { return kde_create(dim, capacity, out); }
-int ics_op_kde_destroy(ics_kde* h) { return kde_destroy(h); }
-int ics_op_kde_append(ics_kde* h, const float* codes, int rows) { return kde_append_host(h, codes, rows); }
 // encode -> append with nothing to the host: z_mean is the first half of each row of the zml layer's stored output (as
 // ics_op_tsne_append_vae reads it), the sampled z is z_buf as vae_encode_fwd's sampling kernel left it
 int ics_op_kde_append_vae(ics_kde* h, ics_net* vae, int batch, int which) {
@@ -3160,40 +3058,6 @@ int ics_op_kde_append_vae(ics_kde* h, ics_net* vae, int batch, int which) {
   VaeRefs r = vae_refs(n);
   return kde_append_device(h, r.zml->s, 2 * (size_t)n.latent, batch, n.st);
 }
-int ics_op_kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status,
-                        int* count) {
-  return kde_evaluate(h, x, npts, density, bandwidth, status, count);
-}
-int ics_op_render_lines(const double* xy, int ncurves, int npts, const double window[4], const float* palette, int npal,
-                        double width_px, float alpha, int width, int height, float* out) {
-  ICS_TRY(lines_check(xy, ncurves, npts, window, palette, npal, width_px, alpha, width, height, out));
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return lines_op(st, xy, ncurves, npts, window, palette, npal, width_px, alpha, width, height, out);
-}
-int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps, int mode,
-                       float* path) {
-  ICS_TRY(latent_path_check("ics_op_latent_path", pairs, latent, alpha, steps, mode));
-  ICS_CHECK(za && zb && path, "ics_op_latent_path: null argument (za, zb, path are required)");
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return latent_path_op(st, za, zb, pairs, latent, alpha, steps, mode, path);
-}
-int ics_op_tsne_knn(const float* x, int n, int dim, int k, int32_t* idx, double* dist2) {
-  ICS_TRY(tsne_knn_check(x, n, dim, k, idx, dist2));
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return tsne_knn_op(st, x, n, dim, k, idx, dist2);
-}
-int ics_op_tsne_affinities(const double* dist2, int n, int k, double perplexity, double* cond_p) {
-  ICS_TRY(tsne_affinities_check(dist2, n, k, perplexity, cond_p));
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return tsne_affinities_op(st, dist2, n, k, perplexity, cond_p);
-}
-int ics_op_tsne_create(const ics_tsne_config* cfg, ics_tsne** out) { return tsne_create(cfg, out); }
-int ics_op_tsne_destroy(ics_tsne* h) { return tsne_destroy(h); }
-int ics_op_tsne_append(ics_tsne* h, const float* codes, int rows) { return tsne_append_host(h, codes, rows); }
 // encode -> append with nothing to the host: z_mean is the first half of each row of the zml layer's stored output,
 // read in place as ics_vae_reconstruct_resident_to_unet_atoms reads zc
 int ics_op_tsne_append_vae(ics_tsne* h, ics_net* vae, int batch) {
@@ -3206,51 +3070,6 @@ int ics_op_tsne_append_vae(ics_tsne* h, ics_net* vae, int batch) {
   ICS_CHECK(batch >= 1 && batch <= n.resident_batch, "ics_op_tsne_append_vae: batch exceeds the engine's resident batch");
   VaeRefs r = vae_refs(n);
   return tsne_append_device(h, r.zml->s, 2 * (size_t)n.latent, batch, n.st);
-}
-int ics_op_tsne_get_codes(ics_tsne* h, float* out, int rows) { return tsne_get_codes(h, out, rows); }
-int ics_op_tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, double seconds[3]) {
-  return tsne_prepare(h, init, init_rows, init_cols, seconds);
-}
-int ics_op_tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* indices, const double* vals,
-                          const float* init, int init_rows, int init_cols) {
-  return tsne_set_graph(h, n, indptr, indices, vals, init, init_rows, init_cols);
-}
-int ics_op_tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals, size_t capacity, size_t* nnz) {
-  return tsne_get_graph(h, indptr, indices, vals, capacity, nnz);
-}
-int ics_op_tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad, double* kl) {
-  return tsne_gradient(h, y, exaggeration, grad, kl);
-}
-int ics_op_tsne_run(ics_tsne* h, int iters, int* done) { return tsne_run(h, iters, done); }
-int ics_op_tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count) {
-  return tsne_read(h, embedding, kl, grad_norm, n_iter, count);
-}
-int ics_op_label_boxes(const int32_t* vols, const int32_t* dims, int nbox, int connectivity, int max_labels,
-                       int32_t* labels, int32_t* nlabels, int32_t* stats) {
-  return segment_label_boxes(op_stream, vols, dims, nbox, connectivity, max_labels, labels, nlabels, stats);
-}
-int ics_op_region_stats(const int32_t* R, const uint8_t* species, int D, int H, int W, int num_labels, int num_species,
-                        int32_t* stats) {
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return segment_region_stats(st, R, species, D, H, W, num_labels, num_species, stats);
-}
-int ics_op_component_bounds(const int32_t* labels, const int32_t* dims, int nbox, const int32_t* nlabels, const int32_t* stats,
-                            int max_labels, int min_voxels, double hull_threshold, int64_t* bounds) {
-  static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
-  return segment_component_bounds(labels, dims, nbox, nlabels, stats, max_labels, min_voxels, hull_threshold,
-                                  reinterpret_cast<long long*>(bounds));
-}
-int ics_op_watershed_split(const int32_t* boxes, const int32_t* dims, const int32_t* cls, int nbox, int tie, int32_t* wss) {
-  // Round 6: the boxes of a level go to host threads (segment_watershed_split_host: the flood is sequential per box and a
-  // CPU core walks it ~30x faster than one GPU lane); ICSG3D_WS_DEVICE=1 keeps the kernel (A/B, tests run both) for the
-  // boxes it takes (extents <= 64), the others still go to the host flood.
-  const char* env = getenv("ICSG3D_WS_DEVICE");       // read per call: tests flip it inside one process
-  const bool on_device = env != nullptr && atoi(env) != 0;
-  if (!on_device) return segment_watershed_split_host(boxes, dims, cls, nbox, tie, wss);
-  hipStream_t st;
-  ICS_TRY(op_stream(&st));
-  return segment_watershed_split(st, boxes, dims, cls, nbox, tie, wss);
 }
 
 // ---------------------------------------------------------------- data parallel
@@ -3367,14 +3186,6 @@ int ics_net_comm_allreduce_max(ics_net* net, double* value) {
 }
 
 // ---------------------------------------------------------------- single-op entry points
-// Short-lived Nets behind the single-op entry points: their buffers are a few KB to MB, so the arena starts at 4 MB (doubling
-// as usual) instead of the 128 MB first slab of a long-lived engine handle -- a 128 MB hipMalloc + a synchronising hipFree per
-// call was the very overhead the box-level ops got rid of in round 5 (ADVICE r5).
-static int op_prepare(Net& n) {
-  n.arena_next = (size_t)1 << 22;
-  return net_common_init(n);
-}
-
 int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int B, int S, int Cin, int Cout,
                           int taps, int pre_act, float* y) {
   ICS_CHECK(x && w && y && (taps == 27 || taps == 1) && S >= 1 && (S & (S - 1)) == 0, "bad conv arguments");

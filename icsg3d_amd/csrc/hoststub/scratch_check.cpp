@@ -1,6 +1,7 @@
 // Stand-alone check of scratch.h / scratch.hip under AddressSanitizer and LeakSanitizer (`make asan`): linked against
 // hip_host_stub.cpp only, so "device" memory is malloc memory and a leaked scratch or stream is a reported leak.
 #include "scratch.h"
+#include "icsg3d.h"
 
 #include <sanitizer/asan_interface.h>
 
@@ -118,9 +119,9 @@ int main() {
   REQUIRE(!__asan_address_is_poisoned(thread_st) && !__asan_address_is_poisoned(thread_buf));   // orphaned, not destroyed
   hipStream_t again = nullptr;
   REQUIRE(op_stream(&again) == 0 && again == main_st);
-  release_thread_caches();
+  (void)ics_release_caches();
   REQUIRE(__asan_address_is_poisoned(thread_st) && __asan_address_is_poisoned(thread_buf) && __asan_address_is_poisoned(main_st));
-  release_thread_caches();                                  // nothing left: a no-op
+  (void)ics_release_caches();                               // nothing left: a no-op
   std::puts("scratch_check: ok");
   return 0;
 }

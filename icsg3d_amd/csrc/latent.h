@@ -19,9 +19,5 @@ int latent_path_check(const char* who, int pairs, int latent, const double* alph
 int launch_latent_path(hipStream_t st, const float* za, const float* zb, size_t z_stride, const float* cond,
                        size_t cond_stride, int ncond, int pairs, int latent, const double* d_alpha, int steps, int mode,
                        float* zc, float* path);
-// Host-pointer op behind ics_op_latent_path on arguments latent_path_check accepted: the pairs in chunks through the
-// calling thread's scratch; synchronous on st.
-int latent_path_op(hipStream_t st, const float* za, const float* zb, int pairs, int latent, const double* alpha,
-                   int steps, int mode, float* path);
 
 }  // namespace ics

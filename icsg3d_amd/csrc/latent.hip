@@ -12,6 +12,7 @@
 // (256 x 8 values per pair at the defaults): the only care taken is that a row is written by consecutive threads.
 #include "latent.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <cmath>
@@ -120,8 +121,17 @@ int launch_latent_path(hipStream_t st, const float* za, const float* zb, size_t 
   return 0;
 }
 
-int latent_path_op(hipStream_t st, const float* za, const float* zb, int pairs, int latent, const double* alpha,
-                   int steps, int mode, float* path) {
+}  // namespace ics
+
+using namespace ics;
+
+// The pairs in chunks through the calling thread's scratch; synchronous on its stream.
+extern "C" int ics_op_latent_path(const float* za, const float* zb, int pairs, int latent, const double* alpha, int steps,
+                                  int mode, float* path) {
+  ICS_TRY(latent_path_check("ics_op_latent_path", pairs, latent, alpha, steps, mode));
+  ICS_CHECK(za && zb && path, "ics_op_latent_path: null argument (za, zb, path are required)");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   const size_t per_pair = (size_t)steps * latent;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)pairs, kLatentChunkFloats / per_pair));
   Layout L;
@@ -142,5 +152,3 @@ int latent_path_op(hipStream_t st, const float* za, const float* zb, int pairs, 
   }
   return 0;
 }
-
-}  // namespace ics

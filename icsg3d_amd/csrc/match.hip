@@ -8,8 +8,8 @@
 // computed on the fly (no n x m matrix), followed by a workgroup argmin: wave64 shuffles, then one LDS slot per wave
 // combined in wave order.  Ties go to an unassigned column, then to the lowest column index, so results are the same
 // run to run.  Only the augmentation walk along the predecessors is serial (thread 0).
-#include "match.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 namespace ics {
 namespace {
 
+constexpr int kMatchMaxPoints = 2048;              // points per set (MAX_SITES true sites, generate.py's max_atoms)
 constexpr size_t kMatchBudget = (size_t)4 << 20;   // points (both sets) per chunk: 96 MB of coordinates
 constexpr int kMatchMaxSamples = 1 << 20;          // samples per chunk
 constexpr double kMatchMaxCoord = 1e150;           // |coordinate| bound: every distance stays finite
@@ -202,17 +203,20 @@ int launch_chunk(hipStream_t st, const double* da, const int* dao, const double*
 
 }  // namespace
 
-int match_emd_check(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
-                    const double* emd) {
+}  // namespace ics
+
+using namespace ics;
+
+// The argument rules of include/icsg3d.h, every sample checked before anything is written; then the batch solved in chunks
+// under a device-memory budget through the calling thread's scratch, synchronous on its stream.
+extern "C" int ics_op_match_emd(const double* a, const int32_t* a_off, const double* b, const int32_t* b_off, int batch,
+                                double* emd, int32_t* match) {
   ICS_CHECK(batch >= 1, "ics_op_match_emd: batch must be >= 1");
   ICS_CHECK(a_off && b_off && emd, "ics_op_match_emd: null argument");
   ICS_TRY(check_set(a, a_off, batch, 'a'));
   ICS_TRY(check_set(b, b_off, batch, 'b'));
-  return 0;
-}
-
-int match_emd_op(hipStream_t st, const double* a, const int32_t* a_off, const double* b, const int32_t* b_off,
-                 int batch, double* emd, int32_t* match) {
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   std::vector<int> ao, bo;
   for (int s0 = 0; s0 < batch;) {
     // one chunk: samples [s0, s1) under the point budget (at least one sample)
@@ -252,5 +256,3 @@ int match_emd_op(hipStream_t st, const double* a, const int32_t* a_off, const do
   }
   return 0;
 }
-
-}  // namespace ics

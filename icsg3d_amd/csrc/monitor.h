@@ -96,25 +96,11 @@ int slice_check(const char* op, int dtype, int count, int d, int stride_c, int c
 // host-pointer op and the two resident entries all come here, which is why their images are the same bits.
 int slice_device(hipStream_t st, const void* src, int dtype, const SliceLayout& lay, int count, int d, const float* d_lut,
                  bool own_range, float* d_range, int zoom, float* d_out);
-// Host-pointer op on checked arguments: the planes are gathered on the host, uploaded, drawn and downloaded in chunks
-// under a device-memory budget through the calling thread's scratch (scratch.h); synchronous on st.
-int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
-             const float* lut, const float* range_or_null, int zoom, float* out);
 
 // ---- the KDE handle (struct ics_kde, defined in monitor.hip): codes resident on the device
-int kde_create(int dim, int capacity, ics_kde** out);
-int kde_destroy(ics_kde* h);
-int kde_append_host(ics_kde* h, const float* codes, int rows);
 // rows of `dim` floats, `stride_floats` apart, already on the handle's device; ordered after the work on src_stream
 int kde_append_device(ics_kde* h, const float* src, size_t stride_floats, int rows, hipStream_t src_stream);
-int kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status, int* count);
 int kde_device(const ics_kde* h);
 int kde_dim(const ics_kde* h);
-
-// Host-pointer polyline plot on checked arguments; synchronous on st.
-int lines_check(const double* xy, int ncurves, int npts, const double* window, const float* palette, int npal,
-                double width_px, float alpha, int width, int height, const float* out);
-int lines_op(hipStream_t st, const double* xy, int ncurves, int npts, const double* window, const float* palette, int npal,
-             double width_px, float alpha, int width, int height, float* out);
 
 }  // namespace ics

@@ -14,6 +14,7 @@
 
 #include "monitor.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <cmath>
@@ -287,8 +288,36 @@ int slice_device(hipStream_t st, const void* src, int dtype, const SliceLayout& 
   return slice_launch<int32_t>(st, src, lay, count, d, d_lut, own_range, d_range, zoom, d_out);
 }
 
-int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
-             const float* lut, const float* range, int zoom, float* out) {
+// ---------------------------------------------------------------- KDE: the handle
+int kde_device(const ics_kde* h) { return h->device; }
+int kde_dim(const ics_kde* h) { return h->dim; }
+
+int kde_append_device(ics_kde* h, const float* src, size_t stride_floats, int rows, hipStream_t src_stream) {
+  ICS_TRY(kde_enter(h, "ics_op_kde_append_vae"));
+  ICS_CHECK(src != nullptr, "ics_op_kde_append_vae: null source");
+  ICS_CHECK(rows >= 1 && rows <= h->capacity - h->count, "ics_op_kde_append_vae: rows exceed the handle's capacity");
+  const size_t w = (size_t)h->dim * 4;
+  ICS_HIP(hipMemcpy2DAsync(h->codes + (size_t)h->count * h->dim, w, src, stride_floats * 4, w, (size_t)rows,
+                           hipMemcpyDeviceToDevice, src_stream));
+  ICS_HIP(hipStreamSynchronize(src_stream));
+  h->count += rows;
+  return 0;
+}
+
+}  // namespace ics
+
+using namespace ics;
+
+extern "C" {
+
+// The planes are gathered on the host, uploaded, drawn and downloaded in chunks under a device-memory budget through the
+// calling thread's scratch (scratch.h); synchronous on the calling thread's stream.
+int ics_op_render_slice(const void* vol, int dtype, int batch, int d, int stride_c, int channel, int axis, int index,
+                        const float* lut, const float* range, int zoom, float* out) {
+  ICS_TRY(slice_check("ics_op_render_slice", dtype, batch, d, stride_c, channel, axis, index, lut, range, zoom, out));
+  ICS_CHECK(vol != nullptr, "ics_op_render_slice: null vol");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   const size_t es = slice_elem_bytes(dtype), side = (size_t)d * zoom;
   const size_t plane_b = (size_t)d * d * es, img_b = side * side * 16;
   const int nb = (int)std::min<size_t>((size_t)batch, std::max<size_t>(1, kMonitorBudget / (plane_b + img_b)));
@@ -322,13 +351,13 @@ int slice_op(hipStream_t st, const void* vol, int dtype, int batch, int d, int s
 }
 
 // ---------------------------------------------------------------- KDE: the handle
-int kde_create(int dim, int capacity, ics_kde** out) {
+int ics_op_kde_create(int dim, int capacity, ics_kde** out) {
   ICS_CHECK(out != nullptr, "ics_op_kde_create: null argument");
   ICS_CHECK(dim >= 1 && dim <= kKdeMaxDim, "ics_op_kde_create: dim must be in [1, 4096]");
   ICS_CHECK(capacity >= 2 && capacity <= kKdeMaxCodes, "ics_op_kde_create: capacity must be in [2, 2^20]");
   ics_kde* h = new ics_kde();
   h->dim = dim; h->capacity = capacity;
-  auto fail = [&]() { (void)kde_destroy(h); return -1; };
+  auto fail = [&]() { (void)ics_op_kde_destroy(h); return -1; };
   if (hipGetDevice(&h->device) != hipSuccess) { set_error("ics_op_kde_create: hipGetDevice failed"); return fail(); }
   if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
     h->st = nullptr;
@@ -345,7 +374,7 @@ int kde_create(int dim, int capacity, ics_kde** out) {
   return 0;
 }
 
-int kde_destroy(ics_kde* h) {
+int ics_op_kde_destroy(ics_kde* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
@@ -355,10 +384,7 @@ int kde_destroy(ics_kde* h) {
   return 0;
 }
 
-int kde_device(const ics_kde* h) { return h->device; }
-int kde_dim(const ics_kde* h) { return h->dim; }
-
-int kde_append_host(ics_kde* h, const float* codes, int rows) {
+int ics_op_kde_append(ics_kde* h, const float* codes, int rows) {
   ICS_TRY(kde_enter(h, "ics_op_kde_append"));
   ICS_CHECK(codes != nullptr, "ics_op_kde_append: null codes");
   ICS_CHECK(rows >= 1 && rows <= h->capacity - h->count, "ics_op_kde_append: rows exceed the handle's capacity");
@@ -370,19 +396,8 @@ int kde_append_host(ics_kde* h, const float* codes, int rows) {
   return 0;
 }
 
-int kde_append_device(ics_kde* h, const float* src, size_t stride_floats, int rows, hipStream_t src_stream) {
-  ICS_TRY(kde_enter(h, "ics_op_kde_append_vae"));
-  ICS_CHECK(src != nullptr, "ics_op_kde_append_vae: null source");
-  ICS_CHECK(rows >= 1 && rows <= h->capacity - h->count, "ics_op_kde_append_vae: rows exceed the handle's capacity");
-  const size_t w = (size_t)h->dim * 4;
-  ICS_HIP(hipMemcpy2DAsync(h->codes + (size_t)h->count * h->dim, w, src, stride_floats * 4, w, (size_t)rows,
-                           hipMemcpyDeviceToDevice, src_stream));
-  ICS_HIP(hipStreamSynchronize(src_stream));
-  h->count += rows;
-  return 0;
-}
-
-int kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status, int* count) {
+int ics_op_kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double* bandwidth, int32_t* status,
+                        int* count) {
   ICS_TRY(kde_enter(h, "ics_op_kde_evaluate"));
   ICS_CHECK(x && density, "ics_op_kde_evaluate: null argument (x, density)");
   ICS_CHECK(npts >= 1 && npts <= kKdeMaxPoints, "ics_op_kde_evaluate: npts must be in [1, 4096]");
@@ -410,9 +425,9 @@ int kde_evaluate(ics_kde* h, const double* x, int npts, double* density, double*
   return 0;
 }
 
-// ---------------------------------------------------------------- lines: host side
-int lines_check(const double* xy, int ncurves, int npts, const double* window, const float* palette, int npal,
-                double width_px, float alpha, int width, int height, const float* out) {
+// ---------------------------------------------------------------- lines
+int ics_op_render_lines(const double* xy, int ncurves, int npts, const double window[4], const float* palette, int npal,
+                        double width_px, float alpha, int width, int height, float* out) {
   const std::string op = "ics_op_render_lines: ";
   ICS_CHECK(xy && window && palette && out, op + "null argument (xy, window, palette, out)");
   ICS_CHECK(npts >= 2 && npts <= kLinesMaxPoints, op + "npts must be in [2, 4096]");
@@ -426,11 +441,8 @@ int lines_check(const double* xy, int ncurves, int npts, const double* window, c
   ICS_CHECK(std::isfinite(width_px) && width_px > 0.0, op + "width_px must be finite and > 0");
   ICS_CHECK(alpha >= 0.f && alpha <= 1.f, op + "alpha must be in [0, 1]");
   ICS_CHECK(npal >= 1, op + "npal must be >= 1");
-  return 0;
-}
-
-int lines_op(hipStream_t st, const double* xy, int ncurves, int npts, const double* window, const float* palette, int npal,
-             double width_px, float alpha, int width, int height, float* out) {
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   Layout L;
   const auto s_xy = L.add<double>((size_t)ncurves * npts * 2);
   const auto s_pal = L.add<float>((size_t)npal * 3);
@@ -452,4 +464,4 @@ int lines_op(hipStream_t st, const double* xy, int ncurves, int npts, const doub
   return 0;
 }
 
-}  // namespace ics
+}  // extern "C"

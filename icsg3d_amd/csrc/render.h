@@ -200,13 +200,5 @@ int render_density_check(const char* op, int stride_c, int channel, const float*
 // ics_vae_render_resident both come here, which is why their images are the same bits.
 int render_density_device(hipStream_t st, const float* vol, int B, int d, int stride_c, int channel, const float* lut,
                           int mode, float alpha, float floor_v, const RenderView<double>& view, int W, int H, float* out);
-// Host-pointer ops on checked arguments: chunked over the batch under a device-memory budget through the calling thread's
-// scratch (scratch.h), one upload, one launch and one download per chunk; synchronous on st.
-int render_density_op(hipStream_t st, const float* vol, int B, int d, int stride_c, int channel, const float* lut, int mode,
-                      float alpha, float floor_v, const double* camera, int W, int H, float* out);
-int render_labels_op(hipStream_t st, const int32_t* labels, int B, int d, const float* palette, int npal, float alpha,
-                     const double* camera, int W, int H, float* out);
-int render_atoms_op(hipStream_t st, const int32_t* offsets, const int32_t* species, const double* xyz, int B, int d,
-                    double radius, const float* palette, int npal, const double* camera, int W, int H, float* out);
 
 }  // namespace ics

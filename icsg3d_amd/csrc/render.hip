@@ -10,6 +10,7 @@
 // 1.4 - 1.6x slower than these global reads, so it is not kept.
 #include "render.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <cmath>
@@ -157,8 +158,21 @@ int render_density_device(hipStream_t st, const float* vol, int B, int d, int st
   return 0;
 }
 
-int render_density_op(hipStream_t st, const float* vol, int B, int d, int stride_c, int channel, const float* lut, int mode,
-                      float alpha, float floor_v, const double* camera, int W, int H, float* out) {
+}  // namespace ics
+
+using namespace ics;
+
+extern "C" {
+
+// Each of the three is chunked over the batch under a device-memory budget through the calling thread's scratch
+// (scratch.h), one upload, one launch and one download per chunk; synchronous on the calling thread's stream.
+int ics_op_render_density(const float* vol, int B, int d, int stride_c, int channel, const float* lut, int mode, float alpha,
+                          float floor_v, const double* camera, int W, int H, float* out) {
+  ICS_TRY(render_check("ics_op_render_density", B, d, camera, W, H, out));
+  ICS_TRY(render_density_check("ics_op_render_density", stride_c, channel, lut, mode, alpha, floor_v));
+  ICS_CHECK(vol != nullptr, "ics_op_render_density: null vol");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   RenderView<double> view;
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_density: camera must be finite");
   const size_t vol_b = (size_t)d * d * d * stride_c * sizeof(float), img_b = (size_t)W * H * 16;
@@ -180,8 +194,14 @@ int render_density_op(hipStream_t st, const float* vol, int B, int d, int stride
   return 0;
 }
 
-int render_labels_op(hipStream_t st, const int32_t* labels, int B, int d, const float* palette, int npal, float alpha,
-                     const double* camera, int W, int H, float* out) {
+int ics_op_render_labels(const int32_t* labels, int B, int d, const float* palette, int npal, float alpha,
+                         const double* camera, int W, int H, float* out) {
+  ICS_TRY(render_check("ics_op_render_labels", B, d, camera, W, H, out));
+  ICS_CHECK(labels && palette, "ics_op_render_labels: null argument (labels, palette)");
+  ICS_CHECK(npal >= 1, "ics_op_render_labels: npal must be >= 1");
+  ICS_CHECK(alpha >= 0.f && alpha <= 1.f, "ics_op_render_labels: alpha must be in [0, 1]");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   RenderView<double> view;
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_labels: camera must be finite");
   const RenderView<float> V = view_f32(view);
@@ -206,8 +226,21 @@ int render_labels_op(hipStream_t st, const int32_t* labels, int B, int d, const 
   return 0;
 }
 
-int render_atoms_op(hipStream_t st, const int32_t* offsets, const int32_t* species, const double* xyz, int B, int d,
-                    double radius, const float* palette, int npal, const double* camera, int W, int H, float* out) {
+int ics_op_render_atoms(const int32_t* offsets, const int32_t* species, const double* xyz, int B, int d, double radius,
+                        const float* palette, int npal, const double* camera, int W, int H, float* out) {
+  const std::string op = "ics_op_render_atoms: ";
+  ICS_TRY(render_check("ics_op_render_atoms", B, d, camera, W, H, out));
+  ICS_CHECK(offsets && palette, op + "null argument (offsets, palette)");
+  ICS_CHECK(npal >= 1, op + "npal must be >= 1");
+  ICS_CHECK(std::isfinite(radius) && radius > 0.0, op + "radius must be finite and > 0");
+  ICS_CHECK(offsets[0] == 0, op + "offsets[0] must be 0");
+  for (int b = 0; b < B; ++b)
+    ICS_CHECK(offsets[b + 1] >= offsets[b], op + "offsets decrease at sample " + std::to_string(b));
+  ICS_CHECK((species && xyz) || offsets[B] == 0, op + "null species or xyz");
+  for (long long k = 0; k < 3LL * offsets[B]; ++k)
+    ICS_CHECK(std::isfinite(xyz[k]), op + "non-finite coordinate");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   RenderView<double> view;
   ICS_CHECK(render_view(camera, d, W, H, &view) == 0, "ics_op_render_atoms: camera must be finite");
   const size_t img_b = (size_t)W * H * 16;
@@ -243,4 +276,4 @@ int render_atoms_op(hipStream_t st, const int32_t* offsets, const int32_t* speci
   return 0;
 }
 
-}  // namespace ics
+}  // extern "C"

@@ -12,8 +12,6 @@ constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 // The calling thread's stream for the host-pointer ops (non-blocking, created on first use and kept: a handle with two
 // streams, two events and its own allocations per call cost 10 - 16 ms against kernels of tens of microseconds).
 int op_stream(hipStream_t* out);
-// frees the calling thread's stream and scratch, and those that exited threads left behind (ics_release_caches)
-void release_thread_caches();
 // The calling thread's grow-only device scratch (>= bytes; contents not kept across calls that grow it).  Layout::reserve
 // is its only caller.
 int scratch_get(size_t bytes, unsigned char** out);

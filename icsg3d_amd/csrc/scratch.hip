@@ -1,5 +1,6 @@
 // The per-thread caches of the host-pointer ops (scratch.h): the op stream and the grow-only device scratch.
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <mutex>
@@ -85,9 +86,11 @@ int scratch_get(size_t bytes, unsigned char** out) {
   return 0;
 }
 
-void release_thread_caches() {
-  StreamCache::release();
-  ScratchCache::release();
-}
-
 }  // namespace ics
+
+// frees the calling thread's stream and scratch, and those that exited threads left behind
+extern "C" int ics_release_caches() {
+  ics::StreamCache::release();
+  ics::ScratchCache::release();
+  return 0;
+}

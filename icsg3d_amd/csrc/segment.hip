@@ -16,6 +16,7 @@
 #include "common.h"
 #include "segment.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -594,35 +595,6 @@ static bool label_host_forced() {
   return e != nullptr && atoi(e) != 0;
 }
 
-int segment_region_stats(hipStream_t st, const int* h_R, const unsigned char* h_species, int D, int H, int W, int nlab,
-                         int nbins, int* h_stats) {
-  ICS_CHECK(h_R && h_species && h_stats && D >= 1 && H >= 1 && W >= 1 && nlab >= 1 && nbins >= 2 && nbins <= 256,
-            "bad region_stats arguments");
-  const size_t V = (size_t)D * H * W;
-  ICS_CHECK(V < (1u << 30), "volume too large");
-  Layout L;
-  const auto s_R = L.add<int>(V);
-  const auto s_sp = L.add<unsigned char>(V);
-  const auto s_st = L.add<int>((size_t)nlab * kSegStatInts);
-  const auto s_h = L.add<unsigned>((size_t)nlab * nbins);
-  int *d_R, *d_st;
-  unsigned char* d_sp;
-  unsigned* d_h;
-  ICS_TRY(L.reserve(s_R, &d_R, s_sp, &d_sp, s_st, &d_st, s_h, &d_h));
-  ICS_TRY(L.upload(s_R, h_R, V, st));
-  ICS_TRY(L.upload(s_sp, h_species, V, st));
-  ICS_TRY(L.fill(s_h, 0, s_h.count, st));
-  const int dmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
-  ICS_LAUNCH(seg_stats_init_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_st, (size_t)nlab, dmax);
-  ICS_LAUNCH(region_stats_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_R, d_sp, D, H, W, nlab, nbins,
-             d_st, d_h);
-  ICS_LAUNCH(seg_vote_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_h, nbins, (size_t)nlab, d_st);
-  ICS_HIP(hipGetLastError());
-  ICS_TRY(L.download(h_stats, s_st, s_st.count, st));
-  ICS_HIP(hipStreamSynchronize(st));
-  return 0;
-}
-
 // ---- a persistent pool of host threads for the box-level host operations below (round 6).  They are called several times per
 // recursion level with a few milliseconds of work each; spawning up to 64 std::threads per call cost 1 - 2 ms of that.  The
 // pool is created on first use, never destroyed (its threads are detached and die with the process: no static-destruction
@@ -887,9 +859,9 @@ size_t pack_device_boxes(const int* h_vols, const std::vector<BoxDesc>& desc, co
                 (size_t)desc[pos[k]].D * desc[pos[k]].H * desc[pos[k]].W * sizeof(int));
   return off;
 }
-}  // namespace
-
-int segment_watershed_split_host(const int* h_boxes, const int* h_dims, const int* h_cls, int nbox, int tie, int* h_wss) {
+// The split on host threads (no device work: the flood is a chain of dependent heap operations);
+// bit-identical to the kernel.
+int watershed_split_host(const int* h_boxes, const int* h_dims, const int* h_cls, int nbox, int tie, int* h_wss) {
   ICS_CHECK(h_boxes && h_dims && h_cls && h_wss && nbox >= 1 && (tie == 0 || tie == 1), "bad watershed_split arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
@@ -902,70 +874,7 @@ int segment_watershed_split_host(const int* h_boxes, const int* h_dims, const in
   });
   return 0;
 }
-
-// Boxes with an extent above 64 (or every box, ICSG3D_LABEL_HOST=1) go to host_label_box on host threads, the others to
-// label_boxes_kernel; the stream is only asked for when a box goes to the device.
-int segment_label_boxes(int (*get_stream)(hipStream_t*), const int* h_vols, const int* h_dims, int nbox, int connectivity,
-                        int max_labels, int* h_labels, int* h_nlabels, int* h_stats) {
-  ICS_CHECK(h_vols && h_dims && h_labels && h_nlabels && nbox >= 1 && max_labels >= 1, "bad label_boxes arguments");
-  ICS_CHECK(connectivity == 1 || connectivity == 3, "connectivity must be 1 (6 neighbours) or 3 (26)");
-  std::vector<BoxDesc> desc;
-  size_t total = 0;
-  ICS_TRY(box_descs(h_dims, nullptr, nbox, kBoxHostMax, &desc, &total));
-  const bool host_all = label_host_forced();
-  std::vector<int> on_host, on_dev;
-  for (int b = 0; b < nbox; ++b) (host_all || !box_fits_device(desc[b]) ? on_host : on_dev).push_back(b);
-  const size_t row = (size_t)max_labels * 7;
-  host_boxes_run(desc, on_host, [&](int b) {
-    const BoxDesc& d = desc[b];
-    host_label_box(h_vols + d.off, d.D, d.H, d.W, connectivity == 3, max_labels, h_labels + d.off, h_nlabels + b,
-                   h_stats ? h_stats + b * row : nullptr);
-  });
-  if (on_dev.empty()) return 0;
-  // a mixed call: the device boxes are packed, and their results dealt back afterwards
-  const bool mixed = (int)on_dev.size() != nbox;
-  std::vector<int> pvol, plab, pn, pst;
-  std::vector<BoxDesc> pdesc;
-  const int* vols = h_vols;
-  int *labels = h_labels, *nlabels = h_nlabels, *stats = h_stats;
-  const std::vector<BoxDesc>* dd = &desc;
-  size_t dtotal = total;
-  if (mixed) {
-    dtotal = pack_device_boxes(h_vols, desc, on_dev, &pvol, &pdesc);
-    plab.resize(dtotal); pn.resize(on_dev.size());
-    if (h_stats) pst.resize(on_dev.size() * row);
-    vols = pvol.data(); labels = plab.data(); nlabels = pn.data(); stats = h_stats ? pst.data() : nullptr; dd = &pdesc;
-  }
-  const int ndev = (int)on_dev.size();
-  hipStream_t st;
-  ICS_TRY(get_stream(&st));
-  Layout L;
-  const auto s_vol = L.add<int>(dtotal), s_lab = L.add<int>(dtotal);
-  const auto s_desc = L.add<BoxDesc>(ndev);
-  const auto s_n = L.add<int>(ndev);
-  const auto s_st = L.add<int>((size_t)ndev * row);
-  int *d_vol, *d_lab, *d_n, *d_st;
-  BoxDesc* d_desc;
-  ICS_TRY(L.reserve(s_vol, &d_vol, s_lab, &d_lab, s_desc, &d_desc, s_n, &d_n, s_st, &d_st));
-  ICS_TRY(L.upload(s_vol, vols, dtotal, st));
-  ICS_TRY(L.upload(s_desc, dd->data(), ndev, st));
-  ICS_LAUNCH(label_boxes_kernel, dim3(ndev), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
-             d_lab, d_n, d_st);
-  ICS_HIP(hipGetLastError());
-  ICS_TRY(L.download(labels, s_lab, dtotal, st));
-  ICS_TRY(L.download(nlabels, s_n, ndev, st));
-  if (stats) ICS_TRY(L.download(stats, s_st, s_st.count, st));
-  ICS_HIP(hipStreamSynchronize(st));
-  if (mixed)
-    for (int k = 0; k < ndev; ++k) {
-      const int b = on_dev[k];
-      const BoxDesc &d = desc[b], &p = pdesc[k];
-      std::memcpy(h_labels + d.off, plab.data() + p.off, (size_t)d.D * d.H * d.W * sizeof(int));
-      h_nlabels[b] = pn[k];
-      if (h_stats) std::memcpy(h_stats + b * row, pst.data() + k * row, row * sizeof(int));
-    }
-  return 0;
-}
+}  // namespace
 
 // ---- exact-integer convexity bounds of the components of labelled boxes, on host threads (round 6).
 // icsg3d_amd/watershed.py decides `voxels / count_nonzero(convex_hull_image(component)) >= min_convexity`
@@ -1262,8 +1171,114 @@ void component_bounds_one(const int* lab, int H, int W, int cl, const int* st, d
 }
 }  // namespace
 
-int segment_component_bounds(const int* h_labels, const int* h_dims, int nbox, const int* h_nlabels, const int* h_stats,
-                             int max_labels, int min_voxels, double hull_threshold, long long* h_bounds) {
+}  // namespace ics
+
+// ==========================================================================================
+// C ABI: the box-level ops, HOST pointers in and out (include/icsg3d.h)
+// ==========================================================================================
+using namespace ics;
+
+extern "C" {
+
+// Boxes with an extent above 64 (or every box, ICSG3D_LABEL_HOST=1) go to host_label_box on host threads, the others to
+// label_boxes_kernel; the stream is only asked for when a box goes to the device.
+int ics_op_label_boxes(const int32_t* h_vols, const int32_t* h_dims, int nbox, int connectivity, int max_labels,
+                       int32_t* h_labels, int32_t* h_nlabels, int32_t* h_stats) {
+  ICS_CHECK(h_vols && h_dims && h_labels && h_nlabels && nbox >= 1 && max_labels >= 1, "bad label_boxes arguments");
+  ICS_CHECK(connectivity == 1 || connectivity == 3, "connectivity must be 1 (6 neighbours) or 3 (26)");
+  std::vector<BoxDesc> desc;
+  size_t total = 0;
+  ICS_TRY(box_descs(h_dims, nullptr, nbox, kBoxHostMax, &desc, &total));
+  const bool host_all = label_host_forced();
+  std::vector<int> on_host, on_dev;
+  for (int b = 0; b < nbox; ++b) (host_all || !box_fits_device(desc[b]) ? on_host : on_dev).push_back(b);
+  const size_t row = (size_t)max_labels * 7;
+  host_boxes_run(desc, on_host, [&](int b) {
+    const BoxDesc& d = desc[b];
+    host_label_box(h_vols + d.off, d.D, d.H, d.W, connectivity == 3, max_labels, h_labels + d.off, h_nlabels + b,
+                   h_stats ? h_stats + b * row : nullptr);
+  });
+  if (on_dev.empty()) return 0;
+  // a mixed call: the device boxes are packed, and their results dealt back afterwards
+  const bool mixed = (int)on_dev.size() != nbox;
+  std::vector<int> pvol, plab, pn, pst;
+  std::vector<BoxDesc> pdesc;
+  const int* vols = h_vols;
+  int *labels = h_labels, *nlabels = h_nlabels, *stats = h_stats;
+  const std::vector<BoxDesc>* dd = &desc;
+  size_t dtotal = total;
+  if (mixed) {
+    dtotal = pack_device_boxes(h_vols, desc, on_dev, &pvol, &pdesc);
+    plab.resize(dtotal); pn.resize(on_dev.size());
+    if (h_stats) pst.resize(on_dev.size() * row);
+    vols = pvol.data(); labels = plab.data(); nlabels = pn.data(); stats = h_stats ? pst.data() : nullptr; dd = &pdesc;
+  }
+  const int ndev = (int)on_dev.size();
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_vol = L.add<int>(dtotal), s_lab = L.add<int>(dtotal);
+  const auto s_desc = L.add<BoxDesc>(ndev);
+  const auto s_n = L.add<int>(ndev);
+  const auto s_st = L.add<int>((size_t)ndev * row);
+  int *d_vol, *d_lab, *d_n, *d_st;
+  BoxDesc* d_desc;
+  ICS_TRY(L.reserve(s_vol, &d_vol, s_lab, &d_lab, s_desc, &d_desc, s_n, &d_n, s_st, &d_st));
+  ICS_TRY(L.upload(s_vol, vols, dtotal, st));
+  ICS_TRY(L.upload(s_desc, dd->data(), ndev, st));
+  ICS_LAUNCH(label_boxes_kernel, dim3(ndev), dim3(1024), 0, st, d_vol, d_desc, connectivity == 3 ? 1 : 0, max_labels,
+             d_lab, d_n, d_st);
+  ICS_HIP(hipGetLastError());
+  ICS_TRY(L.download(labels, s_lab, dtotal, st));
+  ICS_TRY(L.download(nlabels, s_n, ndev, st));
+  if (stats) ICS_TRY(L.download(stats, s_st, s_st.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  if (mixed)
+    for (int k = 0; k < ndev; ++k) {
+      const int b = on_dev[k];
+      const BoxDesc &d = desc[b], &p = pdesc[k];
+      std::memcpy(h_labels + d.off, plab.data() + p.off, (size_t)d.D * d.H * d.W * sizeof(int));
+      h_nlabels[b] = pn[k];
+      if (h_stats) std::memcpy(h_stats + b * row, pst.data() + k * row, row * sizeof(int));
+    }
+  return 0;
+}
+
+int ics_op_region_stats(const int32_t* h_R, const uint8_t* h_species, int D, int H, int W, int nlab, int nbins,
+                        int32_t* h_stats) {
+  ICS_CHECK(h_R && h_species && h_stats && D >= 1 && H >= 1 && W >= 1 && nlab >= 1 && nbins >= 2 && nbins <= 256,
+            "bad region_stats arguments");
+  const size_t V = (size_t)D * H * W;
+  ICS_CHECK(V < (1u << 30), "volume too large");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_R = L.add<int>(V);
+  const auto s_sp = L.add<unsigned char>(V);
+  const auto s_st = L.add<int>((size_t)nlab * kSegStatInts);
+  const auto s_h = L.add<unsigned>((size_t)nlab * nbins);
+  int *d_R, *d_st;
+  unsigned char* d_sp;
+  unsigned* d_h;
+  ICS_TRY(L.reserve(s_R, &d_R, s_sp, &d_sp, s_st, &d_st, s_h, &d_h));
+  ICS_TRY(L.upload(s_R, h_R, V, st));
+  ICS_TRY(L.upload(s_sp, h_species, V, st));
+  ICS_TRY(L.fill(s_h, 0, s_h.count, st));
+  const int dmax = D > H ? (D > W ? D : W) : (H > W ? H : W);
+  ICS_LAUNCH(seg_stats_init_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_st, (size_t)nlab, dmax);
+  ICS_LAUNCH(region_stats_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_R, d_sp, D, H, W, nlab, nbins,
+             d_st, d_h);
+  ICS_LAUNCH(seg_vote_kernel, dim3((unsigned)((nlab + 255) / 256)), dim3(256), 0, st, d_h, nbins, (size_t)nlab, d_st);
+  ICS_HIP(hipGetLastError());
+  ICS_TRY(L.download(h_stats, s_st, s_st.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int ics_op_component_bounds(const int32_t* h_labels, const int32_t* h_dims, int nbox, const int32_t* h_nlabels,
+                            const int32_t* h_stats, int max_labels, int min_voxels, double hull_threshold, int64_t* bounds) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
+  long long* h_bounds = reinterpret_cast<long long*>(bounds);
   ICS_CHECK(h_labels && h_dims && h_nlabels && h_stats && h_bounds && nbox >= 1 && max_labels >= 1, "bad component_bounds arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
@@ -1300,14 +1315,20 @@ int segment_component_bounds(const int* h_labels, const int* h_dims, int nbox, c
   return 0;
 }
 
-// ICSG3D_WS_DEVICE=1: ws_split_kernel for the boxes it takes; boxes with an extent above 64 go to the host flood
-// (host_split_box, the same arithmetic) instead of being refused.
-int segment_watershed_split(hipStream_t st, const int* h_boxes, const int* h_dims, const int* h_cls, int nbox, int tie,
-                            int* h_wss) {
+int ics_op_watershed_split(const int32_t* h_boxes, const int32_t* h_dims, const int32_t* h_cls, int nbox, int tie,
+                           int32_t* h_wss) {
+  // Round 6: the boxes of a level go to host threads (watershed_split_host: the flood is sequential per box and a CPU core
+  // walks it ~30x faster than one GPU lane); ICSG3D_WS_DEVICE=1 keeps the kernel (A/B, tests run both) for the boxes it
+  // takes (extents <= 64), the others still go to the host flood (host_split_box, the same arithmetic).
+  const char* env = getenv("ICSG3D_WS_DEVICE");       // read per call: tests flip it inside one process
+  const bool on_device = env != nullptr && atoi(env) != 0;
+  if (!on_device) return watershed_split_host(h_boxes, h_dims, h_cls, nbox, tie, h_wss);
   ICS_CHECK(h_boxes && h_dims && h_cls && h_wss && nbox >= 1 && (tie == 0 || tie == 1), "bad watershed_split arguments");
   std::vector<BoxDesc> desc;
   size_t total = 0;
   ICS_TRY(box_descs(h_dims, h_cls, nbox, kBoxHostMax, &desc, &total));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   std::vector<int> on_host, on_dev;
   for (int b = 0; b < nbox; ++b) (box_fits_device(desc[b]) ? on_dev : on_host).push_back(b);
   host_boxes_run(desc, on_host, [&](int b) {
@@ -1352,4 +1373,4 @@ int segment_watershed_split(hipStream_t st, const int* h_boxes, const int* h_dim
   return 0;
 }
 
-}  // namespace ics
+}  // extern "C"

@@ -13,8 +13,8 @@
 // through wave shuffles, then one LDS slot per wave combined in wave order; the per-atom minimum is an integer LDS
 // atomic min on the bit pattern of the (non-negative) distance and the histogram an integer LDS atomic add, so no result
 // depends on arrival order.
-#include "structure.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <cmath>
@@ -22,6 +22,16 @@
 
 namespace ics {
 namespace {
+
+constexpr int kStructMaxAtoms = 2048;   // atoms per structure (generate.py's max_atoms)
+constexpr int kStructMaxImage = 32;     // lattice translations searched per axis: |n| <= 32
+constexpr int kStructHist = 95;         // histogram row: atomic numbers 0..94 (0 is never counted)
+constexpr double kStructMaxCoord = 1e150;
+
+// reason bits of an invalid structure (ics_op_structure_screen's `reason`)
+constexpr int kStructReasonClose = 1;     // a pair at or under tol
+constexpr int kStructReasonSpecies = 2;   // a species outside 1..94
+constexpr int kStructReasonEmpty = 4;     // no atoms
 
 constexpr size_t kStructBudget = (size_t)1 << 20;   // atoms per chunk
 constexpr int kStructMaxChunk = 1 << 16;            // structures per chunk
@@ -179,8 +189,8 @@ int launch_screen(hipStream_t st, const int* ids, int nids, int cap, const int* 
   return 0;
 }
 
-}  // namespace
-
+// Per structure: the lattice of Lattice.from_parameters (rows va, vb, vc), its volume and the norms of the columns of
+// its inverse.  0, or -1 where the six parameters make no cell.
 int structure_cell(const double abc[3], const double angles[3], double M[9], double* volume, double g[3]) {
   // Lattice.from_parameters; the sine and cosine of exactly 90 degrees are taken as 1 and 0
   double sn[3], cs[3];
@@ -210,8 +220,18 @@ int structure_cell(const double abc[3], const double angles[3], double M[9], dou
   return 0;
 }
 
-int structure_screen_check(const int32_t* offsets, const int32_t* species, const double* xyz, const double* abc,
-                           const double* angles, int batch, double tol) {
+}  // namespace
+}  // namespace ics
+
+using namespace ics;
+
+// The argument rules of include/icsg3d.h, every structure checked before anything is written.  Then chunked under a
+// device-memory budget through the calling thread's scratch, one upload, at most two launches and one download per chunk;
+// synchronous on the calling thread's stream.
+extern "C" int ics_op_structure_screen(const int32_t* offsets, const int32_t* species, const double* xyz, const double* abc,
+                                       const double* angles, int batch, double tol, double* lattice, double* volume,
+                                       double* frac, double* min_dist, int32_t* min_pair, int32_t* n_close, int32_t* valid,
+                                       int32_t* reason, double* nearest, int32_t* hist) {
   const std::string op = "ics_op_structure_screen: ";
   ICS_CHECK(batch >= 1, op + "batch must be >= 1");
   ICS_CHECK(offsets && abc && angles, op + "null argument");
@@ -244,13 +264,11 @@ int structure_screen_check(const int32_t* offsets, const int32_t* species, const
       ICS_CHECK(std::isfinite(xyz[k]) && std::fabs(xyz[k]) <= kStructMaxCoord,
                 who + " has a non-finite or out-of-range (> 1e150) coordinate");
   }
-  return 0;
-}
-
-int structure_screen_op(hipStream_t st, const int32_t* offsets, const int32_t* species, const double* xyz,
-                        const double* abc, const double* angles, int batch, double tol, double* lattice,
-                        double* volume, double* frac, double* min_dist, int32_t* min_pair, int32_t* n_close,
-                        int32_t* valid, int32_t* reason, double* nearest, int32_t* hist) {
+  ICS_CHECK(lattice && volume && min_dist && min_pair && n_close && valid && reason && hist,
+            "ics_op_structure_screen: null output");
+  ICS_CHECK((frac && nearest) || offsets[batch] == 0, "ics_op_structure_screen: null frac or nearest");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   std::vector<unsigned char> hin, hout;
   for (int s0 = 0; s0 < batch;) {
     // one chunk: structures [s0, s1) under the atom budget (at least one structure)
@@ -331,5 +349,3 @@ int structure_screen_op(hipStream_t st, const int32_t* offsets, const int32_t* s
   }
   return 0;
 }
-
-}  // namespace ics

@@ -18,8 +18,8 @@
 // same bits run to run.  Pair results of a chunk are reduced per query by a second kernel (one wave per query) into a
 // per-query state that is merged by key -- (partner) for duplicates, (rms, partner) for references -- so neither the
 // chunking nor any arrival order shows in the result.
-#include "structure_match.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <climits>
@@ -31,6 +31,10 @@
 namespace ics {
 namespace {
 
+constexpr int kMatchMaxAtoms = 256;   // atoms per structure: one thread per atom of A
+constexpr int kMatchSmall = 64;       // atoms one wave takes
+constexpr int kMatchOps = 48;
+constexpr int kMatchMaxSpecies = 94;
 constexpr long long kMatchChunkPairs = 1 << 20;        // pair results per chunk: 16 B each
 constexpr size_t kMatchTableBudget = (size_t)1 << 31;  // resident structure tables
 constexpr int kCell = 16;                              // doubles per structure: M[9], G[6] (00 01 02 11 12 22), pad
@@ -264,8 +268,11 @@ void cell_norms(const double* M, double* vol, double g[3]) {
   g[0] = norm(bc) / *vol; g[1] = norm(ca) / *vol; g[2] = norm(ab) / *vol;
 }
 
-}  // namespace
-
+// The op list of `ops_mode` (0..2): perm[k][3], sign[k][3] with f'_k = sign_k f[perm_k]; returns the count (1, 24, 48).
+// Order: lexicographic over (permutation, sign pattern) -- permutations (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0), and
+// per permutation the sign patterns (+,+,+) (+,+,-) (+,-,+) (+,-,-) (-,+,+) (-,+,-) (-,-,+) (-,-,-).  Index 0 is the
+// identity.  ops_mode 0 keeps index 0, ops_mode 1 the 24 of determinant +1 in that order, ops_mode 2 all 48; a reported
+// `op` indexes the mode's own list.
 int structure_match_ops(int ops_mode, int perm[][3], int sign[][3]) {
   static const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
   static const int parity[6] = {1, -1, -1, 1, 1, -1};
@@ -281,6 +288,8 @@ int structure_match_ops(int ops_mode, int perm[][3], int sign[][3]) {
   return n;
 }
 
+// The argument rules of ics_op_structure_match for its inputs, every structure checked before anything is written: 0, or
+// -1 with the error set naming the structure.
 int structure_match_check(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
                           const int32_t* eligible, int nq, int nref, double tol, double ltol, int ops_mode) {
   const std::string op = "ics_op_structure_match: ";
@@ -320,10 +329,21 @@ int structure_match_check(const int32_t* offsets, const int32_t* species, const 
   return 0;
 }
 
-int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* species, const double* frac,
-                       const double* lattice, const int32_t* eligible, int nq, int nref, double tol, double ltol,
-                       int ops_mode, int32_t* dup_of, double* dup_rms, int32_t* dup_op, int32_t* ref_of,
-                       double* ref_rms, int32_t* ref_op, int32_t* n_cmp) {
+}  // namespace
+}  // namespace ics
+
+using namespace ics;
+
+// Structures ordered by composition key on the host, pairs enumerated on the device from the bucket ranges, pair results
+// chunked under kMatchChunkPairs (ICSG3D_MATCH_CHUNK_PAIRS shrinks it); synchronous on the calling thread's stream.
+extern "C" int ics_op_structure_match(const int32_t* offsets, const int32_t* species, const double* frac,
+                                      const double* lattice, const int32_t* eligible, int nq, int nref, double tol,
+                                      double ltol, int ops_mode, int32_t* dup_of, double* dup_rms, int32_t* dup_op,
+                                      int32_t* ref_of, double* ref_rms, int32_t* ref_op, int32_t* n_cmp) {
+  ICS_TRY(structure_match_check(offsets, species, frac, lattice, eligible, nq, nref, tol, ltol, ops_mode));
+  ICS_CHECK(dup_of && dup_rms && dup_op && ref_of && ref_rms && ref_op && n_cmp, "ics_op_structure_match: null output");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   const int ns = nq + nref;
   const double kInf = std::numeric_limits<double>::infinity();
   for (int q = 0; q < nq; ++q) {
@@ -493,5 +513,3 @@ int structure_match_op(hipStream_t st, const int32_t* offsets, const int32_t* sp
   }
   return 0;
 }
-
-}  // namespace ics

@@ -21,8 +21,8 @@
 //   multiplicities, sym_G, sym_shift and sym_resid.
 // The candidate table, the maps and the operation lists are chunked over structures under a byte cap; no result depends
 // on the chunking, and no floating-point atomic is used anywhere: the same bits run to run.
-#include "structure_symmetry.h"
 #include "scratch.h"
+#include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <climits>
@@ -32,6 +32,30 @@
 #include <limits>
 
 namespace ics {
+
+constexpr int kSymMaxAtoms = 256;      // atoms per structure: one thread per atom
+constexpr int kSymSmall = 64;          // atoms one wave takes
+constexpr int kSymLatCap = 64;         // admissible lattice operations kept per structure
+constexpr int kSymMaxSpecies = 94;
+constexpr int kSymMaxOpsLimit = 4096;  // largest max_ops accepted
+constexpr int kSymCodes = 19683;       // 3^9 matrices with entries in {-1, 0, 1}
+constexpr int kSymIdentityCode = 16484;
+
+// code = sum_k (W[k/3][k%3] + 1) 3^(8-k)  ->  W, row-major
+__host__ __device__ inline void sym_decode(int code, int w[9]) {
+  for (int k = 8; k >= 0; --k) { w[k] = code % 3 - 1; code /= 3; }
+}
+__host__ __device__ inline int sym_det(const int w[9]) {
+  return w[0] * (w[4] * w[8] - w[5] * w[7]) - w[1] * (w[3] * w[8] - w[5] * w[6]) + w[2] * (w[3] * w[7] - w[4] * w[6]);
+}
+// index into the rotation-type histogram (-6, -4, -3, -2, -1, 1, 2, 3, 4, 6), or -1 for a (det, trace) in no row of the table
+__host__ __device__ inline int sym_type_index(const int w[9]) {
+  const int det = sym_det(w), tr = w[0] + w[4] + w[8];
+  if (det == 1) return tr == 3 ? 5 : (tr >= -1 && tr <= 2 ? 7 + tr : -1);
+  if (det == -1) return tr == -3 ? 4 : (tr >= -2 && tr <= 1 ? 2 + tr : -1);
+  return -1;
+}
+
 namespace {
 
 constexpr size_t kSymChunkBytes = (size_t)256 << 20;   // candidate table + maps + operation lists of one chunk
@@ -513,8 +537,8 @@ void metric(const double* M, double G[9]) {
     for (int j = 0; j < 3; ++j) G[3 * i + j] = M[3 * i] * M[3 * j] + M[3 * i + 1] * M[3 * j + 1] + M[3 * i + 2] * M[3 * j + 2];
 }
 
-}  // namespace
-
+// The argument rules of ics_op_structure_symmetry for its inputs, every structure checked before anything is written: 0,
+// or -1 with the error set naming the structure.
 int structure_symmetry_check(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
                              const int32_t* eligible, int ns, double tol, double ltol, int max_ops) {
   const std::string op = "ics_op_structure_symmetry: ";
@@ -552,12 +576,27 @@ int structure_symmetry_check(const int32_t* offsets, const int32_t* species, con
   return 0;
 }
 
-int structure_symmetry_op(hipStream_t st, const int32_t* offsets, const int32_t* species, const double* frac,
-                          const double* lattice, const int32_t* eligible, int ns, double tol, double ltol, int max_ops,
-                          int32_t* n_lat, int32_t* n_ops, int32_t* n_point, int32_t* n_trans, int32_t* types,
-                          int32_t* reason, int32_t* op_code, int32_t* op_anchor, double* op_t, double* op_rms,
-                          int32_t* orbit, int32_t* mult, double* sym_frac, double* sym_G, double* sym_shift,
-                          double* sym_resid) {
+}  // namespace
+}  // namespace ics
+
+using namespace ics;
+
+// Eligible structures sorted by atom count on the host, one upload, lattice operations for all of them, then per chunk of
+// structures (candidate table, nearest-atom maps and operation lists under kSymChunkBytes; ICSG3D_SYMMETRY_CHUNK_BYTES
+// shrinks it) the operation, scan and group kernels; synchronous on the calling thread's stream.
+extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* species, const double* frac,
+                                         const double* lattice, const int32_t* eligible, int ns, double tol, double ltol,
+                                         int max_ops, int32_t* n_lat, int32_t* n_ops, int32_t* n_point, int32_t* n_trans,
+                                         int32_t* types, int32_t* reason, int32_t* op_code, int32_t* op_anchor, double* op_t,
+                                         double* op_rms, int32_t* orbit, int32_t* mult, double* sym_frac, double* sym_G,
+                                         double* sym_shift, double* sym_resid) {
+  ICS_TRY(structure_symmetry_check(offsets, species, frac, lattice, eligible, ns, tol, ltol, max_ops));
+  ICS_CHECK(n_lat && n_ops && n_point && n_trans && types && reason && op_code && op_anchor && op_t && op_rms && sym_G &&
+                sym_shift && sym_resid,
+            "ics_op_structure_symmetry: null output");
+  ICS_CHECK((orbit && mult && sym_frac) || offsets[ns] == 0, "ics_op_structure_symmetry: null orbit, mult or sym_frac");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   const double kNaN = std::numeric_limits<double>::quiet_NaN();
   // ---- the neutral result everywhere; eligible structures are overwritten below
   for (int s = 0; s < ns; ++s) {
@@ -753,5 +792,3 @@ int structure_symmetry_op(hipStream_t st, const int32_t* offsets, const int32_t*
   }
   return 0;
 }
-
-}  // namespace ics

@@ -500,18 +500,38 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
+// ---------------------------------------------------------------- what the engine's encode -> append path uses
+int tsne_device(const ics_tsne* h) { return h->device; }
+int tsne_dim(const ics_tsne* h) { return h->cfg.dim; }
+
+int tsne_append_device(ics_tsne* h, const float* src, size_t stride_floats, int rows, hipStream_t src_stream) {
+  ICS_TRY(handle_enter(h));
+  ICS_CHECK(src != nullptr, "ics_op_tsne_append_vae: null source");
+  ICS_CHECK(rows >= 1 && rows <= h->cfg.capacity - h->count, "ics_op_tsne_append_vae: rows exceed the handle's capacity");
+  const size_t w = (size_t)h->cfg.dim * 4;
+  ICS_HIP(hipMemcpy2DAsync(h->codes + (size_t)h->count * h->cfg.dim, w, src, stride_floats * 4, w, (size_t)rows,
+                           hipMemcpyDeviceToDevice, src_stream));
+  ICS_HIP(hipStreamSynchronize(src_stream));
+  h->count += rows;
+  return 0;
+}
+
+}  // namespace ics
+
+using namespace ics;
+
+extern "C" {
+
 // ---------------------------------------------------------------- ops
-int tsne_knn_check(const float* x, int n, int dim, int k, const int32_t* idx, const double* dist2) {
+int ics_op_tsne_knn(const float* x, int n, int dim, int k, int32_t* idx, double* dist2) {
   ICS_CHECK(x && idx && dist2, "ics_op_tsne_knn: null argument");
   ICS_CHECK(n >= 2 && n <= kTsneMaxPoints, "ics_op_tsne_knn: n must be 2.." + std::to_string(kTsneMaxPoints));
   ICS_CHECK(dim >= 1 && dim <= kTsneMaxDim, "ics_op_tsne_knn: dim must be 1..4096");
   ICS_CHECK(k >= 1 && k <= n - 1, "ics_op_tsne_knn: k must be 1..n-1");
   ICS_CHECK((long long)n * k <= kTsneMaxEdges, "ics_op_tsne_knn: n * k above the limit of 2^28");
   for (size_t i = 0; i < (size_t)n * dim; ++i) ICS_CHECK(std::isfinite(x[i]), "ics_op_tsne_knn: x is not finite");
-  return 0;
-}
-
-int tsne_knn_op(hipStream_t st, const float* x, int n, int dim, int k, int32_t* idx, double* dist2) {
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   Layout L;
   const auto s_x = L.add<float>((size_t)n * dim);
   const auto s_i = L.add<int>((size_t)n * k);
@@ -528,17 +548,15 @@ int tsne_knn_op(hipStream_t st, const float* x, int n, int dim, int k, int32_t* 
   return 0;
 }
 
-int tsne_affinities_check(const double* dist2, int n, int k, double perplexity, const double* cond_p) {
+int ics_op_tsne_affinities(const double* dist2, int n, int k, double perplexity, double* cond_p) {
   ICS_CHECK(dist2 && cond_p, "ics_op_tsne_affinities: null argument");
   ICS_CHECK(n >= 1 && n <= kTsneMaxPoints, "ics_op_tsne_affinities: n must be 1.." + std::to_string(kTsneMaxPoints));
   ICS_CHECK(k >= 1 && (long long)n * k <= kTsneMaxEdges, "ics_op_tsne_affinities: k must be >= 1 and n * k <= 2^28");
   ICS_CHECK(std::isfinite(perplexity) && perplexity > 0.0, "ics_op_tsne_affinities: perplexity must be positive");
   for (size_t i = 0; i < (size_t)n * k; ++i)
     ICS_CHECK(std::isfinite(dist2[i]) && dist2[i] >= 0.0, "ics_op_tsne_affinities: dist2 must be finite and >= 0");
-  return 0;
-}
-
-int tsne_affinities_op(hipStream_t st, const double* dist2, int n, int k, double perplexity, double* cond_p) {
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   Layout L;
   const auto s_d = L.add<double>((size_t)n * k), s_p = L.add<double>((size_t)n * k);
   double *dd, *dp;
@@ -551,7 +569,7 @@ int tsne_affinities_op(hipStream_t st, const double* dist2, int n, int k, double
 }
 
 // ---------------------------------------------------------------- handle
-int tsne_create(const ics_tsne_config* cfg, ics_tsne** out) {
+int ics_op_tsne_create(const ics_tsne_config* cfg, ics_tsne** out) {
   ICS_CHECK(cfg && out, "ics_op_tsne_create: null argument");
   ICS_CHECK(cfg->n_components == 2, "ics_op_tsne_create: n_components must be 2");
   ICS_CHECK(cfg->dim >= 1 && cfg->dim <= kTsneMaxDim, "ics_op_tsne_create: dim must be 1..4096");
@@ -568,7 +586,7 @@ int tsne_create(const ics_tsne_config* cfg, ics_tsne** out) {
             "ics_op_tsne_create: min_grad_norm / learning_rate must be finite");
   ics_tsne* h = new ics_tsne();
   h->cfg = *cfg;
-  auto fail = [&]() { (void)tsne_destroy(h); return -1; };
+  auto fail = [&]() { (void)ics_op_tsne_destroy(h); return -1; };
   if (hipGetDevice(&h->device) != hipSuccess) { set_error("ics_op_tsne_create: hipGetDevice failed"); return fail(); }
   if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
     h->st = nullptr;
@@ -585,7 +603,7 @@ int tsne_create(const ics_tsne_config* cfg, ics_tsne** out) {
   return 0;
 }
 
-int tsne_destroy(ics_tsne* h) {
+int ics_op_tsne_destroy(ics_tsne* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
@@ -596,10 +614,7 @@ int tsne_destroy(ics_tsne* h) {
   return 0;
 }
 
-int tsne_device(const ics_tsne* h) { return h->device; }
-int tsne_dim(const ics_tsne* h) { return h->cfg.dim; }
-
-int tsne_append_host(ics_tsne* h, const float* codes, int rows) {
+int ics_op_tsne_append(ics_tsne* h, const float* codes, int rows) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(codes != nullptr, "ics_op_tsne_append: null codes");
   ICS_CHECK(rows >= 1 && rows <= h->cfg.capacity - h->count, "ics_op_tsne_append: rows exceed the handle's capacity");
@@ -611,19 +626,7 @@ int tsne_append_host(ics_tsne* h, const float* codes, int rows) {
   return 0;
 }
 
-int tsne_append_device(ics_tsne* h, const float* src, size_t stride_floats, int rows, hipStream_t src_stream) {
-  ICS_TRY(handle_enter(h));
-  ICS_CHECK(src != nullptr, "ics_op_tsne_append_vae: null source");
-  ICS_CHECK(rows >= 1 && rows <= h->cfg.capacity - h->count, "ics_op_tsne_append_vae: rows exceed the handle's capacity");
-  const size_t w = (size_t)h->cfg.dim * 4;
-  ICS_HIP(hipMemcpy2DAsync(h->codes + (size_t)h->count * h->cfg.dim, w, src, stride_floats * 4, w, (size_t)rows,
-                           hipMemcpyDeviceToDevice, src_stream));
-  ICS_HIP(hipStreamSynchronize(src_stream));
-  h->count += rows;
-  return 0;
-}
-
-int tsne_get_codes(ics_tsne* h, float* out, int rows) {
+int ics_op_tsne_get_codes(ics_tsne* h, float* out, int rows) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(out != nullptr, "ics_op_tsne_get_codes: null out");
   ICS_CHECK(rows >= 1 && rows <= h->count, "ics_op_tsne_get_codes: rows exceed the codes appended");
@@ -632,7 +635,7 @@ int tsne_get_codes(ics_tsne* h, float* out, int rows) {
   return 0;
 }
 
-int tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, double seconds[3]) {
+int ics_op_tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, double seconds[3]) {
   ICS_TRY(handle_enter(h));
   const int n = h->count, dim = h->cfg.dim;
   ICS_CHECK(n >= 2, "ics_op_tsne_prepare: at least 2 codes are needed, the handle has " + std::to_string(n));
@@ -711,8 +714,8 @@ int tsne_prepare(ics_tsne* h, const float* init, int init_rows, int init_cols, d
   return 0;
 }
 
-int tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* indices, const double* vals,
-                   const float* init, int init_rows, int init_cols) {
+int ics_op_tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* indices, const double* vals,
+                          const float* init, int init_rows, int init_cols) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(indptr != nullptr, "ics_op_tsne_set_graph: null indptr");
   ICS_CHECK(n >= 2 && n <= h->cfg.capacity, "ics_op_tsne_set_graph: n must be 2..capacity");
@@ -729,7 +732,7 @@ int tsne_set_graph(ics_tsne* h, int n, const int64_t* indptr, const int32_t* ind
   return install(h, n, reinterpret_cast<const long long*>(indptr), indices, vals, init);
 }
 
-int tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals, size_t capacity, size_t* nnz) {
+int ics_op_tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals, size_t capacity, size_t* nnz) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(h->n > 0, "ics_op_tsne_get_graph: no graph yet (ics_op_tsne_prepare / ics_op_tsne_set_graph)");
   ICS_CHECK(nnz != nullptr, "ics_op_tsne_get_graph: null nnz");
@@ -746,7 +749,7 @@ int tsne_get_graph(ics_tsne* h, int64_t* indptr, int32_t* indices, double* vals,
   return 0;
 }
 
-int tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad, double* kl) {
+int ics_op_tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad, double* kl) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(h->n > 0, "ics_op_tsne_gradient: no graph yet (ics_op_tsne_prepare / ics_op_tsne_set_graph)");
   ICS_CHECK(y && grad && kl, "ics_op_tsne_gradient: null argument");
@@ -767,7 +770,7 @@ int tsne_gradient(ics_tsne* h, const float* y, double exaggeration, float* grad,
   return 0;
 }
 
-int tsne_run(ics_tsne* h, int iters, int* done) {
+int ics_op_tsne_run(ics_tsne* h, int iters, int* done) {
   ICS_TRY(handle_enter(h));
   ICS_CHECK(h->n > 0, "ics_op_tsne_run: no graph yet (ics_op_tsne_prepare / ics_op_tsne_set_graph)");
   ICS_CHECK(iters >= 0, "ics_op_tsne_run: iters must be >= 0");
@@ -827,7 +830,7 @@ int tsne_run(ics_tsne* h, int iters, int* done) {
   return 0;
 }
 
-int tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count) {
+int ics_op_tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count) {
   ICS_TRY(handle_enter(h));
   if (embedding) {
     ICS_CHECK(h->n > 0, "ics_op_tsne_read: no embedding yet (ics_op_tsne_prepare / ics_op_tsne_set_graph)");
@@ -841,4 +844,4 @@ int tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int*
   return 0;
 }
 
-}  // namespace ics
+}  // extern "C"

@@ -41,9 +41,4 @@ int voxelise_engine(hipStream_t st, VoxStage& stage, const ics_structures* s, co
                     double eps_frac, double label_frac, float* x, int C, unsigned char* labels, const VoxBlob* blobs,
                     int nblob);
 
-// Host-pointer op: fp64 M / S [njobs][d][d][d], p [njobs][d][d][d][3] (each optional), chunked under a device-memory
-// budget through the calling thread's scratch (scratch.h); synchronous.
-int voxelise_op(hipStream_t st, const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac,
-                double label_frac, double* M, double* S, double* p);
-
 }  // namespace ics

@@ -271,9 +271,17 @@ int voxelise_engine(hipStream_t st, VoxStage& stage, const ics_structures* s, co
   return vox_launch(st, true, stage.dev, job_off, batch, d, eps_frac, out);
 }
 
-int voxelise_op(hipStream_t st, const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac,
-                double label_frac, double* M, double* S, double* p) {
+}  // namespace ics
+
+using namespace ics;
+
+// Host-pointer op: fp64 M / S [njobs][d][d][d], p [njobs][d][d][d][3] (each optional), chunked under a device-memory
+// budget through the calling thread's scratch (scratch.h); synchronous.
+extern "C" int ics_op_voxelise(const ics_structures* s, const int32_t* jobs, int njobs, int d, double eps_frac,
+                               double label_frac, double* M, double* S, double* p) {
   ICS_TRY(voxelise_check(s, jobs, njobs, d, eps_frac, label_frac, 0));
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
   if (!M && !S && !p) return 0;
   const size_t V = (size_t)d * d * d;
   const size_t per_job = V * sizeof(double) * ((M ? 1 : 0) + (S ? 1 : 0) + (p ? 3 : 0));
@@ -302,5 +310,3 @@ int voxelise_op(hipStream_t st, const ics_structures* s, const int32_t* jobs, in
   }
   return 0;
 }
-
-}  // namespace ics

@@ -153,3 +153,14 @@ def test_script_lists_the_reference_flags_with_their_defaults():
     for n, t, dflt in zip(names, types, defaults):
         assert repr(getattr(ns, n[2:])) == dflt, (n, getattr(ns, n[2:]), dflt)
         assert acts[n].type.__name__ == t, n
+
+
+def test_latent_path_refuses_null_codes_before_any_device_call():
+    from icsg3d_amd import _lib as L
+    lib = L.load()
+    za, zb, alpha = np.zeros((1, 4), np.float32), np.ones((1, 4), np.float32), np.linspace(0.0, 1.0, 3)
+    path = np.zeros((1, 3, 4), np.float32)
+    for a, b, p in ((None, zb, path), (za, None, path), (za, zb, None)):
+        rc = lib.ics_op_latent_path(L.fptr(a), L.fptr(b), 1, 4, L.f64ptr(alpha), 3, 0, L.fptr(p))
+        msg = (lib.ics_last_error() or b"").decode()
+        assert rc != 0 and msg.startswith("ics_op_latent_path: null argument (za, zb, path are required) ("), msg

@@ -243,3 +243,12 @@ def test_train_entry_points_take_the_monitor_switch_and_default_to_off(monkeypat
     for script in ("train_unet.py", "train_vae.py"):
         text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), script)).read()
         assert '"--monitor"' in text and "monitor=a.monitor" in text
+
+
+def test_render_slice_refuses_a_null_volume_before_any_device_call():
+    from icsg3d_amd import _lib as L
+    lib = L.load()
+    lut, out = np.zeros((256, 3), np.float32), np.zeros((1, 4, 4, 4), np.float32)
+    rc = lib.ics_op_render_slice(None, 0, 1, 4, 1, 0, 2, 0, L.fptr(lut), None, 1, L.fptr(out))
+    msg = (lib.ics_last_error() or b"").decode()
+    assert rc != 0 and msg.startswith("ics_op_render_slice: null vol ("), msg

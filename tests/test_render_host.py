@@ -138,3 +138,49 @@ def test_view_results_parser_has_the_reference_defaults():
     assert (a.channels, a.synthetic, a.count, a.size, a.elev, a.azim, a.mode, a.out, a.seed) == (
         4, False, 8, 256, 30.0, -60.0, "value", None, 0)
     assert view_results.TITLES[4] % 0.1234 == "M Pred, MSE = 0.123" and view_results.TITLES[5] % 0.5 == "S pred F1 = 0.500"
+
+
+def test_entry_points_refuse_bad_arguments_before_any_device_call():
+    """The argument rules of the three render ops that are stated in their entry points."""
+    import ctypes
+    from icsg3d_amd import _lib as L
+    lib = L.load()
+    d, W, H = 4, 8, 8
+    cam, out = np.array([30.0, -60.0]), np.zeros((1, H, W, 4), np.float32)
+    lut, pal = np.zeros((256, 3), np.float32), np.ones((3, 3), np.float32)
+    lab = np.zeros((1, d, d, d), np.int32)
+    f = ctypes.c_float
+
+    def msg_of(rc):
+        assert rc != 0
+        return (lib.ics_last_error() or b"").decode()
+
+    m = msg_of(lib.ics_op_render_density(None, 1, d, 1, 0, L.fptr(lut), 0, f(0.5), f(0.0), L.f64ptr(cam), W, H, L.fptr(out)))
+    assert m.startswith("ics_op_render_density: null vol ("), m
+
+    def labels(labels_=lab, pal_=pal, npal=3, alpha=0.5):
+        return msg_of(lib.ics_op_render_labels(L.i32ptr(labels_), 1, d, L.fptr(pal_), npal, f(alpha), L.f64ptr(cam), W, H,
+                                               L.fptr(out)))
+    for kw, text in ((dict(labels_=None), "null argument (labels, palette)"), (dict(pal_=None), "null argument (labels, palette)"),
+                     (dict(npal=0), "npal must be >= 1"), (dict(alpha=1.5), "alpha must be in [0, 1]"),
+                     (dict(alpha=-0.1), "alpha must be in [0, 1]")):
+        m = labels(**kw)
+        assert m.startswith("ics_op_render_labels: " + text + " ("), (kw, m)
+
+    off, sp, xyz = np.array([0, 1, 2], np.int32), np.array([8, 8], np.int32), np.ones((2, 3))
+    out2 = np.zeros((2, H, W, 4), np.float32)
+
+    def atoms(off_=off, sp_=sp, xyz_=xyz, pal_=pal, npal=3, radius=1.0):
+        return msg_of(lib.ics_op_render_atoms(L.i32ptr(off_), L.i32ptr(sp_), L.f64ptr(xyz_), 2, d, ctypes.c_double(radius),
+                                              L.fptr(pal_), npal, L.f64ptr(cam), W, H, L.fptr(out2)))
+    bad_xyz = xyz.copy()
+    bad_xyz[1, 2] = np.inf
+    for kw, text in ((dict(off_=None), "null argument (offsets, palette)"), (dict(pal_=None), "null argument (offsets, palette)"),
+                     (dict(npal=0), "npal must be >= 1"), (dict(radius=0.0), "radius must be finite and > 0"),
+                     (dict(radius=float("nan")), "radius must be finite and > 0"),
+                     (dict(off_=np.array([1, 1, 2], np.int32)), "offsets[0] must be 0"),
+                     (dict(off_=np.array([0, 2, 1], np.int32)), "offsets decrease at sample 1"),
+                     (dict(sp_=None), "null species or xyz"), (dict(xyz_=None), "null species or xyz"),
+                     (dict(xyz_=bad_xyz), "non-finite coordinate")):
+        m = atoms(**kw)
+        assert m.startswith("ics_op_render_atoms: " + text + " ("), (kw, m)

@@ -1,6 +1,7 @@
 """generate.py's structure stage without a GPU: the fp64 restatement tests/structure_ref.py (what the GPU tests hold
 ics_op_structure_screen to) against hand-derived cases, and the host side of icsg3d_amd.structures: formulas, the CIF
 writer / reader, the duplicate numbering."""
+import ctypes
 import math
 
 import numpy as np
@@ -123,3 +124,27 @@ def test_cif_round_trip(tmp_path):
     np.testing.assert_allclose(S.read_cif(path)["volume"], np.linalg.det(M), atol=1e-7, rtol=0)
     with pytest.raises(ValueError):
         S.write_cif(path, abc, angles, [0, 8], frac[:2])
+
+
+def test_screen_entry_point_refuses_null_outputs():
+    """The output-pointer rules of ics_op_structure_screen, refused before any device call."""
+    from icsg3d_amd import _lib as L
+    lib = L.load()
+    off, sp = np.array([0, 2], np.int32), np.array([8, 8], np.int32)
+    xyz, abc, ang = np.array([[0.0, 0, 0], [2.0, 2, 2]]), np.array([[4.0, 4, 4]]), np.array([[90.0, 90, 90]])
+
+    def call(null):
+        outs = {"lattice": np.zeros(9), "volume": np.zeros(1), "frac": np.zeros(6), "min_dist": np.zeros(1),
+                "min_pair": np.zeros(2, np.int32), "n_close": np.zeros(1, np.int32), "valid": np.zeros(1, np.int32),
+                "reason": np.zeros(1, np.int32), "nearest": np.zeros(2), "hist": np.zeros(95, np.int32)}
+        ptr = [None if k == null else (L.f64ptr(a) if a.dtype == np.float64 else L.i32ptr(a)) for k, a in outs.items()]
+        rc = lib.ics_op_structure_screen(L.i32ptr(off), L.i32ptr(sp), L.f64ptr(xyz), L.f64ptr(abc), L.f64ptr(ang), 1,
+                                         ctypes.c_double(0.5), *ptr)
+        return rc, (lib.ics_last_error() or b"").decode()
+
+    for null in ("lattice", "volume", "min_dist", "min_pair", "n_close", "valid", "reason", "hist"):
+        rc, msg = call(null)
+        assert rc != 0 and msg.startswith("ics_op_structure_screen: null output ("), (null, msg)
+    for null in ("frac", "nearest"):
+        rc, msg = call(null)
+        assert rc != 0 and msg.startswith("ics_op_structure_screen: null frac or nearest ("), (null, msg)
