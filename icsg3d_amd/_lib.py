@@ -50,6 +50,22 @@ class TsneConfig(C.Structure):
 
 
 _F = C.POINTER(C.c_float)
+
+
+class ConvLayerSrc(C.Structure):
+    _fields_ = [("x", _F), ("scale", _F), ("shift", _F), ("C", C.c_int), ("up", C.c_int), ("act", C.c_int), ("dx", _F)]
+
+
+class ConvLayerArgs(C.Structure):
+    """ics_conv_layer (include/icsg3d.h)."""
+    _fields_ = [("B", C.c_int), ("max_batch", C.c_int), ("S", C.c_int), ("taps", C.c_int), ("Cout", C.c_int),
+                ("pre_act", C.c_int), ("has_bn", C.c_int), ("post_act", C.c_int), ("pad_input", C.c_int), ("nsrc", C.c_int),
+                ("src", ConvLayerSrc * 2), ("w", _F), ("bias", _F), ("gamma", _F), ("beta", _F), ("dout", _F), ("y", _F),
+                ("mean", _F), ("rstd", _F), ("scale", _F), ("shift", _F), ("moving_mean", _F), ("moving_var", _F),
+                ("rows_per_block", C.c_int), ("blocks", C.c_int), ("dw", _F), ("dbias", _F), ("dgamma", _F), ("dbeta", _F),
+                ("kernels", C.c_void_p), ("kernels_cap", C.c_int)]
+
+
 _U8 = C.POINTER(C.c_uint8)
 _I32 = C.POINTER(C.c_int32)
 _I64 = C.POINTER(C.c_int64)
@@ -168,6 +184,7 @@ SIGNATURES = {
     "ics_net_comm_info": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ics_op_unet_head": (C.c_int, [_F, _F, _F, _F, _F, _U8, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _F, _F,
                                   C.POINTER(C.c_double)]),
+    "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv3d_bench": (C.c_int, [C.c_int] * 8 + [_F]),
     "ics_op_conv3d_backward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F]),

@@ -165,6 +165,8 @@ struct ConvLayer {
   float* c1c2 = nullptr;
   float* db_partial = nullptr;          // [blocks][Cout] bias-gradient partials of the BatchNorm-backward apply pass (own buffer:
                                         // finalized with every other layer's in one launch, Net::colsum)
+  int stat_rpb = 0, stat_nblk = 0;      // rows per block (0: a parity launch's low-res blocks) and block count the last
+                                        // training forward handed to bn_finalize (reported by ics_op_conv_layer)
   int db_blocks = 0;                    // rows of db_partial the last backward pass wrote
   size_t db_rows = 0;                   // rows db_partial holds
   // round 4 (conv_bnfuse_kernel): this layer's BatchNorm-backward apply inside its CONSUMER's backward-data launch
@@ -852,6 +854,7 @@ static int conv_forward(Net& n, ConvLayer& L, int B, bool training, bool update_
     if (training && n.sync() == nullptr) bn.xs = L.xs;
     if (training) {
       const int nblk = par_blocks ? par_blocks : (int)((M + rpb - 1) / rpb);
+      L.stat_rpb = par_blocks ? 0 : rpb; L.stat_nblk = nblk;
       ICS_TRY(launch_bn_finalize(n.st, n.ws_stat, nblk, L.Npad, bn, L.Cout, update_moving ? 1 : 0, n.bn_unbias, n.sync()));
     } else {
       ICS_TRY(launch_bn_eval_prepare(n.st, bn, L.Cout));
@@ -3220,6 +3223,155 @@ int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int
   }
   ICS_HIP(hipMemcpyAsync(y, dyv, M * Cout * 4, hipMemcpyDeviceToHost, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
+  return 0;
+}
+
+// One layer through the engines' own construction and dispatch (include/icsg3d.h): a Net with a single ConvLayer, built,
+// packed and stepped by the functions unet_build / vae_build and the train steps use -- nothing here chooses a kernel.
+// The per-launch kernel ids come from the handle's profiler rows (labels ending in '|', see Profiler::begin).
+int ics_op_conv_layer(ics_conv_layer* a) {
+  const std::string op = "ics_op_conv_layer: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
+  ICS_CHECK(a->S >= 1 && (a->S & (a->S - 1)) == 0 && (a->taps == 27 || a->taps == 1) && a->Cout >= 1, op + "bad geometry");
+  ICS_CHECK(a->nsrc == 1 || a->nsrc == 2, op + "nsrc must be 1 or 2");
+  auto act_ok = [](int v) { return v == ACT_NONE || v == ACT_RELU || v == ACT_LRELU; };
+  ICS_CHECK(act_ok(a->pre_act) && act_ok(a->post_act), op + "bad activation");
+  ICS_CHECK(a->w && a->y, op + "w and y are required");
+  ICS_CHECK(!a->has_bn || (a->gamma && a->beta), op + "gamma and beta are required with has_bn");
+  ICS_CHECK(a->has_bn || a->post_act == ACT_NONE, op + "post_act needs has_bn");
+  int Cin = 0;
+  bool want_dx = false;
+  for (int i = 0; i < a->nsrc; ++i) {
+    const ics_conv_layer_src& s = a->src[i];
+    ICS_CHECK(s.x && s.C >= 1 && (s.up == 0 || s.up == 1) && act_ok(s.act), op + "bad source");
+    ICS_CHECK((s.scale == nullptr) == (s.shift == nullptr), op + "a source has scale and shift, or neither");
+    ICS_CHECK(!s.up || a->S >= 2, op + "an upsampled source needs S >= 2");
+    ICS_CHECK(!s.dx || a->dout, op + "source gradients need dout");
+    Cin += s.C;
+    want_dx = want_dx || s.dx != nullptr;
+  }
+  ICS_CHECK(a->dout || !(a->dw || a->dbias || a->dgamma || a->dbeta), op + "parameter gradients need dout");
+  Net n;
+  ICS_TRY(op_prepare(n));
+  n.maxB = a->max_batch; n.d = a->S; n.C = Cin;
+  const bool bwd = a->dout != nullptr;
+  const int B = a->B, S = a->S, Cout = a->Cout;
+  ConvLayer& L = *add_conv(n, "L", Cin, Cout, a->taps, S, a->pre_act, a->has_bn ? 1 : 0, a->post_act, false, true,
+                           a->pad_input != 0);
+  ICS_TRY(alloc_params(n));
+  // buffers first, sources after: a source's affine sits in the handle like a producer layer's
+  ICS_TRY(alloc_layer(n, L, true, false));
+  const size_t M = n.rows(L, B), Mmax = n.rows(L, n.maxB);
+  ConvSrc srcs[2];
+  size_t src_rows[2] = {0, 0};
+  for (int i = 0; i < a->nsrc; ++i) {
+    const ics_conv_layer_src& s = a->src[i];
+    float *dx = nullptr, *dsc = nullptr, *dsh = nullptr;
+    src_rows[i] = s.up ? M / 8 : M;
+    ICS_TRY(n.alloc(&dx, (s.up ? Mmax / 8 : Mmax) * s.C));
+    ICS_HIP(hipMemcpyAsync(dx, s.x, src_rows[i] * s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
+    if (s.scale) {
+      ICS_TRY(n.alloc(&dsc, (size_t)s.C)); ICS_TRY(n.alloc(&dsh, (size_t)s.C));
+      ICS_HIP(hipMemcpyAsync(dsc, s.scale, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
+      ICS_HIP(hipMemcpyAsync(dsh, s.shift, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
+    }
+    srcs[i] = ConvSrc{dx, dsc, dsh, s.C, s.up, s.act, 0};
+    L.src[i] = srcs[i];
+  }
+  L.nsrc = a->nsrc;
+  use_padded_input(L);
+  if (srcs[a->nsrc - 1].up) ICS_TRY(enable_split_up(n, L));
+  ICS_TRY(enable_wino(n, L, true));
+  ICS_TRY(enable_winog(n, L, true));
+  ICS_TRY(alloc_workspaces(n, true));
+  ICS_TRY(init_bn_defaults(n));
+  float* d_dout = nullptr;
+  if (bwd) {
+    ICS_TRY(n.alloc(&d_dout, Mmax * Cout));
+    ICS_HIP(hipMemcpyAsync(d_dout, a->dout, M * Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+  }
+  const size_t wn = (size_t)a->taps * Cin * Cout;
+  ICS_HIP(hipMemcpyAsync(n.tp(L.t_w), a->w, wn * sizeof(float), hipMemcpyHostToDevice, n.st));
+  if (a->bias) ICS_HIP(hipMemcpyAsync(n.tp(L.t_b), a->bias, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+  if (a->has_bn) {
+    ICS_HIP(hipMemcpyAsync(n.tp(L.t_gamma), a->gamma, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_HIP(hipMemcpyAsync(n.tp(L.t_beta), a->beta, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+  }
+  ICS_TRY(pack_layer(n, L, true));
+  n.prof.on = true;              // every launch site of the step becomes a row "site|kernel id"
+  n.splitk = true;               // as inside a train step
+  n.want_wgrad_inputs = bwd;
+  ICS_TRY(conv_forward(n, L, B, true, true, n.tp(L.t_b)));
+  if (bwd) {
+    ICS_TRY(conv_backward(n, L, B, gs_direct(d_dout, Cout, 0), gs_none(), nullptr, want_dx, true));
+    ICS_TRY(colsum_flush(n));
+    ICS_TRY(side_join(n));
+  }
+  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
+    return 0;
+  };
+  ICS_TRY(down(a->y, L.s, M * Cout));
+  a->rows_per_block = 0; a->blocks = 0;
+  if (a->has_bn) {
+    ICS_TRY(down(a->mean, L.mean, Cout)); ICS_TRY(down(a->rstd, L.rstd, Cout));
+    ICS_TRY(down(a->scale, L.scale, Cout)); ICS_TRY(down(a->shift, L.shift, Cout));
+    ICS_TRY(down(a->moving_mean, L.mm, Cout)); ICS_TRY(down(a->moving_var, L.mv, Cout));
+    a->rows_per_block = L.stat_rpb; a->blocks = L.stat_nblk;
+  }
+  std::vector<float> hA;         // the full-width input gradient of a layer that did not split its sources
+  if (bwd) {
+    ICS_TRY(down(a->dw, n.tg(L.t_w), wn)); ICS_TRY(down(a->dbias, n.tg(L.t_b), Cout));
+    if (a->has_bn) { ICS_TRY(down(a->dgamma, n.tg(L.t_gamma), Cout)); ICS_TRY(down(a->dbeta, n.tg(L.t_beta), Cout)); }
+    if (want_dx && L.split_up) {
+      if (L.Cs) ICS_TRY(down(a->src[0].dx, L.dA_skip, M * L.Cs));
+      ICS_TRY(down(a->src[a->nsrc - 1].dx, L.dxl, M / 8 * L.Cu));
+    } else if (want_dx) {
+      hA.resize(M * L.CinG);
+      ICS_TRY(down(hA.data(), L.dA, hA.size()));
+    }
+  }
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  if (!hA.empty()) {
+    // columns [c0, c0 + C) of dA belong to source i; an upsampled source receives the sum over its 8 children (what a
+    // producer layer's backward pass does with GS_UP)
+    int c0 = 0;
+    const int ld = L.CinG, h = S / 2;
+    for (int i = 0; i < a->nsrc; c0 += a->src[i].C, ++i) {
+      const ics_conv_layer_src& s = a->src[i];
+      if (!s.dx) continue;
+      if (!s.up) {
+        for (size_t m = 0; m < M; ++m)
+          for (int c = 0; c < s.C; ++c) s.dx[m * s.C + c] = hA[m * ld + c0 + c];
+        continue;
+      }
+      for (int b = 0; b < B; ++b)
+        for (int z = 0; z < h; ++z)
+          for (int y = 0; y < h; ++y)
+            for (int x = 0; x < h; ++x) {
+              float* o = s.dx + ((((size_t)b * h + z) * h + y) * h + x) * s.C;
+              for (int c = 0; c < s.C; ++c) o[c] = 0.f;
+              for (int k = 0; k < 8; ++k) {
+                const size_t m = (((size_t)b * S + 2 * z + (k >> 2)) * S + 2 * y + ((k >> 1) & 1)) * S + 2 * x + (k & 1);
+                for (int c = 0; c < s.C; ++c) o[c] += hA[m * ld + c0 + c];
+              }
+            }
+    }
+  }
+  if (a->kernels && a->kernels_cap > 0) {
+    std::string txt;
+    for (const auto& r : n.prof.rows)
+      if (r.label.find('|') != std::string::npos) txt += r.label + "\n";
+    std::strncpy(a->kernels, txt.c_str(), (size_t)a->kernels_cap - 1);
+    a->kernels[a->kernels_cap - 1] = 0;
+  }
+  if (n.canary_on) {
+    std::string msg;
+    const int bad = n.canaries_dirty(&msg);
+    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
+  }
   return 0;
 }
 

@@ -986,6 +986,98 @@ static int run(int d, int C, int B, int with_comm) {
   return 0;
 }
 
+/* ics_op_conv_layer: one layer through the engines' construction and dispatch at every geometry class its planners
+ * distinguish (Winograd 64 / 32 / S = 4, implicit GEMM, 1x1x1, thin-N, padded thin input, [skip | up], up only), forward
+ * only and with the backward pass, on a handle larger than the batch, with buffers of the exact size; then the same
+ * upsampled layers with the up-split switched off (the host-side 8-children sum) and every refusal. */
+static int conv_layer_one(int B, int maxB, int S, int taps, int Cout, int form, int pad, int nsrc, const int* sc, const int* sup,
+                          int aff, int bwd) {
+  ics_conv_layer a;
+  char text[4096];
+  size_t M = (size_t)B * S * S * S;
+  int Cin = 0;
+  memset(&a, 0, sizeof a);
+  a.B = B; a.max_batch = maxB; a.S = S; a.taps = taps; a.Cout = Cout; a.pad_input = pad; a.nsrc = nsrc;
+  a.has_bn = form != 2; a.pre_act = form == 0 ? 1 : 0; a.post_act = form == 1 ? 2 : 0;
+  for (int i = 0; i < nsrc; ++i) {
+    size_t rows = sup[i] ? M / 8 : M;
+    a.src[i].C = sc[i]; a.src[i].up = sup[i]; a.src[i].act = (aff && form == 1) ? 2 : 0;
+    a.src[i].x = calloc(rows * sc[i], 4);
+    if (aff) { a.src[i].scale = calloc(sc[i], 4); a.src[i].shift = calloc(sc[i], 4); }
+    if (bwd) a.src[i].dx = malloc(rows * sc[i] * 4);
+    Cin += sc[i];
+  }
+  a.w = calloc((size_t)taps * Cin * Cout, 4); a.bias = calloc(Cout, 4); a.gamma = calloc(Cout, 4); a.beta = calloc(Cout, 4);
+  a.y = malloc(M * Cout * 4);
+  a.mean = malloc(Cout * 4); a.rstd = malloc(Cout * 4); a.scale = malloc(Cout * 4); a.shift = malloc(Cout * 4);
+  a.moving_mean = malloc(Cout * 4); a.moving_var = malloc(Cout * 4);
+  if (bwd) {
+    a.dout = calloc(M * Cout, 4);
+    a.dw = malloc((size_t)taps * Cin * Cout * 4); a.dbias = malloc(Cout * 4); a.dgamma = malloc(Cout * 4); a.dbeta = malloc(Cout * 4);
+  }
+  a.kernels = text; a.kernels_cap = (int)sizeof text;
+  OK(ics_op_conv_layer(&a));
+  if (!strstr(text, "conv_fwd:L")) { fprintf(stderr, "conv layer: no forward launch site reported\n"); return 1; }
+  a.kernels_cap = 9;                                   /* truncated, still terminated */
+  OK(ics_op_conv_layer(&a));
+  if (strlen(text) > 8) { fprintf(stderr, "conv layer: kernel text not truncated\n"); return 1; }
+  for (int i = 0; i < nsrc; ++i) { free((void*)a.src[i].x); free((void*)a.src[i].scale); free((void*)a.src[i].shift); free(a.src[i].dx); }
+  free((void*)a.w); free((void*)a.bias); free((void*)a.gamma); free((void*)a.beta); free((void*)a.dout); free(a.y);
+  free(a.mean); free(a.rstd); free(a.scale); free(a.shift); free(a.moving_mean); free(a.moving_var);
+  free(a.dw); free(a.dbias); free(a.dgamma); free(a.dbeta);
+  return 0;
+}
+static int conv_layer_walk(void) {
+  const int one[2] = {0, 0}, up1[2] = {1, 0}, su[2] = {0, 1};
+  int c[2];
+  for (int form = 0; form < 3; ++form)
+    for (int bwd = 0; bwd < 2; ++bwd) {
+      const int aff = form != 2;
+      c[0] = 64; if (conv_layer_one(3, 5, 8, 27, 64, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 32; if (conv_layer_one(2, 2, 8, 27, 96, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 64; if (conv_layer_one(4, 4, 4, 27, 64, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 128; if (conv_layer_one(3, 5, 4, 27, 64, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 40; if (conv_layer_one(2, 3, 8, 27, 24, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 96; if (conv_layer_one(3, 5, 4, 1, 48, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 512; if (conv_layer_one(1, 2, 2, 27, 64, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 16; if (conv_layer_one(2, 7, 8, 27, 1, form, 0, 1, c, one, aff, bwd)) return 1;
+      c[0] = 1; if (conv_layer_one(2, 3, 8, 27, 16, form, 1, 1, c, one, 0, bwd)) return 1;
+      c[0] = 4; if (conv_layer_one(2, 2, 8, 27, 32, form, 1, 1, c, one, 0, bwd)) return 1;
+      c[0] = 11; if (conv_layer_one(2, 2, 8, 27, 16, form, 1, 1, c, one, aff, bwd)) return 1;
+      c[0] = 32; c[1] = 64; if (conv_layer_one(2, 5, 8, 27, 64, form, 0, 2, c, su, aff, bwd)) return 1;
+      c[0] = 32; if (conv_layer_one(3, 7, 8, 27, 16, form, 0, 1, c, up1, aff, bwd)) return 1;
+    }
+  setenv("ICSG3D_NO_UPSPLIT", "1", 1);
+  c[0] = 32; c[1] = 64; if (conv_layer_one(2, 3, 4, 27, 64, 0, 0, 2, c, su, 1, 1)) return 1;
+  c[0] = 32; if (conv_layer_one(3, 3, 4, 27, 16, 1, 0, 1, c, up1, 1, 1)) return 1;
+  unsetenv("ICSG3D_NO_UPSPLIT");
+  {
+    ics_conv_layer a;
+    float buf[8 * 4] = {0};
+    int bad = 0;
+    memset(&a, 0, sizeof a);
+    a.B = 1; a.max_batch = 1; a.S = 2; a.taps = 1; a.Cout = 4; a.nsrc = 1;
+    a.src[0].x = buf; a.src[0].C = 4; a.w = buf; a.y = buf;
+    OK(ics_op_conv_layer(&a));
+    bad += ics_op_conv_layer(NULL) == 0;
+    a.max_batch = 0; bad += ics_op_conv_layer(&a) == 0; a.max_batch = 1;
+    a.S = 3; bad += ics_op_conv_layer(&a) == 0; a.S = 2;
+    a.taps = 9; bad += ics_op_conv_layer(&a) == 0; a.taps = 1;
+    a.nsrc = 3; bad += ics_op_conv_layer(&a) == 0; a.nsrc = 1;
+    a.pre_act = 3; bad += ics_op_conv_layer(&a) == 0; a.pre_act = 0;
+    a.has_bn = 1; bad += ics_op_conv_layer(&a) == 0; a.has_bn = 0;          /* no gamma / beta */
+    a.post_act = 1; bad += ics_op_conv_layer(&a) == 0; a.post_act = 0;      /* post_act without BatchNorm */
+    a.src[0].scale = buf; bad += ics_op_conv_layer(&a) == 0; a.src[0].scale = NULL;
+    a.src[0].dx = buf; bad += ics_op_conv_layer(&a) == 0; a.src[0].dx = NULL;   /* gradients without dout */
+    a.dw = buf; bad += ics_op_conv_layer(&a) == 0; a.dw = NULL;
+    a.S = 1; a.src[0].up = 1; bad += ics_op_conv_layer(&a) == 0; a.S = 2; a.src[0].up = 0;
+    a.w = NULL; bad += ics_op_conv_layer(&a) == 0; a.w = buf;
+    if (bad) { fprintf(stderr, "conv layer: %d invalid argument sets accepted\n", bad); return 1; }
+    OK(ics_op_conv_layer(&a));                                              /* still usable */
+  }
+  return 0;
+}
+
 int main(void) {
   char name[256]; int cus; size_t hbm; int ndev = 0;
   OK(ics_device_count(&ndev));
@@ -1017,6 +1109,7 @@ int main(void) {
     OK(ics_op_conv3d_backward(x, w, y, B, S, Cin, Cout, 27, dx, dw));
     free(x); free(y); free(w); free(dx); free(dw);
   }
+  if (conv_layer_walk()) return 1;
   {   /* the op-level head: both launch sequences */
     const size_t M = 64;
     float *x = calloc(M * 128, 4), *ws = calloc(128 * 95, 4), *bs = calloc(95, 4), *wg = calloc(128, 4), bg[1] = {0.f};

@@ -569,6 +569,79 @@ def conv3d_forward(x, w, bias=None, pre_act=0):
     return y
 
 
+def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=0, has_bn=True, post_act=0,
+               pad_input=False, max_batch=None, want_dx=True):
+    """Single-op entry (ics_op_conv_layer): one layer through the engines' own construction and dispatch -- affine /
+    activated / upsampled sources, the statistics epilogue, workspaces sized for max_batch.
+
+    sources: one or two dicts {"x": (B,s,s,s,C) with s = S, or S/2 with "up": 1; "scale", "shift": (C,) or absent;
+    "act": 0/1/2}.  w (k,k,k,Cin,Cout) with Cin the sum of the sources' C.  dout (B,S,S,S,Cout): gradient w.r.t. the
+    layer's output (post_act(BN(y)), or y without BatchNorm); None runs the forward pass only.
+
+    Returns a dict: y; with has_bn mean, rstd, scale, shift, moving_mean, moving_var, rows_per_block, blocks; with dout
+    dw, dbias, (dgamma, dbeta), dx (a list, one array per source, shaped as its x); and kernels: {"fwd": [...],
+    "dgrad": [...], "wgrad": [...]} -- "<launch site>|<kernel template instantiation>" of every conv launch."""
+    lib = L.load()
+    a = L.ConvLayerArgs()
+    keep = []                                     # arrays the struct points into
+
+    def f(v):
+        if v is None:
+            return None
+        v = _f32(v)
+        keep.append(v)
+        return L.fptr(v)
+
+    def out(shape):
+        v = np.empty(shape, np.float32)
+        keep.append(v)
+        return v
+
+    w = _f32(w)
+    taps, Cout = w.shape[0] ** 3, w.shape[4]
+    srcs = [dict(s) for s in sources]
+    x0 = _f32(srcs[0]["x"])
+    B = x0.shape[0]
+    S = x0.shape[1] * (2 if srcs[0].get("up") else 1)
+    if sum(_f32(s["x"]).shape[4] for s in srcs) != w.shape[3]:
+        raise ValueError("the sources' channels do not add up to the kernel's Cin")
+    a.B, a.max_batch, a.S, a.taps, a.Cout = B, int(max_batch or B), S, taps, Cout
+    a.pre_act, a.has_bn, a.post_act, a.pad_input, a.nsrc = int(pre_act), int(bool(has_bn)), int(post_act), int(bool(pad_input)), len(srcs)
+    dxs = []
+    for i, s in enumerate(srcs):
+        x = _f32(s["x"])
+        up = 1 if s.get("up") else 0
+        if x.shape[:4] != (B,) + (S // 2 if up else S,) * 3:
+            raise ValueError("source %d has shape %s" % (i, x.shape))
+        a.src[i].x, a.src[i].scale, a.src[i].shift = f(x), f(s.get("scale")), f(s.get("shift"))
+        a.src[i].C, a.src[i].up, a.src[i].act = x.shape[4], up, int(s.get("act", 0))
+        if dout is not None and want_dx:
+            dxs.append(out(x.shape))
+            a.src[i].dx = L.fptr(dxs[-1])
+    a.w, a.bias, a.gamma, a.beta, a.dout = f(w), f(bias), f(gamma), f(beta), f(dout)
+    r = {"y": out((B, S, S, S, Cout))}
+    a.y = L.fptr(r["y"])
+    if has_bn:
+        for k in ("mean", "rstd", "scale", "shift", "moving_mean", "moving_var"):
+            r[k] = out((Cout,))
+            setattr(a, k, L.fptr(r[k]))
+    if dout is not None:
+        r["dw"], r["dbias"] = out(w.shape), out((Cout,))
+        a.dw, a.dbias = L.fptr(r["dw"]), L.fptr(r["dbias"])
+        if has_bn:
+            r["dgamma"], r["dbeta"] = out((Cout,)), out((Cout,))
+            a.dgamma, a.dbeta = L.fptr(r["dgamma"]), L.fptr(r["dbeta"])
+        r["dx"] = dxs
+    text = C.create_string_buffer(16384)
+    a.kernels, a.kernels_cap = C.cast(text, C.c_void_p), len(text)
+    L.check(lib.ics_op_conv_layer(C.byref(a)))
+    if has_bn:
+        r["rows_per_block"], r["blocks"] = a.rows_per_block, a.blocks
+    lines = text.value.decode().splitlines()
+    r["kernels"] = {k: [ln for ln in lines if ln.startswith("conv_%s:" % k)] for k in ("fwd", "dgrad", "wgrad")}
+    return r
+
+
 def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False):
     """Single-op entry (kernel parity tests): the heads + losses + metrics on a given trunk output x (M,128).
     Returns (out (M, ncls+1) | None, metrics (5,), sums dict) -- see ics_op_unet_head."""

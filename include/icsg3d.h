@@ -658,6 +658,51 @@ int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int
 int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int B, int S, int Cin,
                            int Cout, int taps, float* dx, float* dw);
 
+/* One convolution layer the way the ENGINES run it (kernel parity tests, tests/test_gpu_conv_layer.py): a temporary handle
+ * with a single layer is built from the engines' own construction, packing and dispatch code, so a launch here takes the
+ * template instantiation a training step takes -- BatchNorm-affine / activated / upsampled sources, the per-block
+ * (count, mean, M2) statistics epilogue, accumulate on top of the up-channel launch, workspaces sized for max_batch.
+ * The two entry points above launch the kernels in their plain form (one plain source, no statistics).
+ *
+ *   virtual input = channel concat over the sources of  act(x * scale + shift), nearest-upsampled by 2 where up = 1,
+ *                   zero "same" padding AFTER that
+ *   y     = pre_act(conv(virtual input, w) + bias)                       (stored, returned in y)
+ *   o     = post_act(y * scale + shift), scale = gamma * rstd, shift = beta - mean * scale   (has_bn; batch statistics)
+ *   dout  = gradient w.r.t. o (has_bn = 0: w.r.t. y), optional: without it only the forward pass runs
+ *
+ * Activations: 0 none, 1 ReLU, 2 LeakyReLU(0.3).  The broadcast / condition-fold source is not served.
+ * The ICSG3D_NO_* switches are read when the call builds its handle, as for every handle.  With ICSG3D_DEBUG_CANARY=1 the
+ * call checks the guard bytes behind every buffer of the handle and fails, naming the buffers, if any was written to. */
+typedef struct ics_conv_layer_src {
+  const float* x;     /* [B][S^3][C], or [B][(S/2)^3][C] with up = 1                                     */
+  const float* scale; /* [C] per-channel affine, or NULL (then shift is NULL too)                        */
+  const float* shift;
+  int C, up, act;
+  float* dx;          /* out, optional (needs dout): gradient w.r.t. act(x * scale + shift), shaped as x */
+} ics_conv_layer_src;
+typedef struct ics_conv_layer {
+  int B, max_batch;   /* the step runs B <= max_batch samples; the handle and every workspace are sized for max_batch */
+  int S, taps, Cout;  /* S a power of two (>= 2 with an upsampled source); taps 27 (3x3x3 same) or 1                   */
+  int pre_act, has_bn, post_act;
+  int pad_input;      /* 1: thin inputs are zero-padded to the vector loaders' width (U-Net c1, VAE e0)                */
+  int nsrc;           /* 1 or 2                                                                                        */
+  ics_conv_layer_src src[2];
+  const float *w, *bias, *gamma, *beta; /* w [taps][Cin][Cout], Cin = sum of src[].C; bias optional (zeros); gamma / beta
+                                           [Cout], required with has_bn                                               */
+  const float* dout;  /* [B][S^3][Cout] or NULL                                                                        */
+  float* y;           /* out [B][S^3][Cout]                                                                            */
+  float *mean, *rstd, *scale, *shift, *moving_mean, *moving_var; /* out [Cout], each optional (has_bn): the batch
+                                           statistics, the affine, and the moving statistics after one update from (0, 1) */
+  int rows_per_block; /* out: rows per statistics block (0: blocks of a parity launch over the low-res grid) ...      */
+  int blocks;         /* ... and the number of blocks handed to the finalize kernel (has_bn)                           */
+  float *dw, *dbias, *dgamma, *dbeta; /* out, each optional (need dout): [taps][Cin][Cout], [Cout], [Cout], [Cout]    */
+  char* kernels;      /* out, optional: one line per launch site, "conv_fwd:L|<kernel>", "conv_fwd:L.up|<kernel>",
+                         "conv_dgrad:L|<kernel>", "conv_wgrad:L.skip|<kernel>", ... -- <kernel> is the exact template
+                         instantiation (as rocprofv3 names it) the site launched                                       */
+  int kernels_cap;    /* bytes behind `kernels` (the text is truncated to fit, always NUL-terminated)                 */
+} ics_conv_layer;
+int ics_op_conv_layer(ics_conv_layer* a);
+
 /* The two 1x1x1 heads with their losses and metrics on a GIVEN trunk output (kernel parity tests against the reference's own
  * formulas): soft = softmax(x wsoft + bsoft), sig = sigmoid(x wsig + bsig) (unet/unet.py:339-352), then
  * weighted_categorical_crossentropy / binary_crossentropy / f1_m / wr_m (unet/unet.py:159-221,252-259).

@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import conv_layer_ref as CR
 from oracle import numpy_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -87,6 +88,11 @@ def test_unet_train_step_matches_oracle(ties, B, fuse, C, relerr, monkeypatch):
     assert (fused <= sites) if fuse else not (fused & sites), sorted(x for x in sites if x.startswith("bnfuse"))
     kink = {n: eng.get_activation(n, _layer_shape(n, B, d)) for n in UNET_LAYERS}
     affine = {n: eng.get_bn_affine(n, _layer_shape(n, B, d)[-1]) for n in ("c2", "c4", "c6")}
+    # every layer's batch statistics (as its consumers see them, through the affine) against fp64 statistics of the layer's
+    # own stored activations, per channel: the statistics epilogue of each kernel in place (tests/test_gpu_conv_layer.py)
+    worst_stat = [CR.check_bn_affine(n, kink[n], *eng.get_bn_affine(n, _layer_shape(n, B, d)[-1]), p0[n + "/gamma"], p0[n + "/beta"])
+                  for n in UNET_LAYERS]
+    print("batch statistics: mean <= %.2f ulps, var + eps <= %.3g of its bound" % tuple(np.max(worst_stat, 0)))
     m_ref = orc.train_on_batch(X, lab, kink=kink, affine=affine)
     print("relu masks flipped within rounding of 0:", sum(orc.kink_flips.values()), "of",
           sum(np.prod(_layer_shape(n, B, d)) for n in UNET_LAYERS))

@@ -3,6 +3,7 @@ loss, /root/reference/vae/lattice_vae.py:160-270) with eps injected.
 import numpy as np
 import pytest
 
+import conv_layer_ref as CR
 from oracle import numpy_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -75,6 +76,12 @@ def test_vae_train_step_matches_oracle(B, C, relerr):
     kink_pm = {n: ue.get_activation(n, s) for n, s in _pm_layer_shapes(B, d).items()}
     aff = {n: ve.get_bn_affine(n, _vae_layer_shapes(B, d, C)[n][-1]) for n in ("e0", "e1", "e2", "e3", "d0", "d1", "d2", "d3", "dout")}
     aff_pm = {n: ue.get_bn_affine(n, _pm_layer_shapes(B, d)[n][-1]) for n in ("c2", "c4", "c6")}
+    # every BatchNorm layer's batch statistics (through its affine) against fp64 statistics of its own stored activations,
+    # per channel (tests/test_gpu_conv_layer.py): the VAE's layers, and the perceptual U-Net's as its last pass left them
+    worst_stat = [CR.check_bn_affine(n, kink[n], *aff[n], vo.P[n + "/gamma"], vo.P[n + "/beta"]) for n in aff]
+    worst_stat += [CR.check_bn_affine("pm " + n, kink_pm[n], *ue.get_bn_affine(n, s[-1]), uo.P[n + "/gamma"], uo.P[n + "/beta"])
+                   for n, s in _pm_layer_shapes(B, d).items()]
+    print("batch statistics: mean <= %.2f ulps, var + eps <= %.3g of its bound" % tuple(np.max(worst_stat, 0)))
     m_r = vo.train_on_batch(X, cond, eps, kink=kink, kink_pm=kink_pm, affine=aff, affine_pm=aff_pm)
     print("kink flips:", {k: v for k, v in vo.kink_flips.items() if v})
     np.testing.assert_allclose(m, m_r, rtol=2e-5)
