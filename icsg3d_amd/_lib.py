@@ -66,6 +66,19 @@ class ConvLayerArgs(C.Structure):
                 ("kernels", C.c_void_p), ("kernels_cap", C.c_int)]
 
 
+class ConvLinkLayer(C.Structure):
+    _fields_ = [("Cout", C.c_int), ("w", _F), ("bias", _F), ("gamma", _F), ("beta", _F), ("y", _F), ("mean", _F), ("rstd", _F),
+                ("scale", _F), ("shift", _F), ("dw", _F), ("dbias", _F), ("dgamma", _F), ("dbeta", _F)]
+
+
+class ConvLinkArgs(C.Structure):
+    """ics_conv_link (include/icsg3d.h)."""
+    _fields_ = [("link", C.c_int), ("form", C.c_int), ("B", C.c_int), ("max_batch", C.c_int), ("S", C.c_int), ("C0", C.c_int),
+                ("Cq", C.c_int), ("pool_ties_all", C.c_int), ("x0", _F), ("q", _F), ("P", ConvLinkLayer), ("K", ConvLinkLayer),
+                ("L", ConvLinkLayer), ("dout", _F), ("dout_l", _F), ("pooled", _F), ("dy_p", _F), ("dx0", _F),
+                ("sites", C.c_void_p), ("sites_cap", C.c_int)]
+
+
 _U8 = C.POINTER(C.c_uint8)
 _I32 = C.POINTER(C.c_int32)
 _I64 = C.POINTER(C.c_int64)
@@ -185,6 +198,7 @@ SIGNATURES = {
     "ics_op_unet_head": (C.c_int, [_F, _F, _F, _F, _F, _U8, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _F, _F,
                                   C.POINTER(C.c_double)]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
+    "ics_op_conv_link": (C.c_int, [C.POINTER(ConvLinkArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv3d_bench": (C.c_int, [C.c_int] * 8 + [_F]),
     "ics_op_conv3d_backward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F]),

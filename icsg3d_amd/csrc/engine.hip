@@ -3375,6 +3375,149 @@ int ics_op_conv_layer(ics_conv_layer* a) {
   return 0;
 }
 
+// A producer and its consumer(s) through the engines' own construction and dispatch (include/icsg3d.h): what unet_build,
+// unet_forward_trunk and unet_backward do for that link, on a Net of two or three layers.  Nothing here chooses a kernel or
+// decides whether a fold is taken: the op only hands conv_backward the gradient sources and `next` of the link.
+int ics_op_conv_link(ics_conv_link* a) {
+  const std::string op = "ics_op_conv_link: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->link >= ICS_LINK_SAME && a->link <= ICS_LINK_POOL_SKIP, op + "unknown link");
+  ICS_CHECK(a->form == 0 || a->form == 1, op + "form must be 0 (U-Net) or 1 (VAE)");
+  ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
+  const bool has_k = a->link == ICS_LINK_POOL || a->link == ICS_LINK_POOL_SKIP, has_l = a->link != ICS_LINK_POOL;
+  const bool skip = a->link == ICS_LINK_POOL_SKIP;
+  ICS_CHECK(a->S >= (has_k ? 2 : 1) && (a->S & (a->S - 1)) == 0, op + "S must be a power of two (>= 2 in front of a pool)");
+  ICS_CHECK(a->C0 >= 1 && a->x0 != nullptr, op + "x0 and C0 are required");
+  ICS_CHECK(a->dout != nullptr, op + "dout is required");
+  ICS_CHECK(!skip || (a->q != nullptr && a->Cq >= 1 && a->dout_l != nullptr), op + "POOL_SKIP needs q, Cq and dout_l");
+  ICS_CHECK(a->pool_ties_all == 0 || a->pool_ties_all == 1, op + "pool_ties_all must be 0 or 1");
+  ICS_CHECK(has_k || a->pooled == nullptr, op + "pooled needs a pool link");
+  auto layer_ok = [](const ics_conv_link_layer& l) { return l.Cout >= 1 && l.w && l.gamma && l.beta; };
+  ICS_CHECK(layer_ok(a->P), op + "P needs Cout, w, gamma and beta");
+  ICS_CHECK(!has_k || layer_ok(a->K), op + "K needs Cout, w, gamma and beta");
+  ICS_CHECK(!has_l || layer_ok(a->L), op + "L needs Cout, w, gamma and beta");
+  Net n;
+  ICS_TRY(op_prepare(n));
+  n.side_on = false;             // as unet_build
+  n.maxB = a->max_batch; n.d = a->S; n.C = a->C0; n.pool_ties_all = a->pool_ties_all;
+  const int B = a->B, S = a->S, Cp = a->P.Cout;
+  const int pre = a->form == 0 ? ACT_RELU : ACT_NONE, post = a->form == 0 ? ACT_NONE : ACT_LRELU;
+  ConvLayer* P = add_conv(n, "P", a->C0, Cp, 27, S, pre, 1, post, false);
+  ConvLayer* K = has_k ? add_conv(n, "K", Cp, a->K.Cout, 27, S / 2, pre, 1, post, false) : nullptr;
+  ConvLayer* L = nullptr;
+  if (has_l)
+    L = add_conv(n, "L", Cp + (skip ? a->Cq : 0), a->L.Cout, 27, a->link == ICS_LINK_UP ? 2 * S : S, pre, 1, post, false);
+  ICS_TRY(alloc_params(n));
+  ICS_TRY(alloc_layer(n, *P, true, has_k));
+  if (K) ICS_TRY(alloc_layer(n, *K, true, false));
+  if (L) ICS_TRY(alloc_layer(n, *L, true, false));
+  const size_t M = n.rows(*P, B), Mmax = n.rows(*P, n.maxB);
+  float *d_x0 = nullptr, *d_q = nullptr, *d_dout = nullptr, *d_dout_l = nullptr;
+  ICS_TRY(n.alloc(&d_x0, Mmax * a->C0));
+  ICS_HIP(hipMemcpyAsync(d_x0, a->x0, M * a->C0 * sizeof(float), hipMemcpyHostToDevice, n.st));
+  P->src[0] = src_plain(d_x0, a->C0);
+  if (K) K->src[0] = src_plain(P->pooled, Cp);
+  if (skip) {
+    ICS_TRY(n.alloc(&d_q, Mmax / 8 * a->Cq));
+    ICS_HIP(hipMemcpyAsync(d_q, a->q, M / 8 * a->Cq * sizeof(float), hipMemcpyHostToDevice, n.st));
+    L->src[0] = src_layer(*P, 0); L->src[1] = ConvSrc{d_q, nullptr, nullptr, a->Cq, 1, ACT_NONE, 0}; L->nsrc = 2;
+    L->skip_prod = P;
+  } else if (L) {
+    L->src[0] = src_layer(*P, a->link == ICS_LINK_UP ? 1 : 0);
+  }
+  for (auto& Lp : n.layers) use_padded_input(*Lp);
+  if (L && L->src[L->nsrc - 1].up) ICS_TRY(enable_split_up(n, *L));
+  for (auto& Lp : n.layers) ICS_TRY(enable_wino(n, *Lp, true));
+  for (auto& Lp : n.layers) ICS_TRY(enable_winog(n, *Lp, true));
+  ICS_TRY(alloc_workspaces(n, true));
+  ICS_TRY(init_bn_defaults(n));
+  ConvLayer* last = has_k ? K : L;     // the layer `dout` belongs to
+  {
+    const size_t rows = n.rows(*last, B), rows_max = n.rows(*last, n.maxB);
+    ICS_TRY(n.alloc(&d_dout, rows_max * last->Cout));
+    ICS_HIP(hipMemcpyAsync(d_dout, a->dout, rows * last->Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+  }
+  if (skip) {
+    ICS_TRY(n.alloc(&d_dout_l, Mmax * L->Cout));
+    ICS_HIP(hipMemcpyAsync(d_dout_l, a->dout_l, M * L->Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+  }
+  struct Io { ConvLayer* l; ics_conv_link_layer* h; };
+  const Io io[3] = {{P, &a->P}, {K, &a->K}, {L, &a->L}};
+  for (const Io& e : io) {
+    if (!e.l) continue;
+    const size_t wn = (size_t)27 * e.l->Cin * e.l->Cout, cb = (size_t)e.l->Cout * sizeof(float);
+    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_w), e.h->w, wn * sizeof(float), hipMemcpyHostToDevice, n.st));
+    if (e.h->bias) ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_b), e.h->bias, cb, hipMemcpyHostToDevice, n.st));
+    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_gamma), e.h->gamma, cb, hipMemcpyHostToDevice, n.st));
+    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_beta), e.h->beta, cb, hipMemcpyHostToDevice, n.st));
+    ICS_TRY(pack_layer(n, *e.l, true));
+  }
+  n.prof.on = true;              // every launch site becomes a row; the conv sites carry their kernel id
+  n.splitk = true;               // as inside a train step
+  n.want_wgrad_inputs = true;
+  for (auto& Lp : n.layers) ICS_TRY(conv_forward(n, *Lp, B, true, true, n.tp(Lp->t_b)));
+  // ---- backward: the calls of unet_backward for this link (c18 -> c17 | c17 -> c16 | c3 -> c2 | c17, c3 -> c2)
+  reset_backward_state(n);
+  auto bw = [&](ConvLayer* l, GradSrc g0, GradSrc g1, ConvLayer* next = nullptr) {
+    return conv_backward(n, *l, B, g0, g1, nullptr, true, true, -1, next);
+  };
+  auto g_skip = [&](ConvLayer* c) { return c->split_up ? gs_direct(c->dA_skip, c->Cs, 0) : gs_direct(c->dA, c->Cin, 0); };
+  auto g_up = [&](ConvLayer* c) {
+    return c->split_up ? gs_direct(c->dxl, c->Cu, 0) : gs_up(c->dA, c->Cin, c->nsrc == 2 ? c->src[0].C : 0);
+  };
+  switch (a->link) {
+    case ICS_LINK_SAME:
+      ICS_TRY(bw(L, gs_direct(d_dout, L->Cout, 0), gs_none(), P));
+      ICS_TRY(bw(P, gs_direct(L->dA, L->Cin, 0), gs_none()));
+      break;
+    case ICS_LINK_UP:
+      ICS_TRY(bw(L, gs_direct(d_dout, L->Cout, 0), gs_none(), L->split_up ? P : nullptr));
+      ICS_TRY(bw(P, g_up(L), gs_none()));
+      break;
+    case ICS_LINK_POOL:
+      ICS_TRY(bw(K, gs_direct(d_dout, K->Cout, 0), gs_none()));
+      ICS_TRY(bw(P, gs_pool(K->dA, K->Cin, *P), gs_none()));
+      break;
+    default:
+      ICS_TRY(bw(L, gs_direct(d_dout_l, L->Cout, 0), gs_none()));     // (next would be the producer of q)
+      ICS_TRY(bw(K, gs_direct(d_dout, K->Cout, 0), gs_none()));
+      ICS_TRY(bw(P, gs_pool(K->dA, K->Cin, *P), g_skip(L)));
+      break;
+  }
+  ICS_TRY(colsum_flush(n));
+  ICS_TRY(side_join(n));
+  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
+    return 0;
+  };
+  for (const Io& e : io) {
+    if (!e.l) continue;
+    const size_t C = (size_t)e.l->Cout;
+    ICS_TRY(down(e.h->y, e.l->s, n.rows(*e.l, B) * C));
+    ICS_TRY(down(e.h->mean, e.l->mean, C)); ICS_TRY(down(e.h->rstd, e.l->rstd, C));
+    ICS_TRY(down(e.h->scale, e.l->scale, C)); ICS_TRY(down(e.h->shift, e.l->shift, C));
+    ICS_TRY(down(e.h->dw, n.tg(e.l->t_w), (size_t)27 * e.l->Cin * C)); ICS_TRY(down(e.h->dbias, n.tg(e.l->t_b), C));
+    ICS_TRY(down(e.h->dgamma, n.tg(e.l->t_gamma), C)); ICS_TRY(down(e.h->dbeta, n.tg(e.l->t_beta), C));
+  }
+  if (has_k) ICS_TRY(down(a->pooled, P->pooled, M / 8 * Cp));
+  ICS_TRY(down(a->dy_p, P->dy, M * Cp));
+  ICS_TRY(down(a->dx0, P->dA, M * a->C0));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  if (a->sites && a->sites_cap > 0) {
+    std::string txt;
+    for (const auto& r : n.prof.rows) txt += r.label + "\n";
+    std::strncpy(a->sites, txt.c_str(), (size_t)a->sites_cap - 1);
+    a->sites[a->sites_cap - 1] = 0;
+  }
+  if (n.canary_on) {
+    std::string msg;
+    const int bad = n.canaries_dirty(&msg);
+    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
+  }
+  return 0;
+}
+
 // The two 1x1x1 heads + losses + metrics on a given trunk output (kernel parity tests against the reference's own formulas,
 // tests/golden/loss_golden.npz): the same two launch sequences unet_head_loss chooses between.
 int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,

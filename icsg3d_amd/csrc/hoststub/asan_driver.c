@@ -1078,6 +1078,110 @@ static int conv_layer_walk(void) {
   return 0;
 }
 
+/* ics_op_conv_link: every link in both forms, on a handle larger than the batch, with the linear folds at their default
+ * threshold and forced on (ICSG3D_DGRAD_BNFUSE_MIN=0), without the up-split, under both tie rules; then every refusal. */
+static void link_layer(ics_conv_link_layer* l, int Cin, int Cout, size_t rows) {
+  l->Cout = Cout;
+  l->w = calloc((size_t)27 * Cin * Cout, 4); l->bias = calloc(Cout, 4); l->gamma = calloc(Cout, 4); l->beta = calloc(Cout, 4);
+  l->y = malloc(rows * Cout * 4);
+  l->mean = malloc(Cout * 4); l->rstd = malloc(Cout * 4); l->scale = malloc(Cout * 4); l->shift = malloc(Cout * 4);
+  l->dw = malloc((size_t)27 * Cin * Cout * 4); l->dbias = malloc(Cout * 4); l->dgamma = malloc(Cout * 4); l->dbeta = malloc(Cout * 4);
+}
+static void link_layer_free(ics_conv_link_layer* l) {
+  free((void*)l->w); free((void*)l->bias); free((void*)l->gamma); free((void*)l->beta); free(l->y);
+  free(l->mean); free(l->rstd); free(l->scale); free(l->shift); free(l->dw); free(l->dbias); free(l->dgamma); free(l->dbeta);
+}
+static int conv_link_one(int link, int form, int B, int maxB, int S, int C0, int Cp, int Ck, int Cl, int Cq, int ties,
+                         const char* site) {
+  ics_conv_link a;
+  char text[8192];
+  const size_t M = (size_t)B * S * S * S;
+  const int has_k = link >= ICS_LINK_POOL, has_l = link != ICS_LINK_POOL;
+  const size_t ML = link == ICS_LINK_UP ? 8 * M : M;
+  memset(&a, 0, sizeof a);
+  a.link = link; a.form = form; a.B = B; a.max_batch = maxB; a.S = S; a.C0 = C0; a.pool_ties_all = ties;
+  a.x0 = calloc(M * C0, 4);
+  link_layer(&a.P, C0, Cp, M);
+  if (has_k) link_layer(&a.K, Cp, Ck, M / 8);
+  if (has_l) link_layer(&a.L, Cp + (link == ICS_LINK_POOL_SKIP ? Cq : 0), Cl, ML);
+  a.dout = has_k ? calloc(M / 8 * Ck, 4) : calloc(ML * Cl, 4);
+  if (link == ICS_LINK_POOL_SKIP) { a.Cq = Cq; a.q = calloc(M / 8 * Cq, 4); a.dout_l = calloc(M * Cl, 4); }
+  if (has_k) a.pooled = malloc(M / 8 * Cp * 4);
+  a.dy_p = malloc(M * Cp * 4); a.dx0 = malloc(M * C0 * 4);
+  a.sites = text; a.sites_cap = (int)sizeof text;
+  OK(ics_op_conv_link(&a));
+  if (!strstr(text, "conv_fwd:P|") || !strstr(text, "bn_act_bwd:") || (site && !strstr(text, site))) {
+    fprintf(stderr, "conv link %d form %d: launch sites missing (%s) in\n%s", link, form, site ? site : "-", text);
+    return 1;
+  }
+  a.sites_cap = 9;                                     /* truncated, still terminated */
+  OK(ics_op_conv_link(&a));
+  if (strlen(text) > 8) { fprintf(stderr, "conv link: site text not truncated\n"); return 1; }
+  free((void*)a.x0); free((void*)a.q); free((void*)a.dout); free((void*)a.dout_l); free(a.pooled); free(a.dy_p); free(a.dx0);
+  link_layer_free(&a.P);
+  if (has_k) link_layer_free(&a.K);
+  if (has_l) link_layer_free(&a.L);
+  return 0;
+}
+static int conv_link_walk(void) {
+  for (int fused = 0; fused < 2; ++fused) {
+    if (fused) setenv("ICSG3D_DGRAD_BNFUSE_MIN", "0", 1);
+    for (int form = 0; form < 2; ++form)
+      for (int big = 0; big < 2; ++big) {
+        const int mb = big ? 5 : 3, u = fused && form == 0;
+        if (conv_link_one(ICS_LINK_SAME, form, 3, mb, 8, 16, 64, 0, 128, 0, 1, u ? "bnfuse:L" : NULL)) return 1;
+        if (conv_link_one(ICS_LINK_SAME, form, 2, mb, 8, 16, 96, 0, 32, 0, 1, NULL)) return 1;
+        if (conv_link_one(ICS_LINK_SAME, form, 4, mb + 1, 4, 16, 64, 0, 64, 0, 1, NULL)) return 1;
+        if (conv_link_one(ICS_LINK_SAME, form, 2, mb, 8, 16, 40, 0, 24, 0, 1, NULL)) return 1;
+        if (conv_link_one(ICS_LINK_SAME, form, 3, mb, 4, 16, 128, 0, 40, 0, 1, NULL)) return 1;
+        if (conv_link_one(ICS_LINK_UP, form, 2, mb, 4, 16, 64, 0, 64, 0, 1, "conv_dgrad:L.up|")) return 1;
+        if (conv_link_one(ICS_LINK_UP, form, 2, mb, 4, 16, 32, 0, 16, 0, 1, "conv_dgrad:L.up|")) return 1;
+        for (int ties = 0; ties < 2; ++ties) {
+          if (conv_link_one(ICS_LINK_POOL, form, 3, mb, 8, 16, 64, 64, 0, 0, ties, form == 0 ? "pool_presum:P" : "pool_fwd")) return 1;
+          if (conv_link_one(ICS_LINK_POOL, form, 2, mb, 8, 16, 16, 32, 0, 0, ties, "pool_fwd")) return 1;
+          if (conv_link_one(ICS_LINK_POOL_SKIP, form, 2, mb, 8, 16, 64, 64, 128, 128, ties, u ? "bnfuse:P.pool" : "conv_dgrad:L.skip|"))
+            return 1;
+        }
+      }
+  }
+  unsetenv("ICSG3D_DGRAD_BNFUSE_MIN");
+  setenv("ICSG3D_NO_UPSPLIT", "1", 1);
+  if (conv_link_one(ICS_LINK_UP, 0, 2, 3, 4, 16, 64, 0, 64, 0, 1, "conv_dgrad:L|")) return 1;
+  if (conv_link_one(ICS_LINK_POOL_SKIP, 1, 2, 3, 4, 16, 32, 32, 32, 64, 0, "conv_dgrad:L|")) return 1;
+  unsetenv("ICSG3D_NO_UPSPLIT");
+  setenv("ICSG3D_NO_POOL_PRESUM", "1", 1);
+  if (conv_link_one(ICS_LINK_POOL, 0, 3, 5, 8, 16, 64, 64, 0, 0, 1, "pool_fwd")) return 1;
+  unsetenv("ICSG3D_NO_POOL_PRESUM");
+  {
+    ics_conv_link a;
+    float buf[27 * 4 * 4 + 64] = {0};
+    int bad = 0;
+    memset(&a, 0, sizeof a);
+    a.link = ICS_LINK_SAME; a.B = 1; a.max_batch = 1; a.S = 2; a.C0 = 4; a.pool_ties_all = 1; a.x0 = buf; a.dout = buf;
+    a.P.Cout = 4; a.P.w = buf; a.P.gamma = buf; a.P.beta = buf;
+    a.L = a.P;
+    OK(ics_op_conv_link(&a));
+    bad += ics_op_conv_link(NULL) == 0;
+    a.link = 4; bad += ics_op_conv_link(&a) == 0; a.link = ICS_LINK_SAME;
+    a.form = 2; bad += ics_op_conv_link(&a) == 0; a.form = 0;
+    a.max_batch = 0; bad += ics_op_conv_link(&a) == 0; a.max_batch = 1;
+    a.S = 3; bad += ics_op_conv_link(&a) == 0; a.S = 2;
+    a.x0 = NULL; bad += ics_op_conv_link(&a) == 0; a.x0 = buf;
+    a.dout = NULL; bad += ics_op_conv_link(&a) == 0; a.dout = buf;
+    a.pool_ties_all = 2; bad += ics_op_conv_link(&a) == 0; a.pool_ties_all = 1;
+    a.pooled = buf; bad += ics_op_conv_link(&a) == 0; a.pooled = NULL;             /* no pool in this link */
+    a.L.gamma = NULL; bad += ics_op_conv_link(&a) == 0; a.L.gamma = buf;
+    a.P.w = NULL; bad += ics_op_conv_link(&a) == 0; a.P.w = buf;
+    a.link = ICS_LINK_POOL; bad += ics_op_conv_link(&a) == 0;                       /* K missing */
+    a.S = 1; a.K = a.P; bad += ics_op_conv_link(&a) == 0; a.S = 2;                  /* nothing to pool */
+    a.link = ICS_LINK_POOL_SKIP; bad += ics_op_conv_link(&a) == 0;                  /* q, Cq, dout_l missing */
+    a.link = ICS_LINK_SAME;
+    if (bad) { fprintf(stderr, "conv link: %d invalid argument sets accepted\n", bad); return 1; }
+    OK(ics_op_conv_link(&a));                                                       /* still usable */
+  }
+  return 0;
+}
+
 int main(void) {
   char name[256]; int cus; size_t hbm; int ndev = 0;
   OK(ics_device_count(&ndev));
@@ -1110,6 +1214,7 @@ int main(void) {
     free(x); free(y); free(w); free(dx); free(dw);
   }
   if (conv_layer_walk()) return 1;
+  if (conv_link_walk()) return 1;
   {   /* the op-level head: both launch sequences */
     const size_t M = 64;
     float *x = calloc(M * 128, 4), *ws = calloc(128 * 95, 4), *bs = calloc(95, 4), *wg = calloc(128, 4), bg[1] = {0.f};

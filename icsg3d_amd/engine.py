@@ -642,6 +642,67 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     return r
 
 
+LINKS = ("same", "up", "pool", "pool_skip")
+
+
+def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_ties_all=True, max_batch=None):
+    """Single-op entry (ics_op_conv_link): a producer P and its consumer(s) through the engines' own construction,
+    forward (training) and backward calls, with the gradient sources and `next` unet_backward gives that link.
+
+    link: one of LINKS.  x0 (B,S,S,S,C0).  layers: {"P": {...}, "K": {...}, "L": {...}} (K behind the MaxPool; L the
+    same-resolution / upsampled / [P | up(q)] consumer), each {"w": (3,3,3,Cin,Cout), "bias", "gamma", "beta"}.
+    dout: gradient w.r.t. the output of L ("same", "up") or K ("pool", "pool_skip"); dout_l and q: "pool_skip" only.
+
+    Returns {"P": {...}, "K": {...}, "L": {...}} with y, mean, rstd, scale, shift, dw, dbias, dgamma, dbeta per layer,
+    plus pooled (pool links), dy_p, dx0 and sites: the profiler's rows in launch order ("<site>" or "<site>|<kernel>")."""
+    lib = L.load()
+    a = L.ConvLinkArgs()
+    keep = []
+
+    def f(v):
+        if v is None:
+            return None
+        v = _f32(v)
+        keep.append(v)
+        return L.fptr(v)
+
+    def out(shape):
+        v = np.empty(shape, np.float32)
+        keep.append(v)
+        return v
+
+    x0 = _f32(x0)
+    B, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
+    a.link, a.form = LINKS.index(link), {"unet": 0, "vae": 1}[form]
+    a.B, a.max_batch, a.S, a.C0 = B, int(max_batch or B), S, C0
+    a.pool_ties_all = int(bool(pool_ties_all))
+    a.x0, a.q, a.dout, a.dout_l = f(x0), f(q), f(dout), f(dout_l)
+    a.Cq = 0 if q is None else _f32(q).shape[4]
+    side = {"P": S, "K": S // 2, "L": 2 * S if link == "up" else S}
+    r = {}
+    for name, p in layers.items():
+        h = getattr(a, name)
+        w = _f32(p["w"])
+        Cout = w.shape[4]
+        h.Cout, h.w, h.bias, h.gamma, h.beta = Cout, f(w), f(p.get("bias")), f(p["gamma"]), f(p["beta"])
+        o = r[name] = {"y": out((B,) + (side[name],) * 3 + (Cout,)), "dw": out(w.shape)}
+        for k in ("mean", "rstd", "scale", "shift", "dbias", "dgamma", "dbeta"):
+            o[k] = out((Cout,))
+        for k, v in o.items():
+            setattr(h, k, L.fptr(v))
+    Cp = r["P"]["y"].shape[4]
+    if "K" in layers:
+        r["pooled"] = out((B,) + (S // 2,) * 3 + (Cp,))
+        a.pooled = L.fptr(r["pooled"])
+    r["dy_p"], r["dx0"] = out((B, S, S, S, Cp)), out(x0.shape)
+    a.dy_p, a.dx0 = L.fptr(r["dy_p"]), L.fptr(r["dx0"])
+    text = C.create_string_buffer(32768)
+    a.sites, a.sites_cap = C.cast(text, C.c_void_p), len(text)
+    L.check(lib.ics_op_conv_link(C.byref(a)))
+    r["sites"] = text.value.decode().splitlines()
+    return r
+
+
 def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False):
     """Single-op entry (kernel parity tests): the heads + losses + metrics on a given trunk output x (M,128).
     Returns (out (M, ncls+1) | None, metrics (5,), sums dict) -- see ics_op_unet_head."""

@@ -703,6 +703,53 @@ typedef struct ics_conv_layer {
 } ics_conv_layer;
 int ics_op_conv_layer(ics_conv_layer* a);
 
+/* Two or three layers LINKED the way the engines link them (kernel parity tests, tests/test_gpu_conv_link.py): a producer
+ * P, fed by the plain tensor x0, and its consumer(s), built, packed, run forward (training) and backward by the engines' own
+ * functions, with the gradient sources and the `next` argument unet_backward gives that link.  What one layer alone cannot
+ * reach runs here: the consumer's backward-data launch that sums, or applies, the PRODUCER's BatchNorm backward (BwdStat,
+ * conv_bnfuse_kernel, pool_bnfuse_kernel), the pool / upsample gradient sources of the BatchNorm-backward kernels, the
+ * pooled-grid sums (launch_pool_presum) and the tie masks pool_fwd4_kernel leaves for them.
+ *
+ *   link ICS_LINK_SAME       P -> L                  L: gs_direct(dout), next = P;  P: gs_direct(L.dA)
+ *        ICS_LINK_UP         P -> up -> L            L (up-split): next = P;  P: gs_direct(L.dxl) -- without the up-split
+ *                                                    (ICSG3D_NO_UPSPLIT, or a width it refuses): P: gs_up(L.dA)
+ *        ICS_LINK_POOL       P -> MaxPool -> K       K: gs_direct(dout);  P: gs_pool(K.dA), gs_none()
+ *        ICS_LINK_POOL_SKIP  P -> MaxPool -> K  and  L = [P | up(q)], L.skip_prod = P
+ *                                                    L (dout_l), then K (dout), then P: gs_pool(K.dA), g_skip(L)
+ *   form 0: every layer is Conv -> ReLU -> BatchNorm (U-Net);  1: Conv -> BatchNorm -> LeakyReLU(0.3) (VAE).
+ *
+ * Geometry: P works on S^3 voxels (S a power of two), L on S^3 (SAME, POOL_SKIP) or (2S)^3 (UP), K on (S/2)^3; q is
+ * [B][(S/2)^3][Cq].  All kernels are 3x3x3.  The handle is built as unet_build builds its own (weight gradients on the main
+ * stream, Winograd kernels where their predicates accept the layer) in both forms: the VAE engine's own backward pass hands
+ * no `next` to conv_backward, so form 1 of SAME / UP runs the LeakyReLU branches of the folds as a U-Net-style pass would.
+ * The ICSG3D_* switches, ICSG3D_DGRAD_BNFUSE_MIN and ICSG3D_DEBUG_CANARY are honoured as in ics_op_conv_layer. */
+enum { ICS_LINK_SAME = 0, ICS_LINK_UP = 1, ICS_LINK_POOL = 2, ICS_LINK_POOL_SKIP = 3 };
+typedef struct ics_conv_link_layer {
+  int Cout;           /* Cin follows from the link: P: C0; K: P.Cout; L: P.Cout (+ Cq in POOL_SKIP)                   */
+  const float *w, *bias, *gamma, *beta; /* [27][Cin][Cout], [Cout] x 3; bias optional (zeros)                         */
+  float* y;           /* out, optional: the stored activation [B][S_layer^3][Cout]                                    */
+  float *mean, *rstd, *scale, *shift;   /* out, optional [Cout]                                                       */
+  float *dw, *dbias, *dgamma, *dbeta;   /* out, optional                                                              */
+} ics_conv_link_layer;
+typedef struct ics_conv_link {
+  int link, form;
+  int B, max_batch, S;
+  int C0, Cq;         /* channels of x0; of q (POOL_SKIP only)                                                        */
+  int pool_ties_all;  /* MaxPool3D backward: 1 every tied element (TensorFlow CPU), 0 the first                        */
+  const float* x0;    /* [B][S^3][C0]                                                                                 */
+  const float* q;     /* [B][(S/2)^3][Cq], POOL_SKIP only                                                            */
+  ics_conv_link_layer P, K, L;          /* K: POOL, POOL_SKIP; L: SAME, UP, POOL_SKIP                                 */
+  const float* dout;  /* gradient w.r.t. the output of L (SAME, UP) or of K (POOL, POOL_SKIP)                         */
+  const float* dout_l;/* POOL_SKIP: gradient w.r.t. the output of L                                                   */
+  float* pooled;      /* out, optional: MaxPool3D(post_act(BN(P.y))) [B][(S/2)^3][P.Cout] (POOL, POOL_SKIP)           */
+  float* dy_p;        /* out, optional: P's gradient w.r.t. its convolution output (behind the activation) [B][S^3][P.Cout] */
+  float* dx0;         /* out, optional: [B][S^3][C0]                                                                  */
+  char* sites;        /* out, optional: every profiler row of the call, one per line, in first-launch order: "bnfuse:L",
+                         "pool_presum:P", "bn_act_bwd:P", "conv_dgrad:L|<kernel template instantiation>", ...          */
+  int sites_cap;      /* bytes behind `sites` (truncated to fit, always NUL-terminated)                               */
+} ics_conv_link;
+int ics_op_conv_link(ics_conv_link* a);
+
 /* The two 1x1x1 heads with their losses and metrics on a GIVEN trunk output (kernel parity tests against the reference's own
  * formulas): soft = softmax(x wsoft + bsoft), sig = sigmoid(x wsig + bsig) (unet/unet.py:339-352), then
  * weighted_categorical_crossentropy / binary_crossentropy / f1_m / wr_m (unet/unet.py:159-221,252-259).
