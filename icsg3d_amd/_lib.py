@@ -63,7 +63,7 @@ class ConvLayerArgs(C.Structure):
                 ("src", ConvLayerSrc * 2), ("w", _F), ("bias", _F), ("gamma", _F), ("beta", _F), ("dout", _F), ("y", _F),
                 ("mean", _F), ("rstd", _F), ("scale", _F), ("shift", _F), ("moving_mean", _F), ("moving_var", _F),
                 ("rows_per_block", C.c_int), ("blocks", C.c_int), ("dw", _F), ("dbias", _F), ("dgamma", _F), ("dbeta", _F),
-                ("kernels", C.c_void_p), ("kernels_cap", C.c_int)]
+                ("kernels", C.c_void_p), ("kernels_cap", C.c_int), ("ranks", C.c_int)]
 
 
 class ConvLinkLayer(C.Structure):
@@ -76,7 +76,7 @@ class ConvLinkArgs(C.Structure):
     _fields_ = [("link", C.c_int), ("form", C.c_int), ("B", C.c_int), ("max_batch", C.c_int), ("S", C.c_int), ("C0", C.c_int),
                 ("Cq", C.c_int), ("pool_ties_all", C.c_int), ("x0", _F), ("q", _F), ("P", ConvLinkLayer), ("K", ConvLinkLayer),
                 ("L", ConvLinkLayer), ("dout", _F), ("dout_l", _F), ("pooled", _F), ("dy_p", _F), ("dx0", _F),
-                ("sites", C.c_void_p), ("sites_cap", C.c_int)]
+                ("sites", C.c_void_p), ("sites_cap", C.c_int), ("ranks", C.c_int)]
 
 
 _U8 = C.POINTER(C.c_uint8)
@@ -197,6 +197,9 @@ SIGNATURES = {
     "ics_net_comm_info": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ics_op_unet_head": (C.c_int, [_F, _F, _F, _F, _F, _U8, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _F, _F,
                                   C.POINTER(C.c_double)]),
+    "ics_op_unet_metrics_from_sums": (C.c_int, [_D, _F]),
+    "ics_op_vae_loss": (C.c_int, [_F, C.c_int, C.c_int, _D, C.c_int, C.c_double, _D, C.POINTER(C.c_int), _D, _F, C.c_float,
+                                  C.c_float, C.c_int, _D, _F]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
     "ics_op_conv_link": (C.c_int, [C.POINTER(ConvLinkArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

@@ -21,12 +21,27 @@ struct BnParams {
 
 // SyncBN exchange (opt-in data-parallel mode): `local` holds 3*C doubles (forward: n, mean, M2) or 2*C
 // (backward: sum d, sum d*xhat); `gathered` nranks * 3*C.
+// Emulated rank exchange (ics_op_conv_layer / ics_op_conv_link with ranks >= 1): the ranks of ONE process run one after
+// another on one stream, and every SyncBN collective goes through device tables that outlive a rank's handle instead of
+// through RCCL.  Call `call` of a body copies this rank's `local` into its slot of the table and reads the nranks slots
+// back (gather), or their sum in rank order (reduce); the caller repeats the bodies until the tables stop changing.
+struct BnSyncEmu {
+  int rank, nranks;
+  double* fwd;        // [cap][nranks][3 * cmax]  forward (n, mean, M2)
+  double* bwd;        // [cap][nranks][2 * cmax]  backward (sum d, sum d * xhat)
+  int cmax, cap;      // widest layer the tables hold; collectives per body they hold
+  int call;           // running index of the next collective of this body
+};
 struct BnSync {
   ncclComm_t comm;
   int nranks;
   double* local;
   double* gathered;
+  BnSyncEmu* emu = nullptr;   // optional: the collectives are emulated (comm is not used)
 };
+// the one place the SyncBN launch functions exchange `count` doubles of sync->local: all-gather into sync->gathered
+// (gather) or sum over the ranks in place; RCCL on sync->comm, or the emulation tables
+int bn_sync_exchange(hipStream_t st, const BnSync* sync, bool gather, size_t count, const char* what);
 
 enum GradSrcKind : int { GS_NONE = 0, GS_DIRECT = 1, GS_UP = 2, GS_POOL = 3 };
 

@@ -49,6 +49,15 @@ __device__ __forceinline__ double block_sum_dn(double v, double* sh /*[16]*/) {
 // BatchNorm forward statistics: merge per-block (count, mean, M2) -> mean/var -> scale/shift,
 // moving-average update.  One block per channel, fp64 merge (Chan et al.).
 // ------------------------------------------------------------------------------------------
+// the moving-average update, each product and the sum rounded on its own: left to the compiler's contraction
+// bn_finalize_kernel came out as two products and a sum and bn_sync_finalize_kernel as a product and an fma for the
+// variance, one ulp apart on the same statistics (found by tests/test_gpu_syncbn.py: one emulated rank against none)
+__device__ __forceinline__ float bn_ema(float old, float x, float momentum) {
+#pragma clang fp contract(off)
+  const float a = old * momentum, b = x * (1.f - momentum);
+  return a + b;
+}
+
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ partial, int nblk,
                                                             int Npad, BnParams bn, int update_moving,
                                                             float momentum, int unbias) {
@@ -90,8 +99,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
       // keras 2.3.1 BatchNormalization.call: variance fed to the moving average is rescaled by
       // n/(n-(1+eps)); plain EMA with momentum 0.99
       const double v = unbias ? var * (n / (n - (1.0 + (double)kBnEps))) : var;
-      bn.moving_mean[c] = bn.moving_mean[c] * momentum + (float)mean * (1.f - momentum);
-      bn.moving_var[c] = bn.moving_var[c] * momentum + (float)v * (1.f - momentum);
+      bn.moving_mean[c] = bn_ema(bn.moving_mean[c], (float)mean, momentum);
+      bn.moving_var[c] = bn_ema(bn.moving_var[c], (float)v, momentum);
     }
   }
 }
@@ -157,9 +166,44 @@ __global__ void bn_sync_finalize_kernel(const double* __restrict__ gathered, int
   bn.shift[c] = bn.beta[c] - (float)mean * sc;
   if (update_moving) {
     const double v = unbias ? var * (n / (n - (1.0 + (double)kBnEps))) : var;
-    bn.moving_mean[c] = bn.moving_mean[c] * momentum + (float)mean * (1.f - momentum);
-    bn.moving_var[c] = bn.moving_var[c] * momentum + (float)v * (1.f - momentum);
+    bn.moving_mean[c] = bn_ema(bn.moving_mean[c], (float)mean, momentum);
+    bn.moving_var[c] = bn_ema(bn.moving_var[c], (float)v, momentum);
   }
+}
+
+// emulated reduce: the slots of one call summed in rank order
+__global__ void bn_sync_emu_reduce_kernel(const double* __restrict__ slots, int nranks, size_t stride, int count,
+                                          double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  double s = 0.0;
+  for (int r = 0; r < nranks; ++r) s += slots[(size_t)r * stride + i];
+  out[i] = s;
+}
+int bn_sync_exchange(hipStream_t st, const BnSync* sync, bool gather, size_t count, const char* what) {
+  BnSyncEmu* e = sync->emu;
+  if (e == nullptr) {
+    ncclResult_t r = gather ? ncclAllGather(sync->local, sync->gathered, count, ncclDouble, sync->comm, st)
+                            : ncclAllReduce(sync->local, sync->local, count, ncclDouble, ncclSum, sync->comm, st);
+    ICS_CHECK(r == ncclSuccess, std::string(gather ? "ncclAllGather(" : "ncclAllReduce(") + what + "): " + ncclGetErrorString(r));
+    return 0;
+  }
+  const size_t stride = (size_t)(gather ? 3 : 2) * e->cmax;
+  ICS_CHECK(e->call < e->cap && count <= stride && e->rank >= 0 && e->rank < e->nranks && sync->nranks == e->nranks,
+            std::string("emulated ") + what + ": collective " + std::to_string(e->call) + " does not fit the tables");
+  double* slots = (gather ? e->fwd : e->bwd) + (size_t)e->call * e->nranks * stride;
+  ICS_HIP(hipMemcpyAsync(slots + (size_t)e->rank * stride, sync->local, count * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (gather) {
+    for (int r = 0; r < e->nranks; ++r)
+      ICS_HIP(hipMemcpyAsync(sync->gathered + (size_t)r * count, slots + (size_t)r * stride, count * sizeof(double),
+                             hipMemcpyDeviceToDevice, st));
+  } else {
+    ICS_LAUNCH(bn_sync_emu_reduce_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, slots, e->nranks, stride,
+               (int)count, sync->local);
+    ICS_HIP(hipGetLastError());
+  }
+  ++e->call;
+  return 0;
 }
 
 int launch_bn_finalize(hipStream_t st, const float* partial, int nblk, int Npad, const BnParams& bn,
@@ -167,8 +211,7 @@ int launch_bn_finalize(hipStream_t st, const float* partial, int nblk, int Npad,
   if (sync != nullptr) {
     ICS_LAUNCH(bn_local_merge_kernel, dim3(C), dim3(256), 0, st, partial, nblk, Npad, C, sync->local);
     ICS_HIP(hipGetLastError());
-    ncclResult_t r = ncclAllGather(sync->local, sync->gathered, (size_t)3 * C, ncclDouble, sync->comm, st);
-    ICS_CHECK(r == ncclSuccess, std::string("ncclAllGather(SyncBN): ") + ncclGetErrorString(r));
+    ICS_TRY(bn_sync_exchange(st, sync, true, (size_t)3 * C, "SyncBN"));
     ICS_LAUNCH(bn_sync_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, st, sync->gathered, sync->nranks, C,
                        bn, update_moving, 0.99f, unbias);
     ICS_HIP(hipGetLastError());
@@ -797,8 +840,7 @@ int launch_layer_bwd(hipStream_t st, const LayerBwd& L, float* dy, float* ws_par
                        c2, dgamma, dbeta, sync ? sync->local : nullptr);
     ICS_HIP(hipGetLastError());
     if (sync) {   // every rank holds the same number of rows (equal shards): n_global = n * nranks
-      ncclResult_t r = ncclAllReduce(sync->local, sync->local, (size_t)2 * L.C, ncclDouble, ncclSum, sync->comm, st);
-      ICS_CHECK(r == ncclSuccess, std::string("ncclAllReduce(SyncBN bwd): ") + ncclGetErrorString(r));
+      ICS_TRY(bn_sync_exchange(st, sync, false, (size_t)2 * L.C, "SyncBN bwd"));
       ICS_LAUNCH(bn_bwd_sync_c_kernel, dim3((L.C + 63) / 64), dim3(64), 0, st, sync->local, L.C,
                          n * (double)sync->nranks, c1, c2);
       ICS_HIP(hipGetLastError());
@@ -1465,8 +1507,7 @@ int launch_head_bnfuse(hipStream_t st, const float* Q, const float* dzsum, const
              dgamma, dbeta, sync ? sync->local : nullptr);
   ICS_HIP(hipGetLastError());
   if (sync) {   // global-batch statistics: the two sums over ALL ranks' voxels (every rank holds the same number of rows)
-    ncclResult_t r = ncclAllReduce(sync->local, sync->local, (size_t)256, ncclDouble, ncclSum, sync->comm, st);
-    ICS_CHECK(r == ncclSuccess, std::string("ncclAllReduce(SyncBN head fuse): ") + ncclGetErrorString(r));
+    ICS_TRY(bn_sync_exchange(st, sync, false, (size_t)256, "SyncBN head fuse"));
     ICS_LAUNCH(bn_bwd_sync_c_kernel, dim3(2), dim3(64), 0, st, sync->local, 128, n * (double)sync->nranks, c1c2, c1c2 + 128);
     ICS_HIP(hipGetLastError());
   }

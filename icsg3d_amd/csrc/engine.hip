@@ -20,6 +20,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -266,7 +267,7 @@ struct Net {
   double* sync_gathered = nullptr;   // [nranks][3*Cmax]
   int sync_cmax = 0;
   BnSync bn_sync{};
-  const BnSync* sync() const { return (sync_bn && comm) ? &bn_sync : nullptr; }
+  const BnSync* sync() const { return (sync_bn && (comm || bn_sync.emu)) ? &bn_sync : nullptr; }
   int head_nblk = 0;
   ColsumJobs colsum{};               // bias-gradient finalizes pending since the last flush (colsum_flush)
   float* ws_cls = nullptr; size_t ws_cls_n = 0;   // conv_bnfuse: per-block border-class sums of a dy
@@ -3229,9 +3230,56 @@ int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int
 // One layer through the engines' own construction and dispatch (include/icsg3d.h): a Net with a single ConvLayer, built,
 // packed and stepped by the functions unet_build / vae_build and the train steps use -- nothing here chooses a kernel.
 // The per-launch kernel ids come from the handle's profiler rows (labels ending in '|', see Profiler::begin).
-int ics_op_conv_layer(ics_conv_layer* a) {
-  const std::string op = "ics_op_conv_layer: ";
-  ICS_CHECK(a != nullptr, op + "null argument");
+// ---- emulated ranks (ranks >= 1 of the two ops below; BnSyncEmu in elementwise.h).  The tables live in a handle of their
+// own, outside the per-rank handles.  A sweep runs every rank's body once; rank r reads, at collective c, whatever the
+// other ranks left in the table of c so far.  The table of collective c is complete after sweep c (its inputs depend on
+// collectives < c only, and the body is deterministic), so sweep ncoll changes nothing and returns the right outputs: the
+// sweeps stop at the first one that leaves every slot bitwise unchanged, and ncoll + 1 of them is the cap.
+static int emu_attach(Net& n, BnSyncEmu* emu) {
+  if (emu == nullptr) return 0;
+  ICS_CHECK(n.sync_cmax <= emu->cmax, "emulated ranks: a layer is wider than the exchange tables");
+  ICS_TRY(n.alloc(&n.sync_local, (size_t)3 * emu->cmax));
+  ICS_TRY(n.alloc(&n.sync_gathered, (size_t)emu->nranks * 3 * emu->cmax));
+  n.rank = emu->rank; n.nranks = emu->nranks; n.sync_bn = 1;
+  n.bn_sync = BnSync{nullptr, emu->nranks, n.sync_local, n.sync_gathered, emu};
+  return 0;
+}
+static int run_emulated_ranks(const std::string& op, int R, int cmax, int cap, const std::function<int(int, BnSyncEmu*)>& body) {
+  Net holder;
+  ICS_TRY(op_prepare(holder));
+  BnSyncEmu emu{0, R, nullptr, nullptr, cmax, cap, 0};
+  const size_t nf = (size_t)cap * R * 3 * cmax, nb = (size_t)cap * R * 2 * cmax;
+  ICS_TRY(holder.alloc(&emu.fwd, nf));
+  ICS_TRY(holder.alloc(&emu.bwd, nb));
+  ICS_HIP(hipStreamSynchronize(holder.st));
+  std::vector<double> prev(nf + nb, 0.0), cur(nf + nb);
+  for (int sweep = 0;; ++sweep) {
+    int ncoll = -1;
+    for (int r = 0; r < R; ++r) {
+      emu.rank = r; emu.call = 0;
+      ICS_TRY(body(r, &emu));           // ends with a stream synchronize: the table writes are done
+      ICS_CHECK(ncoll < 0 || ncoll == emu.call, op + "the emulated ranks issued different numbers of collectives");
+      ncoll = emu.call;
+    }
+    ICS_HIP(hipMemcpy(cur.data(), emu.fwd, nf * sizeof(double), hipMemcpyDeviceToHost));
+    ICS_HIP(hipMemcpy(cur.data() + nf, emu.bwd, nb * sizeof(double), hipMemcpyDeviceToHost));
+    int first = -1;
+    for (int c = 0; c < cap && first < 0; ++c) {
+      const size_t f0 = (size_t)c * R * 3 * cmax, b0 = nf + (size_t)c * R * 2 * cmax;
+      if (std::memcmp(&cur[f0], &prev[f0], (size_t)R * 3 * cmax * sizeof(double)) != 0 ||
+          std::memcmp(&cur[b0], &prev[b0], (size_t)R * 2 * cmax * sizeof(double)) != 0)
+        first = c;
+    }
+    if (first < 0) break;
+    ICS_CHECK(sweep < ncoll, op + "emulated ranks: the exchange of collective " + std::to_string(first) + " (of " +
+                                 std::to_string(ncoll) + ") still changed in sweep " + std::to_string(sweep) +
+                                 " -- a statistic that is not reproducible run to run");
+    prev.swap(cur);
+  }
+  return 0;
+}
+
+static int conv_layer_check(const ics_conv_layer* a, const std::string& op) {
   ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
   ICS_CHECK(a->S >= 1 && (a->S & (a->S - 1)) == 0 && (a->taps == 27 || a->taps == 1) && a->Cout >= 1, op + "bad geometry");
   ICS_CHECK(a->nsrc == 1 || a->nsrc == 2, op + "nsrc must be 1 or 2");
@@ -3252,6 +3300,16 @@ int ics_op_conv_layer(ics_conv_layer* a) {
     want_dx = want_dx || s.dx != nullptr;
   }
   ICS_CHECK(a->dout || !(a->dw || a->dbias || a->dgamma || a->dbeta), op + "parameter gradients need dout");
+  return 0;
+}
+static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
+  const std::string op = "ics_op_conv_layer: ";
+  int Cin = 0;
+  bool want_dx = false;
+  for (int i = 0; i < a->nsrc; ++i) {
+    Cin += a->src[i].C;
+    want_dx = want_dx || a->src[i].dx != nullptr;
+  }
   Net n;
   ICS_TRY(op_prepare(n));
   n.maxB = a->max_batch; n.d = a->S; n.C = Cin;
@@ -3259,6 +3317,7 @@ int ics_op_conv_layer(ics_conv_layer* a) {
   const int B = a->B, S = a->S, Cout = a->Cout;
   ConvLayer& L = *add_conv(n, "L", Cin, Cout, a->taps, S, a->pre_act, a->has_bn ? 1 : 0, a->post_act, false, true,
                            a->pad_input != 0);
+  ICS_TRY(emu_attach(n, emu));
   ICS_TRY(alloc_params(n));
   // buffers first, sources after: a source's affine sits in the handle like a producer layer's
   ICS_TRY(alloc_layer(n, L, true, false));
@@ -3374,13 +3433,40 @@ int ics_op_conv_layer(ics_conv_layer* a) {
   }
   return 0;
 }
+int ics_op_conv_layer(ics_conv_layer* a) {
+  const std::string op = "ics_op_conv_layer: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(conv_layer_check(a, op));
+  if (a->ranks == 0) return conv_layer_body(a, nullptr);
+  int Cin = 0;
+  for (int i = 0; i < a->nsrc; ++i) Cin += a->src[i].C;
+  const size_t M = (size_t)a->B * a->S * a->S * a->S, C = (size_t)a->Cout, wn = (size_t)a->taps * Cin * C;
+  // rank r's view: its B samples of every [ranks * B] tensor, its row of every per-rank [ranks] output
+  auto body = [&](int r, BnSyncEmu* emu) -> int {
+    ics_conv_layer v = *a;
+    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
+    for (int i = 0; i < v.nsrc; ++i) {
+      const size_t cnt = (v.src[i].up ? M / 8 : M) * v.src[i].C;
+      v.src[i].x += (size_t)r * cnt;
+      off(v.src[i].dx, cnt);
+    }
+    if (v.dout) v.dout += (size_t)r * M * C;
+    off(v.y, M * C);
+    off(v.mean, C); off(v.rstd, C); off(v.scale, C); off(v.shift, C); off(v.moving_mean, C); off(v.moving_var, C);
+    off(v.dw, wn); off(v.dbias, C); off(v.dgamma, C); off(v.dbeta, C);
+    if (v.kernels) v.kernels += (size_t)r * (v.kernels_cap > 0 ? v.kernels_cap : 0);
+    ICS_TRY(conv_layer_body(&v, emu));
+    a->rows_per_block = v.rows_per_block; a->blocks = v.blocks;
+    return 0;
+  };
+  return run_emulated_ranks(op, a->ranks, a->Cout, 2, body);
+}
 
 // A producer and its consumer(s) through the engines' own construction and dispatch (include/icsg3d.h): what unet_build,
 // unet_forward_trunk and unet_backward do for that link, on a Net of two or three layers.  Nothing here chooses a kernel or
 // decides whether a fold is taken: the op only hands conv_backward the gradient sources and `next` of the link.
-int ics_op_conv_link(ics_conv_link* a) {
-  const std::string op = "ics_op_conv_link: ";
-  ICS_CHECK(a != nullptr, op + "null argument");
+static int conv_link_check(const ics_conv_link* a, const std::string& op) {
   ICS_CHECK(a->link >= ICS_LINK_SAME && a->link <= ICS_LINK_POOL_SKIP, op + "unknown link");
   ICS_CHECK(a->form == 0 || a->form == 1, op + "form must be 0 (U-Net) or 1 (VAE)");
   ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
@@ -3396,6 +3482,12 @@ int ics_op_conv_link(ics_conv_link* a) {
   ICS_CHECK(layer_ok(a->P), op + "P needs Cout, w, gamma and beta");
   ICS_CHECK(!has_k || layer_ok(a->K), op + "K needs Cout, w, gamma and beta");
   ICS_CHECK(!has_l || layer_ok(a->L), op + "L needs Cout, w, gamma and beta");
+  return 0;
+}
+static int conv_link_body(ics_conv_link* a, BnSyncEmu* emu) {
+  const std::string op = "ics_op_conv_link: ";
+  const bool has_k = a->link == ICS_LINK_POOL || a->link == ICS_LINK_POOL_SKIP, has_l = a->link != ICS_LINK_POOL;
+  const bool skip = a->link == ICS_LINK_POOL_SKIP;
   Net n;
   ICS_TRY(op_prepare(n));
   n.side_on = false;             // as unet_build
@@ -3407,6 +3499,7 @@ int ics_op_conv_link(ics_conv_link* a) {
   ConvLayer* L = nullptr;
   if (has_l)
     L = add_conv(n, "L", Cp + (skip ? a->Cq : 0), a->L.Cout, 27, a->link == ICS_LINK_UP ? 2 * S : S, pre, 1, post, false);
+  ICS_TRY(emu_attach(n, emu));
   ICS_TRY(alloc_params(n));
   ICS_TRY(alloc_layer(n, *P, true, has_k));
   if (K) ICS_TRY(alloc_layer(n, *K, true, false));
@@ -3517,6 +3610,37 @@ int ics_op_conv_link(ics_conv_link* a) {
   }
   return 0;
 }
+int ics_op_conv_link(ics_conv_link* a) {
+  const std::string op = "ics_op_conv_link: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(conv_link_check(a, op));
+  if (a->ranks == 0) return conv_link_body(a, nullptr);
+  const bool has_k = a->link == ICS_LINK_POOL || a->link == ICS_LINK_POOL_SKIP, skip = a->link == ICS_LINK_POOL_SKIP;
+  const size_t M = (size_t)a->B * a->S * a->S * a->S, Cp = (size_t)a->P.Cout;
+  const size_t rows_l = a->link == ICS_LINK_UP ? 8 * M : M;
+  const size_t cin_l = Cp + (skip ? (size_t)a->Cq : 0);
+  auto body = [&](int r, BnSyncEmu* emu) -> int {
+    ics_conv_link v = *a;
+    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
+    auto layer = [&](ics_conv_link_layer& l, size_t rows, size_t cin) {
+      const size_t C = (size_t)l.Cout;
+      off(l.y, rows * C);
+      off(l.mean, C); off(l.rstd, C); off(l.scale, C); off(l.shift, C);
+      off(l.dw, 27 * cin * C); off(l.dbias, C); off(l.dgamma, C); off(l.dbeta, C);
+    };
+    layer(v.P, M, (size_t)a->C0); layer(v.K, M / 8, Cp); layer(v.L, rows_l, cin_l);
+    v.x0 += (size_t)r * M * a->C0;
+    if (v.q) v.q += (size_t)r * (M / 8) * a->Cq;
+    v.dout += (size_t)r * (has_k ? (M / 8) * (size_t)a->K.Cout : rows_l * (size_t)a->L.Cout);
+    if (v.dout_l) v.dout_l += (size_t)r * M * a->L.Cout;
+    off(v.pooled, M / 8 * Cp); off(v.dy_p, M * Cp); off(v.dx0, M * a->C0);
+    if (v.sites) v.sites += (size_t)r * (v.sites_cap > 0 ? v.sites_cap : 0);
+    return conv_link_body(&v, emu);
+  };
+  const int cmax = std::max(a->P.Cout, std::max(has_k ? a->K.Cout : 0, a->link != ICS_LINK_POOL ? a->L.Cout : 0));
+  return run_emulated_ranks(op, a->ranks, cmax, 6, body);
+}
 
 // The two 1x1x1 heads + losses + metrics on a given trunk output (kernel parity tests against the reference's own formulas,
 // tests/golden/loss_golden.npz): the same two launch sequences unet_head_loss chooses between.
@@ -3563,6 +3687,67 @@ int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, con
   if (hmode && metrics) ICS_HIP(hipMemcpyAsync(metrics, dmet, 5 * 4, hipMemcpyDeviceToHost, n.st));
   if (hmode && sums) ICS_HIP(hipMemcpyAsync(sums, dsum, 7 * 8, hipMemcpyDeviceToHost, n.st));
   ICS_HIP(hipStreamSynchronize(n.st));
+  return 0;
+}
+
+// The U-Net's five metrics from the seven sums behind them (head_finalize_kernel, phase 2): what every rank of a
+// data-parallel step computes after the all-reduce of the per-rank sums ics_op_unet_head returns.
+int ics_op_unet_metrics_from_sums(const double sums[7], float metrics[5]) {
+  ICS_CHECK(sums && metrics, "ics_op_unet_metrics_from_sums: null argument");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_sum = L.add<double>(7);
+  const auto s_met = L.add<float>(8);
+  double* d_sum; float* d_met;
+  ICS_TRY(L.reserve(s_sum, &d_sum, s_met, &d_met));
+  ICS_TRY(L.upload(s_sum, sums, 7, st));
+  ICS_TRY(launch_head_metrics(st, nullptr, 0, 0.0, d_met, d_sum, 2));
+  ICS_TRY(L.download(metrics, s_met, 5, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// The DFC-VAE's loss assembly (vae_loss_kernel) in its three phases, on given partial sums (include/icsg3d.h).
+int ics_op_vae_loss(const float* mulv, int B, int latent, const double* mse_partial, int n_mse, double n_elems,
+                    const double* pm_partial, const int pm_n[4], const double pm_per[4], const float pm_w[4], float alpha,
+                    float beta, int phase, double sums[5], float metrics[4]) {
+  const std::string op = "ics_op_vae_loss: ";
+  ICS_CHECK(phase >= 0 && phase <= 2, op + "phase must be 0, 1 or 2");
+  ICS_CHECK(phase == 1 ? sums != nullptr : metrics != nullptr, op + "phase 1 needs sums, phases 0 and 2 need metrics");
+  ICS_CHECK(phase != 2 || sums != nullptr, op + "phase 2 needs sums");
+  PmSums pmc{};
+  size_t n_pm = 0;
+  if (phase != 2) {
+    ICS_CHECK(mulv && pm_n && pm_per && pm_w, op + "mulv, pm_n, pm_per and pm_w are required");
+    ICS_CHECK(B >= 1 && latent >= 1 && (size_t)B * latent <= ((size_t)1 << 24), op + "need B, latent >= 1 and B * latent <= 2^24");
+    ICS_CHECK(n_mse >= 0 && n_mse <= (1 << 20) && (n_mse == 0 || mse_partial) && n_elems > 0.0, op + "bad squared-error partials");
+    for (int l = 0; l < 4; ++l) {
+      ICS_CHECK(pm_n[l] >= 0 && pm_n[l] <= (1 << 20) && pm_per[l] > 0.0, op + "bad perceptual partials");
+      pmc.n[l] = pm_n[l]; pmc.per[l] = pm_per[l]; pmc.w[l] = pm_w[l];
+      n_pm += (size_t)pm_n[l];
+    }
+    ICS_CHECK(n_pm == 0 || pm_partial, op + "pm_partial is required");
+  }
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_mulv = L.add<float>(phase != 2 ? (size_t)B * 2 * latent : 0);
+  const auto s_mse = L.add<double>(phase != 2 ? (size_t)n_mse : 0);
+  const auto s_pm = L.add<double>(n_pm);
+  const auto s_sum = L.add<double>(8);
+  const auto s_met = L.add<float>(8);
+  float *d_mulv, *d_met;
+  double *d_mse, *d_pm, *d_sum;
+  ICS_TRY(L.reserve(s_mulv, &d_mulv, s_mse, &d_mse, s_pm, &d_pm, s_sum, &d_sum, s_met, &d_met));
+  ICS_TRY(L.upload(s_mulv, mulv, s_mulv.count, st));
+  ICS_TRY(L.upload(s_mse, mse_partial, s_mse.count, st));
+  ICS_TRY(L.upload(s_pm, pm_partial, s_pm.count, st));
+  if (phase == 2) ICS_TRY(L.upload(s_sum, sums, 5, st));
+  ICS_TRY(launch_vae_loss(st, d_mulv, 2 * latent, latent, B, d_mse, n_mse, n_elems, d_pm, pmc, alpha, beta, d_met, d_sum, phase));
+  if (phase == 1) ICS_TRY(L.download(sums, s_sum, 5, st));
+  else ICS_TRY(L.download(metrics, s_met, 4, st));
+  ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }
 

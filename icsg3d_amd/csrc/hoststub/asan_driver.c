@@ -990,13 +990,18 @@ static int run(int d, int C, int B, int with_comm) {
  * distinguish (Winograd 64 / 32 / S = 4, implicit GEMM, 1x1x1, thin-N, padded thin input, [skip | up], up only), forward
  * only and with the backward pass, on a handle larger than the batch, with buffers of the exact size; then the same
  * upsampled layers with the up-split switched off (the host-side 8-children sum) and every refusal. */
+static int g_ranks = 0;   /* ics_conv_layer.ranks / ics_conv_link.ranks of the *_one walkers: every buffer is sized for exactly
+                             that many ranks (batch tensors R * B samples, per-rank outputs [R], R site texts) */
 static int conv_layer_one(int B, int maxB, int S, int taps, int Cout, int form, int pad, int nsrc, const int* sc, const int* sup,
                           int aff, int bwd) {
   ics_conv_layer a;
-  char text[4096];
-  size_t M = (size_t)B * S * S * S;
+  const int R = g_ranks > 0 ? g_ranks : 1;
+  const int cap = 4096;
+  char* text = malloc((size_t)cap * R);
+  size_t M = (size_t)R * B * S * S * S;
   int Cin = 0;
   memset(&a, 0, sizeof a);
+  a.ranks = g_ranks;
   a.B = B; a.max_batch = maxB; a.S = S; a.taps = taps; a.Cout = Cout; a.pad_input = pad; a.nsrc = nsrc;
   a.has_bn = form != 2; a.pre_act = form == 0 ? 1 : 0; a.post_act = form == 1 ? 2 : 0;
   for (int i = 0; i < nsrc; ++i) {
@@ -1009,18 +1014,24 @@ static int conv_layer_one(int B, int maxB, int S, int taps, int Cout, int form, 
   }
   a.w = calloc((size_t)taps * Cin * Cout, 4); a.bias = calloc(Cout, 4); a.gamma = calloc(Cout, 4); a.beta = calloc(Cout, 4);
   a.y = malloc(M * Cout * 4);
-  a.mean = malloc(Cout * 4); a.rstd = malloc(Cout * 4); a.scale = malloc(Cout * 4); a.shift = malloc(Cout * 4);
-  a.moving_mean = malloc(Cout * 4); a.moving_var = malloc(Cout * 4);
-  if (bwd) {
-    a.dout = calloc(M * Cout, 4);
-    a.dw = malloc((size_t)taps * Cin * Cout * 4); a.dbias = malloc(Cout * 4); a.dgamma = malloc(Cout * 4); a.dbeta = malloc(Cout * 4);
+  {
+    const size_t pc = (size_t)R * Cout * 4;            /* per-rank outputs: [R][Cout] */
+    a.mean = malloc(pc); a.rstd = malloc(pc); a.scale = malloc(pc); a.shift = malloc(pc);
+    a.moving_mean = malloc(pc); a.moving_var = malloc(pc);
+    if (bwd) {
+      a.dout = calloc(M * Cout, 4);
+      a.dw = malloc((size_t)R * taps * Cin * Cout * 4); a.dbias = malloc(pc); a.dgamma = malloc(pc); a.dbeta = malloc(pc);
+    }
   }
-  a.kernels = text; a.kernels_cap = (int)sizeof text;
+  a.kernels = text; a.kernels_cap = cap;
   OK(ics_op_conv_layer(&a));
-  if (!strstr(text, "conv_fwd:L")) { fprintf(stderr, "conv layer: no forward launch site reported\n"); return 1; }
+  for (int r = 0; r < R; ++r)
+    if (!strstr(text + (size_t)r * cap, "conv_fwd:L")) { fprintf(stderr, "conv layer: no forward launch site reported\n"); return 1; }
   a.kernels_cap = 9;                                   /* truncated, still terminated */
   OK(ics_op_conv_layer(&a));
-  if (strlen(text) > 8) { fprintf(stderr, "conv layer: kernel text not truncated\n"); return 1; }
+  for (int r = 0; r < R; ++r)
+    if (strlen(text + 9 * r) > 8) { fprintf(stderr, "conv layer: kernel text not truncated\n"); return 1; }
+  free(text);
   for (int i = 0; i < nsrc; ++i) { free((void*)a.src[i].x); free((void*)a.src[i].scale); free((void*)a.src[i].shift); free(a.src[i].dx); }
   free((void*)a.w); free((void*)a.bias); free((void*)a.gamma); free((void*)a.beta); free((void*)a.dout); free(a.y);
   free(a.mean); free(a.rstd); free(a.scale); free(a.shift); free(a.moving_mean); free(a.moving_var);
@@ -1051,6 +1062,17 @@ static int conv_layer_walk(void) {
   c[0] = 32; c[1] = 64; if (conv_layer_one(2, 3, 4, 27, 64, 0, 0, 2, c, su, 1, 1)) return 1;
   c[0] = 32; if (conv_layer_one(3, 3, 4, 27, 16, 1, 0, 1, c, up1, 1, 1)) return 1;
   unsetenv("ICSG3D_NO_UPSPLIT");
+  /* emulated ranks (SyncBN through the rank tables): the geometry classes of tests/syncbn_cases.py, handle = and > batch */
+  for (g_ranks = 1; g_ranks <= 3; ++g_ranks)
+    for (int form = 0; form < 2; ++form)
+      for (int bwd = 0; bwd < 2; ++bwd) {
+        c[0] = 16; if (conv_layer_one(2, 2, 8, 27, 64, form, 0, 1, c, one, 1, bwd)) return 1;
+        c[0] = 16; if (conv_layer_one(2, 4, 4, 27, 6, form, 0, 1, c, one, 1, bwd)) return 1;
+        c[0] = 1; if (conv_layer_one(2, 3, 8, 27, 16, form, 1, 1, c, one, 0, bwd)) return 1;
+        c[0] = 16; c[1] = 32; if (conv_layer_one(2, 3, 8, 27, 16, form, 0, 2, c, su, 1, bwd)) return 1;
+        c[0] = 64; if (conv_layer_one(4, 4, 4, 27, 64, form, 0, 1, c, one, 1, bwd)) return 1;
+      }
+  g_ranks = 0;
   {
     ics_conv_layer a;
     float buf[8 * 4] = {0};
@@ -1072,6 +1094,9 @@ static int conv_layer_walk(void) {
     a.dw = buf; bad += ics_op_conv_layer(&a) == 0; a.dw = NULL;
     a.S = 1; a.src[0].up = 1; bad += ics_op_conv_layer(&a) == 0; a.S = 2; a.src[0].up = 0;
     a.w = NULL; bad += ics_op_conv_layer(&a) == 0; a.w = buf;
+    a.ranks = 5; bad += ics_op_conv_layer(&a) == 0;
+    a.ranks = -1; bad += ics_op_conv_layer(&a) == 0;
+    a.ranks = 2; a.max_batch = 0; bad += ics_op_conv_layer(&a) == 0; a.max_batch = 1; a.ranks = 0;   /* max_batch < B */
     if (bad) { fprintf(stderr, "conv layer: %d invalid argument sets accepted\n", bad); return 1; }
     OK(ics_op_conv_layer(&a));                                              /* still usable */
   }
@@ -1081,11 +1106,12 @@ static int conv_layer_walk(void) {
 /* ics_op_conv_link: every link in both forms, on a handle larger than the batch, with the linear folds at their default
  * threshold and forced on (ICSG3D_DGRAD_BNFUSE_MIN=0), without the up-split, under both tie rules; then every refusal. */
 static void link_layer(ics_conv_link_layer* l, int Cin, int Cout, size_t rows) {
+  const size_t pc = (size_t)(g_ranks > 0 ? g_ranks : 1) * Cout * 4;     /* per-rank outputs: [R][Cout] */
   l->Cout = Cout;
   l->w = calloc((size_t)27 * Cin * Cout, 4); l->bias = calloc(Cout, 4); l->gamma = calloc(Cout, 4); l->beta = calloc(Cout, 4);
   l->y = malloc(rows * Cout * 4);
-  l->mean = malloc(Cout * 4); l->rstd = malloc(Cout * 4); l->scale = malloc(Cout * 4); l->shift = malloc(Cout * 4);
-  l->dw = malloc((size_t)27 * Cin * Cout * 4); l->dbias = malloc(Cout * 4); l->dgamma = malloc(Cout * 4); l->dbeta = malloc(Cout * 4);
+  l->mean = malloc(pc); l->rstd = malloc(pc); l->scale = malloc(pc); l->shift = malloc(pc);
+  l->dw = malloc(pc * 27 * Cin); l->dbias = malloc(pc); l->dgamma = malloc(pc); l->dbeta = malloc(pc);
 }
 static void link_layer_free(ics_conv_link_layer* l) {
   free((void*)l->w); free((void*)l->bias); free((void*)l->gamma); free((void*)l->beta); free(l->y);
@@ -1094,11 +1120,14 @@ static void link_layer_free(ics_conv_link_layer* l) {
 static int conv_link_one(int link, int form, int B, int maxB, int S, int C0, int Cp, int Ck, int Cl, int Cq, int ties,
                          const char* site) {
   ics_conv_link a;
-  char text[8192];
-  const size_t M = (size_t)B * S * S * S;
+  const int R = g_ranks > 0 ? g_ranks : 1;
+  const int cap = 8192;
+  char* text = malloc((size_t)cap * R);
+  const size_t M = (size_t)R * B * S * S * S;            /* rows of every batch tensor: R * B samples */
   const int has_k = link >= ICS_LINK_POOL, has_l = link != ICS_LINK_POOL;
   const size_t ML = link == ICS_LINK_UP ? 8 * M : M;
   memset(&a, 0, sizeof a);
+  a.ranks = g_ranks;
   a.link = link; a.form = form; a.B = B; a.max_batch = maxB; a.S = S; a.C0 = C0; a.pool_ties_all = ties;
   a.x0 = calloc(M * C0, 4);
   link_layer(&a.P, C0, Cp, M);
@@ -1108,15 +1137,21 @@ static int conv_link_one(int link, int form, int B, int maxB, int S, int C0, int
   if (link == ICS_LINK_POOL_SKIP) { a.Cq = Cq; a.q = calloc(M / 8 * Cq, 4); a.dout_l = calloc(M * Cl, 4); }
   if (has_k) a.pooled = malloc(M / 8 * Cp * 4);
   a.dy_p = malloc(M * Cp * 4); a.dx0 = malloc(M * C0 * 4);
-  a.sites = text; a.sites_cap = (int)sizeof text;
+  a.sites = text; a.sites_cap = cap;
   OK(ics_op_conv_link(&a));
-  if (!strstr(text, "conv_fwd:P|") || !strstr(text, "bn_act_bwd:") || (site && !strstr(text, site))) {
-    fprintf(stderr, "conv link %d form %d: launch sites missing (%s) in\n%s", link, form, site ? site : "-", text);
-    return 1;
+  for (int r = 0; r < R; ++r) {
+    const char* t = text + (size_t)r * cap;
+    if (!strstr(t, "conv_fwd:P|") || !strstr(t, "bn_act_bwd:") || (site && !strstr(t, site)) || (g_ranks && strstr(t, "bnfuse:"))) {
+      fprintf(stderr, "conv link %d form %d ranks %d: launch sites missing (%s), or a fold under SyncBN, in\n%s", link, form,
+              g_ranks, site ? site : "-", t);
+      return 1;
+    }
   }
   a.sites_cap = 9;                                     /* truncated, still terminated */
   OK(ics_op_conv_link(&a));
-  if (strlen(text) > 8) { fprintf(stderr, "conv link: site text not truncated\n"); return 1; }
+  for (int r = 0; r < R; ++r)
+    if (strlen(text + 9 * r) > 8) { fprintf(stderr, "conv link: site text not truncated\n"); return 1; }
+  free(text);
   free((void*)a.x0); free((void*)a.q); free((void*)a.dout); free((void*)a.dout_l); free(a.pooled); free(a.dy_p); free(a.dx0);
   link_layer_free(&a.P);
   if (has_k) link_layer_free(&a.K);
@@ -1152,6 +1187,21 @@ static int conv_link_walk(void) {
   setenv("ICSG3D_NO_POOL_PRESUM", "1", 1);
   if (conv_link_one(ICS_LINK_POOL, 0, 3, 5, 8, 16, 64, 64, 0, 0, 1, "pool_fwd")) return 1;
   unsetenv("ICSG3D_NO_POOL_PRESUM");
+  /* emulated ranks: every link, both forms, the folds forced on (they must be refused: no "bnfuse:" row), handle > batch */
+  setenv("ICSG3D_DGRAD_BNFUSE_MIN", "0", 1);
+  for (g_ranks = 1; g_ranks <= 3; ++g_ranks)
+    for (int form = 0; form < 2; ++form) {
+      if (conv_link_one(ICS_LINK_SAME, form, 2, 2, 8, 16, 64, 0, 128, 0, 1, "bn_act_bwd:P")) return 1;
+      if (conv_link_one(ICS_LINK_SAME, form, 2, 3, 8, 16, 72, 0, 32, 0, 1, "bn_act_bwd:P")) return 1;
+      if (conv_link_one(ICS_LINK_UP, form, 2, 4, 4, 16, 32, 0, 16, 0, 1, "conv_dgrad:L.up|")) return 1;
+      for (int ties = 0; ties < 2; ++ties) {
+        if (conv_link_one(ICS_LINK_POOL, form, 3, 4, 8, 16, 64, 64, 0, 0, ties, form == 0 ? "pool_presum:P" : "pool_fwd")) return 1;
+        if (conv_link_one(ICS_LINK_POOL, form, 2, 2, 8, 16, 16, 32, 0, 0, ties, "pool_fwd")) return 1;
+        if (conv_link_one(ICS_LINK_POOL_SKIP, form, 2, 3, 8, 16, 64, 64, 128, 128, ties, "conv_dgrad:L.skip|")) return 1;
+      }
+    }
+  g_ranks = 0;
+  unsetenv("ICSG3D_DGRAD_BNFUSE_MIN");
   {
     ics_conv_link a;
     float buf[27 * 4 * 4 + 64] = {0};
@@ -1176,6 +1226,9 @@ static int conv_link_walk(void) {
     a.S = 1; a.K = a.P; bad += ics_op_conv_link(&a) == 0; a.S = 2;                  /* nothing to pool */
     a.link = ICS_LINK_POOL_SKIP; bad += ics_op_conv_link(&a) == 0;                  /* q, Cq, dout_l missing */
     a.link = ICS_LINK_SAME;
+    a.ranks = 5; bad += ics_op_conv_link(&a) == 0;
+    a.ranks = -1; bad += ics_op_conv_link(&a) == 0;
+    a.ranks = 3; a.max_batch = 0; bad += ics_op_conv_link(&a) == 0; a.max_batch = 1; a.ranks = 0;   /* max_batch < B */
     if (bad) { fprintf(stderr, "conv link: %d invalid argument sets accepted\n", bad); return 1; }
     OK(ics_op_conv_link(&a));                                                       /* still usable */
   }
@@ -1224,6 +1277,35 @@ int main(void) {
     for (int f = 0; f < 2; ++f)
       for (int mode = 0; mode < 3; ++mode) OK(ics_op_unet_head(x, ws, bs, wg, bg, lab, M, 95, 0.f, mode, f, out, met, sums));
     free(x); free(ws); free(bs); free(wg); free(out); free(lab);
+    /* ... and the finalisation from (all-reduced) sums */
+    sums[6] = 64.0;
+    OK(ics_op_unet_metrics_from_sums(sums, met));
+    if (ics_op_unet_metrics_from_sums(NULL, met) == 0 || ics_op_unet_metrics_from_sums(sums, NULL) == 0) {
+      fprintf(stderr, "metrics from sums: null argument accepted\n"); return 1;
+    }
+  }
+  {   /* the DFC-VAE loss assembly in its three phases, buffers of the exact size */
+    const int B = 3, latent = 20, n_mse = 5, pm_n[4] = {3, 0, 2, 1};
+    const double per[4] = {8, 4, 2, 1};
+    const float w[4] = {1.f, 0.f, 1.f, 1.f};
+    float* mulv = calloc((size_t)B * 2 * latent, 4), met[4];
+    double *mse = calloc(n_mse, 8), *pm = calloc(6, 8), sums[5] = {0, 0, 0, 0, 0};
+    int bad = 0;
+    OK(ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, NULL, met));
+    OK(ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 1, sums, NULL));
+    sums[3] = 3; sums[4] = 100;
+    OK(ics_op_vae_loss(NULL, 0, 0, NULL, 0, 0.0, NULL, NULL, NULL, NULL, 0.5f, 3e-4f, 2, sums, met));
+    bad += ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 3, sums, met) == 0;
+    bad += ics_op_vae_loss(NULL, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, sums, met) == 0;
+    bad += ics_op_vae_loss(mulv, 0, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, sums, met) == 0;
+    bad += ics_op_vae_loss(mulv, B, latent, NULL, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, sums, met) == 0;
+    bad += ics_op_vae_loss(mulv, B, latent, mse, n_mse, 0.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, sums, met) == 0;
+    bad += ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, NULL, pm_n, per, w, 0.5f, 3e-4f, 0, sums, met) == 0;
+    bad += ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 1, NULL, met) == 0;
+    bad += ics_op_vae_loss(mulv, B, latent, mse, n_mse, 100.0, pm, pm_n, per, w, 0.5f, 3e-4f, 0, sums, NULL) == 0;
+    bad += ics_op_vae_loss(NULL, 0, 0, NULL, 0, 0.0, NULL, NULL, NULL, NULL, 0.5f, 3e-4f, 2, NULL, met) == 0;
+    if (bad) { fprintf(stderr, "vae loss: %d invalid argument sets accepted\n", bad); return 1; }
+    free(mulv); free(mse); free(pm);
   }
   {   /* connected components on host arrays */
     const int B = 2, d = 16;

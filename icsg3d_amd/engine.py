@@ -570,7 +570,7 @@ def conv3d_forward(x, w, bias=None, pre_act=0):
 
 
 def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=0, has_bn=True, post_act=0,
-               pad_input=False, max_batch=None, want_dx=True):
+               pad_input=False, max_batch=None, want_dx=True, ranks=0):
     """Single-op entry (ics_op_conv_layer): one layer through the engines' own construction and dispatch -- affine /
     activated / upsampled sources, the statistics epilogue, workspaces sized for max_batch.
 
@@ -580,9 +580,18 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
 
     Returns a dict: y; with has_bn mean, rstd, scale, shift, moving_mean, moving_var, rows_per_block, blocks; with dout
     dw, dbias, (dgamma, dbeta), dx (a list, one array per source, shaped as its x); and kernels: {"fwd": [...],
-    "dgrad": [...], "wgrad": [...]} -- "<launch site>|<kernel template instantiation>" of every conv launch."""
+    "dgrad": [...], "wgrad": [...]} -- "<launch site>|<kernel template instantiation>" of every conv launch.
+
+    ranks = R in 1..4: R emulated data-parallel ranks with SyncBN (ics_conv_layer.ranks).  The sources' x and dout hold
+    R * B samples, rank-major, and so do y and dx; the statistics, the moving statistics and the parameter gradients
+    (each rank's local sums) get a leading (R,), and kernels becomes a list of R such dicts."""
     lib = L.load()
+    R = int(ranks)
+    if not 0 <= R <= 4:
+        raise ValueError("ranks must be in 0..4")
+    lead = (R,) if R else ()
     a = L.ConvLayerArgs()
+    a.ranks = R
     keep = []                                     # arrays the struct points into
 
     def f(v):
@@ -601,7 +610,10 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     taps, Cout = w.shape[0] ** 3, w.shape[4]
     srcs = [dict(s) for s in sources]
     x0 = _f32(srcs[0]["x"])
-    B = x0.shape[0]
+    NB = x0.shape[0]                              # samples in the tensors: B of each rank
+    if NB % max(R, 1):
+        raise ValueError("the batch does not divide into %d equal shards" % R)
+    B = NB // max(R, 1)
     S = x0.shape[1] * (2 if srcs[0].get("up") else 1)
     if sum(_f32(s["x"]).shape[4] for s in srcs) != w.shape[3]:
         raise ValueError("the sources' channels do not add up to the kernel's Cin")
@@ -611,7 +623,7 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     for i, s in enumerate(srcs):
         x = _f32(s["x"])
         up = 1 if s.get("up") else 0
-        if x.shape[:4] != (B,) + (S // 2 if up else S,) * 3:
+        if x.shape[:4] != (NB,) + (S // 2 if up else S,) * 3:
             raise ValueError("source %d has shape %s" % (i, x.shape))
         a.src[i].x, a.src[i].scale, a.src[i].shift = f(x), f(s.get("scale")), f(s.get("shift"))
         a.src[i].C, a.src[i].up, a.src[i].act = x.shape[4], up, int(s.get("act", 0))
@@ -619,33 +631,39 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
             dxs.append(out(x.shape))
             a.src[i].dx = L.fptr(dxs[-1])
     a.w, a.bias, a.gamma, a.beta, a.dout = f(w), f(bias), f(gamma), f(beta), f(dout)
-    r = {"y": out((B, S, S, S, Cout))}
+    r = {"y": out((NB, S, S, S, Cout))}
     a.y = L.fptr(r["y"])
     if has_bn:
         for k in ("mean", "rstd", "scale", "shift", "moving_mean", "moving_var"):
-            r[k] = out((Cout,))
+            r[k] = out(lead + (Cout,))
             setattr(a, k, L.fptr(r[k]))
     if dout is not None:
-        r["dw"], r["dbias"] = out(w.shape), out((Cout,))
+        r["dw"], r["dbias"] = out(lead + w.shape), out(lead + (Cout,))
         a.dw, a.dbias = L.fptr(r["dw"]), L.fptr(r["dbias"])
         if has_bn:
-            r["dgamma"], r["dbeta"] = out((Cout,)), out((Cout,))
+            r["dgamma"], r["dbeta"] = out(lead + (Cout,)), out(lead + (Cout,))
             a.dgamma, a.dbeta = L.fptr(r["dgamma"]), L.fptr(r["dbeta"])
         r["dx"] = dxs
-    text = C.create_string_buffer(16384)
-    a.kernels, a.kernels_cap = C.cast(text, C.c_void_p), len(text)
+    cap = 16384
+    text = C.create_string_buffer(cap * max(R, 1))
+    a.kernels, a.kernels_cap = C.cast(text, C.c_void_p), cap
     L.check(lib.ics_op_conv_layer(C.byref(a)))
     if has_bn:
         r["rows_per_block"], r["blocks"] = a.rows_per_block, a.blocks
-    lines = text.value.decode().splitlines()
-    r["kernels"] = {k: [ln for ln in lines if ln.startswith("conv_%s:" % k)] for k in ("fwd", "dgrad", "wgrad")}
+
+    def kernels(i):
+        lines = text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines()
+        return {k: [ln for ln in lines if ln.startswith("conv_%s:" % k)] for k in ("fwd", "dgrad", "wgrad")}
+
+    r["kernels"] = [kernels(i) for i in range(R)] if R else kernels(0)
     return r
 
 
 LINKS = ("same", "up", "pool", "pool_skip")
+METRIC_SUM_KEYS = ("sum_lsoft", "sum_lsig", "tp", "predicted", "wr_tp", "wr_possible", "voxels")
 
 
-def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_ties_all=True, max_batch=None):
+def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_ties_all=True, max_batch=None, ranks=0):
     """Single-op entry (ics_op_conv_link): a producer P and its consumer(s) through the engines' own construction,
     forward (training) and backward calls, with the gradient sources and `next` unet_backward gives that link.
 
@@ -654,9 +672,18 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
     dout: gradient w.r.t. the output of L ("same", "up") or K ("pool", "pool_skip"); dout_l and q: "pool_skip" only.
 
     Returns {"P": {...}, "K": {...}, "L": {...}} with y, mean, rstd, scale, shift, dw, dbias, dgamma, dbeta per layer,
-    plus pooled (pool links), dy_p, dx0 and sites: the profiler's rows in launch order ("<site>" or "<site>|<kernel>")."""
+    plus pooled (pool links), dy_p, dx0 and sites: the profiler's rows in launch order ("<site>" or "<site>|<kernel>").
+
+    ranks = R in 1..4: R emulated data-parallel ranks with SyncBN (ics_conv_link.ranks): x0, q, dout, dout_l, y, pooled,
+    dy_p and dx0 hold R * B samples, rank-major; the statistics and the parameter gradients (local sums) get a leading
+    (R,); sites becomes a list of R lists."""
     lib = L.load()
+    R = int(ranks)
+    if not 0 <= R <= 4:
+        raise ValueError("ranks must be in 0..4")
+    lead = (R,) if R else ()
     a = L.ConvLinkArgs()
+    a.ranks = R
     keep = []
 
     def f(v):
@@ -672,7 +699,10 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
         return v
 
     x0 = _f32(x0)
-    B, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
+    NB, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
+    if NB % max(R, 1):
+        raise ValueError("the batch does not divide into %d equal shards" % R)
+    B = NB // max(R, 1)
     a.link, a.form = LINKS.index(link), {"unet": 0, "vae": 1}[form]
     a.B, a.max_batch, a.S, a.C0 = B, int(max_batch or B), S, C0
     a.pool_ties_all = int(bool(pool_ties_all))
@@ -685,22 +715,61 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
         w = _f32(p["w"])
         Cout = w.shape[4]
         h.Cout, h.w, h.bias, h.gamma, h.beta = Cout, f(w), f(p.get("bias")), f(p["gamma"]), f(p["beta"])
-        o = r[name] = {"y": out((B,) + (side[name],) * 3 + (Cout,)), "dw": out(w.shape)}
+        o = r[name] = {"y": out((NB,) + (side[name],) * 3 + (Cout,)), "dw": out(lead + w.shape)}
         for k in ("mean", "rstd", "scale", "shift", "dbias", "dgamma", "dbeta"):
-            o[k] = out((Cout,))
+            o[k] = out(lead + (Cout,))
         for k, v in o.items():
             setattr(h, k, L.fptr(v))
     Cp = r["P"]["y"].shape[4]
     if "K" in layers:
-        r["pooled"] = out((B,) + (S // 2,) * 3 + (Cp,))
+        r["pooled"] = out((NB,) + (S // 2,) * 3 + (Cp,))
         a.pooled = L.fptr(r["pooled"])
-    r["dy_p"], r["dx0"] = out((B, S, S, S, Cp)), out(x0.shape)
+    r["dy_p"], r["dx0"] = out((NB, S, S, S, Cp)), out(x0.shape)
     a.dy_p, a.dx0 = L.fptr(r["dy_p"]), L.fptr(r["dx0"])
-    text = C.create_string_buffer(32768)
-    a.sites, a.sites_cap = C.cast(text, C.c_void_p), len(text)
+    cap = 32768
+    text = C.create_string_buffer(cap * max(R, 1))
+    a.sites, a.sites_cap = C.cast(text, C.c_void_p), cap
     L.check(lib.ics_op_conv_link(C.byref(a)))
-    r["sites"] = text.value.decode().splitlines()
+    sites = [text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines() for i in range(max(R, 1))]
+    r["sites"] = sites if R else sites[0]
     return r
+
+
+def unet_metrics_from_sums(sums):
+    """Single-op entry (ics_op_unet_metrics_from_sums): [Loss, lsoft, lsig, f1, wr] from the seven sums unet_head returns
+    (a dict, or 7 numbers in its key order), e.g. added over the shards of a global batch."""
+    lib = L.load()
+    if isinstance(sums, dict):
+        sums = [sums[k] for k in METRIC_SUM_KEYS]
+    s = (C.c_double * 7)(*[float(v) for v in sums])
+    m = np.zeros(5, np.float32)
+    L.check(lib.ics_op_unet_metrics_from_sums(s, L.fptr(m)))
+    return m
+
+
+def vae_loss(mulv=None, mse_partial=(), n_elems=1.0, pm_partials=((), (), (), ()), pm_per=(1.0,) * 4, pm_w=(1.0,) * 4,
+             alpha=0.5, beta=3e-4, phase=0, sums=None):
+    """Single-op entry (ics_op_vae_loss): the DFC-VAE's loss assembly on given partial sums.  mulv (B, 2 * latent);
+    mse_partial: partial sums of the squared error over n_elems elements; pm_partials: four arrays of partial sums, one per
+    perceptual tap, with pm_per elements per sample and the weights pm_w.  phase 0 -> metrics [Loss, PM, MSE, KLD];
+    phase 1 -> sums (5,) float64 {KL, squared error, weighted PM, B, n_elems}; phase 2 (sums given) -> metrics."""
+    lib = L.load()
+    m = np.zeros(4, np.float32)
+    s = (C.c_double * 5)(*([float(v) for v in sums] if sums is not None else [0.0] * 5))
+    if phase == 2:
+        L.check(lib.ics_op_vae_loss(None, 0, 0, None, 0, 0.0, None, None, None, None, float(alpha), float(beta), 2, s, L.fptr(m)))
+        return m
+    mulv = _f32(mulv)
+    B, latent = mulv.shape[0], mulv.shape[1] // 2
+    mse = np.ascontiguousarray(mse_partial, np.float64).reshape(-1)
+    pm = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float64).reshape(-1) for p in pm_partials]), np.float64)
+    n = (C.c_int * 4)(*[int(np.asarray(p).size) for p in pm_partials])
+    per = (C.c_double * 4)(*[float(v) for v in pm_per])
+    w = np.ascontiguousarray(pm_w, np.float32)
+    dp = lambda v: v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None
+    L.check(lib.ics_op_vae_loss(L.fptr(mulv), B, latent, dp(mse), int(mse.size), float(n_elems), dp(pm), n, per, L.fptr(w),
+                                float(alpha), float(beta), int(phase), s, L.fptr(m)))
+    return np.array(list(s), np.float64) if phase == 1 else m
 
 
 def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False):
@@ -716,8 +785,7 @@ def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weig
     L.check(lib.ics_op_unet_head(L.fptr(x), L.fptr(wsoft), L.fptr(bsoft), L.fptr(wsig), L.fptr(bsig), L.u8ptr(lab), M, ncls,
                                  float(loss_weight), int(mode) | (4 if bce_from_logits else 0), 1 if fused else 0, L.fptr(out),
                                  L.fptr(m), s))
-    keys = ("sum_lsoft", "sum_lsig", "tp", "predicted", "wr_tp", "wr_possible", "voxels")
-    return out, m, dict(zip(keys, [float(v) for v in s]))
+    return out, m, dict(zip(METRIC_SUM_KEYS, [float(v) for v in s]))
 
 
 def conv3d_backward(x, w, dy):

@@ -700,7 +700,23 @@ typedef struct ics_conv_layer {
                          "conv_dgrad:L|<kernel>", "conv_wgrad:L.skip|<kernel>", ... -- <kernel> is the exact template
                          instantiation (as rocprofv3 names it) the site launched                                       */
   int kernels_cap;    /* bytes behind `kernels` (the text is truncated to fit, always NUL-terminated)                 */
+  int ranks;          /* 0: one process, no SyncBN (every field as described above).  R = 1 .. 4: R data-parallel ranks
+                         with SyncBN, EMULATED in this one call -- see "emulated ranks" below                          */
 } ics_conv_layer;
+/* Emulated ranks (ics_conv_layer.ranks, ics_conv_link.ranks = R in 1 .. 4).  B is then the PER-RANK batch and every rank
+ * holds an equal shard: the SyncBN backward divides by B * S^3 * R (launch_layer_bwd and launch_head_bnfuse take the global
+ * count as n * nranks), so unequal shards are not served, here or in a real data-parallel run.  Every input and output
+ * tensor with a batch dimension holds R * B samples, rank-major (rank r owns samples [r B, (r + 1) B)); every other output
+ * gets a leading [R]: mean, rstd, scale, shift, the moving statistics, dw, dbias, dgamma, dbeta (the parameter gradients
+ * are each rank's LOCAL sums -- the gradient all-reduce of a train step is not part of this call), and `kernels` /
+ * `sites`, which hold R texts of kernels_cap / sites_cap bytes each.  The parameters are shared by the ranks.
+ * The call runs the body described above once per rank on that rank's shard, one rank after another on one stream, each
+ * with a handle of its own whose SyncBN exchanges (the all-gather of launch_bn_finalize, the all-reduce of
+ * launch_layer_bwd) go through device tables that outlive the handles instead of through RCCL; it repeats the ranks until
+ * no table entry changes any more (at most collectives + 1 times, else it fails naming the collective) and returns the
+ * outputs of the last repetition.  Every decision that depends on SyncBN being on (no producer BatchNorm-backward folds
+ * that need local statistics, no xhat affine) is then taken as in a multi-rank run.  R = 1 runs the SyncBN kernels with
+ * one rank.  No second process, no thread, no RCCL. */
 int ics_op_conv_layer(ics_conv_layer* a);
 
 /* Two or three layers LINKED the way the engines link them (kernel parity tests, tests/test_gpu_conv_link.py): a producer
@@ -747,6 +763,7 @@ typedef struct ics_conv_link {
   char* sites;        /* out, optional: every profiler row of the call, one per line, in first-launch order: "bnfuse:L",
                          "pool_presum:P", "bn_act_bwd:P", "conv_dgrad:L|<kernel template instantiation>", ...          */
   int sites_cap;      /* bytes behind `sites` (truncated to fit, always NUL-terminated)                               */
+  int ranks;          /* 0: no SyncBN; 1 .. 4: emulated data-parallel ranks with SyncBN, B per rank (see ics_conv_layer) */
 } ics_conv_link;
 int ics_op_conv_link(ics_conv_link* a);
 
@@ -760,6 +777,18 @@ int ics_op_conv_link(ics_conv_link* a);
 int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
                      const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
                      float metrics[5], double sums[7]);
+/* metrics[5] = [Loss, lsoft, lsig, f1, wr] from the seven sums of ics_op_unet_head (ics_unet_metric_sums), added over the
+ * shards of a global batch: the finalisation every rank of a data-parallel step runs after the all-reduce of the sums. */
+int ics_op_unet_metrics_from_sums(const double sums[7], float metrics[5]);
+/* The DFC-VAE's loss assembly on given partial sums.  mulv [B][2 * latent] = (mu | log variance); mse_partial [n_mse]
+ * partial sums of the squared error over n_elems = B * voxels * channels elements; pm_partial: the partial sums of the four
+ * perceptual taps one after another, pm_n[l] of them for tap l, pm_per[l] elements per sample and pm_w[l] the tap's weight.
+ * phase 0: metrics[4] = [Loss, PM, MSE, KLD];  1: sums[5] = {KL, squared error, weighted PM, B, n_elems} only (out);
+ * 2: metrics from sums (in; the other inputs are not read) -- the two halves a data-parallel step puts around its
+ * all-reduce.  Loss = MSE + alpha PM + beta KLD. */
+int ics_op_vae_loss(const float* mulv, int B, int latent, const double* mse_partial, int n_mse, double n_elems,
+                    const double* pm_partial, const int pm_n[4], const double pm_per[4], const float pm_w[4], float alpha,
+                    float beta, int phase, double sums[5], float metrics[4]);
 /* kernel micro-benchmark on device-resident constant data, HIP-event timed: mode 0 forward
  * (ablate 0 = full kernel, 1 = MFMA+LDS reads only, 2 = MFMA only), 1 backward-data, 2 backward-weight. */
 int ics_op_conv3d_bench(int B, int S, int Cin, int Cout, int taps, int mode, int ablate, int iters,

@@ -14,7 +14,14 @@ from the convolution's own rounding.
 
 Also here: the value regimes the statistics are tested in (regime_params), two float32 emulations of the statistic
 (two-pass within blocks, merged in fp64, as the kernels do; and the one-pass sum a wrong kernel would do), and the
-per-channel bounds (test_conv_layer_host.py calibrates them on the CPU)."""
+per-channel bounds (test_conv_layer_host.py calibrates them on the CPU).
+
+Data-parallel ranks with SyncBN (ics_conv_layer.ranks): the reference of R ranks at B samples each IS this reference on
+the concatenated batch of R B.  ranks = R in layer_forward / layer_backward evaluates the same thing by the SHARDED route
+instead -- per-shard (n, mean, M2) merged in rank order, per-shard (sum d, sum d xhat) added over the ranks, dy from the
+global sums -- which tests/test_syncbn_host.py shows equal to the whole-batch route at 1e-12; shard_grads gives each
+rank's local parameter gradients (its shard's contribution under the global statistics).  rank_regimes builds the
+rank-heterogeneous inputs, stats_sharded32 the float32 emulation of the kernels' two merges."""
 import numpy as np
 
 from oracle import numpy_ref as R
@@ -87,8 +94,48 @@ def channel_stats(y):
     return mean, ((yf - mean) ** 2).mean(0)
 
 
+def shard_moments(s, R):
+    """(n, mean, M2), each (R, C): the moments of the R equal shards of s (R B, ..., C), rank-major"""
+    xs = np.asarray(s).reshape(R, -1, s.shape[-1])
+    mean = xs.mean(1)
+    return np.full(mean.shape, float(xs.shape[1])), mean, ((xs - mean[:, None]) ** 2).sum(1)
+
+
+def merge_moments(n, mean, M2):
+    """Chan et al., in rank order, as bn_sync_finalize_kernel: (n, mean, biased variance) of the global batch"""
+    nt, mt, qt = np.zeros_like(mean[0]), np.zeros_like(mean[0]), np.zeros_like(mean[0])
+    for nb, mb, qb in zip(n, mean, M2):
+        tot, d = nt + nb, mb - mt
+        qt = qt + qb + d * d * nt * nb / tot
+        mt = mt + d * nb / tot
+        nt = tot
+    return nt, mt, qt / nt
+
+
+def moving_after_one_update(mean, var, n, unbias=True, momentum=0.99):
+    """the moving statistics after one update from (0, 1): the variance fed to the average is rescaled by n / (n - (1 + eps))
+    with n the number of rows of the GLOBAL batch (numpy_ref's note on the Keras 2.3 quirk)"""
+    v = var * (n / (n - (1.0 + EPS))) if unbias else var
+    return mean * (1 - momentum), momentum + v * (1 - momentum)
+
+
+def bn_bwd_sharded(s, gamma, mean, var, d, R, eps):
+    """numpy_ref.bn_train_bwd by the SyncBN route: every shard's (sum d, sum d xhat), added in rank order, divided by the
+    global count.  Returns dx and the PER-SHARD dgamma, dbeta, each (R, C)."""
+    C = s.shape[-1]
+    rstd = 1.0 / np.sqrt(var + eps)
+    xhat = (s - mean) * rstd
+    s1r = d.reshape(R, -1, C).sum(1)
+    s2r = (d * xhat).reshape(R, -1, C).sum(1)
+    s1, s2 = 0.0, 0.0
+    for r in range(R):
+        s1, s2 = s1 + s1r[r], s2 + s2r[r]
+    n = s.size // C
+    return (gamma * rstd) * (d - s1 / n - xhat * (s2 / n)), s2r, s1r
+
+
 def layer_forward(sources, w, bias, gamma=None, beta=None, pre_act=0, has_bn=True, post_act=0, stored_y=None,
-                  dtype=np.float64, eps=EPS):
+                  dtype=np.float64, eps=EPS, ranks=0):
     """Returns a dict: V, y (this evaluation's own), s (the y everything behind it is computed from: stored_y if given),
     and with has_bn mean, var, rstd, scale, shift, bn, o.  eps: the kernels' float32 1e-3 (numpy_ref.BN_EPS is the double)."""
     V = virtual_input(sources, dtype)
@@ -98,7 +145,8 @@ def layer_forward(sources, w, bias, gamma=None, beta=None, pre_act=0, has_bn=Tru
     f = {"V": V, "y": y, "s": y if stored_y is None else np.asarray(stored_y, dtype), "eps": dtype(eps)}
     if has_bn:
         g, bt = np.asarray(gamma, dtype), np.asarray(beta, dtype)
-        bn, mean, var = R.bn_train_fwd(f["s"], g, bt, eps=f["eps"])
+        mom = None if ranks < 2 else (lambda x: merge_moments(*shard_moments(x, ranks))[1:])
+        bn, mean, var = R.bn_train_fwd(f["s"], g, bt, eps=f["eps"], moments=mom)
         rstd = 1.0 / np.sqrt(var + f["eps"])
         f.update(mean=mean, var=var, rstd=rstd, scale=g * rstd, shift=bt - mean * g * rstd, bn=bn,
                  o=R.act_fwd(bn, ACT[post_act]))
@@ -107,11 +155,17 @@ def layer_forward(sources, w, bias, gamma=None, beta=None, pre_act=0, has_bn=Tru
     return f
 
 
-def layer_backward(f, sources, w, gamma, dout, pre_act=0, has_bn=True, post_act=0, kink_y=None, kink_bn=None):
+def layer_backward(f, sources, w, gamma, dout, pre_act=0, has_bn=True, post_act=0, kink_y=None, kink_bn=None, ranks=0,
+                   strict_dtype=False):
     """Gradients of the layer given dout = dLoss/do, in the dtype of f.  kink_y / kink_bn: the implementation's stored y /
     its own fp32 BatchNorm output; they decide act'(.) (numpy_ref.apply_kink's rule).  Returns dw, dbias, dgamma, dbeta, dx
     (one per source: the gradient w.r.t. its part of V, summed over the 8 children where it is upsampled) and `pinned`,
-    the number of decisions that differ from this evaluation's own."""
+    the number of decisions that differ from this evaluation's own.
+    strict_dtype: numpy_ref.act_bwd multiplies by np.where(x > 0, 1.0, 0.3) for the LeakyReLU, a float64 array, so behind
+    it a float32 evaluation silently continues in float64 (sums, c1 / c2, dy, the convolution's gradients) and its error
+    against fp64 is that of the forward pass alone; True casts back to the evaluation's dtype after each activation, which
+    is what "the plain formulas in float32" means.  tests/test_gpu_syncbn.py takes e32 this way; the older tests keep
+    the yardstick they were calibrated with (in the LeakyReLU form a smaller, i.e. stricter, one)."""
     dtype = f["y"].dtype.type
     w = np.asarray(w, dtype)
     d = np.asarray(dout, dtype)
@@ -121,11 +175,21 @@ def layer_backward(f, sources, w, gamma, dout, pre_act=0, has_bn=True, post_act=
         if ACT[post_act] is not None:
             out["pinned"] += int(((dec > 0) != (f["bn"] > 0)).sum())
         d = R.act_bwd(dec, d, ACT[post_act])
-        d, out["dgamma"], out["dbeta"] = R.bn_train_bwd(f["s"], np.asarray(gamma, dtype), f["mean"], f["var"], d, eps=f["eps"])
+        if strict_dtype:
+            d = np.asarray(d, dtype)
+        out["d_bn"] = d
+        if ranks < 2:
+            d, out["dgamma"], out["dbeta"] = R.bn_train_bwd(f["s"], np.asarray(gamma, dtype), f["mean"], f["var"], d, eps=f["eps"])
+        else:
+            d, dg, db = bn_bwd_sharded(f["s"], np.asarray(gamma, dtype), f["mean"], f["var"], d, ranks, f["eps"])
+            out["dgamma"], out["dbeta"] = dg.sum(0), db.sum(0)
     dec = f["s"] if kink_y is None else np.asarray(kink_y, dtype)
     if ACT[pre_act] is not None:
         out["pinned"] += int(((dec > 0) != (f["y"] > 0)).sum())
     dy = R.act_bwd(dec, d, ACT[pre_act])
+    if strict_dtype:
+        dy = np.asarray(dy, dtype)
+    out["dy"] = dy
     dV, out["dw"], out["dbias"] = R.conv3d_bwd(f["V"], w, dy)
     out["dx"], c0 = [], 0
     for s in sources:
@@ -134,6 +198,115 @@ def layer_backward(f, sources, w, gamma, dout, pre_act=0, has_bn=True, post_act=
         out["dx"].append(R.upsample_bwd(g) if s.get("up") else g)
         c0 += C
     return out
+
+
+def shard_grads(f, b, w, R, has_bn=True):
+    """Each rank's LOCAL parameter gradients given the layer's forward f and backward b (of the global batch): the
+    contribution of its shard, with the global statistics.  A list of R dicts dw, dbias, (dgamma, dbeta)."""
+    dtype = f["y"].dtype.type
+    w = np.asarray(w, dtype)
+    B = f["V"].shape[0] // R
+    out = []
+    if has_bn:
+        xhat = (f["s"] - f["mean"]) * f["rstd"]
+        C = xhat.shape[-1]
+        dg = (b["d_bn"] * xhat).reshape(R, -1, C).sum(1)
+        db = b["d_bn"].reshape(R, -1, C).sum(1)
+    for r in range(R):
+        sl = slice(r * B, (r + 1) * B)
+        _, dw, dbias = R_conv3d_bwd(f["V"][sl], w, b["dy"][sl])
+        g = {"dw": dw, "dbias": dbias}
+        if has_bn:
+            g.update(dgamma=dg[r], dbeta=db[r])
+        out.append(g)
+    return out
+
+
+def R_conv3d_bwd(V, w, dy):
+    return R.conv3d_bwd(V, w, dy)
+
+
+# ---- rank-heterogeneous value regimes of y: input channel 0 is the CARRIER, constant within a rank; an output channel in
+# one of these regimes reads it through its centre tap only (which never meets the zero padding), so its y is the
+# ordinary conv part (std ~ 1) plus a per-rank constant, or -- "rank_const", "rank_zero" -- that constant alone
+RANK_REGIMES = ("rank_shift50", "rank_const", "rank_zero", "rank_std100")
+
+
+def rank_regimes(case, R, regime):
+    """`case` (make_case's dict, or link_case_view of a make_link dict) rewritten IN PLACE for R ranks, every output channel:
+      rank_shift50  shard r shifted by 50 r conv-part standard deviations (d^2 n nb / nt carries nearly all the variance)
+      rank_const    constant within every rank, 3 + 2 r on rank r (every local M2 is 0)
+      rank_zero     identically zero on rank R - 1, ordinary elsewhere (that rank's virtual input and the bias are zero)
+      rank_std100   the virtual inputs of the even ranks divided by 100, bias 0: shards with std in the ratio 1 : 100
+    The carrier regimes need a first source that is not upsampled and at least 2 channels wide."""
+    srcs, w = case["sources"], case["w"]
+    R_B = srcs[0]["x"].shape[0]
+    B = R_B // R
+    if regime in ("rank_zero", "rank_std100"):
+        case["bias"][:] = 0
+        for src in srcs:
+            x = src["x"]
+            if regime == "rank_zero":
+                if "shift" in src:
+                    src["shift"][:] = 0
+                x[(R - 1) * B:] = 0
+                continue
+            sc = np.asarray(src.get("scale", np.ones(x.shape[-1])), np.float64)
+            sh = np.asarray(src.get("shift", np.zeros(x.shape[-1])), np.float64)
+            for r in range(0, R, 2):      # x' with x' sc + sh = (x sc + sh) / 100 (an activation in between is positively homogeneous)
+                xs = x[r * B:(r + 1) * B].astype(np.float64)
+                x[r * B:(r + 1) * B] = (((xs * sc + sh) / 100.0 - sh) / sc).astype(np.float32)
+        return case
+    src = srcs[0]
+    x = src["x"]
+    assert x.shape[-1] >= 2 and not src.get("up"), "no carrier channel"     # (the values are >= 0: an activation keeps them)
+    sc0 = float(src["scale"][0]) if "scale" in src else 1.0
+    sh0 = float(src["shift"][0]) if "shift" in src else 0.0
+    value = {"rank_shift50": lambda r: 50.0 * r, "rank_const": lambda r: 3.0 + 2.0 * r}[regime]
+    for r in range(R):          # the carrier's VIRTUAL value on rank r is value(r)
+        x[r * B:(r + 1) * B, ..., 0] = np.float32((value(r) - sh0) / sc0)
+    k = w.shape[0] // 2
+    w[..., 0, :] = 0
+    w[k, k, k, 0, :] = 1
+    if regime == "rank_const":
+        w[..., 1:, :] = 0
+        case["bias"][:] = 0
+    return case
+
+
+def rank_dout(dout, R, regime, seed=0):
+    """the output gradient's regimes: "normal" as it is, "mean30" every column with a mean of 30x its std, "one_rank" zero
+    on every rank but the last"""
+    g = np.array(dout, np.float32)
+    if regime == "mean30":
+        g += (30.0 * np.random.default_rng(seed).choice([-1.0, 1.0], g.shape[-1])).astype(np.float32)
+    elif regime == "one_rank":
+        g[:g.shape[0] // R * (R - 1)] = 0
+    else:
+        assert regime == "normal"
+    return g
+
+
+def stats_sharded32(y, R, rows_per_block):
+    """What the SyncBN kernels do: float32 two-pass block partials (as stats_two_pass32), bn_local_merge_kernel's fp64 merge
+    to the shard's (n, mean, M2) about the SHARD's mean, bn_sync_finalize_kernel's fp64 merge in rank order, and rstd
+    through float(1 / sqrt(var + eps)).  Returns (mean fp64, var + eps recovered from the float32 rstd, float32 mean)."""
+    yf = np.asarray(y, np.float32).reshape(R, -1, y.shape[-1])
+    n, mean, M2 = [], [], []
+    for r in range(R):
+        nb, mb, qb = [], [], []
+        for r0 in range(0, yf.shape[1], rows_per_block):
+            blk = yf[r, r0:r0 + rows_per_block]
+            c = np.float32(blk.shape[0])
+            m = (_tree_sum32(blk) / c).astype(np.float32)
+            nb.append(float(c)); mb.append(m.astype(np.float64)); qb.append(_tree_sum32((blk - m) ** 2).astype(np.float64))
+        nb, mb, qb = np.array(nb)[:, None], np.array(mb), np.array(qb)
+        nr = nb.sum(0)
+        mr = (nb * mb).sum(0) / nr
+        n.append(nr); mean.append(mr); M2.append((qb + nb * (mb - mr) ** 2).sum(0))
+    _, mt, var = merge_moments(n, mean, M2)
+    rstd = (1.0 / np.sqrt(var + EPS)).astype(np.float32)
+    return mt, 1.0 / rstd.astype(np.float64) ** 2, mt.astype(np.float32)
 
 
 # ---- float32 emulations of the per-channel statistic of stored values y (any shape, channels last)

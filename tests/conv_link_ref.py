@@ -71,8 +71,8 @@ def make_link(link, form, B, S, C0, Cp, Ck=0, Cl=0, Cq=0, seed=0, p_regime=None,
     return d
 
 
-def _lf(sources, p, form, dtype, eps):
-    return CR.layer_forward(sources, p["w"], p["bias"], p["gamma"], p["beta"], dtype=dtype, eps=eps, **FORM_KW[form])
+def _lf(sources, p, form, dtype, eps, ranks=0):
+    return CR.layer_forward(sources, p["w"], p["bias"], p["gamma"], p["beta"], dtype=dtype, eps=eps, ranks=ranks, **FORM_KW[form])
 
 
 def consumer_sources(d, oP, pooled):
@@ -90,17 +90,18 @@ def consumer_sources(d, oP, pooled):
     return src
 
 
-def link_forward(d, dtype=np.float64, eps=CR.EPS):
-    """{"P": f, "K": f, "L": f, "pooled": .., "src": ..} with f as conv_layer_ref.layer_forward returns it"""
+def link_forward(d, dtype=np.float64, eps=CR.EPS, ranks=0):
+    """{"P": f, "K": f, "L": f, "pooled": .., "src": ..} with f as conv_layer_ref.layer_forward returns it.  ranks >= 2: the
+    statistics of every layer by the sharded (SyncBN) route of conv_layer_ref, the batch being `ranks` equal shards."""
     form = d["form"]
-    out = {"P": _lf([{"x": d["x0"]}], d["layers"]["P"], form, dtype, eps)}
+    out = {"P": _lf([{"x": d["x0"]}], d["layers"]["P"], form, dtype, eps, ranks)}
     oP = out["P"]["o"]
     pooled = R.maxpool_fwd(oP) if "K" in d["layers"] else None
     out["pooled"] = pooled
     out["src"] = consumer_sources(d, oP, pooled)
     for name in ("K", "L"):
         if name in d["layers"]:
-            out[name] = _lf(out["src"][name], d["layers"][name], form, dtype, eps)
+            out[name] = _lf(out["src"][name], d["layers"][name], form, dtype, eps, ranks)
     return out
 
 
@@ -136,10 +137,10 @@ def _routing_mask(route, ties):
     return np.arange(8).reshape(1, 1, 1, 1, 8, 1) == xw.argmax(axis=4)[..., None, :]
 
 
-def _lb(f, sources, p, dout, form, pin):
+def _lb(f, sources, p, dout, form, pin, ranks=0, strict_dtype=False):
     kw = FORM_KW[form]
     b = CR.layer_backward(f, sources, p["w"], p["gamma"], dout, kink_y=None if pin is None else pin["y"],
-                          kink_bn=None if pin is None else pin["bn"], **kw)
+                          kink_bn=None if pin is None else pin["bn"], ranks=ranks, strict_dtype=strict_dtype, **kw)
     return b
 
 
@@ -153,7 +154,7 @@ def _dy_of(f, p, dout, form, pin):
     return R.act_bwd(np.asarray(f["s"] if pin is None else pin["y"], dtype), d, CR.ACT[kw["pre_act"]])
 
 
-def link_backward(d, f, pins=None, ties="tf_cpu"):
+def link_backward(d, f, pins=None, ties="tf_cpu", ranks=0, strict_dtype=False):
     """Gradients of the whole link in the dtype of f.  Returns {"P": b, "K": b, "L": b, "dO_P", "dy_p", "dx0",
     "pinned": {layer: count}, "rerouted": pool windows whose routing under `pins` differs from this evaluation's own}."""
     link, form, lay = d["link"], d["form"], d["layers"]
@@ -162,7 +163,7 @@ def link_backward(d, f, pins=None, ties="tf_cpu"):
     out = {"pinned": {}, "rerouted": 0}
     dO = 0
     if "K" in lay:
-        out["K"] = _lb(f["K"], f["src"]["K"], lay["K"], d["dout"], form, pin("K"))
+        out["K"] = _lb(f["K"], f["src"]["K"], lay["K"], d["dout"], form, pin("K"), ranks, strict_dtype)
         oP = f["P"]["o"]
         route = None if pins is None else np.asarray(pins["P"]["route"], dtype)
         dO = R.maxpool_bwd(oP, f["pooled"], out["K"]["dx"][0], ties=ties, route=route)
@@ -170,12 +171,12 @@ def link_backward(d, f, pins=None, ties="tf_cpu"):
             diff = _routing_mask(route, ties) != _routing_mask(oP, ties)
             out["rerouted"] = int(diff.any(axis=4).sum())
     if "L" in lay:
-        out["L"] = _lb(f["L"], f["src"]["L"], lay["L"], d["dout_l"] if link == "pool_skip" else d["dout"], form, pin("L"))
+        out["L"] = _lb(f["L"], f["src"]["L"], lay["L"], d["dout_l"] if link == "pool_skip" else d["dout"], form, pin("L"), ranks, strict_dtype)
         dO = dO + out["L"]["dx"][0]
     out["dO_P"] = dO
     srcP = [{"x": d["x0"]}]
-    out["P"] = _lb(f["P"], srcP, lay["P"], dO, form, pin("P"))
-    out["dy_p"] = _dy_of(f["P"], lay["P"], dO, form, pin("P"))
+    out["P"] = _lb(f["P"], srcP, lay["P"], dO, form, pin("P"), ranks, strict_dtype)
+    out["dy_p"] = out["P"]["dy"]
     out["dx0"] = out["P"]["dx"][0]
     for n in ("P", "K", "L"):
         if n in out:
@@ -219,6 +220,17 @@ def rel_errors(got, ref, form):
     return out
 
 
+def link_case_view(d):
+    """P of a make_link dict in the shape conv_layer_ref.rank_regimes rewrites (the arrays are shared)"""
+    P = d["layers"]["P"]
+    return {"sources": [{"x": d["x0"]}], "w": P["w"], "bias": P["bias"]}
+
+
+def shard_grads(d, f, b, R):
+    """{layer: [per-rank dict dw, dbias, dgamma, dbeta]}: every rank's local parameter gradients (conv_layer_ref.shard_grads)"""
+    return {n: CR.shard_grads(f[n], b[n], d["layers"][n]["w"], R) for n in layer_names(d["link"])}
+
+
 def reference(d, pins=None, ties="tf_cpu"):
     """fp64 forward + backward, and the flat dict of gradient tensors (with the `linear:<layer>` flags rel_errors reads)"""
     f = link_forward(d)
@@ -230,10 +242,13 @@ def reference(d, pins=None, ties="tf_cpu"):
     return f, b, t
 
 
-def e32_of(d, f64, t64, ties="tf_cpu"):
-    """the PLAIN formulas in float32 numpy against the fp64 reference, with the fp64 reference's decisions"""
+def e32_of(d, f64, t64, ties="tf_cpu", strict_dtype=False):
+    """the PLAIN formulas in float32 numpy against the fp64 reference, with the fp64 reference's decisions
+    (strict_dtype: conv_layer_ref.layer_backward)"""
     f32 = link_forward(d, np.float32)
-    b32 = link_backward(d, f32, pins_of_forward(f64, d["form"]), ties)
+    b32 = link_backward(d, f32, pins_of_forward(f64, d["form"]), ties, strict_dtype=strict_dtype)
+    if strict_dtype:
+        assert all(v.dtype == np.float32 for v in grad_tensors(b32, layer_names(d["link"])).values())
     return rel_errors(grad_tensors(b32, layer_names(d["link"])), t64, d["form"])
 
 
