@@ -49,6 +49,12 @@ class TsneConfig(C.Structure):
                 ("learning_rate", C.c_double)]
 
 
+class FeedConfig(C.Structure):
+    """ics_feed_config (include/icsg3d.h)."""
+    _fields_ = [("slots", C.c_int), ("x_parts", C.c_int), ("x_channels", C.c_int * 2), ("x_dtype", C.c_int * 2),
+                ("label_kind", C.c_int)]
+
+
 _F = C.POINTER(C.c_float)
 
 
@@ -205,6 +211,18 @@ SIGNATURES = {
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv3d_bench": (C.c_int, [C.c_int] * 8 + [_F]),
     "ics_op_conv3d_backward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F]),
+    "ics_net_feed_open": (C.c_int, [_H, C.POINTER(FeedConfig)]),
+    "ics_net_feed_close": (C.c_int, [_H]),
+    "ics_net_feed_slot": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ics_net_feed_submit": (C.c_int, [_H, C.c_int, C.c_int]),
+    "ics_unet_train_step_fed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
+    "ics_unet_test_step_fed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
+    "ics_vae_train_step_fed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
+    "ics_vae_test_step_fed": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
+    "ics_net_feed_metrics": (C.c_int, [_H, C.c_int, _F]),
+    "ics_op_feed_pack": (C.c_int, [C.POINTER(FeedConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   _F, _U8]),
 }
 
 _lib = None

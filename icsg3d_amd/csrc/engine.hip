@@ -13,6 +13,7 @@
 #include "tsne.h"
 #include "render.h"
 #include "monitor.h"
+#include "feed.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -301,6 +302,9 @@ struct Net {
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
   VoxStage vox;                       // ics_*_voxelise_batch: pinned staging of a batch's site table (voxelise.h)
+  Feed* feed = nullptr;               // the open feed (feed.h; owned by feed.hip, closed by ics_net_feed_close / ics_net_destroy)
+  struct FeedStage { unsigned char* p; size_t bytes; };
+  std::vector<FeedStage> feed_stage;  // device staging of the feed's slots: kept across feeds, so re-opening allocates nothing
 
   // VAE specifics
   Net* pm = nullptr;
@@ -343,6 +347,7 @@ struct Net {
   // ics_net_check_canaries reports the buffers whose guard was written to (a kernel running past the end of its output)
   struct Canary { char* p; size_t len, payload; int index; };
   std::vector<Canary> canaries;
+  int canary_next = 0;               // allocation number of the next guard (entries can go away: feed_port_stage)
   bool canary_on = getenv("ICSG3D_DEBUG_CANARY") != nullptr;
   // number of guards that were written to; *msg describes the first few
   int canaries_dirty(std::string* msg) const {
@@ -391,7 +396,7 @@ struct Net {
     if (guard) {
       char* g = static_cast<char*>(p) + n * sizeof(T);
       ICS_HIP(hipMemsetAsync(g, 0x5A, guard + 256, st));
-      canaries.push_back(Canary{g, guard + 256, n * sizeof(T), (int)canaries.size()});
+      canaries.push_back(Canary{g, guard + 256, n * sizeof(T), canary_next++});
     }
     *out = reinterpret_cast<T*>(p);
     return 0;
@@ -1690,21 +1695,23 @@ static int unet_pm_backward(Net& n, int B) {
   return 0;
 }
 
-static int unet_train_resident_impl(Net& n, int B, float* metrics);
-static int unet_train_resident(Net& n, int B, float* metrics) {
+// defer: the metrics are wanted (the rank reduction of a data-parallel step runs) but stay in d_metrics: no copy, no stream
+// synchronisation -- a fed step reads them through its metrics ring (feed.h)
+static int unet_train_resident_impl(Net& n, int B, float* metrics, bool defer);
+static int unet_train_resident(Net& n, int B, float* metrics, bool defer = false) {
   n.splitk = true;
   n.want_wgrad_inputs = true;
-  const int rc = unet_train_resident_impl(n, B, metrics);
+  const int rc = unet_train_resident_impl(n, B, metrics, defer);
   n.splitk = false;
   n.want_wgrad_inputs = false;
   return rc;
 }
-static int unet_train_resident_impl(Net& n, int B, float* metrics) {
+static int unet_train_resident_impl(Net& n, int B, float* metrics, bool defer) {
   Range step("icsg3d.unet.train_step");
   {
     Range r("icsg3d.unet.forward");
     ICS_TRY(unet_forward_trunk(n, B, true, true, false, n.x_in));
-    ICS_TRY(unet_head_loss(n, B, 1, 1, metrics != nullptr));
+    ICS_TRY(unet_head_loss(n, B, 1, 1, metrics != nullptr || defer));
   }
   {
     Range r("icsg3d.unet.backward");
@@ -1886,7 +1893,8 @@ static int vae_decode_fwd(Net& n, int B, bool training) {
 }
 
 // both engines share one stream in a VAE step: the U-Net is driven on the VAE's stream
-static int vae_step(Net& n, int B, bool training, float* metrics) {
+// defer: as unet_train_resident
+static int vae_step(Net& n, int B, bool training, float* metrics, bool defer = false) {
   ICS_CHECK(n.pm != nullptr, "VAE engine has no perceptual U-Net");
   Range step(training ? "icsg3d.vae.train_step" : "icsg3d.vae.test_step");
   Net& u = *n.pm;
@@ -1981,7 +1989,7 @@ static int vae_step(Net& n, int B, bool training, float* metrics) {
       hipStream_t ls = training ? side_begin(n) : n.st;
       if ((rc = launch_vae_loss(ls, r.zml->s, 2 * n.latent, n.latent, B, mse_part, B * mse_bps, (double)M * n.C,
                                 pm_part, pmc, n.alpha, n.beta, n.d_metrics))) break;
-    } else if (metrics) {
+    } else if (metrics || defer) {
       // data parallel: all-reduce the sums (numerators / denominators), then form the means
       if ((rc = launch_vae_loss(n.st, r.zml->s, 2 * n.latent, n.latent, B, mse_part, B * mse_bps, (double)M * n.C,
                                 pm_part, pmc, n.alpha, n.beta, n.d_metrics, n.d_red, 1))) break;
@@ -2141,6 +2149,72 @@ int ics_device_info(char* name, int* cus, size_t* hbm) {
 // environment already says otherwise.  Runs when the library is loaded; the runtime reads it when HIP initialises.
 __attribute__((constructor)) static void ics_runtime_env_defaults() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- what feed.hip needs of a Net (feed.h)
+namespace ics {
+int feed_port(ics_net* net, FeedPort* out) {
+  ICS_CHECK(net && out, "null handle");
+  Net& n = net->n;
+  out->kind = n.kind; out->max_batch = n.maxB; out->d = n.d; out->C = n.C;
+  out->ncls = n.kind == 0 ? n.ncls : 0; out->ncond = n.ncond; out->latent = n.latent;
+  out->st = n.st;
+  out->x_in = n.x_in; out->labels = n.labels; out->cond_in = n.cond_in; out->eps_in = n.eps_in;
+  out->d_metrics = n.d_metrics;
+  out->feed = &n.feed;
+  return 0;
+}
+int feed_port_stage(ics_net* net, int slot, size_t bytes, unsigned char** out) {
+  Net& n = net->n;
+  ICS_CHECK(slot >= 0 && slot < kFeedMaxSlots, "feed staging: bad slot index");
+  if ((size_t)slot >= n.feed_stage.size()) n.feed_stage.resize(slot + 1, Net::FeedStage{nullptr, 0});
+  Net::FeedStage& s = n.feed_stage[slot];
+  if (s.p == nullptr || s.bytes < bytes) {
+    // An allocation of its own, outside the arena, so that a larger layout than any feed before can give the smaller
+    // buffer back: the engine does not grow with every new layout.
+    if (s.p != nullptr) {
+      ICS_HIP(hipStreamSynchronize(n.st));
+      for (size_t i = 0; i < n.canaries.size(); ++i)
+        if (n.canaries[i].p == reinterpret_cast<char*>(s.p) + s.bytes) { n.canaries.erase(n.canaries.begin() + i); break; }
+      for (size_t i = 0; i < n.allocs.size(); ++i)
+        if (n.allocs[i] == s.p) { n.allocs.erase(n.allocs.begin() + i); break; }
+      ICS_HIP(hipFree(s.p));
+      s.p = nullptr; s.bytes = 0;
+    }
+    const bool arena = n.arena_on;
+    n.arena_on = false;
+    const int rc = n.alloc(&s.p, bytes);
+    n.arena_on = arena;
+    ICS_TRY(rc);
+    s.bytes = bytes;
+  }
+  *out = s.p;
+  return 0;
+}
+int feed_port_step(ics_net* net, int batch, int training) {
+  Net& n = net->n;
+  ICS_CHECK(batch >= 1 && batch <= n.maxB, "batch exceeds max_batch");
+  n.resident_batch = batch;
+  if (n.kind == 0) {
+    n.labels_batch = batch;
+    n.pred_kind = 0;
+    if (training) return unet_train_resident(n, batch, nullptr, true);
+    ICS_TRY(unet_forward_trunk(n, batch, false, false, false, n.x_in));
+    return unet_head_loss(n, batch, 1, 0);
+  }
+  n.enc_batch = 0; n.recon_fresh = 0;
+  return vae_step(n, batch, training != 0, nullptr, true);
+}
+int feed_port_resolve(ics_net* net) {
+  Net& n = net->n;
+  if (n.prof.on) ICS_HIP(hipStreamSynchronize(n.st));   // the events of steps still in flight cannot be read yet
+  n.prof.resolve();
+  return 0;
+}
+}  // namespace ics
+
+extern "C" {
+
 static int net_common_init(Net& n) {
   n.flags = conv_flags_from_env();
   ICS_HIP(hipGetDevice(&n.device));
@@ -2196,6 +2270,7 @@ int ics_vae_create(const ics_vae_config* cfg, ics_net* pm, ics_net** out) {
 
 int ics_net_destroy(ics_net* net) {
   if (!net) return 0;
+  feed_release(net);
   (void)hipStreamSynchronize(net->n.st);
   delete net;            // (with ICSG3D_DEBUG_CANARY=1 the destructor reports overwritten guard bytes on stderr)
   return 0;
@@ -2956,7 +3031,7 @@ int ics_op_segment_atoms(const uint8_t* mask, const uint8_t* species, int batch,
 }
 
 // Every host-pointer op that reads no engine state is defined in its own module (voxelise.hip, match.hip, structure*.hip,
-// render.hip, monitor.hip, latent.hip, tsne.hip, segment.hip, scratch.hip); what follows needs a Net.
+// render.hip, monitor.hip, latent.hip, tsne.hip, segment.hip, scratch.hip, feed.hip); what follows needs a Net.
 // The density picture of what the engine already holds: the resident input (which = 0) or recon as the last decoder pass
 // left it (which = 1), channel 0, read where it lies.  Only the colour table goes up and the pictures come back.
 int ics_vae_render_resident(ics_net* vae, int which, int mode, float alpha, float floor, const float* lut,

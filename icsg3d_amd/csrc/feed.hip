@@ -1,0 +1,423 @@
+// Fed steps (gfx950 / MI355X only): pinned staging slots uploaded on a copy stream while the previous step runs, and the
+// pack kernel that does on the device what the synchronous path does on host threads -- float64 -> float32, the (M | p)
+// channel concatenate, labels to uint8 class ids (argmax of a one-hot included).  feed.h has the ordering rules.
+#include "feed.h"
+#include "scratch.h"
+
+#include <climits>
+#include <cstring>
+#include <memory>
+
+namespace ics {
+
+// ------------------------------------------------------------------------------------------ the pack kernel
+// Purely memory-bound: every byte is read once and written once, so the only rules are wide, contiguous accesses.
+//   quad blocks    one lane = 4 consecutive voxels.  Each x part is read with 16-byte loads (a float32 quad is one load, a
+//                  float64 quad two; a lane's loads are adjacent, a wave covers one contiguous range) and written as
+//                  float4: C = 1 one store per four voxels, C = 4 (1 + 3 channels) one store per voxel.  Id labels ride
+//                  along: four ids in, one 32-bit store of four bytes out.
+//   one-hot blocks 16 lanes per voxel stride the columns (any count from 2 to 127), then four xor-shuffle steps reduce
+//                  (value, index) under np.argmax's rule: the larger value (a NaN above every number), the lower index
+//                  among equals.  Four voxels per wave and pass; lane 0 stores their four bytes at once.
+//   tail blocks    cond and eps, float32 passthrough.
+// nvox is a multiple of 512 (d is a power of two >= 8), so quads and 64-voxel one-hot blocks always divide.
+constexpr int kPackThreads = 256;
+constexpr int kPackOneHotVox = 64;    // voxels per one-hot block: 4 waves x 4 voxels x 4 passes
+constexpr int kPackTailBlocks = 8;
+
+template <typename T> __device__ __forceinline__ float4 load4(const T* p);
+template <> __device__ __forceinline__ float4 load4<float>(const float* p) { return *reinterpret_cast<const float4*>(p); }
+template <> __device__ __forceinline__ float4 load4<double>(const double* p) {
+  const double2 a = reinterpret_cast<const double2*>(p)[0];
+  const double2 b = reinterpret_cast<const double2*>(p)[1];
+  return make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);   // v_cvt_f32_f64: round to nearest even
+}
+__device__ __forceinline__ unsigned id_byte(float v) { return (unsigned)(unsigned char)(int)v; }
+__device__ __forceinline__ unsigned pack_ids(float4 v) {
+  return id_byte(v.x) | (id_byte(v.y) << 8) | (id_byte(v.z) << 16) | (id_byte(v.w) << 24);
+}
+// np.argmax's order: a NaN is above every number (the first NaN wins), two NaNs are equal
+__device__ __forceinline__ bool arg_above(float a, float b) { return a > b || (a != a && b == b); }
+__device__ __forceinline__ float load_as_float(const void* p, int dt, size_t i) {
+  return dt == kDtypeF64 ? (float)static_cast<const double*>(p)[i] : static_cast<const float*>(p)[i];
+}
+
+// MODE 1: one part (any channel count: its layout is the output's).  MODE 4: parts of 1 + 3 channels.  MODE 0: any other
+// split, element by element.
+template <typename T0, typename T1, int MODE>
+__global__ __launch_bounds__(kPackThreads) void feed_pack_kernel(FeedPack p, unsigned quad_blocks, unsigned onehot_blocks) {
+  const unsigned blk = blockIdx.x;
+  if (blk < quad_blocks) {
+    const size_t q = (size_t)blk * kPackThreads + threadIdx.x;
+    if (MODE == 1) {             // a cast copy of nvox * C elements: the quads run over elements, beyond the voxel quads
+      if (q < p.nvox / 4 * p.xc[0]) reinterpret_cast<float4*>(p.x_out)[q] = load4(static_cast<const T0*>(p.x[0]) + 4 * q);
+    }
+    if (q >= p.nvox / 4) return;
+    if (MODE == 4) {
+      const float4 m = load4(static_cast<const T0*>(p.x[0]) + 4 * q);
+      const T1* s = static_cast<const T1*>(p.x[1]) + 12 * q;
+      const float4 a = load4(s), b = load4(s + 4), c = load4(s + 8);
+      float4* o = reinterpret_cast<float4*>(p.x_out) + 4 * q;
+      o[0] = make_float4(m.x, a.x, a.y, a.z);
+      o[1] = make_float4(m.y, a.w, b.x, b.y);
+      o[2] = make_float4(m.z, b.z, b.w, c.x);
+      o[3] = make_float4(m.w, c.y, c.z, c.w);
+    } else if (MODE == 0) {
+      const int C = p.xc[0] + p.xc[1];
+      for (int k = 0; k < 4; ++k) {
+        const size_t v = 4 * q + k;
+        float* o = p.x_out + v * C;
+        for (int c = 0; c < p.xc[0]; ++c) o[c] = load_as_float(p.x[0], p.xdt[0], v * p.xc[0] + c);
+        for (int c = 0; c < p.xc[1]; ++c) o[p.xc[0] + c] = load_as_float(p.x[1], p.xdt[1], v * p.xc[1] + c);
+      }
+    }
+    if (p.label_kind == FEED_LABELS_U8)
+      reinterpret_cast<unsigned*>(p.lab_out)[q] = static_cast<const unsigned*>(p.lab)[q];
+    else if (p.label_kind == FEED_LABELS_F32)
+      reinterpret_cast<unsigned*>(p.lab_out)[q] = pack_ids(load4(static_cast<const float*>(p.lab) + 4 * q));
+    else if (p.label_kind == FEED_LABELS_F64)
+      reinterpret_cast<unsigned*>(p.lab_out)[q] = pack_ids(load4(static_cast<const double*>(p.lab) + 4 * q));
+    return;
+  }
+  if (blk < quad_blocks + onehot_blocks) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane >> 4, gl = lane & 15;
+    const float* lab = static_cast<const float*>(p.lab);
+    for (int pass = 0; pass < 4; ++pass) {
+      const size_t base = (size_t)(blk - quad_blocks) * kPackOneHotVox + pass * 16 + wave * 4;   // wave-uniform
+      if (base + 4 > p.nvox) break;
+      const float* row = lab + (base + grp) * (size_t)p.ncls;
+      float best = -INFINITY;
+      int bidx = INT_MAX;                        // no column taken yet: loses every tie
+      for (int c = gl; c < p.ncls; c += 16) {
+        const float v = row[c];
+        if (arg_above(v, best)) { best = v; bidx = c; }   // ascending columns, strictly above: the lowest index of this lane's maxima
+      }
+      for (int off = 8; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bidx, off);
+        if (arg_above(ov, best) || (!arg_above(best, ov) && oi < bidx)) { best = ov; bidx = oi; }
+      }
+      if (bidx == INT_MAX) bidx = 0;             // a row without a value above -inf: argmax's first column
+      const unsigned r0 = (unsigned)__shfl(bidx, 0), r1 = (unsigned)__shfl(bidx, 16), r2 = (unsigned)__shfl(bidx, 32),
+                     r3 = (unsigned)__shfl(bidx, 48);
+      if (lane == 0) reinterpret_cast<unsigned*>(p.lab_out)[base / 4] = r0 | (r1 << 8) | (r2 << 16) | (r3 << 24);
+    }
+    return;
+  }
+  const size_t t0 = (size_t)(blk - quad_blocks - onehot_blocks) * kPackThreads + threadIdx.x;
+  const size_t stride = (size_t)kPackTailBlocks * kPackThreads;
+  for (int k = 0; k < 2; ++k)
+    for (size_t i = t0; i < p.tail_n[k]; i += stride) p.tail_dst[k][i] = p.tail_src[k][i];
+}
+
+size_t feed_label_bytes(int label_kind, int ncls) {
+  switch (label_kind) {
+    case FEED_LABELS_U8: return 1;
+    case FEED_LABELS_F64: return 8;
+    case FEED_LABELS_F32: return 4;
+    case FEED_LABELS_ONEHOT: return (size_t)ncls * 4;
+    default: return 0;
+  }
+}
+static size_t dtype_bytes(int dt) { return dt == kDtypeF64 ? 8 : 4; }
+
+int feed_config_check(const char* who, const ics_feed_config* cfg, int in_channels, int ncls, bool want_labels) {
+  const std::string w = std::string(who) + ": ";
+  ICS_CHECK(cfg != nullptr, w + "null feed config");
+  ICS_CHECK(cfg->x_parts == 1 || cfg->x_parts == 2, w + "x_parts must be 1 or 2");
+  int sum = 0;
+  for (int i = 0; i < cfg->x_parts; ++i) {
+    ICS_CHECK(cfg->x_channels[i] >= 1 && cfg->x_channels[i] <= 16384, w + "every x part needs 1..16384 channels");
+    ICS_CHECK(cfg->x_dtype[i] == kDtypeF32 || cfg->x_dtype[i] == kDtypeF64, w + "x_dtype must be 0 (float32) or 3 (float64)");
+    sum += cfg->x_channels[i];
+  }
+  ICS_CHECK(sum == in_channels, w + "the x parts' channels do not add up to in_channels");
+  ICS_CHECK(cfg->label_kind >= FEED_LABELS_NONE && cfg->label_kind <= FEED_LABELS_ONEHOT, w + "label_kind must be in 0..4");
+  ICS_CHECK(want_labels || cfg->label_kind == FEED_LABELS_NONE, w + "a VAE engine takes no labels: label_kind must be 0");
+  ICS_CHECK(!want_labels || cfg->label_kind != FEED_LABELS_NONE, w + "a U-Net engine needs labels: label_kind must be 1..4");
+  ICS_CHECK(cfg->label_kind != FEED_LABELS_ONEHOT || (ncls >= 2 && ncls <= 127), w + "one-hot labels need 2..127 columns");
+  return 0;
+}
+
+int launch_feed_pack(hipStream_t st, const FeedPack& p) {
+  ICS_CHECK(p.nvox > 0 && p.nvox % 512 == 0, "feed pack: the voxel count must be a positive multiple of 512");
+  ICS_CHECK(p.x_out && p.x[0] && (p.nparts == 1 || (p.nparts == 2 && p.x[1])), "feed pack: null x pointer");
+  ICS_CHECK(p.label_kind == FEED_LABELS_NONE || (p.lab && p.lab_out), "feed pack: null label pointer");
+  const size_t quads = p.nvox / 4 * (p.nparts == 1 ? (size_t)p.xc[0] : 1);
+  const size_t qb = (quads + kPackThreads - 1) / kPackThreads;
+  const size_t ob = p.label_kind == FEED_LABELS_ONEHOT ? p.nvox / kPackOneHotVox : 0;
+  const size_t tb = (p.tail_n[0] + p.tail_n[1]) ? kPackTailBlocks : 0;
+  ICS_CHECK(qb + ob + tb < ((size_t)1 << 31), "feed pack: batch too large for one launch");
+  const dim3 grid((unsigned)(qb + ob + tb)), block(kPackThreads);
+  const bool d0 = p.xdt[0] == kDtypeF64, d1 = p.xdt[1] == kDtypeF64;
+  const unsigned uq = (unsigned)qb, uo = (unsigned)ob;
+  if (p.nparts == 1) {
+    if (d0) ICS_LAUNCH(feed_pack_kernel<double, float, 1>, grid, block, 0, st, p, uq, uo);
+    else ICS_LAUNCH(feed_pack_kernel<float, float, 1>, grid, block, 0, st, p, uq, uo);
+  } else if (p.nparts == 2 && p.xc[0] == 1 && p.xc[1] == 3) {
+    if (d0 && d1) ICS_LAUNCH(feed_pack_kernel<double, double, 4>, grid, block, 0, st, p, uq, uo);
+    else if (d0) ICS_LAUNCH(feed_pack_kernel<double, float, 4>, grid, block, 0, st, p, uq, uo);
+    else if (d1) ICS_LAUNCH(feed_pack_kernel<float, double, 4>, grid, block, 0, st, p, uq, uo);
+    else ICS_LAUNCH(feed_pack_kernel<float, float, 4>, grid, block, 0, st, p, uq, uo);
+  } else {
+    ICS_LAUNCH(feed_pack_kernel<float, float, 0>, grid, block, 0, st, p, uq, uo);
+  }
+  ICS_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the feed of an engine
+struct FeedSlot {
+  unsigned char* host = nullptr;   // pinned
+  unsigned char* dev = nullptr;    // the engine's
+  hipEvent_t uploaded = nullptr, consumed = nullptr;
+  bool obtained = false;           // the host holds the views (ics_net_feed_slot since the last submit)
+  bool pending = false;            // submitted and not consumed by a step yet
+  bool ever = false;               // submitted at least once
+  int batch = 0;
+};
+struct Feed {
+  ics_feed_config cfg{};
+  int max_batch = 0, d = 0, C = 0, ncls = 0, ncond = 0, latent = 0, kind = 0;
+  size_t off_x[2] = {0, 0}, off_lab = 0, off_cond = 0, off_eps = 0, slot_bytes = 0;   // the layout of every slot
+  size_t vox_x[2] = {0, 0}, vox_lab = 0;                                                // bytes per voxel
+  hipStream_t feed_st = nullptr;
+  FeedSlot slot[kFeedMaxSlots];
+  float* ring = nullptr;           // pinned [kFeedRing][kFeedMetricFloats]
+  hipEvent_t ring_ev[kFeedRing] = {};
+  long long next_ticket = 0;
+  ~Feed() {
+    if (feed_st) { (void)hipStreamSynchronize(feed_st); (void)hipStreamDestroy(feed_st); }
+    for (FeedSlot& s : slot) {
+      if (s.uploaded) (void)hipEventDestroy(s.uploaded);
+      if (s.consumed) (void)hipEventDestroy(s.consumed);
+      if (s.host) (void)hipHostFree(s.host);
+    }
+    for (hipEvent_t e : ring_ev) if (e) (void)hipEventDestroy(e);
+    if (ring) (void)hipHostFree(ring);
+  }
+};
+
+static int feed_get(ics_net* net, const char* who, FeedPort* port, Feed** f) {
+  ICS_CHECK(net != nullptr, std::string(who) + ": null handle");
+  ICS_TRY(feed_port(net, port));
+  ICS_CHECK(*port->feed != nullptr, std::string(who) + ": the engine has no open feed (ics_net_feed_open)");
+  *f = *port->feed;
+  return 0;
+}
+static int slot_check(const char* who, const Feed& f, int slot) {
+  ICS_CHECK(slot >= 0 && slot < f.cfg.slots,
+            std::string(who) + ": bad slot index " + std::to_string(slot) + " (the feed has " + std::to_string(f.cfg.slots) + " slots)");
+  return 0;
+}
+
+static int feed_open(ics_net* net, const ics_feed_config* cfg) {
+  ICS_CHECK(net != nullptr, "ics_net_feed_open: null handle");
+  FeedPort P;
+  ICS_TRY(feed_port(net, &P));
+  ICS_CHECK(*P.feed == nullptr, "ics_net_feed_open: a feed is already open on this engine (ics_net_feed_close first)");
+  ICS_TRY(feed_config_check("ics_net_feed_open", cfg, P.C, P.ncls, P.kind == 0));
+  ICS_CHECK(cfg->slots >= 2 && cfg->slots <= kFeedMaxSlots, "ics_net_feed_open: slots must be in 2..4");
+  auto f = std::make_unique<Feed>();
+  f->cfg = *cfg;
+  f->max_batch = P.max_batch; f->d = P.d; f->C = P.C; f->ncls = P.ncls; f->kind = P.kind;
+  f->ncond = P.kind == 1 ? P.ncond : 0;
+  f->latent = P.kind == 1 ? P.latent : 0;
+  const size_t vox = (size_t)P.max_batch * P.d * P.d * P.d;
+  Layout L;                       // every part at a 256-byte aligned offset
+  for (int i = 0; i < cfg->x_parts; ++i) {
+    f->vox_x[i] = (size_t)cfg->x_channels[i] * dtype_bytes(cfg->x_dtype[i]);
+    f->off_x[i] = L.add<unsigned char>(vox * f->vox_x[i]).off;
+  }
+  f->vox_lab = feed_label_bytes(cfg->label_kind, P.ncls);
+  f->off_lab = L.add<unsigned char>(vox * f->vox_lab).off;
+  f->off_cond = L.add<float>((size_t)P.max_batch * f->ncond).off;
+  f->off_eps = L.add<float>((size_t)P.max_batch * f->latent).off;
+  f->slot_bytes = L.bytes();
+  ICS_HIP(hipStreamCreateWithFlags(&f->feed_st, hipStreamNonBlocking));
+  for (int s = 0; s < cfg->slots; ++s) {
+    FeedSlot& S = f->slot[s];
+    ICS_HIP(hipHostMalloc(reinterpret_cast<void**>(&S.host), f->slot_bytes, hipHostMallocDefault));
+    ICS_TRY(feed_port_stage(net, s, f->slot_bytes, &S.dev));
+    ICS_HIP(hipEventCreateWithFlags(&S.uploaded, hipEventDisableTiming));
+    ICS_HIP(hipEventCreateWithFlags(&S.consumed, hipEventDisableTiming));
+  }
+  ICS_HIP(hipHostMalloc(reinterpret_cast<void**>(&f->ring), sizeof(float) * kFeedRing * kFeedMetricFloats, hipHostMallocDefault));
+  std::memset(f->ring, 0, sizeof(float) * kFeedRing * kFeedMetricFloats);
+  for (hipEvent_t& e : f->ring_ev) ICS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  ICS_HIP(hipStreamSynchronize(P.st));     // the staging buffers' zero fill (the engine's allocator enqueues it)
+  *P.feed = f.release();
+  return 0;
+}
+
+static int feed_close(ics_net* net) {
+  FeedPort P;
+  Feed* f;
+  ICS_TRY(feed_get(net, "ics_net_feed_close", &P, &f));
+  const hipError_t e0 = hipStreamSynchronize(f->feed_st), e1 = hipStreamSynchronize(P.st);
+  *P.feed = nullptr;
+  delete f;
+  ICS_HIP(e0);
+  ICS_HIP(e1);
+  return feed_port_resolve(net);
+}
+
+void feed_release(ics_net* net) {
+  FeedPort P;
+  if (net == nullptr || feed_port(net, &P) != 0 || *P.feed == nullptr) return;
+  (void)feed_close(net);
+}
+
+static int feed_step(ics_net* net, const char* who, int kind, int training, int slot, int* ticket) {
+  FeedPort P;
+  Feed* f;
+  ICS_TRY(feed_get(net, who, &P, &f));
+  ICS_CHECK(P.kind == kind, std::string(who) + (kind == 0 ? ": wrong engine kind: a U-Net engine is required"
+                                                          : ": wrong engine kind: a VAE engine is required"));
+  ICS_CHECK(ticket != nullptr, std::string(who) + ": null ticket");
+  ICS_TRY(slot_check(who, *f, slot));
+  FeedSlot& S = f->slot[slot];
+  ICS_CHECK(S.ever, std::string(who) + ": slot " + std::to_string(slot) + " was never submitted");
+  ICS_CHECK(S.pending, std::string(who) + ": slot " + std::to_string(slot) + " was already consumed by a step: submit it again first");
+  const int B = S.batch;
+  ICS_HIP(hipStreamWaitEvent(P.st, S.uploaded, 0));
+  FeedPack k;
+  k.nparts = f->cfg.x_parts;
+  for (int i = 0; i < k.nparts; ++i) {
+    k.x[i] = S.dev + f->off_x[i];
+    k.xc[i] = f->cfg.x_channels[i];
+    k.xdt[i] = f->cfg.x_dtype[i];
+  }
+  k.label_kind = f->cfg.label_kind;
+  k.ncls = f->ncls;
+  if (k.label_kind != FEED_LABELS_NONE) { k.lab = S.dev + f->off_lab; k.lab_out = P.labels; }
+  k.nvox = (size_t)B * f->d * f->d * f->d;
+  k.x_out = P.x_in;
+  if (kind == 1) {
+    k.tail_src[0] = reinterpret_cast<const float*>(S.dev + f->off_cond); k.tail_dst[0] = P.cond_in; k.tail_n[0] = (size_t)B * f->ncond;
+    k.tail_src[1] = reinterpret_cast<const float*>(S.dev + f->off_eps);  k.tail_dst[1] = P.eps_in;  k.tail_n[1] = (size_t)B * f->latent;
+  }
+  ICS_TRY(launch_feed_pack(P.st, k));
+  ICS_HIP(hipEventRecord(S.consumed, P.st));
+  S.pending = false;
+  ICS_TRY(feed_port_step(net, B, training));
+  ICS_CHECK(f->next_ticket < INT_MAX, std::string(who) + ": out of tickets: close the feed and open it again");
+  const int entry = (int)(f->next_ticket % kFeedRing);
+  ICS_HIP(hipMemcpyAsync(f->ring + (size_t)entry * kFeedMetricFloats, P.d_metrics, (kind == 0 ? 5 : 4) * sizeof(float),
+                         hipMemcpyDeviceToHost, P.st));
+  ICS_HIP(hipEventRecord(f->ring_ev[entry], P.st));
+  *ticket = (int)f->next_ticket;
+  f->next_ticket += 1;
+  return 0;
+}
+
+}  // namespace ics
+
+// ==========================================================================================
+// C ABI
+// ==========================================================================================
+using namespace ics;
+
+extern "C" {
+
+int ics_net_feed_open(ics_net* net, const ics_feed_config* cfg) { return feed_open(net, cfg); }
+int ics_net_feed_close(ics_net* net) { return feed_close(net); }
+
+int ics_net_feed_slot(ics_net* net, int slot, void** x0, void** x1, void** labels, float** cond, float** eps) {
+  FeedPort P;
+  Feed* f;
+  ICS_TRY(feed_get(net, "ics_net_feed_slot", &P, &f));
+  ICS_TRY(slot_check("ics_net_feed_slot", *f, slot));
+  FeedSlot& S = f->slot[slot];
+  if (S.ever) ICS_HIP(hipEventSynchronize(S.uploaded));     // the one wait: the slot's last upload has left the pinned buffer
+  S.obtained = true;
+  if (x0) *x0 = S.host + f->off_x[0];
+  if (x1) *x1 = f->cfg.x_parts == 2 ? S.host + f->off_x[1] : nullptr;
+  if (labels) *labels = f->vox_lab ? S.host + f->off_lab : nullptr;
+  if (cond) *cond = f->ncond ? reinterpret_cast<float*>(S.host + f->off_cond) : nullptr;
+  if (eps) *eps = f->latent ? reinterpret_cast<float*>(S.host + f->off_eps) : nullptr;
+  return 0;
+}
+
+int ics_net_feed_submit(ics_net* net, int slot, int batch) {
+  FeedPort P;
+  Feed* f;
+  ICS_TRY(feed_get(net, "ics_net_feed_submit", &P, &f));
+  ICS_TRY(slot_check("ics_net_feed_submit", *f, slot));
+  FeedSlot& S = f->slot[slot];
+  ICS_CHECK(batch >= 1 && batch <= f->max_batch, "ics_net_feed_submit: batch exceeds max_batch (or is below 1)");
+  ICS_CHECK(!S.pending, "ics_net_feed_submit: slot " + std::to_string(slot) + " holds a submitted batch that no step has consumed");
+  ICS_CHECK(S.obtained, "ics_net_feed_submit: slot " + std::to_string(slot) + " was never obtained: call ics_net_feed_slot and fill it first");
+  const size_t vox = (size_t)batch * f->d * f->d * f->d;
+  ICS_HIP(hipStreamWaitEvent(f->feed_st, S.consumed, 0));   // (never recorded yet: no wait)
+  auto up = [&](size_t off, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(S.dev + off, S.host + off, bytes, hipMemcpyHostToDevice, f->feed_st) : hipSuccess;
+  };
+  for (int i = 0; i < f->cfg.x_parts; ++i) ICS_HIP(up(f->off_x[i], vox * f->vox_x[i]));
+  ICS_HIP(up(f->off_lab, vox * f->vox_lab));
+  ICS_HIP(up(f->off_cond, (size_t)batch * f->ncond * sizeof(float)));
+  ICS_HIP(up(f->off_eps, (size_t)batch * f->latent * sizeof(float)));
+  ICS_HIP(hipEventRecord(S.uploaded, f->feed_st));
+  S.obtained = false; S.pending = true; S.ever = true; S.batch = batch;
+  return 0;
+}
+
+int ics_unet_train_step_fed(ics_net* net, int slot, int* ticket) { return feed_step(net, "ics_unet_train_step_fed", 0, 1, slot, ticket); }
+int ics_unet_test_step_fed(ics_net* net, int slot, int* ticket) { return feed_step(net, "ics_unet_test_step_fed", 0, 0, slot, ticket); }
+int ics_vae_train_step_fed(ics_net* net, int slot, int* ticket) { return feed_step(net, "ics_vae_train_step_fed", 1, 1, slot, ticket); }
+int ics_vae_test_step_fed(ics_net* net, int slot, int* ticket) { return feed_step(net, "ics_vae_test_step_fed", 1, 0, slot, ticket); }
+
+int ics_net_feed_metrics(ics_net* net, int ticket, float* metrics) {
+  FeedPort P;
+  Feed* f;
+  ICS_TRY(feed_get(net, "ics_net_feed_metrics", &P, &f));
+  ICS_CHECK(metrics != nullptr, "ics_net_feed_metrics: null argument");
+  ICS_CHECK(ticket >= 0 && ticket < f->next_ticket, "ics_net_feed_metrics: no step has returned ticket " + std::to_string(ticket));
+  ICS_CHECK(f->next_ticket - ticket <= kFeedRing,
+            "ics_net_feed_metrics: ticket " + std::to_string(ticket) + " is older than the ring of " + std::to_string(kFeedRing) + " entries");
+  const int entry = ticket % kFeedRing;
+  ICS_HIP(hipEventSynchronize(f->ring_ev[entry]));
+  std::memcpy(metrics, f->ring + (size_t)entry * kFeedMetricFloats, (f->kind == 0 ? 5 : 4) * sizeof(float));
+  return feed_port_resolve(net);
+}
+
+int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1, const void* labels, int batch, int d,
+                     int num_classes, float* x, uint8_t* out_labels) {
+  ICS_CHECK(cfg != nullptr, "ics_op_feed_pack: null feed config");
+  ICS_CHECK(batch >= 1 && batch <= 65535, "ics_op_feed_pack: batch must be in 1..65535");
+  ICS_CHECK(d >= 8 && d <= 256 && (d & (d - 1)) == 0, "ics_op_feed_pack: d must be a power of two in 8..256");
+  const int C = cfg->x_parts >= 1 && cfg->x_parts <= 2 ? cfg->x_channels[0] + (cfg->x_parts == 2 ? cfg->x_channels[1] : 0) : 0;
+  ICS_TRY(feed_config_check("ics_op_feed_pack", cfg, C, num_classes, cfg->label_kind != FEED_LABELS_NONE));
+  ICS_CHECK(x0 && x && (cfg->x_parts == 1 || x1), "ics_op_feed_pack: null x pointer");
+  ICS_CHECK(cfg->label_kind == FEED_LABELS_NONE || (labels && out_labels), "ics_op_feed_pack: null label pointer");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  const size_t vox = (size_t)batch * d * d * d;
+  const size_t lab_bytes = vox * feed_label_bytes(cfg->label_kind, num_classes);
+  Layout L;
+  const auto s_x0 = L.add<unsigned char>(vox * cfg->x_channels[0] * dtype_bytes(cfg->x_dtype[0]));
+  const auto s_x1 = L.add<unsigned char>(cfg->x_parts == 2 ? vox * cfg->x_channels[1] * dtype_bytes(cfg->x_dtype[1]) : 0);
+  const auto s_lab = L.add<unsigned char>(lab_bytes);
+  const auto s_out = L.add<float>(vox * C);
+  const auto s_lout = L.add<unsigned char>(lab_bytes ? vox : 0);
+  unsigned char *d_x0, *d_x1, *d_lab, *d_lout;
+  float* d_out;
+  ICS_TRY(L.reserve(s_x0, &d_x0, s_x1, &d_x1, s_lab, &d_lab, s_out, &d_out, s_lout, &d_lout));
+  ICS_TRY(L.upload(s_x0, x0, s_x0.count, st));
+  ICS_TRY(L.upload(s_x1, x1, s_x1.count, st));
+  ICS_TRY(L.upload(s_lab, labels, s_lab.count, st));
+  FeedPack k;
+  k.nparts = cfg->x_parts;
+  k.x[0] = d_x0; k.x[1] = d_x1;
+  for (int i = 0; i < k.nparts; ++i) { k.xc[i] = cfg->x_channels[i]; k.xdt[i] = cfg->x_dtype[i]; }
+  k.lab = d_lab; k.label_kind = cfg->label_kind; k.ncls = num_classes;
+  k.nvox = vox; k.x_out = d_out; k.lab_out = d_lout;
+  ICS_TRY(launch_feed_pack(st, k));
+  ICS_TRY(L.download(x, s_out, s_out.count, st));
+  ICS_TRY(L.download(out_labels, s_lout, s_lout.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+}  // extern "C"

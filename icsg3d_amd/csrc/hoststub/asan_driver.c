@@ -871,6 +871,144 @@ static int interp_walk(ics_net* unet, ics_net* vae, const ics_unet_config* uc, c
   return 0;
 }
 
+/* Fed steps: the pack op alone on buffers of the exact size (every dtype mix, every label kind, odd column counts), then the
+ * whole feed on both engines -- open, slot, submit, fed train / test step, metrics (late and twice), close, re-open with
+ * another layout -- and every refusal, after which the feed and the engine still work. */
+static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond, int latent) {
+  const size_t V = (size_t)d * d * d;
+  int bad = 0;
+  if (d >= 8) {   /* ics_op_feed_pack */
+    const int dts[2] = {0, 3}, cols[3] = {2, 95, 127};
+    for (int a = 0; a < 2; ++a)
+      for (int b = 0; b < 2; ++b)
+        for (int kind = 0; kind <= 4; ++kind)
+          for (int parts = 1; parts <= 2; ++parts) {
+            const int ncls = cols[(a + b + kind) % 3], nb = 1 + (a + kind) % 2;
+            ics_feed_config fc = {2, parts, {parts == 1 ? 4 : 1, 3}, {dts[a], dts[b]}, kind};
+            const size_t vox = (size_t)nb * V, lb = kind == 1 ? 1 : kind == 2 ? 8 : kind == 3 ? 4 : kind == 4 ? (size_t)ncls * 4 : 0;
+            void* x0 = calloc(vox * fc.x_channels[0], a ? 8 : 4);
+            void* x1 = parts == 2 ? calloc(vox * 3, b ? 8 : 4) : NULL;
+            void* lab = lb ? calloc(vox, lb) : NULL;
+            float* out = (float*)malloc(vox * 4 * sizeof(float));
+            uint8_t* lo = lb ? (uint8_t*)malloc(vox) : NULL;
+            OK(ics_op_feed_pack(&fc, x0, x1, lab, nb, d, ncls, out, lo));
+            free(x0); free(x1); free(lab); free(out); free(lo);
+          }
+    ics_feed_config fc = {2, 2, {1, 3}, {3, 3}, 4};
+    double* x0 = (double*)calloc(V, 8); double* x1 = (double*)calloc(V * 3, 8);
+    float* lab = (float*)calloc(V * 95, 4); float* out = (float*)malloc(V * 16); uint8_t* lo = (uint8_t*)malloc(V);
+    ics_feed_config t = fc;
+    bad += ics_op_feed_pack(NULL, x0, x1, lab, 1, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, NULL, x1, lab, 1, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, NULL, lab, 1, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, NULL, 1, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 95, NULL, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 95, out, NULL) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 0, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, 12, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, 4, 95, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 1, out, lo) == 0;
+    bad += ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 128, out, lo) == 0;
+    t.x_parts = 3; bad += ics_op_feed_pack(&t, x0, x1, lab, 1, d, 95, out, lo) == 0; t = fc;
+    t.x_channels[1] = 0; bad += ics_op_feed_pack(&t, x0, x1, lab, 1, d, 95, out, lo) == 0; t = fc;
+    t.x_dtype[0] = 1; bad += ics_op_feed_pack(&t, x0, x1, lab, 1, d, 95, out, lo) == 0; t = fc;
+    t.label_kind = 5; bad += ics_op_feed_pack(&t, x0, x1, lab, 1, d, 95, out, lo) == 0; t = fc;
+    if (bad) { fprintf(stderr, "feed pack: %d invalid argument sets accepted\n", bad); return 1; }
+    OK(ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 95, out, lo));
+    free(x0); free(x1); free(lab); free(out); free(lo);
+  }
+  for (int kind = 0; kind < 2; ++kind) {
+    ics_net* net = kind ? vae : unet;
+    for (int lay = 0; lay < 3; ++lay) {   /* raw files (float64 parts, float64 ids); one float32 part; one-hot labels */
+      ics_feed_config fc = {2 + lay, 1, {C, 0}, {lay == 1 ? 0 : 3, 0}, kind ? 0 : (lay == 0 ? 2 : lay == 1 ? 1 : 4)};
+      if (lay == 0 && C == 4) { fc.x_parts = 2; fc.x_channels[0] = 1; fc.x_channels[1] = 3; fc.x_dtype[1] = 3; }
+      OK(ics_net_feed_open(net, &fc));
+      void *x0, *x1, *lab; float *cond, *eps, m[5];
+      int ticket[8], nt = 0;
+      for (int step = 0; step < 6; ++step) {
+        const int slot = step % fc.slots, b = 1 + step % B;
+        OK(ics_net_feed_slot(net, slot, &x0, &x1, &lab, &cond, &eps));
+        /* the last byte of every part a batch of max_batch samples uses: the slot's layout must hold them */
+        const size_t e0 = fc.x_dtype[0] ? 8 : 4;
+        memset(x0, 0, (size_t)B * V * fc.x_channels[0] * e0);
+        if (fc.x_parts == 2) memset(x1, 0, (size_t)B * V * 3 * 8); else if (x1) { fprintf(stderr, "feed: x1 of a one-part feed\n"); return 1; }
+        if (kind == 0) memset(lab, 0, (size_t)B * V * (fc.label_kind == 2 ? 8 : fc.label_kind == 1 ? 1 : 95 * 4));
+        else { if (lab) { fprintf(stderr, "feed: labels of a VAE feed\n"); return 1; } memset(cond, 0, (size_t)B * ncond * sizeof(float)); memset(eps, 0, (size_t)B * latent * sizeof(float)); }
+        OK(ics_net_feed_submit(net, slot, b));
+        if (kind == 0) OK(step == 3 ? ics_unet_test_step_fed(net, slot, &ticket[nt]) : ics_unet_train_step_fed(net, slot, &ticket[nt]));
+        else OK(step == 3 ? ics_vae_test_step_fed(net, slot, &ticket[nt]) : ics_vae_train_step_fed(net, slot, &ticket[nt]));
+        ++nt;
+        if (step >= 2) OK(ics_net_feed_metrics(net, ticket[step - 2], m));     /* two steps late */
+      }
+      OK(ics_net_feed_metrics(net, ticket[nt - 1], m));
+      OK(ics_net_feed_metrics(net, ticket[0], m));                             /* again */
+      /* refusals */
+      bad = 0;
+      int tk = -1;
+      bad += ics_net_feed_open(net, &fc) == 0;                                 /* already open */
+      bad += ics_net_feed_slot(net, -1, &x0, &x1, &lab, &cond, &eps) == 0;
+      bad += ics_net_feed_slot(net, fc.slots, &x0, &x1, &lab, &cond, &eps) == 0;
+      bad += ics_net_feed_submit(net, fc.slots, 1) == 0;
+      bad += ics_net_feed_submit(net, 1, 1) == 0;                              /* not obtained since its last submit */
+      OK(ics_net_feed_slot(net, 1, NULL, NULL, NULL, NULL, NULL));
+      bad += ics_net_feed_submit(net, 1, B + 1) == 0;
+      bad += ics_net_feed_submit(net, 1, 0) == 0;
+      bad += (kind ? ics_vae_train_step_fed(net, 1, &tk) : ics_unet_train_step_fed(net, 1, &tk)) == 0;   /* consumed */
+      bad += (kind ? ics_vae_train_step_fed(net, 9, &tk) : ics_unet_train_step_fed(net, 9, &tk)) == 0;
+      bad += (kind ? ics_unet_train_step_fed(net, 1, &tk) : ics_vae_train_step_fed(net, 1, &tk)) == 0;   /* wrong kind */
+      bad += (kind ? ics_unet_test_step_fed(net, 1, &tk) : ics_vae_test_step_fed(net, 1, &tk)) == 0;
+      bad += (kind ? ics_vae_test_step_fed(net, 1, NULL) : ics_unet_test_step_fed(net, 1, NULL)) == 0;
+      OK(ics_net_feed_submit(net, 1, B));
+      bad += ics_net_feed_submit(net, 1, B) == 0;                              /* pending */
+      bad += ics_net_feed_metrics(net, nt, m) == 0;
+      bad += ics_net_feed_metrics(net, -1, m) == 0;
+      bad += ics_net_feed_metrics(net, 0, NULL) == 0;
+      if (bad) { fprintf(stderr, "feed (kind %d, layout %d): %d invalid calls accepted\n", kind, lay, bad); return 1; }
+      if (!ics_last_error()[0]) { fprintf(stderr, "feed: no error message\n"); return 1; }
+      OK(kind ? ics_vae_train_step_fed(net, 1, &tk) : ics_unet_train_step_fed(net, 1, &tk));   /* still usable */
+      OK(ics_net_feed_metrics(net, tk, m));
+      if (lay == 2) {   /* a ticket older than the ring */
+        for (int step = 0; step < 70; ++step) {
+          OK(ics_net_feed_slot(net, 0, NULL, NULL, NULL, NULL, NULL));
+          OK(ics_net_feed_submit(net, 0, 1));
+          OK(kind ? ics_vae_test_step_fed(net, 0, &tk) : ics_unet_test_step_fed(net, 0, &tk));
+        }
+        if (ics_net_feed_metrics(net, ticket[0], m) == 0) { fprintf(stderr, "feed: a ticket older than the ring was read\n"); return 1; }
+        OK(ics_net_feed_metrics(net, tk, m));
+        /* left open: ics_net_destroy closes it */
+      } else {
+        OK(ics_net_feed_close(net));
+      }
+    }
+  }
+  {   /* engines without a feed, and configs that do not match the engine */
+    ics_net* u2 = NULL;
+    ics_unet_config uc = {C, 95, d, B, 1e-3f, 0.f, 1, 1, 0};
+    OK(ics_unet_create(&uc, &u2));
+    ics_feed_config fc = {2, 1, {C, 0}, {0, 0}, 1}, t = fc;
+    float m[5]; int tk;
+    bad = 0;
+    bad += ics_net_feed_close(u2) == 0;
+    bad += ics_net_feed_slot(u2, 0, NULL, NULL, NULL, NULL, NULL) == 0;
+    bad += ics_net_feed_submit(u2, 0, 1) == 0;
+    bad += ics_unet_train_step_fed(u2, 0, &tk) == 0;
+    bad += ics_net_feed_metrics(u2, 0, m) == 0;
+    bad += ics_net_feed_open(NULL, &fc) == 0;
+    bad += ics_net_feed_open(u2, NULL) == 0;
+    t.slots = 1; bad += ics_net_feed_open(u2, &t) == 0; t = fc;
+    t.slots = 5; bad += ics_net_feed_open(u2, &t) == 0; t = fc;
+    t.x_channels[0] = C + 1; bad += ics_net_feed_open(u2, &t) == 0; t = fc;
+    t.label_kind = 0; bad += ics_net_feed_open(u2, &t) == 0; t = fc;
+    t.x_dtype[0] = 2; bad += ics_net_feed_open(u2, &t) == 0; t = fc;
+    if (bad) { fprintf(stderr, "feed: %d invalid open / no-feed calls accepted\n", bad); return 1; }
+    OK(ics_net_feed_open(u2, &fc));
+    OK(ics_net_feed_slot(u2, 0, NULL, NULL, NULL, NULL, NULL));
+    OK(ics_net_feed_submit(u2, 0, B));
+    OK(ics_net_destroy(u2));               /* with an open feed and an upload that no step consumed */
+  }
+  return 0;
+}
+
 static int run(int d, int C, int B, int with_comm) {
   const size_t M = (size_t)B * d * d * d;
   ics_unet_config uc = {C, 95, d, B, 1e-3f, 0.f, 1, 1, with_comm == 2};
@@ -939,6 +1077,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_train_step_resident(vae, mv));
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
+  if (feed_walk(unet, vae, d, C, B, vc.cond_shape, vc.latent_dim)) return 1;
   if (B >= 2 && B <= 8 && tsne_walk(vae, unet, x, cond, eps, B)) return 1;
   if (reconstruct_refusals(unet, &vc, &uc, x, cond, eps, B)) return 1;
   if (C == 1 && B >= 2 && B <= 8 && monitor_walk(unet, vae, x, lab, cond, eps, B, d)) return 1;

@@ -189,13 +189,111 @@ class _Net:
         return v.value
 
 
+FEED_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 3}       # ics_feed_config.x_dtype
+FEED_LABELS = {"none": (0, None), "u8": (1, np.uint8), "f64": (2, np.float64), "f32": (3, np.float32),
+               "onehot": (4, np.float32)}                                # ics_feed_config.label_kind, dtype of the source
+
+
+def feed_config(x_channels, x_dtypes, label_kind="none", slots=2):
+    """ics_feed_config for x parts of x_channels[i] channels and numpy dtypes x_dtypes[i], labels of kind `label_kind`."""
+    x_channels, x_dtypes = [int(c) for c in x_channels], [np.dtype(t) for t in x_dtypes]
+    if not 1 <= len(x_channels) <= 2 or len(x_dtypes) != len(x_channels):
+        raise ValueError("a feed takes one or two x parts, each with a dtype")
+    for t in x_dtypes:
+        if t not in FEED_DTYPES:
+            raise ValueError("x parts are float32 or float64, not %s" % t)
+    if label_kind not in FEED_LABELS:
+        raise ValueError("label_kind must be one of %s" % sorted(FEED_LABELS))
+    pad = [0] * (2 - len(x_channels))
+    return L.FeedConfig(int(slots), len(x_channels), (C.c_int * 2)(*(x_channels + pad)),
+                        (C.c_int * 2)(*([FEED_DTYPES[t] for t in x_dtypes] + pad)), FEED_LABELS[label_kind][0])
+
+
+class _FeedMixin:
+    """Fed steps (include/icsg3d.h, csrc/feed.h): pinned staging slots the host fills with raw arrays, uploaded on a copy
+    stream while the previous step runs and packed (cast, concatenate, labels) on the device."""
+
+    _feed = None      # (x_channels, x_dtypes, label_kind, slots) of the open feed
+
+    def feed_open(self, x_channels, x_dtypes, label_kind="none", slots=2):
+        cfg = feed_config(x_channels, x_dtypes, label_kind, slots)
+        L.check(self._lib.ics_net_feed_open(self._h, C.byref(cfg)))
+        self._feed = (tuple(int(c) for c in x_channels), tuple(np.dtype(t) for t in x_dtypes), label_kind, int(slots))
+
+    def feed_close(self):
+        self._feed = None
+        L.check(self._lib.ics_net_feed_close(self._h))
+
+    def feed_slot(self, slot):
+        """numpy views over the slot's pinned memory, each with max_batch leading rows: {"x": [part, ...], "labels",
+        "cond", "eps"} (None for what the feed does not carry).  Returns once the slot's last upload has left the pinned
+        memory; the views die with feed_close."""
+        if self._feed is None:
+            raise L.IcsError("the engine has no open feed (feed_open)")
+        xc, xt, kind, _ = self._feed
+        p = [C.c_void_p() for _ in range(5)]
+        L.check(self._lib.ics_net_feed_slot(self._h, int(slot), *[C.byref(v) for v in p]))
+        B, d = self.max_batch, self.d
+
+        def view(ptr, shape, dtype):
+            if not ptr.value:
+                return None
+            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+            return np.frombuffer((C.c_char * n).from_address(ptr.value), dtype=dtype).reshape(shape)
+
+        out = {"x": [view(p[i], (B, d, d, d, xc[i]), xt[i]) for i in range(len(xc))]}
+        ldt = FEED_LABELS[kind][1]
+        out["labels"] = None if ldt is None else view(
+            p[2], (B, d, d, d, self.num_classes) if kind == "onehot" else (B, d, d, d), ldt)
+        out["cond"] = view(p[3], (B, getattr(self, "cond_shape", 0)), np.float32)
+        out["eps"] = view(p[4], (B, getattr(self, "latent_dim", 0)), np.float32)
+        return out
+
+    def feed_submit(self, slot, batch):
+        L.check(self._lib.ics_net_feed_submit(self._h, int(slot), int(batch)))
+
+    def _step_fed(self, fn, slot):
+        t = C.c_int(-1)
+        L.check(fn(self._h, int(slot), C.byref(t)))
+        return t.value
+
+    def feed_metrics(self, ticket):
+        m = np.zeros(8, np.float32)
+        L.check(self._lib.ics_net_feed_metrics(self._h, int(ticket), L.fptr(m)))
+        return m[:self._n_metrics]
+
+
+def feed_pack(x_parts, labels=None, label_kind="none", num_classes=0):
+    """Single-op entry (ics_op_feed_pack): the pack kernel alone on host arrays.  x_parts: one or two (B,d,d,d,c) float32 /
+    float64 arrays; labels as label_kind says.  Returns (x float32 (B,d,d,d,sum c), labels uint8 (B,d,d,d) | None)."""
+    lib = L.load()
+    parts = [np.ascontiguousarray(a) for a in x_parts]
+    B, d = parts[0].shape[0], parts[0].shape[1]
+    cfg = feed_config([a.shape[4] for a in parts], [a.dtype for a in parts], label_kind)
+    lab = None
+    if label_kind != "none":
+        lab = np.ascontiguousarray(labels, FEED_LABELS[label_kind][1])
+        want = (B, d, d, d, num_classes) if label_kind == "onehot" else (B, d, d, d)
+        if lab.shape != want:
+            raise ValueError("labels must be %s, got %s" % (want, lab.shape))
+    for a in parts:
+        if a.shape[:4] != (B, d, d, d):
+            raise ValueError("bad x part shape %s" % (a.shape,))
+    x = np.empty((B, d, d, d, sum(a.shape[4] for a in parts)), np.float32)
+    out = np.empty((B, d, d, d), np.uint8) if lab is not None else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    L.check(lib.ics_op_feed_pack(C.byref(cfg), vp(parts[0]), vp(parts[1]) if len(parts) == 2 else None, vp(lab), B, d,
+                                 int(num_classes), L.fptr(x), L.u8ptr(out)))
+    return x, out
+
+
 def comm_unique_id():
     buf = C.create_string_buffer(128)
     L.check(L.load().ics_comm_unique_id(buf))
     return buf.raw
 
 
-class UnetEngine(_Net):
+class UnetEngine(_Net, _FeedMixin):
     def __init__(self, in_channels=1, num_classes=95, d=32, max_batch=32, lr=1e-6, loss_weight=0.0,
                  pool_ties="tf_cpu", bn_unbias=True, device=None, bce_from_logits=False):
         super().__init__()
@@ -280,6 +378,15 @@ class UnetEngine(_Net):
         """model.predict on the uploaded batch, enqueued only; the outputs stay in HBM (benchmark path)."""
         L.check(self._lib.ics_unet_predict_resident(self._h, 1 if labels_only else 0, float(thresh)))
 
+    _n_metrics = 5
+
+    def train_step_fed(self, slot):
+        """the train step on a submitted slot, enqueued only -> the ticket of its metrics (feed_metrics)"""
+        return self._step_fed(self._lib.ics_unet_train_step_fed, slot)
+
+    def test_step_fed(self, slot):
+        return self._step_fed(self._lib.ics_unet_test_step_fed, slot)
+
     def train_step_resident(self, want_metrics=False):
         if want_metrics:
             m = np.zeros(5, np.float32)
@@ -327,7 +434,7 @@ class _AtomsOut:
                 "failed": failed}
 
 
-class VaeEngine(_Net):
+class VaeEngine(_Net, _FeedMixin):
     def __init__(self, unet: UnetEngine, in_channels=1, cond_shape=10, latent_dim=256,
                  filters=(16, 32, 64, 128), d=32, max_batch=32, lr=5e-4, alpha=0.5, beta=3e-4,
                  pm_layer_weights=(1.0, 1.0, 1.0, 1.0), bn_unbias=True):
@@ -336,6 +443,7 @@ class VaeEngine(_Net):
         self.in_channels, self.cond_shape, self.latent_dim, self.d, self.max_batch = (
             in_channels, cond_shape, latent_dim, d, max_batch)
         self._resident = 0   # batch of the engine's resident inputs (every call that uploads x, cond, eps sets it)
+        self._slot_batch = {}   # batch submitted to each feed slot: the resident batch once a fed step has packed it
         cfg = L.VaeConfig(in_channels, cond_shape, latent_dim, (C.c_int * 4)(*filters), d, max_batch, lr,
                           alpha, beta, (C.c_float * 4)(*pm_layer_weights), 1 if bn_unbias else 0)
         L.check(self._lib.ics_vae_create(C.byref(cfg), unet._h if unet is not None else None, C.byref(self._h)))
@@ -520,6 +628,22 @@ class VaeEngine(_Net):
         L.check(self._lib.ics_vae_voxelise_batch(self._h, C.byref(cs), L.i32ptr(jobs), B, float(eps_frac),
                                                  float(label_frac), L.fptr(cond), L.fptr(eps)))
         self._resident = B
+
+    _n_metrics = 4
+
+    def feed_submit(self, slot, batch):
+        super().feed_submit(slot, batch)
+        self._slot_batch[int(slot)] = int(batch)
+
+    def train_step_fed(self, slot):
+        t = self._step_fed(self._lib.ics_vae_train_step_fed, slot)
+        self._resident = self._slot_batch[int(slot)]
+        return t
+
+    def test_step_fed(self, slot):
+        t = self._step_fed(self._lib.ics_vae_test_step_fed, slot)
+        self._resident = self._slot_batch[int(slot)]
+        return t
 
     def train_step_resident(self, want_metrics=False):
         if want_metrics:

@@ -9,6 +9,48 @@ import numpy as np
 from ..synthetic import synthetic_batch
 
 
+_FEED_LABEL_KINDS = {np.dtype(np.uint8): "u8", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+
+
+def _raw(path):
+    """a saved grid as it lies in its file: memory-mapped, no copy, no cast"""
+    return np.load(path, mmap_mode="r")
+
+
+def _read_into(path, dst):
+    """The payload of a saved grid into dst, a flat C-contiguous view of a staging slot.  A file of dst's dtype is read
+    straight into it (one copy, no temporary array, no mapping to set up and tear down per file: with two files per
+    sample that overhead, not the bytes, bounded a fed DFC-VAE loop: DESIGN section 24, "Before"); any other file is
+    loaded and cast while copied.  read_magic / read_array_header_1_0 / _2_0 are numpy.lib.format's documented readers of
+    the .npy header (what np.load itself calls); a file of a later format version takes the np.load path."""
+    F = np.lib.format
+    with open(path, "rb") as f:
+        version = F.read_magic(f)
+        if version in ((1, 0), (2, 0)):
+            shape, fortran, dtype = (F.read_array_header_1_0 if version == (1, 0) else F.read_array_header_2_0)(f)
+            if dtype == dst.dtype and not dtype.hasobject and int(np.prod(shape)) == dst.size and (not fortran or len(shape) <= 1):
+                if f.readinto(memoryview(dst).cast("B")) != dst.nbytes:
+                    raise ValueError("%s is shorter than its header says" % path)
+                return
+    np.copyto(dst, np.load(path).reshape(-1), casting="unsafe")
+
+
+def _feed_x_spec(data_path, ID, n_channels):
+    """(x_channels, x_dtypes) of the files behind create_lattice_meshgrid, or None when the pack kernel does not read them"""
+    names = ["density_matrices"] + (["coordinate_grids"] if n_channels != 1 else [])
+    dts = tuple(_raw(os.path.join(data_path, n, ID)).dtype for n in names)
+    if n_channels not in (1, 4) or any(t not in (np.dtype(np.float32), np.dtype(np.float64)) for t in dts):
+        return None
+    return ((1,) if n_channels == 1 else (1, 3)), dts
+
+
+def _fill_x(data_path, ID, views, i):
+    """sample i of a slot: the density grid into part 0, the coordinate grids into part 1, as raw payloads"""
+    _read_into(os.path.join(data_path, "density_matrices", ID), views["x"][0][i].reshape(-1))
+    if len(views["x"]) == 2:
+        _read_into(os.path.join(data_path, "coordinate_grids", ID), views["x"][1][i].reshape(-1))
+
+
 class UnetDataGenerator:
     def __init__(self, list_IDs, data_path, batch_size=2, dim=(32, 32, 32), n_channels=7, n_classes=95,
                  shuffle=False, one_hot=False):
@@ -47,6 +89,28 @@ class UnetDataGenerator:
             return M
         p = np.load(os.path.join(self.data_path, "coordinate_grids", ID)).reshape(*self.dim, 3)
         return np.concatenate((M, p), axis=-1)
+
+    # ---- fed steps (icsg3d_amd.feed.Feeder): the files' payloads go into a staging slot as they are; the cast to float32,
+    # the (M | p) concatenate and the uint8 labels happen on the device
+    def feed_spec(self):
+        """(x_channels, x_dtypes, label_kind) of the files, or None: then the Feeder copies __getitem__'s arrays"""
+        if not self.list_IDs:
+            return None
+        x = _feed_x_spec(self.data_path, self.list_IDs[0], self.n_channels)
+        # ids saved in another dtype (integers, say) are cast to uint8 on the host while they are copied: a byte per voxel
+        kind = _FEED_LABEL_KINDS.get(_raw(os.path.join(self.data_path, "species_matrices", self.list_IDs[0])).dtype, "u8")
+        return None if x is None else x + (kind,)
+
+    def fill(self, index, views, map=lambda f, it: [f(i) for i in it]):
+        """batch `index` into the views of a slot (UnetEngine.feed_slot), one sample per call of `map`; returns its size"""
+        ids = [self.list_IDs[k] for k in self.indexes[index * self.batch_size:(index + 1) * self.batch_size]]
+
+        def one(i):
+            _fill_x(self.data_path, ids[i], views, i)
+            _read_into(os.path.join(self.data_path, "species_matrices", ids[i]), views["labels"][i].reshape(-1))
+
+        map(one, range(len(ids)))
+        return len(ids)
 
 
 class SyntheticUnetGenerator:

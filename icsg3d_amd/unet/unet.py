@@ -146,10 +146,14 @@ class _UnetModel:
             return [float(v) for v in self._o._engine(len(X), grow=True).test_step(X, labels)]
 
     def fit_generator(self, generator, validation_data=None, epochs=1, callbacks=None, workers=4,
-                      use_multiprocessing=False, verbose=1, max_queue_size=10):
+                      use_multiprocessing=False, verbose=1, max_queue_size=10, feed=False):
         """Epoch loop of unet/unet.py:370-377: mean of per-batch metrics as the epoch log.  `workers` loader
         threads fill a bounded queue with ready batches (labels already reduced to uint8 class ids) while
-        the GPU runs the previous step -- Keras' OrderedEnqueuer with use_multiprocessing=False."""
+        the GPU runs the previous step -- Keras' OrderedEnqueuer with use_multiprocessing=False.
+
+        feed=True: fed steps (icsg3d_amd.feed.Feeder) -- the batches travel as raw arrays through pinned staging slots,
+        uploaded while the previous step runs; cast, concatenate and label conversion happen on the device, and the
+        metrics come back without a stall per step.  Same logs and weights, bit for bit."""
         from ..prefetch import prefetched
         nc = self._o.num_classes
 
@@ -157,23 +161,39 @@ class _UnetModel:
             X, y = item
             return np.asarray(X, np.float32), _to_labels(y[0] if isinstance(y, (list, tuple)) else y, nc)
 
+        def fed(gen, training):
+            # one feed for all epochs and both generators (a Feeder reuses the open feed when its layout is the same);
+            # the engine grows like the unfed loop's when a batch outgrows it
+            from ..feed import Feeder
+            o = self._o
+            return list(Feeder(o._engine(getattr(gen, "batch_size", 0) or 1, grow=True), gen, workers=workers,
+                               training=training, close=False, grow=lambda b: o._engine(b, grow=True),
+                               watch=lambda: o._dp_watch("AtomUnet fit_generator(feed=True)")))
+
         history = []
-        for e in range(epochs):
-            tm = np.mean([[float(v) for v in self._o._engine(len(X), grow=True).train_step(X, lab)]
-                          for X, lab in prefetched(generator, workers, max_queue_size, prep)], axis=0)
-            logs = dict(zip(self.metrics_names, tm))
-            if validation_data is not None and len(validation_data):
-                vm = np.mean([[float(v) for v in self._o._engine(len(X), grow=True).test_step(X, lab)]
-                              for X, lab in prefetched(validation_data, workers, max_queue_size, prep)], axis=0)
-                logs.update({"val_" + k: v for k, v in zip(self.metrics_names, vm)})
-            if verbose:
-                print("Epoch %d/%d  " % (e + 1, epochs) + "  ".join("%s: %.4f" % kv for kv in logs.items()))
-            for cb in callbacks or []:
-                cb.on_epoch_end(e, logs)
-            for g in (generator, validation_data):
-                if g is not None and hasattr(g, "on_epoch_end"):
-                    g.on_epoch_end()
-            history.append(logs)
+        try:
+            for e in range(epochs):
+                tm = np.mean(fed(generator, True) if feed else
+                             [[float(v) for v in self._o._engine(len(X), grow=True).train_step(X, lab)]
+                              for X, lab in prefetched(generator, workers, max_queue_size, prep)], axis=0)
+                logs = dict(zip(self.metrics_names, tm))
+                if validation_data is not None and len(validation_data):
+                    vm = np.mean(fed(validation_data, False) if feed else
+                                 [[float(v) for v in self._o._engine(len(X), grow=True).test_step(X, lab)]
+                                  for X, lab in prefetched(validation_data, workers, max_queue_size, prep)], axis=0)
+                    logs.update({"val_" + k: v for k, v in zip(self.metrics_names, vm)})
+                if verbose:
+                    print("Epoch %d/%d  " % (e + 1, epochs) + "  ".join("%s: %.4f" % kv for kv in logs.items()))
+                for cb in callbacks or []:
+                    cb.on_epoch_end(e, logs)
+                for g in (generator, validation_data):
+                    if g is not None and hasattr(g, "on_epoch_end"):
+                        g.on_epoch_end()
+                history.append(logs)
+        finally:
+            eng = self._o._eng
+            if feed and eng is not None and eng._feed is not None:
+                eng.feed_close()
         return history
 
     # -- checkpoints (unet/unet.py:261-264,378-379,387-390)
@@ -293,8 +313,9 @@ class AtomUnet(DataParallelMixin):
             self._host_weights.update({k: np.asarray(v, np.float32) for k, v in w.items()})
 
     # ---- reference methods
-    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/", monitor=False):
-        """monitor=True: the writer rank also draws TrainingPlot's pictures on the GPU (icsg3d_amd.monitor.UnetMonitor):
+    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/", monitor=False, feed=False):
+        """feed=True: fed steps, see fit_generator.
+        monitor=True: the writer rank also draws TrainingPlot's pictures on the GPU (icsg3d_amd.monitor.UnetMonitor):
         the segmentation sheets on a new best val_loss and the loss curve every epoch, without matplotlib."""
         print("Training...")
         callbacks = [_BestCheckpoint(self.model, self.filepath)]
@@ -305,7 +326,7 @@ class AtomUnet(DataParallelMixin):
                 callbacks.append(UnetMonitor(val_gen, output_dir))
                 callbacks[-1].set_model(self)
         self.model.fit_generator(generator=train_gen, validation_data=val_gen, use_multiprocessing=False,
-                                 workers=4, epochs=epochs, callbacks=callbacks)
+                                 workers=4, epochs=epochs, callbacks=callbacks, feed=feed)
         self._dp_barrier()                               # rank 0 has finished writing the best checkpoint
         if os.path.exists(self.filepath):
             self.model.load_weights(self.filepath)

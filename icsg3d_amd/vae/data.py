@@ -6,6 +6,7 @@ import re
 import numpy as np
 
 from ..synthetic import synthetic_batch
+from ..unet.data import _feed_x_spec, _fill_x
 
 
 class VAEDataGenerator:
@@ -61,6 +62,25 @@ class VAEDataGenerator:
             return M
         p = np.load(os.path.join(self.data_path, "coordinate_grids", ID)).reshape(*self.dim, 3)
         return np.concatenate((M, p), axis=-1)
+
+    # ---- fed steps (icsg3d_amd.feed.Feeder): the files' payloads go into a staging slot as they are
+    def feed_spec(self):
+        """(x_channels, x_dtypes, "none") of the files, or None: then the Feeder copies __getitem__'s arrays"""
+        if not self.list_IDs or self.return_S:
+            return None
+        x = _feed_x_spec(self.data_path, self.list_IDs[0], self.n_channels)
+        return None if x is None else x + ("none",)
+
+    def fill(self, index, views, map=lambda f, it: [f(i) for i in it]):
+        """batch `index` into the views of a slot (VaeEngine.feed_slot), one sample per call of `map`; returns its size"""
+        ids = [self.list_IDs[k] for k in self.indexes[index * self.batch_size:(index + 1) * self.batch_size]]
+
+        def one(i):
+            _fill_x(self.data_path, ids[i], views, i)
+            views["cond"][i] = self.property_to_categorical(ids[i])
+
+        map(one, range(len(ids)))
+        return len(ids)
 
 
 class SyntheticVAEGenerator:

@@ -203,8 +203,11 @@ class LatticeDFCVAE(DataParallelMixin):
         else:
             self.filepath = "saved_models/lattice_dfc_vae_weights.best.hdf5"
 
-    def train(self, train_gen, val_gen, epochs, weights=None, monitor=False, monitor_seed=0):
-        """monitor=True: the writer rank draws the reference loop's pictures on the GPU (icsg3d_amd.monitor.VaeMonitor):
+    def train(self, train_gen, val_gen, epochs, weights=None, monitor=False, monitor_seed=0, feed=False):
+        """feed=True: fed steps (icsg3d_amd.feed.Feeder) -- the batches travel as raw arrays through pinned staging slots,
+        uploaded while the previous step runs, and the metrics come back without a stall per step; eps is drawn by the same
+        call in the same step order.  Same losses and weights, bit for bit.
+        monitor=True: the writer rank draws the reference loop's pictures on the GPU (icsg3d_amd.monitor.VaeMonitor):
         reconstructions, prior samples and the latent KDE on a new best validation loss, the loss curves every 10 epochs."""
         best_loss = np.inf
         mon = None
@@ -220,27 +223,35 @@ class LatticeDFCVAE(DataParallelMixin):
               % (len(train_gen.list_IDs), self.train_batch_size, train_steps))
         self._set_model(weights, batch_size=self.train_batch_size)
         self.losses = np.empty((self.num_epochs, 2))
-        for e in range(self.num_epochs):
-            print("Epoch %s:" % e)
-            t0 = time.time()
-            # each batch is read from disk ONCE (the target is the input) and one batch ahead of the GPU step
-            tm = np.mean([self.model.train_on_batch([M, cond], M) for M, cond in self._batches(train_gen, train_steps)], axis=0)
-            vm = np.mean([self.model.test_on_batch([M, cond], M) for M, cond in self._batches(val_gen, val_steps)], axis=0) \
-                if val_steps else tm
-            s = "Time: %.3f s   " % (time.time() - t0)
-            s += "".join("Train %s: %.3f    " % (n, v) for n, v in zip(self.metric_names, tm))
-            s += "".join("Val %s: %.3f    " % (n, v) for n, v in zip(self.metric_names, vm))
-            print(s)
-            self.losses[e] = [tm[0], vm[0]]
-            if vm[0] < best_loss:
-                best_loss = vm[0]
-                if self._dp_is_writer():                 # data parallel: vm is rank-reduced, rank 0 writes
-                    print("Saving Model")
-                    self.model.save_weights(self.filepath)
-                if mon is not None:
-                    mon.best(e)
-            if mon is not None and e % 10 == 0:
-                mon.losses(self.losses, e + 1)
+        try:
+            for e in range(self.num_epochs):
+                print("Epoch %s:" % e)
+                t0 = time.time()
+                # each batch is read from disk ONCE (the target is the input) and one batch ahead of the GPU step
+                if feed:
+                    tm = np.mean(self._fed(train_gen, train_steps, True), axis=0)
+                    vm = np.mean(self._fed(val_gen, val_steps, False), axis=0) if val_steps else tm
+                else:
+                    tm = np.mean([self.model.train_on_batch([M, cond], M) for M, cond in self._batches(train_gen, train_steps)], axis=0)
+                    vm = np.mean([self.model.test_on_batch([M, cond], M) for M, cond in self._batches(val_gen, val_steps)], axis=0) \
+                        if val_steps else tm
+                s = "Time: %.3f s   " % (time.time() - t0)
+                s += "".join("Train %s: %.3f    " % (n, v) for n, v in zip(self.metric_names, tm))
+                s += "".join("Val %s: %.3f    " % (n, v) for n, v in zip(self.metric_names, vm))
+                print(s)
+                self.losses[e] = [tm[0], vm[0]]
+                if vm[0] < best_loss:
+                    best_loss = vm[0]
+                    if self._dp_is_writer():                 # data parallel: vm is rank-reduced, rank 0 writes
+                        print("Saving Model")
+                        self.model.save_weights(self.filepath)
+                    if mon is not None:
+                        mon.best(e)
+                if mon is not None and e % 10 == 0:
+                    mon.losses(self.losses, e + 1)
+        finally:
+            if feed and self._eng is not None and self._eng._feed is not None:
+                self._eng.feed_close()
         self._dp_barrier()
         if os.path.exists(self.filepath):
             self.model.load_weights(self.filepath)
@@ -248,6 +259,13 @@ class LatticeDFCVAE(DataParallelMixin):
             self.model.save(os.path.splitext(self.filepath)[0] + ".h5")
             print("Model saved")
         self._dp_barrier()
+
+    def _fed(self, gen, steps, training):
+        # one feed for all epochs and both generators: a Feeder reuses the open feed when its layout is the same
+        from ..feed import Feeder
+        return list(Feeder(self._engine(gen.batch_size, grow=True), gen, training=training, steps=steps, close=False,
+                           eps=lambda n: self.model._eps(n, None), grow=lambda b: self._engine(b, grow=True),
+                           watch=lambda: self._dp_watch("LatticeDFCVAE train(feed=True)")))
 
     @staticmethod
     def _batches(gen, steps):

@@ -851,6 +851,57 @@ int ics_op_tsne_run(ics_tsne* h, int iters, int* done);
  * the last iteration run, -1 before the first) and the number of points; every pointer is optional. */
 int ics_op_tsne_read(ics_tsne* h, float* embedding, double* kl, double* grad_norm, int* n_iter, int* count);
 
+/* ---------------------------------------------------------------- fed steps: batch upload overlapped with the train step
+ * The synchronous ics_*_train_step copies the batch from pageable memory on the compute stream and waits for the metrics.
+ * A feed attached to an engine takes both off the step: the host writes the RAW arrays of a batch (the on-disk dtypes of
+ * create_matrices.py's files, or a generator's float64 X and one-hot y) into one of `slots` pinned staging slots, a copy
+ * stream uploads the slot while the previous step runs, and one pack kernel on the compute stream does what the host did
+ * before: the cast to float32 (IEEE round to nearest even, ndarray.astype(np.float32)), the channel concatenate of up to
+ * two x parts into NDHWC, and the labels as uint8 class ids.  The result is bit-identical to the synchronous step on the
+ * host-prepared arrays.  icsg3d_amd/csrc/feed.h states the ordering rules.
+ *
+ * x parts: part i is [batch][d][d][d][x_channels[i]] of x_dtype[i] = 0 (float32, the code of ics_op_render_slice) or 3
+ * (float64); the channels add up to the engine's in_channels.  label_kind: 0 none (VAE engines), 1 uint8 ids, 2 float64
+ * ids (species_matrices), 3 float32 ids -- each [batch][d][d][d] -- or 4 one-hot float32 [batch][d][d][d][num_classes],
+ * reduced by np.argmax's rule (the lowest index among equal maxima; the first NaN, if there is one).  Ids outside 0..255
+ * and non-integer ids are the caller's error: they are converted as (uint8)(int)v, and nothing checks them.  A U-Net
+ * feed needs labels (kind 1..4), a VAE feed carries cond [batch][cond_shape] and eps [batch][latent_dim] float32. */
+typedef struct ics_feed_config {
+  int slots;          /* 2..4 staging slots, each laid out for max_batch samples               */
+  int x_parts;        /* 1 or 2                                                                */
+  int x_channels[2];  /* channels of each part; their sum is the engine's in_channels          */
+  int x_dtype[2];     /* 0 float32, 3 float64                                                  */
+  int label_kind;     /* 0 none, 1 uint8 ids, 2 float64 ids, 3 float32 ids, 4 one-hot float32  */
+} ics_feed_config;
+/* Refused while a feed is open, and on any mismatch with the engine (channel sum, a label kind the engine has no use for). */
+int ics_net_feed_open(ics_net* net, const ics_feed_config* cfg);
+/* Drains the copy stream and the compute stream first; the pinned memory of every slot is gone afterwards.  Closing an
+ * engine without a feed is refused; ics_net_destroy closes an open feed itself. */
+int ics_net_feed_close(ics_net* net);
+/* The pinned arrays of `slot`, each sized for max_batch samples (NULL for what the feed does not carry; every output
+ * pointer is optional).  Blocks until the slot's last upload has completed -- on that event and on nothing else -- after
+ * which the host may rewrite them. */
+int ics_net_feed_slot(ics_net* net, int slot, void** x0, void** x1, void** labels, float** cond, float** eps);
+/* Enqueues the upload of the first `batch` samples of the slot on the copy stream and returns.  Refused: a slot that was
+ * not obtained (ics_net_feed_slot) since its last submit, a slot whose submitted batch no step has consumed yet,
+ * batch outside [1, max_batch]. */
+int ics_net_feed_submit(ics_net* net, int slot, int batch);
+/* Pack the submitted slot into the engine's input buffers and run the resident step on it, enqueued only: *ticket names
+ * the step's metrics.  Refused: a slot that was never submitted or whose batch a step has already consumed, the other
+ * engine kind. */
+int ics_unet_train_step_fed(ics_net* net, int slot, int* ticket);
+int ics_unet_test_step_fed(ics_net* net, int slot, int* ticket);
+int ics_vae_train_step_fed(ics_net* net, int slot, int* ticket);
+int ics_vae_test_step_fed(ics_net* net, int slot, int* ticket);
+/* Waits for the step behind `ticket` only and returns its 5 (U-Net) or 4 (VAE) metrics.  The 64 most recent tickets
+ * can be read, in any order and more than once; an older one is refused. */
+int ics_net_feed_metrics(ics_net* net, int ticket, float* metrics);
+/* The pack kernel alone on host arrays: x [batch][d][d][d][sum of x_channels] float32 and, with a label kind,
+ * out_labels [batch][d][d][d] uint8.  cfg->slots is not read; d a power of two >= 8; num_classes 2..127 (one-hot only).
+ * Synchronous, the calling thread's op stream and scratch. */
+int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1, const void* labels, int batch, int d,
+                     int num_classes, float* x, uint8_t* out_labels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ if __name__ == "__main__":
     p.add_argument("--channels", type=int, default=4, help="input channels (density + 3 coordinate grids)")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic grids instead of data/<name>")
     p.add_argument("--sync_bn", type=int, default=0, help="data parallel: BatchNorm statistics over all ranks")
+    p.add_argument("--feed", action="store_true",
+                   help="fed steps: upload each batch through pinned staging slots while the previous step runs")
     p.add_argument("--monitor", action="store_true",
                    help="draw the reference's training pictures on the GPU into the output folder (icsg3d_amd/monitor.py)")
     p.add_argument("--gpus", type=int, default=0,
@@ -99,7 +101,7 @@ if __name__ == "__main__":
     if dp:
         unet.enable_data_parallel(dp[0], rank, world, sync_bn=bool(a.sync_bn), force=world == 1)
     unet.train_generator(training_generator, validation_generator, epochs=a.epochs,
-                         output_dir=os.path.join("output", "unet", mode), monitor=a.monitor)
+                         output_dir=os.path.join("output", "unet", mode), monitor=a.monitor, feed=a.feed)
     if rank == 0:
         unet.save_(weights, os.path.splitext(weights)[0] + ".h5")
     if dp:

@@ -33,6 +33,8 @@ if __name__ == "__main__":
     p.add_argument("--channels", type=int, default=4)
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--sync_bn", type=int, default=0)
+    p.add_argument("--feed", action="store_true",
+                   help="fed steps: upload each batch through pinned staging slots while the previous step runs")
     p.add_argument("--monitor", action="store_true",
                    help="draw the reference's training pictures on the GPU into the output folder (icsg3d_amd/monitor.py)")
     p.add_argument("--gpus", type=int, default=0,
@@ -81,7 +83,8 @@ if __name__ == "__main__":
                                 output_dir=os.path.join("output", "vae", mode))
     if dp:
         lattice_vae.enable_data_parallel(dp[0], rank, world, sync_bn=bool(a.sync_bn), force=world == 1)
-    lattice_vae.train(training_generator, validation_generator, epochs=a.epochs, weights=weights, monitor=a.monitor)
+    lattice_vae.train(training_generator, validation_generator, epochs=a.epochs, weights=weights, monitor=a.monitor,
+                      feed=a.feed)
     if dp:
         dp[0].barrier()
         dp[0].destroy_process_group()
