@@ -204,6 +204,11 @@ SIGNATURES = {
     "ics_op_unet_head": (C.c_int, [_F, _F, _F, _F, _F, _U8, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _F, _F,
                                   C.POINTER(C.c_double)]),
     "ics_op_unet_metrics_from_sums": (C.c_int, [_D, _F]),
+    "ics_op_unet_head_weighted": (C.c_int, [_F, _F, _F, _F, _F, _U8, C.c_size_t, C.c_int, C.c_float, C.c_int, C.c_int, _F,
+                                           _F, C.POINTER(C.c_double), _F]),
+    "ics_unet_set_class_weights": (C.c_int, [_H, _F, C.c_int]),
+    "ics_unet_get_class_weights": (C.c_int, [_H, _F, C.c_int, C.POINTER(C.c_int)]),
+    "ics_op_label_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _I64, _I64]),
     "ics_op_vae_loss": (C.c_int, [_F, C.c_int, C.c_int, _D, C.c_int, C.c_double, _D, C.POINTER(C.c_int), _D, _F, C.c_float,
                                   C.c_float, C.c_int, _D, _F]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),

@@ -137,11 +137,15 @@ int launch_head_fused(hipStream_t st, const float* x, int ldx, const float* scal
                       const float* wsig_k, const float* bsoft, const float* bsig, float* z, const unsigned char* labels,
                       size_t M, int mode, int want_grad, float wsoft, double* partial, int partial_blocks, float* metrics,
                       int* nblk_out = nullptr, float* dz_colsum = nullptr, double* keep = nullptr,
-                      float thresh = 0.f, unsigned char* species = nullptr, unsigned char* mask = nullptr);
+                      float thresh = 0.f, unsigned char* species = nullptr, unsigned char* mask = nullptr,
+                      const float* cw = nullptr);
 // mode 0: probabilities -> z; 1: loss / metrics (+ dz with want_grad); 2: uint8 argmax species + (sig >= thresh) mask only
 int launch_head(hipStream_t st, float* z, int ldz, int ncls, const unsigned char* labels, size_t M,
                 int mode, int want_grad, float wsoft, double* partial, int partial_blocks,
-                float* metrics, int* nblk_out = nullptr, float* dz_colsum = nullptr, double* keep = nullptr);
+                float* metrics, int* nblk_out = nullptr, float* dz_colsum = nullptr, double* keep = nullptr,
+                const float* cw = nullptr);
+// cw (both head launchers): optional device table of per-class loss weights [ncls]; it replaces the scalar wsoft (loss
+// modes only) and selects the kernels' CW instantiation
 // dz_colsum: optional [blocks][ncls+1] per-block column sums of the dz the kernel writes (head bias gradients)
 // phase 0: reduce block partials + finalize; 1: reduce only -> sums[7]; 2: finalize from sums[7]
 // keep: optional [7], receives the (global) sums the ratios were formed from in phases 0 and 2

@@ -942,12 +942,23 @@ size_t layer_bwd_workspace_floats(const LayerBwd& L) {
 // Four voxels per wave: 16 lanes own one voxel's logits (classes sl, sl+16, ... : up to 8 per lane, ncls <= 128),
 // so the three row reductions are 4 xor-shuffle steps inside a 16-lane group instead of a 64-lane wave reduction
 // per voxel (the one-wave-per-voxel version was instruction-bound at 1.8 TB/s).
+// CW (per-class loss weights): the weight of a voxel is cw[label] instead of the scalar wsoft.  The
+// table (at most 128 floats) is staged into LDS once per workgroup -- the index differs per lane, so it must not become
+// a global load per voxel -- and REPLACES the scalar in the loss term and in the gradient scale; the normalisation stays
+// 1 / (B V) (Keras takes a plain mean), and the sigmoid head, the clip rule and the metric counts never see a weight.
+// Loss modes only: the predict mode exists for CW = false, which is the kernel as it was before the switch.
+template <bool CW>
 __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ldz, int ncls,
                                                    const unsigned char* __restrict__ labels, size_t M,
                                                    int rows_per_block, int mode, int want_grad,
                                                    float wsoft, float inv_bv, double* __restrict__ partial,
-                                                   float* __restrict__ dz_colsum) {
+                                                   float* __restrict__ dz_colsum, const float* __restrict__ cw) {
   constexpr int J = 8;
+  __shared__ float cwt[CW ? 128 : 1];
+  if (CW) {
+    if (threadIdx.x < 128) cwt[threadIdx.x] = (int)threadIdx.x < ncls ? cw[threadIdx.x] : 0.f;
+    __syncthreads();
+  }
   // want_grad bit 1: binary_crossentropy in TF 2.1's logits form (tf.keras.backend.binary_crossentropy short-circuits to
   // sigmoid_cross_entropy_with_logits when the prediction's producer op is a Sigmoid -- SURVEY App. B, confidence M):
   // max(z, 0) - z t + log1p(exp(-|z|)), gradient sigmoid(z) - t with no clip kink.  Default: the clipped-probability form.
@@ -999,7 +1010,7 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
 #pragma unroll
     for (int j = 0; j < J; ++j) { p[j] = p[j] / sum; psl += p[j]; }
     const float ps = 1.f / (1.f + expf(-zsig));
-    if (mode == 0) {
+    if (!CW && mode == 0) {
       if (rv) {
 #pragma unroll
         for (int j = 0; j < J; ++j) {
@@ -1011,6 +1022,7 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
       continue;
     }
     const int lab = rv ? labels[row] : 0;
+    const float wv = CW ? cwt[lab & 127] : wsoft;           // (labels are below ncls <= 127: the mask only bounds the read)
     // renormalise (p /= sum p), clip, -w*log  (only the true class contributes)
     const float psum = gsum(psl);
     float mine = 0.f, cnt = 0.f;
@@ -1030,7 +1042,7 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
     const bool inside_s = ps >= kKEps && ps <= 1.f - kKEps;
     const float pc = fminf(fmaxf(ps, kKEps), 1.f - kKEps);
     if (sl == 0 && rv) {
-      a_ls += (double)(-wsoft * logf(qc));
+      a_ls += (double)(-wv * logf(qc));
       a_lg += bce_z ? (double)(fmaxf(zsig, 0.f) - zsig * tsig + log1pf(expf(-fabsf(zsig))))
                     : (double)(-(tsig * logf(pc) + (1.f - tsig) * logf(1.f - pc)));
       const bool hit = pt_raw > 0.5f;
@@ -1040,7 +1052,7 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
     }
     if (want_grad && rv) {
       // d lsoft/dz = w*(p - y)/(B*V) when the true-class probability is not clipped, else 0
-      const float gs = inside ? wsoft * inv_bv : 0.f;
+      const float gs = inside ? wv * inv_bv : 0.f;
 #pragma unroll
       for (int j = 0; j < J; ++j) {
         const int c = sl + 16 * j;
@@ -1051,7 +1063,7 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
       if (sl == 0) { zr[ncls] = dzs; cacc_sig += dzs; }
     }
   }
-  if (mode == 0) return;
+  if (!CW && mode == 0) return;
   if (want_grad && dz_colsum != nullptr) {
     // per-block column sums of dz (soft | sig bias gradients): 4 voxel slots x 4 waves, fixed order
 #pragma unroll
@@ -1100,6 +1112,9 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
 typedef float hv4 __attribute__((ext_vector_type(4)));
 constexpr int kHeadWP = 132;             // LDS pitch of a class row of Wt (floats)
 
+// CW: per-class loss weights from an LDS table, as in head_kernel<true> (512 more bytes of LDS: two workgroups per CU
+// still fit); the inference modes 0 and 2 exist for CW = false only.
+template <bool CW>
 __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restrict__ x, int ldx,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          const float* __restrict__ wsoft_k, const float* __restrict__ wsig_k,
@@ -1108,7 +1123,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
                                                          int ntiles, int mode, int want_grad, float wsoft, float inv_bv,
                                                          double* __restrict__ partial, float* __restrict__ dz_colsum,
                                                          float thresh, unsigned char* __restrict__ species,
-                                                         unsigned char* __restrict__ mask) {
+                                                         unsigned char* __restrict__ mask, const float* __restrict__ cw) {
   constexpr int NC = 95, NZ = 96, CH = 128;
   const bool bce_z = (want_grad & 2) != 0;                 // binary_crossentropy in the logits form (see head_kernel)
   want_grad &= 1;
@@ -1116,7 +1131,9 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
   __shared__ __attribute__((aligned(16))) float biasp[NZ];
   __shared__ float shc[4][NZ];
   __shared__ double shd[4][6];
+  __shared__ float cwt[CW ? 128 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (CW && tid < 128) cwt[tid] = tid < NC ? cw[tid] : 0.f;
   for (int i = tid; i < NZ * CH; i += 256) {
     const int cls = i >> 7, ch = i & 127;
     const float w = cls < NC ? wsoft_k[ch * NC + cls] : wsig_k[ch];
@@ -1199,7 +1216,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
       for (int r = 0; r < 4; ++r) { p[t][r] = p[t][r] * rsum; psl += p[t][r]; }
     const float ps = 1.f / (1.f + expf(-zsig));
     float* zr = z + row * NZ + 4 * g;
-    if (mode == 2) {
+    if (!CW && mode == 2) {
       // generate.py:221-225 without the probabilities ever leaving the registers: np.argmax over the 95 class
       // probabilities (first maximum = lowest class among equals) and sig >= thresh, one byte each per voxel.
       // The same p values mode 0 stores, so the labels equal argmax / threshold of a mode-0 output bit for bit.
@@ -1224,7 +1241,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
       }
       continue;
     }
-    if (mode == 0) {
+    if (!CW && mode == 0) {
 #pragma unroll
       for (int t = 0; t < 6; ++t) {
         hv4 o = {p[t][0], p[t][1], p[t][2], p[t][3]};
@@ -1234,6 +1251,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
       continue;
     }
     const int lab = labels[row];
+    const float wv = CW ? cwt[lab & 127] : wsoft;
     const float psum = xsum(psl);
     float mine = 0.f, cnt = 0.f;
 #pragma unroll
@@ -1253,7 +1271,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
     const bool inside_s = ps >= kKEps && ps <= 1.f - kKEps;
     const float pc = fminf(fmaxf(ps, kKEps), 1.f - kKEps);
     if (g == 0) {
-      a_ls += (double)(-wsoft * logf(qc));
+      a_ls += (double)(-wv * logf(qc));
       a_lg += bce_z ? (double)(fmaxf(zsig, 0.f) - zsig * tsig + log1pf(expf(-fabsf(zsig))))
                     : (double)(-(tsig * logf(pc) + (1.f - tsig) * logf(1.f - pc)));
       const bool hit = pt_raw > 0.5f;
@@ -1262,7 +1280,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
       if (lab != 0) { a_posw += 1.0; a_tpw += hit ? 1.0 : 0.0; }
     }
     if (want_grad) {
-      const float gs = inside ? wsoft * inv_bv : 0.f;
+      const float gs = inside ? wv * inv_bv : 0.f;
       const float dzs = (inside_s || bce_z) ? (ps - tsig) * inv_bv : 0.f;
 #pragma unroll
       for (int t = 0; t < 6; ++t) {
@@ -1279,7 +1297,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
       }
     }
   }
-  if (mode == 0 || mode == 2) return;
+  if (!CW && (mode == 0 || mode == 2)) return;
   if (want_grad && dz_colsum != nullptr) {
     // per-block column sums of dz (soft | sig bias gradients): 16 voxel lanes, then the 4 waves, fixed order
 #pragma unroll
@@ -1311,15 +1329,21 @@ int launch_head_fused(hipStream_t st, const float* x, int ldx, const float* scal
                       const float* wsig_k, const float* bsoft, const float* bsig, float* z, const unsigned char* labels,
                       size_t M, int mode, int want_grad, float wsoft, double* partial, int partial_blocks, float* metrics,
                       int* nblk_out, float* dz_colsum, double* keep, float thresh, unsigned char* species,
-                      unsigned char* mask) {
+                      unsigned char* mask, const float* cw) {
   ICS_CHECK(mode != 2 || (species != nullptr && mask != nullptr), "fused head, label mode: null output");
+  ICS_CHECK(cw == nullptr || mode == 1, "fused head: class weights belong to the loss mode only");
   ICS_CHECK(M % 16 == 0 && ldx % 4 == 0, "fused head: rows must come in sixteens, float4-aligned");
   const int ntiles = (int)(M / 16);
   int nblk = (ntiles + 3) / 4;
   const int cap = partial_blocks < 512 ? partial_blocks : 512;   // 2 workgroups per CU, whole rounds of tiles at B = 32
   if (nblk > cap) nblk = cap;
-  ICS_LAUNCH(head_fused_kernel, dim3(nblk), dim3(256), 0, st, x, ldx, scale, shift, wsoft_k, wsig_k, bsoft, bsig, z,
-                     labels, ntiles, mode, want_grad, wsoft, (float)(1.0 / (double)M), partial, dz_colsum, thresh, species, mask);
+  const float inv_bv = (float)(1.0 / (double)M);
+  if (cw)
+    ICS_LAUNCH(head_fused_kernel<true>, dim3(nblk), dim3(256), 0, st, x, ldx, scale, shift, wsoft_k, wsig_k, bsoft, bsig, z,
+                       labels, ntiles, mode, want_grad, wsoft, inv_bv, partial, dz_colsum, thresh, species, mask, cw);
+  else
+    ICS_LAUNCH(head_fused_kernel<false>, dim3(nblk), dim3(256), 0, st, x, ldx, scale, shift, wsoft_k, wsig_k, bsoft, bsig, z,
+                       labels, ntiles, mode, want_grad, wsoft, inv_bv, partial, dz_colsum, thresh, species, mask, cw);
   ICS_HIP(hipGetLastError());
   if (nblk_out) *nblk_out = nblk;
   if (mode == 1 && metrics != nullptr) ICS_TRY(launch_head_metrics(st, partial, nblk, (double)M, metrics, nullptr, 0, keep));
@@ -1910,13 +1934,19 @@ int launch_head_metrics(hipStream_t st, const double* partial, int nblk, double 
 
 int launch_head(hipStream_t st, float* z, int ldz, int ncls, const unsigned char* labels, size_t M,
                 int mode, int want_grad, float wsoft, double* partial, int partial_blocks,
-                float* metrics, int* nblk_out, float* dz_colsum, double* keep) {
+                float* metrics, int* nblk_out, float* dz_colsum, double* keep, const float* cw) {
   ICS_CHECK(ncls <= 128, "head kernel supports at most 128 classes");
+  ICS_CHECK(cw == nullptr || mode != 0, "head kernel: class weights belong to the loss mode only");
   int rpb = (int)((M + partial_blocks - 1) / partial_blocks);
   rpb = (rpb + 15) / 16 * 16;
   const int nblk = (int)((M + rpb - 1) / rpb);
-  ICS_LAUNCH(head_kernel, dim3(nblk), dim3(256), 0, st, z, ldz, ncls, labels, M, rpb, mode,
-                     want_grad, wsoft, (float)(1.0 / (double)M), partial, dz_colsum);
+  const float inv_bv = (float)(1.0 / (double)M);
+  if (cw)
+    ICS_LAUNCH(head_kernel<true>, dim3(nblk), dim3(256), 0, st, z, ldz, ncls, labels, M, rpb, mode, want_grad, wsoft, inv_bv,
+                       partial, dz_colsum, cw);
+  else
+    ICS_LAUNCH(head_kernel<false>, dim3(nblk), dim3(256), 0, st, z, ldz, ncls, labels, M, rpb, mode, want_grad, wsoft, inv_bv,
+                       partial, dz_colsum, cw);
   ICS_HIP(hipGetLastError());
   if (nblk_out) *nblk_out = nblk;
   if (mode != 0 && metrics != nullptr) ICS_TRY(launch_head_metrics(st, partial, nblk, (double)M, metrics, nullptr, 0, keep));

@@ -279,6 +279,13 @@ struct Net {
   // U-Net specifics
   int ncls = 95;
   float loss_weight = 95.f;
+  // per-class loss weights (ics_unet_set_class_weights): [kCwFloats] device floats, allocated by the
+  // first set; [0..ncls-1] the table, [kCwFlag] 1 while the table is active -- the flag sits next to the table so that one
+  // broadcast carries both (ics_net_comm_broadcast_state).  Loss steps then launch the head kernels' CW instantiation.
+  static constexpr int kCwFlag = 128, kCwFloats = 132;
+  float* cw_tab = nullptr;
+  bool cw_on = false;
+  const float* cw(int mode) const { return cw_on && mode == 1 ? cw_tab : nullptr; }
   float* x_in = nullptr;              // [maxB][d^3][C]
   unsigned char* labels = nullptr;    // [maxB][d^3]
   ConvLayer* head = nullptr;
@@ -1468,6 +1475,12 @@ static int unet_head_forward(Net& n, int B) {
   return conv_forward(n, H, B, false, false, n.tp(H.t_b));
 }
 
+// the class-weight table's device memory, from the engine's allocator (guard bytes under ICSG3D_DEBUG_CANARY) on first use
+static int cw_table(Net& n) {
+  if (n.cw_tab == nullptr) ICS_TRY(n.alloc(&n.cw_tab, (size_t)Net::kCwFloats));
+  return 0;
+}
+
 // mode 1 metrics: single GPU -> finalized on the spot.  With a communicator the six sums and the voxel
 // count are all-reduced first (numerators / denominators, not ratios: SURVEY 8(e)); that costs a small
 // collective on st, so it only happens when the caller reads the metrics (want_metrics) -- every rank
@@ -1476,7 +1489,8 @@ static int unet_loss(Net& n, int B, int mode, int want_grad, bool want_metrics =
   const size_t M = n.rows(*n.head, B);
   n.prof.begin(n.st, "head_softmax_loss", 0, 4.0 * M * (n.ncls + 1) * 2);
   ICS_TRY(launch_head(n.st, n.head->s, n.ncls + 1, n.ncls, n.labels, M, mode, want_grad | (n.bce_from_logits << 1), n.loss_weight,
-                      n.ws_dbl, 2048, n.comm ? nullptr : n.d_metrics, &n.head_nblk, want_grad ? n.ws_bwd : nullptr, n.d_red + 8));
+                      n.ws_dbl, 2048, n.comm ? nullptr : n.d_metrics, &n.head_nblk, want_grad ? n.ws_bwd : nullptr, n.d_red + 8,
+                      n.cw(mode)));
   n.prof.end(n.st);
   if (mode != 0 && n.comm && want_metrics) {
     ICS_TRY(launch_head_metrics(n.st, n.ws_dbl, n.head_nblk, (double)M, n.d_metrics, n.d_red, 1));
@@ -1503,7 +1517,8 @@ static int unet_head_loss(Net& n, int B, int mode, int want_grad, bool want_metr
   n.prof.begin(n.st, "head_fused", 2.0 * M * 128 * (n.ncls + 1), 4.0 * M * (128 + (mode == 1 && !want_grad ? 0 : n.ncls + 1)));
   ICS_TRY(launch_head_fused(n.st, s0.p, s0.C, s0.scale, s0.shift, n.tp(H.t_w), n.tp(H.t_gamma), n.tp(H.t_b),
                             n.tp(H.t_b) + n.ncls, H.s, n.labels, M, mode, want_grad | (n.bce_from_logits << 1), n.loss_weight, n.ws_dbl, 2048,
-                            n.comm ? nullptr : n.d_metrics, &n.head_nblk, want_grad ? n.ws_bwd : nullptr, n.d_red + 8));
+                            n.comm ? nullptr : n.d_metrics, &n.head_nblk, want_grad ? n.ws_bwd : nullptr, n.d_red + 8,
+                            0.f, nullptr, nullptr, n.cw(mode)));
   n.prof.end(n.st);
   if (mode != 0 && n.comm && want_metrics) {
     ICS_TRY(launch_head_metrics(n.st, n.ws_dbl, n.head_nblk, (double)M, n.d_metrics, n.d_red, 1));
@@ -2644,6 +2659,45 @@ int ics_unet_test_step(ics_net* net, const float* x, const uint8_t* labels, int 
   return 0;
 }
 
+int ics_unet_set_class_weights(ics_net* net, const float* w, int count) {
+  ICS_CHECK(net && net->n.kind == 0, "ics_unet_set_class_weights: a U-Net engine is required");
+  Net& n = net->n;
+  ICS_HIP(hipSetDevice(n.device));
+  if (w == nullptr) {                       // back to the scalar loss_weight
+    if (n.cw_tab) {
+      ICS_HIP(hipMemsetAsync(n.cw_tab + Net::kCwFlag, 0, sizeof(float), n.st));
+      ICS_HIP(hipStreamSynchronize(n.st));
+    }
+    n.cw_on = false;
+    return 0;
+  }
+  ICS_CHECK(count == n.ncls, "ics_unet_set_class_weights: count must equal num_classes");
+  for (int c = 0; c < count; ++c)
+    ICS_CHECK(std::isfinite(w[c]) && w[c] >= 0.f, "ics_unet_set_class_weights: every weight must be finite and >= 0 (class " + std::to_string(c) + ")");
+  ICS_TRY(cw_table(n));
+  float host[Net::kCwFloats] = {};
+  std::memcpy(host, w, sizeof(float) * (size_t)count);
+  host[Net::kCwFlag] = 1.f;
+  ICS_HIP(hipMemcpyAsync(n.cw_tab, host, sizeof(host), hipMemcpyHostToDevice, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));      // `host` is a stack temporary
+  n.cw_on = true;
+  return 0;
+}
+int ics_unet_get_class_weights(ics_net* net, float* w, int count, int* active) {
+  ICS_CHECK(net && net->n.kind == 0, "ics_unet_get_class_weights: a U-Net engine is required");
+  Net& n = net->n;
+  ICS_CHECK(w == nullptr || count == n.ncls, "ics_unet_get_class_weights: count must equal num_classes");
+  if (active) *active = n.cw_on ? 1 : 0;
+  if (w == nullptr) return 0;
+  if (!n.cw_on) {                           // the scalar path: what every class weighs
+    for (int c = 0; c < count; ++c) w[c] = n.loss_weight;
+    return 0;
+  }
+  ICS_HIP(hipSetDevice(n.device));
+  ICS_HIP(hipMemcpyAsync(w, n.cw_tab, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  return 0;
+}
 int ics_unet_metric_sums(ics_net* net, double sums[7]) {
   ICS_TRY(require_kind(net, 0));
   ICS_CHECK(sums, "null argument");
@@ -3235,8 +3289,18 @@ int ics_net_comm_broadcast_state(ics_net* net, int root) {
   ncclResult_t r = ncclBroadcast(n.d_red, n.d_red, 1, ncclDouble, root, n.comm, n.st);
   ICS_CHECK(r == ncclSuccess, std::string("ncclBroadcast(t): ") + ncclGetErrorString(r));
   ICS_HIP(hipMemcpyAsync(&t, n.d_red, sizeof(double), hipMemcpyDeviceToHost, n.st));
+  float cw_flag = 0.f;
+  if (n.kind == 0) {
+    // the class-weight table and its flag: every rank takes part (a rank that never set a table allocates a zeroed,
+    // inactive one), so the replicas cannot train with different losses
+    ICS_TRY(cw_table(n));
+    r = ncclBroadcast(n.cw_tab, n.cw_tab, Net::kCwFloats, ncclFloat, root, n.comm, n.st);
+    ICS_CHECK(r == ncclSuccess, std::string("ncclBroadcast(class weights): ") + ncclGetErrorString(r));
+    ICS_HIP(hipMemcpyAsync(&cw_flag, n.cw_tab + Net::kCwFlag, sizeof(float), hipMemcpyDeviceToHost, n.st));
+  }
   ICS_HIP(hipStreamSynchronize(n.st));
   n.adam_t = (int)t;
+  n.cw_on = cw_flag != 0.f;
   n.packed_valid = false;
   return 0;
 }
@@ -3722,10 +3786,21 @@ int ics_op_conv_link(ics_conv_link* a) {
 int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
                      const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
                      float metrics[5], double sums[7]) {
+  return ics_op_unet_head_weighted(x, wsoft, bsoft, wsig, bsig, labels, M, ncls, loss_weight, mode, fused, out, metrics, sums,
+                                   nullptr);
+}
+// The same with a per-class weight table in place of the scalar (NULL: the scalar): the kernels' CW instantiation.
+int ics_op_unet_head_weighted(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
+                              const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
+                              float metrics[5], double sums[7], const float* class_weights) {
   const int bce = ((mode >> 2) & 1) << 1;
   mode &= 3;
   ICS_CHECK(x && wsoft && bsoft && wsig && bsig && labels && M >= 1 && mode >= 0 && mode <= 2, "bad head arguments");
   ICS_CHECK(ncls >= 2 && ncls <= 127, "bad head arguments: ncls must be in [2, 127] (ics_unet_config.num_classes)");
+  ICS_CHECK(class_weights == nullptr || mode != 0, "bad head arguments: class weights belong to the loss modes (1, 2)");
+  if (class_weights)
+    for (int c = 0; c < ncls; ++c)
+      ICS_CHECK(std::isfinite(class_weights[c]) && class_weights[c] >= 0.f, "bad head arguments: every class weight must be finite and >= 0");
   Net n;
   ICS_TRY(op_prepare(n));
   const int nz = ncls + 1, Kpad = 128, Npad = round_up(nz, 32);
@@ -3742,12 +3817,17 @@ int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, con
   ICS_HIP(hipMemcpyAsync(db, bsoft, (size_t)ncls * 4, hipMemcpyHostToDevice, n.st));
   ICS_HIP(hipMemcpyAsync(db + ncls, bsig, 4, hipMemcpyHostToDevice, n.st));
   ICS_HIP(hipMemcpyAsync(dlab, labels, M, hipMemcpyHostToDevice, n.st));
+  float* dcw = nullptr;
+  if (class_weights) {
+    ICS_TRY(n.alloc(&dcw, (size_t)128));
+    ICS_HIP(hipMemcpyAsync(dcw, class_weights, (size_t)ncls * 4, hipMemcpyHostToDevice, n.st));
+  }
   const float lw = loss_weight > 0.f ? loss_weight : (float)ncls;       // unet/unet.py:253: the integer 95
   const int hmode = mode == 0 ? 0 : 1, want_grad = mode == 2;
   if (fused) {
     ICS_CHECK(head_fused_ok(ncls, 128, M, ACT_NONE, 0), "this shape has no fused head kernel");
     ICS_TRY(launch_head_fused(n.st, dx, 128, nullptr, nullptr, dws, dwg, db, db + ncls, dz, dlab, M, hmode, want_grad | bce, lw,
-                              dpart, 2048, dmet, nullptr, want_grad ? dcol : nullptr, dsum));
+                              dpart, 2048, dmet, nullptr, want_grad ? dcol : nullptr, dsum, 0.f, nullptr, nullptr, dcw));
   } else {
     ICS_TRY(launch_pack_fwd(n.st, dws, 128, ncls, dwp, Kpad, Npad, 0, 0, 1));
     ICS_TRY(launch_pack_fwd(n.st, dwg, 128, 1, dwp, Kpad, Npad, 0, ncls, 0));
@@ -3756,7 +3836,7 @@ int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, con
     ConvSrc s = src_plain(dx, 128);
     ICS_TRY(launch_conv_fwd(n.st, g, &s, 1, dwp, db, dz, nz, ACT_NONE, nullptr, nullptr));
     ICS_TRY(launch_head(n.st, dz, nz, ncls, dlab, M, hmode, want_grad | bce, lw, dpart, 2048, dmet, nullptr,
-                        want_grad ? dcol : nullptr, dsum));
+                        want_grad ? dcol : nullptr, dsum, dcw));
   }
   if (out) ICS_HIP(hipMemcpyAsync(out, dz, M * nz * 4, hipMemcpyDeviceToHost, n.st));
   if (hmode && metrics) ICS_HIP(hipMemcpyAsync(metrics, dmet, 5 * 4, hipMemcpyDeviceToHost, n.st));

@@ -167,6 +167,84 @@ int launch_feed_pack(hipStream_t st, const FeedPack& p) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------ class counts of labels
+// Exact counts per class id over n labels (the inverse-frequency class weights of train_unet.py: DESIGN.md section 25).
+// The labels are what the pack kernel converts -- uint8, float32 or float64 ids -- but nothing is converted blindly here:
+// a value outside 0..ncls-1 or a non-integral one (compared in its own type) goes to bin kCountOor and indexes nothing.
+//   * one lane = 16 bytes per pass (16 / 4 / 2 labels), grid-stride; the n % (labels per 16 bytes) last labels are
+//     taken one per lane by block 0;
+//   * every wave owns a row of LDS bins.  About 98 % of the voxels are background, so 64 atomics of a wave would queue
+//     on one address: the lanes that agree with the wave's first active lane are counted by ONE add of their number
+//     (a ballot), the others add their own 1;
+//   * the four rows merge once per block, then one 64-bit atomic add per non-empty bin and block.  Integer sums: the
+//     order does not matter.  A block sees at most 2^31 labels (launch_label_counts), so the 32-bit bins cannot wrap.
+constexpr int kCountThreads = 256, kCountMaxBlocks = 2048;
+typedef unsigned cv4 __attribute__((ext_vector_type(4)));
+constexpr int kCountOor = 128, kCountBins = kCountOor + 1;     // ncls <= 127
+
+__device__ __forceinline__ int count_bin(unsigned char v, int ncls) { return (int)v < ncls ? (int)v : kCountOor; }
+__device__ __forceinline__ int count_bin(float v, int ncls) {
+  return (v >= 0.f && v < (float)ncls && v == truncf(v)) ? (int)v : kCountOor;       // a NaN fails the first comparison
+}
+__device__ __forceinline__ int count_bin(double v, int ncls) {
+  return (v >= 0.0 && v < (double)ncls && v == trunc(v)) ? (int)v : kCountOor;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kCountThreads) void label_counts_kernel(const T* __restrict__ lab, size_t n, int ncls,
+                                                                     unsigned long long* __restrict__ counts) {
+  constexpr int V = 16 / (int)sizeof(T);
+  __shared__ unsigned bins[kCountThreads / 64][kCountBins];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < (kCountThreads / 64) * kCountBins; i += kCountThreads) (&bins[0][0])[i] = 0u;
+  __syncthreads();
+  unsigned* mine = bins[wave];
+  auto add = [&](int bin) {                                    // called by any subset of a wave's lanes
+    const unsigned long long active = __ballot(1);
+    const int first = __builtin_amdgcn_readfirstlane(bin);    // the first active lane's bin
+    const unsigned long long same = __ballot(bin == first);
+    if (lane == __ffsll((long long)active) - 1) atomicAdd(&mine[first], (unsigned)__popcll(same));
+    else if (bin != first) atomicAdd(&mine[bin], 1u);
+  };
+  const size_t nvec = n / V;
+  for (size_t q = (size_t)blockIdx.x * kCountThreads + tid; q < nvec; q += (size_t)gridDim.x * kCountThreads) {
+    union { cv4 u; T v[V]; } w;
+    w.u = reinterpret_cast<const cv4*>(lab)[q];                // one 16-byte load
+#pragma unroll
+    for (int k = 0; k < V; ++k) add(count_bin(w.v[k], ncls));
+  }
+  if (blockIdx.x == 0 && (size_t)tid < n - nvec * V) add(count_bin(lab[nvec * V + tid], ncls));
+  __syncthreads();
+  if (tid < kCountBins) {
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kCountThreads / 64; ++w) s += bins[w][tid];
+    if (s) atomicAdd(&counts[tid], s);
+  }
+}
+
+// counts: [kCountBins] device, zeroed here; [0..ncls-1] the classes, [kCountOor] everything that is no class id
+static int launch_label_counts(hipStream_t st, const void* lab, int label_kind, size_t n, int ncls, unsigned long long* counts) {
+  ICS_CHECK(ncls >= 2 && ncls <= 127, "label counts: num_classes must be in [2, 127]");
+  ICS_CHECK(n <= ((size_t)1 << 40), "label counts: at most 2^40 labels per call");
+  ICS_CHECK((reinterpret_cast<uintptr_t>(lab) & 15) == 0, "label counts: the labels must be 16-byte aligned");
+  ICS_HIP(hipMemsetAsync(counts, 0, kCountBins * sizeof(unsigned long long), st));
+  if (n == 0) return 0;
+  const size_t per = label_kind == FEED_LABELS_U8 ? 16 : (label_kind == FEED_LABELS_F32 ? 4 : 2);
+  const size_t nvec = n / per;
+  size_t nblk = (nvec + kCountThreads - 1) / kCountThreads;
+  nblk = nblk < 1 ? 1 : (nblk > (size_t)kCountMaxBlocks ? (size_t)kCountMaxBlocks : nblk);      // 2^40 / 2048 = 2^29 labels a block
+  const dim3 grid((unsigned)nblk), block(kCountThreads);
+  if (label_kind == FEED_LABELS_U8)
+    ICS_LAUNCH(label_counts_kernel<unsigned char>, grid, block, 0, st, static_cast<const unsigned char*>(lab), n, ncls, counts);
+  else if (label_kind == FEED_LABELS_F32)
+    ICS_LAUNCH(label_counts_kernel<float>, grid, block, 0, st, static_cast<const float*>(lab), n, ncls, counts);
+  else
+    ICS_LAUNCH(label_counts_kernel<double>, grid, block, 0, st, static_cast<const double*>(lab), n, ncls, counts);
+  ICS_HIP(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ the feed of an engine
 struct FeedSlot {
   unsigned char* host = nullptr;   // pinned
@@ -417,6 +495,30 @@ int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1,
   ICS_TRY(L.download(x, s_out, s_out.count, st));
   ICS_TRY(L.download(out_labels, s_lout, s_lout.count, st));
   ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int ics_op_label_counts(const void* labels, int label_kind, size_t n, int ncls, int64_t* counts, int64_t* out_of_range) {
+  ICS_CHECK(label_kind != FEED_LABELS_ONEHOT, "ics_op_label_counts: one-hot labels are not class ids: count their argmax instead");
+  ICS_CHECK(label_kind == FEED_LABELS_U8 || label_kind == FEED_LABELS_F64 || label_kind == FEED_LABELS_F32,
+            "ics_op_label_counts: label_kind must be 1 (uint8), 2 (float64) or 3 (float32)");
+  ICS_CHECK(ncls >= 2 && ncls <= 127, "ics_op_label_counts: num_classes must be in [2, 127]");
+  ICS_CHECK(counts && out_of_range && (labels || n == 0), "ics_op_label_counts: null argument");
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_lab = L.add<unsigned char>(n * feed_label_bytes(label_kind, ncls));
+  const auto s_cnt = L.add<unsigned long long>(kCountBins);
+  unsigned char* d_lab;
+  unsigned long long* d_cnt;
+  ICS_TRY(L.reserve(s_lab, &d_lab, s_cnt, &d_cnt));
+  ICS_TRY(L.upload(s_lab, labels, s_lab.count, st));
+  ICS_TRY(launch_label_counts(st, d_lab, label_kind, n, ncls, d_cnt));
+  unsigned long long host[kCountBins];
+  ICS_TRY(L.download(host, s_cnt, s_cnt.count, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  for (int c = 0; c < ncls; ++c) counts[c] = (int64_t)host[c];
+  *out_of_range = (int64_t)host[kCountOor];
   return 0;
 }
 

@@ -871,6 +871,80 @@ static int interp_walk(ics_net* unet, ics_net* vae, const ics_unet_config* uc, c
   return 0;
 }
 
+/* Per-class loss weights: set / get / unset around every kind of step, the refusals, and the table through a state
+ * broadcast; the label histogram on buffers of the exact size (every id kind, lengths that are no multiple of a
+ * 16-byte load, the empty array) and its refusals. */
+static int class_weight_walk(ics_net* unet, ics_net* vae, int ncls, const float* x, const uint8_t* lab, int B, int with_comm) {
+  float* w = (float*)malloc((size_t)ncls * sizeof(float));
+  float* back = (float*)malloc((size_t)ncls * sizeof(float));
+  float mm[5];
+  int active = -1, bad = 0;
+  for (int c = 0; c < ncls; ++c) w[c] = c == 0 ? 0.f : 0.25f + (float)(c % 7);
+  OK(ics_unet_get_class_weights(unet, back, ncls, &active));
+  if (active != 0) { fprintf(stderr, "class weights: active before any set\n"); return 1; }
+  OK(ics_unet_set_class_weights(unet, w, ncls));
+  OK(ics_unet_get_class_weights(unet, back, ncls, &active));
+  OK(ics_unet_get_class_weights(unet, NULL, 0, NULL));
+  if (active != 1 || memcmp(w, back, (size_t)ncls * sizeof(float)) != 0) { fprintf(stderr, "class weights: table not returned\n"); return 1; }
+  OK(ics_unet_train_step(unet, x, lab, B, mm));
+  OK(ics_unet_test_step(unet, x, lab, B, mm));
+  OK(ics_unet_upload_batch(unet, x, lab, B));
+  OK(ics_unet_train_step_resident(unet, mm));
+  if (with_comm) {
+    OK(ics_net_comm_broadcast_state(unet, 0));
+    OK(ics_unet_get_class_weights(unet, back, ncls, &active));
+    if (active != 1 || memcmp(w, back, (size_t)ncls * sizeof(float)) != 0) { fprintf(stderr, "class weights: lost in the broadcast\n"); return 1; }
+  }
+  bad += ics_unet_set_class_weights(NULL, w, ncls) == 0;
+  bad += ics_unet_set_class_weights(vae, w, ncls) == 0;
+  bad += ics_unet_set_class_weights(unet, w, ncls - 1) == 0;
+  bad += ics_unet_set_class_weights(unet, w, ncls + 1) == 0;
+  w[1] = -1.f; bad += ics_unet_set_class_weights(unet, w, ncls) == 0;
+  w[1] = NAN; bad += ics_unet_set_class_weights(unet, w, ncls) == 0;
+  w[1] = INFINITY; bad += ics_unet_set_class_weights(unet, w, ncls) == 0;
+  w[1] = 1.f;
+  bad += ics_unet_get_class_weights(NULL, back, ncls, &active) == 0;
+  bad += ics_unet_get_class_weights(vae, back, ncls, &active) == 0;
+  bad += ics_unet_get_class_weights(unet, back, ncls - 1, &active) == 0;
+  if (bad) { fprintf(stderr, "class weights: %d invalid argument sets accepted\n", bad); return 1; }
+  OK(ics_unet_get_class_weights(unet, back, ncls, &active));      /* a refused set leaves the table in force */
+  if (active != 1) { fprintf(stderr, "class weights: a refused set cleared the table\n"); return 1; }
+  OK(ics_unet_set_class_weights(unet, NULL, 0));
+  OK(ics_unet_get_class_weights(unet, back, ncls, &active));
+  if (active != 0) { fprintf(stderr, "class weights: still active after NULL\n"); return 1; }
+  OK(ics_unet_train_step(unet, x, lab, B, mm));
+  free(w); free(back);
+  return 0;
+}
+static int label_counts_walk(void) {
+  const size_t ns[6] = {0, 1, 15, 16, 1037, 4099};
+  const int cols[3] = {2, 95, 127};
+  int bad = 0;
+  for (int kind = 1; kind <= 3; ++kind)
+    for (int i = 0; i < 6; ++i) {
+      const size_t n = ns[i], lb = kind == 1 ? 1 : kind == 2 ? 8 : 4;
+      const int ncls = cols[(kind + i) % 3];
+      void* lab = n ? calloc(n, lb) : NULL;
+      int64_t* counts = (int64_t*)malloc((size_t)ncls * sizeof(int64_t));
+      int64_t oor = -1;
+      OK(ics_op_label_counts(lab, kind, n, ncls, counts, &oor));
+      free(lab); free(counts);
+    }
+  float lab[16] = {0};
+  int64_t counts[127], oor;
+  bad += ics_op_label_counts(lab, 4, 16, 95, counts, &oor) == 0;      /* one-hot: no class ids */
+  bad += ics_op_label_counts(lab, 0, 16, 95, counts, &oor) == 0;
+  bad += ics_op_label_counts(lab, 5, 16, 95, counts, &oor) == 0;
+  bad += ics_op_label_counts(NULL, 3, 16, 95, counts, &oor) == 0;
+  bad += ics_op_label_counts(lab, 3, 16, 95, NULL, &oor) == 0;
+  bad += ics_op_label_counts(lab, 3, 16, 95, counts, NULL) == 0;
+  bad += ics_op_label_counts(lab, 3, 16, 1, counts, &oor) == 0;
+  bad += ics_op_label_counts(lab, 3, 16, 128, counts, &oor) == 0;
+  if (bad) { fprintf(stderr, "label counts: %d invalid argument sets accepted\n", bad); return 1; }
+  OK(ics_op_label_counts(lab, 3, 16, 95, counts, &oor));
+  return 0;
+}
+
 /* Fed steps: the pack op alone on buffers of the exact size (every dtype mix, every label kind, odd column counts), then the
  * whole feed on both engines -- open, slot, submit, fed train / test step, metrics (late and twice), close, re-open with
  * another layout -- and every refusal, after which the feed and the engine still work. */
@@ -1075,6 +1149,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_unet_train_step_resident(unet, NULL));
   OK(ics_vae_upload_batch(vae, x, cond, eps, B));
   OK(ics_vae_train_step_resident(vae, mv));
+  if (class_weight_walk(unet, vae, uc.num_classes, x, lab, B, with_comm)) return 1;
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
   if (feed_walk(unet, vae, d, C, B, vc.cond_shape, vc.latent_dim)) return 1;
@@ -1415,6 +1490,18 @@ int main(void) {
     uint8_t* lab = calloc(M, 1);
     for (int f = 0; f < 2; ++f)
       for (int mode = 0; mode < 3; ++mode) OK(ics_op_unet_head(x, ws, bs, wg, bg, lab, M, 95, 0.f, mode, f, out, met, sums));
+    {   /* the same with a class-weight table: the loss modes, a NULL table, and the refusals */
+      float cw[95];
+      for (int c = 0; c < 95; ++c) cw[c] = c ? 0.5f + (float)(c % 5) : 0.f;
+      for (int f = 0; f < 2; ++f)
+        for (int mode = 1; mode < 3; ++mode) OK(ics_op_unet_head_weighted(x, ws, bs, wg, bg, lab, M, 95, 0.f, mode, f, out, met, sums, cw));
+      OK(ics_op_unet_head_weighted(x, ws, bs, wg, bg, lab, M, 95, 0.f, 0, 1, out, met, sums, NULL));
+      int badw = ics_op_unet_head_weighted(x, ws, bs, wg, bg, lab, M, 95, 0.f, 0, 1, out, met, sums, cw) == 0;
+      cw[3] = -2.f; badw += ics_op_unet_head_weighted(x, ws, bs, wg, bg, lab, M, 95, 0.f, 1, 1, out, met, sums, cw) == 0;
+      cw[3] = NAN; badw += ics_op_unet_head_weighted(x, ws, bs, wg, bg, lab, M, 95, 0.f, 1, 0, out, met, sums, cw) == 0;
+      if (badw) { fprintf(stderr, "weighted head: %d invalid argument sets accepted\n", badw); return 1; }
+    }
+    if (label_counts_walk()) return 1;
     free(x); free(ws); free(bs); free(wg); free(out); free(lab);
     /* ... and the finalisation from (all-reduced) sums */
     sums[6] = 64.0;

@@ -287,6 +287,31 @@ def feed_pack(x_parts, labels=None, label_kind="none", num_classes=0):
     return x, out
 
 
+def label_counts(labels, num_classes, label_kind=None):
+    """Single-op entry (ics_op_label_counts): exact counts per class id of a uint8 / float32 / float64 label array of any
+    shape, computed on the device.  Returns (counts int64 (num_classes,), out_of_range int): values that are no class id
+    (below 0, >= num_classes, non-integral, NaN) are counted in out_of_range and in no bin.  label_kind "onehot" is
+    refused by the library (class ids only); by default the kind follows the array's dtype."""
+    lib = L.load()
+    lab = np.asarray(labels)
+    if label_kind is None:
+        kinds = {np.dtype(np.uint8): "u8", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+        if lab.dtype not in kinds:
+            raise ValueError("labels must be uint8, float32 or float64 class ids, not %s" % lab.dtype)
+        label_kind = kinds[lab.dtype]
+    if label_kind not in FEED_LABELS or label_kind == "none":
+        raise ValueError("label_kind must be one of u8, f32, f64")
+    if label_kind != "onehot":
+        lab = np.ascontiguousarray(lab, FEED_LABELS[label_kind][1]).reshape(-1)
+    else:
+        lab = np.ascontiguousarray(lab, np.float32).reshape(-1)
+    counts = np.zeros(int(num_classes), np.int64)
+    oor = np.zeros(1, np.int64)
+    L.check(lib.ics_op_label_counts(lab.ctypes.data_as(C.c_void_p), FEED_LABELS[label_kind][0], lab.size, int(num_classes),
+                                    L.i64ptr(counts), L.i64ptr(oor)))
+    return counts, int(oor[0])
+
+
 def comm_unique_id():
     buf = C.create_string_buffer(128)
     L.check(L.load().ics_comm_unique_id(buf))
@@ -352,6 +377,22 @@ class UnetEngine(_Net, _FeedMixin):
         m = np.zeros(5, np.float32)
         L.check(self._lib.ics_unet_test_step(self._h, L.fptr(x), L.u8ptr(lab), x.shape[0], L.fptr(m)))
         return m
+
+    def set_class_weights(self, w):
+        """Per-class loss weights (num_classes,) for every later train / test step (ics_unet_set_class_weights); None
+        switches back to the scalar loss_weight."""
+        if w is None:
+            L.check(self._lib.ics_unet_set_class_weights(self._h, None, 0))
+            return
+        w = np.ascontiguousarray(w, np.float32).reshape(-1)
+        L.check(self._lib.ics_unet_set_class_weights(self._h, L.fptr(w), int(w.size)))
+
+    def get_class_weights(self):
+        """The active table (num_classes,) float32, or None while the scalar loss_weight is in force."""
+        w = np.zeros(self.num_classes, np.float32)
+        active = C.c_int(0)
+        L.check(self._lib.ics_unet_get_class_weights(self._h, L.fptr(w), self.num_classes, C.byref(active)))
+        return w if active.value else None
 
     def metric_sums(self):
         """The K.sum terms of the last step's metrics (unet/unet.py:159-193): dict(sum_lsoft, sum_lsig, tp, predicted,
@@ -896,8 +937,10 @@ def vae_loss(mulv=None, mse_partial=(), n_elems=1.0, pm_partials=((), (), (), ()
     return np.array(list(s), np.float64) if phase == 1 else m
 
 
-def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False):
+def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False,
+              class_weights=None):
     """Single-op entry (kernel parity tests): the heads + losses + metrics on a given trunk output x (M,128).
+    class_weights (ncls,): a per-class table in place of the scalar loss_weight (ics_op_unet_head_weighted).
     Returns (out (M, ncls+1) | None, metrics (5,), sums dict) -- see ics_op_unet_head."""
     lib = L.load()
     x, wsoft, bsoft, wsig, bsig = _f32(x), _f32(wsoft), _f32(bsoft), _f32(wsig), _f32(bsig)
@@ -906,9 +949,15 @@ def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weig
     out = np.empty((M, ncls + 1), np.float32) if mode != 1 else None
     m = np.zeros(5, np.float32)
     s = (C.c_double * 7)()
-    L.check(lib.ics_op_unet_head(L.fptr(x), L.fptr(wsoft), L.fptr(bsoft), L.fptr(wsig), L.fptr(bsig), L.u8ptr(lab), M, ncls,
-                                 float(loss_weight), int(mode) | (4 if bce_from_logits else 0), 1 if fused else 0, L.fptr(out),
-                                 L.fptr(m), s))
+    args = (L.fptr(x), L.fptr(wsoft), L.fptr(bsoft), L.fptr(wsig), L.fptr(bsig), L.u8ptr(lab), M, ncls, float(loss_weight),
+            int(mode) | (4 if bce_from_logits else 0), 1 if fused else 0, L.fptr(out), L.fptr(m), s)
+    if class_weights is None:
+        L.check(lib.ics_op_unet_head(*args))
+    else:
+        cw = np.ascontiguousarray(class_weights, np.float32).reshape(-1)
+        if cw.size != ncls:
+            raise ValueError("class_weights must have %d entries, got %d" % (ncls, cw.size))
+        L.check(lib.ics_op_unet_head_weighted(*args, L.fptr(cw)))
     return out, m, dict(zip(METRIC_SUM_KEYS, [float(v) for v in s]))
 
 

@@ -246,17 +246,29 @@ class _BestCheckpoint:
 class AtomUnet(DataParallelMixin):
     """U-Net for semantic segmentation of electron-density maps (unet/unet.py:224-391).
 
-    num_classes, class_weights, weights, input_shape, lr: as the reference.  class_weights is
+    num_classes, class_weights, weights, input_shape, lr: as the reference.  By default class_weights is
     stored and, as in the reference, not used by the loss: the compiled loss weight is
-    the scalar float(num_classes).  Extra keyword `pool_ties`: "tf_cpu" (TensorFlow-CPU
+    the scalar float(num_classes).  `weighted_loss=True` is the opt-in SURVEY F11 names: class_weights, a vector of
+    length num_classes (finite, >= 0), becomes the engine's per-class table and every train / test step weighs a
+    voxel's softmax loss by class_weights[label].  Extra keyword `pool_ties`: "tf_cpu" (TensorFlow-CPU
     MaxPool3DGrad tie rule, default) or "first"; `bce_from_logits`: False (default) = "binary_crossentropy" on clipped
     probabilities, True = TF 2.1's short-circuit to sigmoid_cross_entropy_with_logits for a Sigmoid output (SURVEY
     App. B: which of the two Keras 2.3.1 / TF 2.1 takes cannot be checked offline; they differ only at saturation).
     """
 
     def __init__(self, num_classes=95, class_weights=None, weights=None, input_shape=(32, 32, 32, 4),
-                 lr=1e-6, pool_ties="tf_cpu", max_batch=None, bce_from_logits=False):
+                 lr=1e-6, pool_ties="tf_cpu", max_batch=None, bce_from_logits=False, weighted_loss=False):
         self.class_weights = class_weights
+        self.weighted_loss = bool(weighted_loss)
+        self._cw_table = None
+        if self.weighted_loss:
+            cw = None if class_weights is None else np.asarray(class_weights, np.float32)
+            if cw is None or cw.ndim != 1 or cw.size != num_classes:
+                raise ValueError("weighted_loss=True needs class_weights of length num_classes (%d), got %s"
+                                 % (num_classes, "None" if cw is None else "shape %s" % (cw.shape,)))
+            if not np.all(np.isfinite(cw)) or np.any(cw < 0):
+                raise ValueError("weighted_loss=True: every class weight must be finite and >= 0")
+            self._cw_table = cw.copy()
         self.bce_from_logits = bool(bce_from_logits)
         self.input_shape = tuple(input_shape)
         self.lr = lr
@@ -283,22 +295,23 @@ class AtomUnet(DataParallelMixin):
     # never re-creates it (the engine streams larger inputs in chunks of max_batch); a TRAINING batch larger
     # than max_batch does, and then weights, BN moving statistics AND the Adam state (moments, step count)
     # move to the new engine -- keras.optimizers.Adam keeps its state for the life of the model.
+    def _new_engine(self, max_batch, carry):
+        eng = UnetEngine(in_channels=self.input_shape[-1], num_classes=self.num_classes, d=self.input_shape[0],
+                         max_batch=max_batch, lr=self.lr, pool_ties=self.pool_ties, bce_from_logits=self.bce_from_logits)
+        eng.set_weights(carry)
+        if self._cw_table is not None:      # the loss travels with the weights: a re-created engine trains with the same table
+            eng.set_class_weights(self._cw_table)
+        return eng
+
     def _engine(self, batch, grow=False):
         batch = max(int(batch), 1)
         if self._eng is None:
-            carry = dict(self._host_weights)
-            self._eng = UnetEngine(in_channels=self.input_shape[-1], num_classes=self.num_classes,
-                                   d=self.input_shape[0], max_batch=max(batch, self._max_batch or 0), lr=self.lr,
-                                   pool_ties=self.pool_ties, bce_from_logits=self.bce_from_logits)
-            self._eng.set_weights(carry)
+            self._eng = self._new_engine(max(batch, self._max_batch or 0), dict(self._host_weights))
             self._dp_attach(self._eng)
         elif grow and batch > self._eng.max_batch:
             carry, opt = self._eng.get_weights(), self._eng.get_optimizer_state()
             self._eng.close()
-            self._eng = UnetEngine(in_channels=self.input_shape[-1], num_classes=self.num_classes,
-                                   d=self.input_shape[0], max_batch=batch, lr=self.lr, pool_ties=self.pool_ties,
-                                   bce_from_logits=self.bce_from_logits)
-            self._eng.set_weights(carry)
+            self._eng = self._new_engine(batch, carry)
             self._eng.set_optimizer_state(*opt)
             self._dp_attach(self._eng)
         return self._eng

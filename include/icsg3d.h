@@ -82,6 +82,17 @@ int ics_unet_test_step(ics_net* net, const float* x, const uint8_t* labels, int 
  * metrics pointer): a resident step enqueued without metrics skips the reduction over the ranks under data parallelism, and
  * the sums then still hold the last metric-returning step's values. */
 int ics_unet_metric_sums(ics_net* net, double sums[7]);
+/* Per-class loss weights (weighted_categorical_crossentropy's `weights` as the array of shape (C,) its docstring names,
+ * unet/unet.py:196-221): w[count], count == num_classes, every weight finite and >= 0.  From then on every train and test
+ * step -- synchronous, resident, fed -- weighs a voxel's softmax loss and its gradient by w[label] instead of the scalar
+ * ics_unet_config.loss_weight; the mean is still taken over all B V voxels, the sigmoid loss and f1 / wr do not change, and
+ * a voxel of a class with weight 0 contributes exactly 0 to the loss and an exactly zero softmax gradient row.  Predict
+ * paths are unaffected.  w == NULL: back to the scalar.  The table lives in the engine's own device memory; with a
+ * communicator ics_net_comm_broadcast_state sends it, and whether it is active, from the root to every rank. */
+int ics_unet_set_class_weights(ics_net* net, const float* w, int count);
+/* *active = 1 while a table is set (active may be NULL); w (may be NULL, else count == num_classes) receives the table, or
+ * num_classes copies of the scalar loss weight while none is set. */
+int ics_unet_get_class_weights(ics_net* net, float* w, int count, int* active);
 
 /* Benchmark path: batch resident in HBM, steps enqueued back-to-back on the engine's stream. */
 int ics_unet_upload_batch(ics_net* net, const float* x, const uint8_t* labels, int batch);
@@ -640,8 +651,9 @@ int ics_net_profile_row(ics_net* net, int row, const char** label, int64_t* laun
 int ics_comm_unique_id(char uid[128]);
 int ics_net_comm_init(ics_net* net, int rank, int nranks, const char uid[128]);
 int ics_net_comm_allreduce_max(ics_net* net, double* value); /* barrier + max over ranks */
-/* rank `root`'s parameters, BN moving statistics, Adam moments and step count overwrite everyone's:
- * replicas start identical (the class API initialises from an unseeded RNG).  No-op without a communicator. */
+/* rank `root`'s parameters, BN moving statistics, Adam moments, step count and (U-Net) class-weight table with its
+ * active flag overwrite everyone's: replicas start identical (the class API initialises from an unseeded RNG) and train
+ * with one loss.  No-op without a communicator. */
 int ics_net_comm_broadcast_state(ics_net* net, int root);
 /* 1: BatchNorm batch statistics (forward) and their gradient sums (backward) are exchanged over the
  * communicator, so N replicas x B grids normalise exactly like one process at N*B (the reference is
@@ -777,6 +789,11 @@ int ics_op_conv_link(ics_conv_link* a);
 int ics_op_unet_head(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
                      const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
                      float metrics[5], double sums[7]);
+/* The same with per-class loss weights: class_weights [ncls] (finite, >= 0) replaces the scalar in modes 1 and 2 (with a
+ * table mode 0 is refused); NULL: ics_op_unet_head exactly. */
+int ics_op_unet_head_weighted(const float* x, const float* wsoft, const float* bsoft, const float* wsig, const float* bsig,
+                              const uint8_t* labels, size_t M, int ncls, float loss_weight, int mode, int fused, float* out,
+                              float metrics[5], double sums[7], const float* class_weights);
 /* metrics[5] = [Loss, lsoft, lsig, f1, wr] from the seven sums of ics_op_unet_head (ics_unet_metric_sums), added over the
  * shards of a global batch: the finalisation every rank of a data-parallel step runs after the all-reduce of the sums. */
 int ics_op_unet_metrics_from_sums(const double sums[7], float metrics[5]);
@@ -901,6 +918,12 @@ int ics_net_feed_metrics(ics_net* net, int ticket, float* metrics);
  * Synchronous, the calling thread's op stream and scratch. */
 int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1, const void* labels, int batch, int d,
                      int num_classes, float* x, uint8_t* out_labels);
+/* Exact class counts of n label ids on the device (train_unet.py's inverse-frequency class weights): labels are uint8,
+ * float64 or float32 ids (label_kind 1, 2, 3 of ics_feed_config; the one-hot kind 4 is refused), counts [ncls] is
+ * OVERWRITTEN with the number of labels equal to each class id, and *out_of_range receives the number of values that are
+ * no class id -- below 0, at or above ncls, non-integral, NaN -- which are counted there and index nothing.  n is arbitrary
+ * (0 gives zeros); ncls 2 .. 127.  Synchronous, the calling thread's op stream and scratch. */
+int ics_op_label_counts(const void* labels, int label_kind, size_t n, int ncls, int64_t* counts, int64_t* out_of_range);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ train_unet.py:84) and --synthetic N (Gaussian-blob grids of SURVEY 8(d); no data
 
   python3 train_unet.py --name heusler --samples 5000 --epochs 100
   python3 train_unet.py --name demo --synthetic 64 --channels 1 --epochs 2 --batch_size 8
+  python3 train_unet.py --name heusler --samples 5000 --epochs 100 --weighted_loss     (per-class loss weights)
 
 Data parallel (new; the reference is single-process): launch one process per GPU,
   python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train_unet.py ...
@@ -45,6 +46,9 @@ if __name__ == "__main__":
     p.add_argument("--sync_bn", type=int, default=0, help="data parallel: BatchNorm statistics over all ranks")
     p.add_argument("--feed", action="store_true",
                    help="fed steps: upload each batch through pinned staging slots while the previous step runs")
+    p.add_argument("--weighted_loss", action="store_true",
+                   help="weigh each voxel's softmax loss by its class's inverse-frequency weight (class_weights.npy, "
+                        "background 0) instead of the reference's scalar num_classes; the counts are taken on the GPU")
     p.add_argument("--monitor", action="store_true",
                    help="draw the reference's training pictures on the GPU into the output folder (icsg3d_amd/monitor.py)")
     p.add_argument("--gpus", type=int, default=0,
@@ -74,7 +78,7 @@ if __name__ == "__main__":
                                                     seed=rank * 10 ** 7)
         validation_generator = SyntheticUnetGenerator(n_val, a.batch_size, (d, d, d), a.channels,
                                                       a.nclasses, seed=10 ** 6 + rank * 10 ** 7)
-        class_weights = get_weights()
+        class_weights = get_weights(n_classes=a.nclasses) if a.weighted_loss else get_weights()
     else:
         training_ids, validation_ids = data_split(path, a.samples, frac=a.split, n_rot=a.nrot)
         all_training_ids, all_validation_ids = training_ids, validation_ids
@@ -91,13 +95,17 @@ if __name__ == "__main__":
         try:
             class_weights = np.load(weights_dir + "/class_weights.npy")
         except Exception:
-            class_weights = get_weights(path, all_training_ids, a.nclasses)
+            class_weights = get_weights(path, all_training_ids, a.nclasses, device=a.weighted_loss)
             class_weights[0] = 0.0
             if rank == 0:
                 np.save(weights_dir + "/class_weights.npy", class_weights)
 
+    if a.weighted_loss and rank == 0:
+        nz = np.asarray(class_weights)[np.asarray(class_weights) > 0]
+        print("weighted loss: %d of %d classes with non-zero weight, smallest %g, largest %g"
+              % (nz.size, a.nclasses, nz.min() if nz.size else 0.0, nz.max() if nz.size else 0.0))
     unet = AtomUnet(num_classes=a.nclasses, class_weights=class_weights, input_shape=input_shape, weights=weights,
-                    lr=a.lr, max_batch=a.batch_size)
+                    lr=a.lr, max_batch=a.batch_size, weighted_loss=a.weighted_loss)
     if dp:
         unet.enable_data_parallel(dp[0], rank, world, sync_bn=bool(a.sync_bn), force=world == 1)
     unet.train_generator(training_generator, validation_generator, epochs=a.epochs,
