@@ -59,7 +59,8 @@ _F = C.POINTER(C.c_float)
 
 
 class ConvLayerSrc(C.Structure):
-    _fields_ = [("x", _F), ("scale", _F), ("shift", _F), ("C", C.c_int), ("up", C.c_int), ("act", C.c_int), ("dx", _F)]
+    _fields_ = [("x", _F), ("scale", _F), ("shift", _F), ("C", C.c_int), ("up", C.c_int), ("act", C.c_int), ("bcast", C.c_int),
+                ("dx", _F)]
 
 
 class ConvLayerArgs(C.Structure):
@@ -70,6 +71,13 @@ class ConvLayerArgs(C.Structure):
                 ("mean", _F), ("rstd", _F), ("scale", _F), ("shift", _F), ("moving_mean", _F), ("moving_var", _F),
                 ("rows_per_block", C.c_int), ("blocks", C.c_int), ("dw", _F), ("dbias", _F), ("dgamma", _F), ("dbeta", _F),
                 ("kernels", C.c_void_p), ("kernels_cap", C.c_int), ("ranks", C.c_int)]
+
+
+class VaeLatentArgs(C.Structure):
+    """ics_vae_latent (include/icsg3d.h)."""
+    _fields_ = [("B", C.c_int), ("max_batch", C.c_int), ("latent", C.c_int), ("ncond", C.c_int), ("beta", C.c_float),
+                ("h", _F), ("w_mean", _F), ("w_lv", _F), ("b_mean", _F), ("b_lv", _F), ("eps", _F), ("cond", _F), ("dzc", _F),
+                ("mulv", _F), ("z", _F), ("zc", _F), ("dmulv", _F), ("dw_mean", _F), ("dw_lv", _F), ("dbias", _F), ("dh", _F)]
 
 
 class ConvLinkLayer(C.Structure):
@@ -211,6 +219,8 @@ SIGNATURES = {
     "ics_op_label_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _I64, _I64]),
     "ics_op_vae_loss": (C.c_int, [_F, C.c_int, C.c_int, _D, C.c_int, C.c_double, _D, C.POINTER(C.c_int), _D, _F, C.c_float,
                                   C.c_float, C.c_int, _D, _F]),
+    "ics_op_vae_latent": (C.c_int, [C.POINTER(VaeLatentArgs)]),
+    "ics_op_sqdiff": (C.c_int, [_F, _F, C.c_int, C.c_size_t, C.c_int, C.c_float, C.c_int, _F, _D]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
     "ics_op_conv_link": (C.c_int, [C.POINTER(ConvLinkArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

@@ -842,6 +842,9 @@ static int conv_forward(Net& n, ConvLayer& L, int B, bool training, bool update_
     ICS_TRY(launch_cond_bias_table(n.st, n.tp(L.t_w), bias, cs.p, L.vsrc[0].C, cs.bcast, L.Cin, L.Cout, B, L.cond_T));
     ICS_TRY(launch_conv_fwd_thin_c(n.st, g, L.vsrc[0], L.vsrc[0].C, L.CinG, L.wp, nullptr, L.s, L.Cout, L.pre_act,
                                    stats ? n.ws_stat : nullptr, &rpb, L.cond_T));
+    // (the site's id names both kernels: the stencil's instantiation is the same with and without a position bias)
+    conv_set_last_kernel_id(L.Cout == 32 ? "cond_bias_table_kernel + conv_thin_c_fwd_kernel<1, 32>"
+                                         : "cond_bias_table_kernel + conv_thin_c_fwd_kernel<1, 16>");
   } else if (L.pad_in && L.nvsrc == 1 && conv_thin_c_ok(g, L.vsrc[0], 1, L.Cin) && L.Cout % 4 == 0) {
     // single-channel input (c1 at C = 1): the direct stencil reads the un-padded tensor; the packed weights keep the
     // padded layout (CinG channels per tap) the backward-weight kernel is built for
@@ -1102,6 +1105,8 @@ static int conv_grads_from_dy(Net& n, ConvLayer& L, int B, bool need_dA, bool pa
                                        n.ws_wgrad_n, 0));
       ICS_TRY(launch_cond_wgrad(ws, L.dy, B, L.S, L.Cout, cs.p, C0, cs.C, cs.bcast, L.Cin, n.tg(L.t_w), n.ws_dbl,
                                 n.ws_dbl_n));
+      conv_set_last_kernel_id(L.Cout == 32 ? "conv_thin_c_wgrad_kernel<32> + cond_wgrad_kernel"
+                                           : "conv_thin_c_wgrad_kernel<16> + cond_wgrad_kernel");
       n.prof.end(ws);
     } else if (thin1) {
       ICS_TRY(launch_conv_wgrad_thin_c(ws, g, L.vsrc[0], L.dy, L.Cout, n.tg(L.t_w), L.Cout, L.Cin, n.ws_wgrad,
@@ -1773,6 +1778,22 @@ static VaeRefs vae_refs(Net& n) {
   return r;
 }
 
+// e0 at C = 1: condition channels folded analytically (exact; needs the single-channel stencil kernels).  The one place
+// that decides it: vae_build and ics_op_conv_layer's condition source both ask here.
+static bool cond_fold_ok(const Net& n, int C, int Cout) {
+  return C == 1 && !(n.flags & (CF_NO_COND_FOLD | CF_NO_THIN_C)) && (Cout == 16 || Cout == 32);
+}
+// z_mean | z_log_var as one GEMM with N = 2*latent; parameters stay two reference layers
+static ConvLayer* add_zmulv(Net& n, int lat) {
+  ConvLayer* zml = add_conv(n, "zmulv", lat, 2 * lat, 1, 1, ACT_NONE, 0, ACT_NONE, true, false);
+  const int t_zm = n.add_tensor("z_mean/kernel", {lat, lat}, true);
+  const int t_zl = n.add_tensor("z_log_var/kernel", {lat, lat}, true);
+  const int t_zb = n.add_tensor("z_mean/bias", {lat}, true);   // z_mean/bias | z_log_var/bias contiguous
+  n.add_tensor("z_log_var/bias", {lat}, true);
+  zml->t_w = t_zm; zml->t_gamma = t_zl; zml->t_b = t_zb;
+  return zml;
+}
+
 static int vae_build(Net& n, const ics_vae_config& cfg, Net* pm) {
   n.kind = 1; n.maxB = cfg.max_batch; n.d = cfg.d; n.C = cfg.in_channels; n.pm = pm;
   n.pm_side = getenv("ICSG3D_NO_PM_SIDE") == nullptr;
@@ -1790,21 +1811,13 @@ static int vae_build(Net& n, const ics_vae_config& cfg, Net* pm) {
   int S = d;
   for (int i = 0; i < 4; ++i) {
     ConvLayer* L = add_conv(n, "e" + std::to_string(i), cin, cfg.filters[i], 27, S, ACT_NONE, 1, ACT_LRELU, false, true, i == 0);
-    // e0 at C = 1: condition channels folded analytically (exact; needs the single-channel stencil kernels)
-    if (i == 0 && C == 1 && !(n.flags & (CF_NO_COND_FOLD | CF_NO_THIN_C)) && (cfg.filters[0] == 16 || cfg.filters[0] == 32))
-      L->cond_fold = true;
+    if (i == 0 && cond_fold_ok(n, C, cfg.filters[0])) L->cond_fold = true;
     cin = cfg.filters[i]; S /= 2;
   }
   add_conv(n, "e4", cin, 4, 27, S, ACT_LRELU, 0, ACT_NONE, false);        // S = d/16
   const int flat = S * S * S * 4;
   add_conv(n, "enc_dense", flat, lat, 1, 1, ACT_RELU, 0, ACT_NONE, true);
-  // z_mean | z_log_var as one GEMM with N = 2*latent; parameters stay two reference layers
-  ConvLayer* zml = add_conv(n, "zmulv", lat, 2 * lat, 1, 1, ACT_NONE, 0, ACT_NONE, true, false);
-  const int t_zm = n.add_tensor("z_mean/kernel", {lat, lat}, true);
-  const int t_zl = n.add_tensor("z_log_var/kernel", {lat, lat}, true);
-  const int t_zb = n.add_tensor("z_mean/bias", {lat}, true);   // z_mean/bias | z_log_var/bias contiguous
-  n.add_tensor("z_log_var/bias", {lat}, true);
-  zml->t_w = t_zm; zml->t_gamma = t_zl; zml->t_b = t_zb;
+  add_zmulv(n, lat);
   const int seedS = d / 8, seed = seedS * seedS * seedS * 4;
   add_conv(n, "dec_dense", lat + cfg.cond_shape, seed, 1, 1, ACT_NONE, 0, ACT_NONE, true);
   cin = 4; S = seedS;
@@ -1865,6 +1878,41 @@ static int vae_build(Net& n, const ics_vae_config& cfg, Net* pm) {
   return 0;
 }
 
+// ---- the latent link: z_mean | z_log_var as one N = 2 * latent GEMM (Z = zmulv, its two kernels in t_w / t_gamma, the joint
+// bias in t_b), sampling, and their hand-assembled backward pass.  vae_build / vae_step use these three on the engine's
+// handle (add_zmulv above vae_build makes the layer), ics_op_vae_latent on a handle that holds nothing else.
+static int vae_latent_pack(Net& n, ConvLayer& Z) {
+  const int lat = n.latent;
+  ICS_TRY(launch_pack_fwd(n.st, n.tp(Z.t_w), lat, lat, Z.wp, Z.Kpad, Z.Npad, 0, 0, 1));
+  ICS_TRY(launch_pack_fwd(n.st, n.tp(Z.t_gamma), lat, lat, Z.wp, Z.Kpad, Z.Npad, 0, lat, 0));
+  ICS_TRY(launch_pack_bwd(n.st, n.tp(Z.t_w), 1, lat, lat, Z.wf, Z.Kpad_b, Z.Npad_b, 2 * lat, 0, 1));
+  ICS_TRY(launch_pack_bwd(n.st, n.tp(Z.t_gamma), 1, lat, lat, Z.wf, Z.Kpad_b, Z.Npad_b, 2 * lat, lat, 0));
+  return 0;
+}
+// mulv = h W + b into Z.s, then z = mu + exp(lv / 2) eps and zc = [z | cond]
+static int vae_latent_forward(Net& n, ConvLayer& Z, int B, bool training) {
+  ICS_TRY(conv_forward(n, Z, B, training, training, n.tp(Z.t_b)));
+  ICS_TRY(launch_sampling(n.st, Z.s, 2 * n.latent, n.latent, n.eps_in, n.cond_in, n.ncond, B, n.z_buf, n.zc));
+  return 0;
+}
+// dzc [B][ldzc]: the gradient w.r.t. zc (dec_dense's dA; its columns beyond latent belong to the condition and are not
+// read).  Leaves dmulv (sampling + KL), the gradients of the two kernels and the joint bias, and Z.dA = d/dh.
+static int vae_latent_backward(Net& n, ConvLayer& Z, const float* dzc, int ldzc, int B) {
+  const int lat = n.latent;
+  // sampling + KL
+  ICS_TRY(launch_vae_dz(n.st, Z.s, 2 * lat, lat, B, n.eps_in, dzc, ldzc, n.beta, n.dmulv));
+  // zmulv given dy = dmulv
+  ConvGeom g1 = geom_fwd(Z, B); g1.Cout = lat; g1.Npad = round_up(lat, 32);
+  hipStream_t ws = side_begin(n);
+  ICS_TRY(launch_conv_wgrad(ws, g1, Z.src, 1, n.dmulv, 2 * lat, n.tg(Z.t_w), lat, n.ws_wgrad, n.ws_wgrad_n));
+  ICS_TRY(launch_conv_wgrad(ws, g1, Z.src, 1, n.dmulv + lat, 2 * lat, n.tg(Z.t_gamma), lat, n.ws_wgrad, n.ws_wgrad_n));
+  ICS_TRY(launch_colsum_small(n.st, n.dmulv, B, 2 * lat, 2 * lat, n.tg(Z.t_b)));
+  const ConvGeom gb = geom_bwd(Z, B);
+  ConvSrc sd = src_plain(n.dmulv, 2 * lat);
+  ICS_TRY(launch_conv_fwd(n.st, gb, &sd, 1, Z.wf, nullptr, Z.dA, lat, ACT_NONE, nullptr, nullptr));
+  return 0;
+}
+
 static int vae_pack_jobs(Net& n) {
   VaeRefs r = vae_refs(n);
   for (auto& Lp : n.layers) {
@@ -1872,13 +1920,7 @@ static int vae_pack_jobs(Net& n) {
     if (&L == r.zml) continue;
     ICS_TRY(pack_layer(n, L, true));
   }
-  ConvLayer& Z = *r.zml;
-  const int lat = n.latent;
-  ICS_TRY(launch_pack_fwd(n.st, n.tp(Z.t_w), lat, lat, Z.wp, Z.Kpad, Z.Npad, 0, 0, 1));
-  ICS_TRY(launch_pack_fwd(n.st, n.tp(Z.t_gamma), lat, lat, Z.wp, Z.Kpad, Z.Npad, 0, lat, 0));
-  ICS_TRY(launch_pack_bwd(n.st, n.tp(Z.t_w), 1, lat, lat, Z.wf, Z.Kpad_b, Z.Npad_b, 2 * lat, 0, 1));
-  ICS_TRY(launch_pack_bwd(n.st, n.tp(Z.t_gamma), 1, lat, lat, Z.wf, Z.Kpad_b, Z.Npad_b, 2 * lat, lat, 0));
-  return 0;
+  return vae_latent_pack(n, *r.zml);
 }
 static int vae_pack(Net& n) { return run_pack_table(n, vae_pack_jobs); }
 
@@ -1888,8 +1930,7 @@ static int vae_encode_fwd(Net& n, int B, bool training) {
   for (int i = 0; i < 4; ++i) ICS_TRY(conv_forward(n, *r.e[i], B, training, training, n.tp(r.e[i]->t_b)));
   ICS_TRY(conv_forward(n, *r.e4, B, training, training, n.tp(r.e4->t_b)));
   ICS_TRY(conv_forward(n, *r.encd, B, training, training, n.tp(r.encd->t_b)));
-  ICS_TRY(conv_forward(n, *r.zml, B, training, training, n.tp(r.zml->t_b)));
-  ICS_TRY(launch_sampling(n.st, r.zml->s, 2 * n.latent, n.latent, n.eps_in, n.cond_in, n.ncond, B, n.z_buf, n.zc));
+  ICS_TRY(vae_latent_forward(n, *r.zml, B, training));
   n.enc_batch = B;
   return 0;
 }
@@ -2028,22 +2069,9 @@ static int vae_step(Net& n, int B, bool training, float* metrics, bool defer = f
       if (rc) break;
       if ((rc = conv_backward(n, *r.decd, B, gs_direct(r.dl[0]->dA, r.decd->Cout, 0), gs_none(), nullptr, true, true))) break;
       if ((rc = grads_ready(n, layer_lo(n, *r.decd)))) break;   // decoder gradients (the tail of the flat buffer)
-      // sampling + KL
-      if ((rc = launch_vae_dz(n.st, r.zml->s, 2 * n.latent, n.latent, B, n.eps_in, r.decd->dA, r.decd->Cin, n.beta, n.dmulv))) break;
-      // zmulv given dy = dmulv
       ConvLayer& Z = *r.zml;
-      const int lat = n.latent;
-      {
-        ConvGeom g1 = geom_fwd(Z, B); g1.Cout = lat; g1.Npad = round_up(lat, 32);
-        hipStream_t ws = side_begin(n);
-        if ((rc = launch_conv_wgrad(ws, g1, Z.src, 1, n.dmulv, 2 * lat, n.tg(Z.t_w), lat, n.ws_wgrad, n.ws_wgrad_n))) break;
-        if ((rc = launch_conv_wgrad(ws, g1, Z.src, 1, n.dmulv + lat, 2 * lat, n.tg(Z.t_gamma), lat, n.ws_wgrad, n.ws_wgrad_n))) break;
-        if ((rc = launch_colsum_small(n.st, n.dmulv, B, 2 * lat, 2 * lat, n.tg(Z.t_b)))) break;
-        const ConvGeom gb = geom_bwd(Z, B);
-        ConvSrc sd = src_plain(n.dmulv, 2 * lat);
-        if ((rc = launch_conv_fwd(n.st, gb, &sd, 1, Z.wf, nullptr, Z.dA, lat, ACT_NONE, nullptr, nullptr))) break;
-      }
-      if ((rc = conv_backward(n, *r.encd, B, gs_direct(Z.dA, lat, 0), gs_none(), nullptr, true, true))) break;
+      if ((rc = vae_latent_backward(n, Z, r.decd->dA, r.decd->Cin, B))) break;
+      if ((rc = conv_backward(n, *r.encd, B, gs_direct(Z.dA, n.latent, 0), gs_none(), nullptr, true, true))) break;
       if ((rc = conv_backward(n, *r.e4, B, gs_direct(r.encd->dA, 4, 0), gs_none(), nullptr, true, true))) break;
       for (int i = 3; i >= 0; --i) {
         ConvLayer* cons = (i == 3) ? r.e4 : r.e[i + 1];
@@ -3435,6 +3463,15 @@ static int conv_layer_check(const ics_conv_layer* a, const std::string& op) {
     ICS_CHECK((s.scale == nullptr) == (s.shift == nullptr), op + "a source has scale and shift, or neither");
     ICS_CHECK(!s.up || a->S >= 2, op + "an upsampled source needs S >= 2");
     ICS_CHECK(!s.dx || a->dout, op + "source gradients need dout");
+    ICS_CHECK(s.bcast >= 0, op + "bcast must be >= 0");
+    if (s.bcast > 0) {
+      // a spatially constant source, as vae_build gives e0: behind the x channels, K.tile'd to C * bcast channels, plain
+      ICS_CHECK(a->nsrc == 2 && i == 1 && a->src[0].bcast == 0, op + "a bcast source must be the last of two");
+      ICS_CHECK(!s.scale && s.act == ACT_NONE && !s.up, op + "a bcast source has no affine, activation or up");
+      ICS_CHECK(s.dx == nullptr, op + "a bcast source has no dx: the engines never differentiate with respect to the condition");
+      ICS_CHECK(a->taps == 27 && !a->src[0].up, op + "a bcast source needs a 3x3x3 layer and a same-resolution first source");
+      ICS_CHECK(s.C == a->src[0].C * s.bcast, op + "a bcast source stands for C = (channels of the first source) * bcast channels");
+    }
     Cin += s.C;
     want_dx = want_dx || s.dx != nullptr;
   }
@@ -3456,6 +3493,12 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
   const int B = a->B, S = a->S, Cout = a->Cout;
   ConvLayer& L = *add_conv(n, "L", Cin, Cout, a->taps, S, a->pre_act, a->has_bn ? 1 : 0, a->post_act, false, true,
                            a->pad_input != 0);
+  // a condition source (bcast > 0): the layer is built as vae_build builds e0, the fold decided by the engine's predicate
+  const int bcast = a->src[a->nsrc - 1].bcast;
+  if (bcast > 0) {
+    n.ncond = bcast;
+    L.cond_fold = cond_fold_ok(n, a->src[0].C, Cout);
+  }
   ICS_TRY(emu_attach(n, emu));
   ICS_TRY(alloc_params(n));
   // buffers first, sources after: a source's affine sits in the handle like a producer layer's
@@ -3467,14 +3510,16 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
     const ics_conv_layer_src& s = a->src[i];
     float *dx = nullptr, *dsc = nullptr, *dsh = nullptr;
     src_rows[i] = s.up ? M / 8 : M;
-    ICS_TRY(n.alloc(&dx, (s.up ? Mmax / 8 : Mmax) * s.C));
-    ICS_HIP(hipMemcpyAsync(dx, s.x, src_rows[i] * s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
+    // x of a bcast source is [B][bcast] (Net::cond_in), whatever number of channels it stands for
+    const size_t cnt = s.bcast > 0 ? (size_t)B * s.bcast : src_rows[i] * s.C;
+    ICS_TRY(n.alloc(&dx, s.bcast > 0 ? (size_t)n.maxB * s.bcast : (s.up ? Mmax / 8 : Mmax) * s.C));
+    ICS_HIP(hipMemcpyAsync(dx, s.x, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
     if (s.scale) {
       ICS_TRY(n.alloc(&dsc, (size_t)s.C)); ICS_TRY(n.alloc(&dsh, (size_t)s.C));
       ICS_HIP(hipMemcpyAsync(dsc, s.scale, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
       ICS_HIP(hipMemcpyAsync(dsh, s.shift, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
     }
-    srcs[i] = ConvSrc{dx, dsc, dsh, s.C, s.up, s.act, 0};
+    srcs[i] = ConvSrc{dx, dsc, dsh, s.C, s.up, s.act, s.bcast};
     L.src[i] = srcs[i];
   }
   L.nsrc = a->nsrc;
@@ -3586,7 +3631,7 @@ int ics_op_conv_layer(ics_conv_layer* a) {
     ics_conv_layer v = *a;
     auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
     for (int i = 0; i < v.nsrc; ++i) {
-      const size_t cnt = (v.src[i].up ? M / 8 : M) * v.src[i].C;
+      const size_t cnt = v.src[i].bcast > 0 ? (size_t)a->B * v.src[i].bcast : (v.src[i].up ? M / 8 : M) * v.src[i].C;
       v.src[i].x += (size_t)r * cnt;
       off(v.src[i].dx, cnt);
     }
@@ -3902,6 +3947,109 @@ int ics_op_vae_loss(const float* mulv, int B, int latent, const double* mse_part
   ICS_TRY(launch_vae_loss(st, d_mulv, 2 * latent, latent, B, d_mse, n_mse, n_elems, d_pm, pmc, alpha, beta, d_met, d_sum, phase));
   if (phase == 1) ICS_TRY(L.download(sums, s_sum, 5, st));
   else ICS_TRY(L.download(metrics, s_met, 4, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// The latent link on its own (include/icsg3d.h): a Net that holds zmulv and the latent buffers and nothing else, built by
+// vae_build's own calls, packed and stepped by the functions vae_encode_fwd / vae_step use.  dzc stands in for dec_dense's dA.
+int ics_op_vae_latent(ics_vae_latent* a) {
+  const std::string op = "ics_op_vae_latent: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
+  ICS_CHECK(a->latent >= 1 && a->ncond >= 1, op + "need latent, ncond >= 1");
+  ICS_CHECK((size_t)a->max_batch * ((size_t)2 * a->latent + a->ncond) <= ((size_t)1 << 24) && a->latent <= (1 << 12),
+            op + "need max_batch * (2 latent + ncond) <= 2^24 and latent <= 4096");
+  ICS_CHECK(a->h && a->w_mean && a->w_lv && a->eps && a->cond, op + "h, w_mean, w_lv, eps and cond are required");
+  ICS_CHECK(a->dzc || !(a->dmulv || a->dw_mean || a->dw_lv || a->dbias || a->dh), op + "gradients need dzc");
+  const int B = a->B, lat = a->latent, nc = a->ncond, W = lat + nc;
+  const bool bwd = a->dzc != nullptr;
+  Net n;
+  ICS_TRY(op_prepare(n));
+  n.side_on = getenv("ICSG3D_NO_VAE_SIDE_WGRAD") == nullptr;       // as vae_build
+  n.maxB = a->max_batch; n.d = 1; n.C = 1; n.latent = lat; n.ncond = nc; n.beta = a->beta;
+  ConvLayer& Z = *add_zmulv(n, lat);
+  ICS_TRY(alloc_params(n));
+  ICS_TRY(n.alloc(&n.cond_in, (size_t)n.maxB * nc));
+  ICS_TRY(n.alloc(&n.eps_in, (size_t)n.maxB * lat));
+  ICS_TRY(n.alloc(&n.z_buf, (size_t)n.maxB * lat));
+  ICS_TRY(n.alloc(&n.zc, (size_t)n.maxB * W));
+  ICS_TRY(n.alloc(&n.dmulv, (size_t)n.maxB * 2 * lat));
+  ICS_TRY(alloc_layer(n, Z, true, false));
+  float *d_h = nullptr, *d_dzc = nullptr;
+  ICS_TRY(n.alloc(&d_h, (size_t)n.maxB * lat));
+  ICS_TRY(n.alloc(&d_dzc, (size_t)n.maxB * W));
+  Z.src[0] = src_plain(d_h, lat);
+  ICS_TRY(alloc_workspaces(n, true));
+  auto up = [&](float* dev, const float* host, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(dev, host, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
+    return 0;
+  };
+  ICS_TRY(up(d_h, a->h, (size_t)B * lat));
+  ICS_TRY(up(n.eps_in, a->eps, (size_t)B * lat));
+  ICS_TRY(up(n.cond_in, a->cond, (size_t)B * nc));
+  ICS_TRY(up(d_dzc, a->dzc, (size_t)B * W));
+  ICS_TRY(up(n.tp(Z.t_w), a->w_mean, (size_t)lat * lat));
+  ICS_TRY(up(n.tp(Z.t_gamma), a->w_lv, (size_t)lat * lat));
+  ICS_TRY(up(n.tp(Z.t_b), a->b_mean, (size_t)lat));              // z_mean/bias | z_log_var/bias are contiguous
+  ICS_TRY(up(n.tp(Z.t_b) + lat, a->b_lv, (size_t)lat));
+  ICS_TRY(vae_latent_pack(n, Z));
+  n.splitk = true;               // as inside a train step
+  n.want_wgrad_inputs = bwd;
+  ICS_TRY(vae_latent_forward(n, Z, B, true));
+  if (bwd) {
+    ICS_TRY(vae_latent_backward(n, Z, d_dzc, W, B));
+    ICS_TRY(side_join(n));
+  }
+  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
+    return 0;
+  };
+  ICS_TRY(down(a->mulv, Z.s, (size_t)B * 2 * lat));
+  ICS_TRY(down(a->z, n.z_buf, (size_t)B * lat));
+  ICS_TRY(down(a->zc, n.zc, (size_t)B * W));
+  if (bwd) {
+    ICS_TRY(down(a->dmulv, n.dmulv, (size_t)B * 2 * lat));
+    ICS_TRY(down(a->dw_mean, n.tg(Z.t_w), (size_t)lat * lat));
+    ICS_TRY(down(a->dw_lv, n.tg(Z.t_gamma), (size_t)lat * lat));
+    ICS_TRY(down(a->dbias, n.tg(Z.t_b), (size_t)2 * lat));
+    ICS_TRY(down(a->dh, Z.dA, (size_t)B * lat));
+  }
+  ICS_HIP(hipStreamSynchronize(n.st));
+  if (n.canary_on) {
+    std::string msg;
+    const int bad = n.canaries_dirty(&msg);
+    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
+  }
+  return 0;
+}
+
+// sqdiff_kernel as the VAE step launches it for the squared error and the perceptual taps (include/icsg3d.h)
+int ics_op_sqdiff(const float* a, const float* b, int B, size_t per_sample, int blocks_per_sample, float coef, int accumulate,
+                  float* grad_in_out, double* partial_out) {
+  const std::string op = "ics_op_sqdiff: ";
+  ICS_CHECK(a && b && partial_out, op + "a, b and partial_out are required");
+  ICS_CHECK(B >= 1 && per_sample >= 1 && blocks_per_sample >= 1, op + "need B, per_sample, blocks_per_sample >= 1");
+  ICS_CHECK((size_t)B * blocks_per_sample <= ((size_t)1 << 20) && per_sample <= ((size_t)1 << 28) / B,
+            op + "need B * blocks_per_sample <= 2^20 and B * per_sample <= 2^28");
+  ICS_CHECK(accumulate == 0 || (accumulate == 1 && grad_in_out), op + "accumulate is 0, or 1 with grad_in_out");
+  const size_t cnt = (size_t)B * per_sample, np = (size_t)B * blocks_per_sample;
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_a = L.add<float>(cnt);
+  const auto s_b = L.add<float>(cnt);
+  const auto s_g = L.add<float>(grad_in_out ? cnt : 0);
+  const auto s_p = L.add<double>(np);
+  float *d_a, *d_b, *d_g;
+  double* d_p;
+  ICS_TRY(L.reserve(s_a, &d_a, s_b, &d_b, s_g, &d_g, s_p, &d_p));
+  ICS_TRY(L.upload(s_a, a, cnt, st));
+  ICS_TRY(L.upload(s_b, b, cnt, st));
+  if (accumulate) ICS_TRY(L.upload(s_g, grad_in_out, cnt, st));
+  ICS_TRY(launch_sqdiff(st, d_a, d_b, B, per_sample, blocks_per_sample, d_p, d_g, coef, accumulate));
+  if (grad_in_out) ICS_TRY(L.download(grad_in_out, s_g, cnt, st));
+  ICS_TRY(L.download(partial_out, s_p, np, st));
   ICS_HIP(hipStreamSynchronize(st));
   return 0;
 }

@@ -1206,6 +1206,7 @@ static int run(int d, int C, int B, int with_comm) {
  * upsampled layers with the up-split switched off (the host-side 8-children sum) and every refusal. */
 static int g_ranks = 0;   /* ics_conv_layer.ranks / ics_conv_link.ranks of the *_one walkers: every buffer is sized for exactly
                              that many ranks (batch tensors R * B samples, per-rank outputs [R], R site texts) */
+static int g_bcast = 0;   /* > 0: the second source of conv_layer_one is a condition, x [R * B][g_bcast] of the exact size */
 static int conv_layer_one(int B, int maxB, int S, int taps, int Cout, int form, int pad, int nsrc, const int* sc, const int* sup,
                           int aff, int bwd) {
   ics_conv_layer a;
@@ -1220,6 +1221,12 @@ static int conv_layer_one(int B, int maxB, int S, int taps, int Cout, int form, 
   a.has_bn = form != 2; a.pre_act = form == 0 ? 1 : 0; a.post_act = form == 1 ? 2 : 0;
   for (int i = 0; i < nsrc; ++i) {
     size_t rows = sup[i] ? M / 8 : M;
+    if (i == 1 && g_bcast > 0) {                       /* no affine, no activation, no dx */
+      a.src[i].C = sc[i]; a.src[i].bcast = g_bcast;
+      a.src[i].x = calloc((size_t)R * B * g_bcast, 4);
+      Cin += sc[i];
+      continue;
+    }
     a.src[i].C = sc[i]; a.src[i].up = sup[i]; a.src[i].act = (aff && form == 1) ? 2 : 0;
     a.src[i].x = calloc(rows * sc[i], 4);
     if (aff) { a.src[i].scale = calloc(sc[i], 4); a.src[i].shift = calloc(sc[i], 4); }
@@ -1287,6 +1294,29 @@ static int conv_layer_walk(void) {
         c[0] = 64; if (conv_layer_one(4, 4, 4, 27, 64, form, 0, 1, c, one, 1, bwd)) return 1;
       }
   g_ranks = 0;
+  /* condition sources: folded (one x channel, 16 / 32 filters; 1 + 3 needs no padding), not folded under either switch,
+   * four x channels through the materialised input (4 + 40 -> 64) and the broadcast loader (4 + 12 = 16), without padding,
+   * and two emulated ranks (the condition is offset per rank by B * bcast) */
+  {
+    const int two[2] = {0, 0};
+    for (int form = 0; form < 3; ++form)
+      for (int bwd = 0; bwd < 2; ++bwd) {
+        g_bcast = 10; c[0] = 1; c[1] = 10; if (conv_layer_one(2, 3, 4, 27, 16, form, 1, 2, c, two, 0, bwd)) return 1;
+        g_bcast = 3; c[0] = 1; c[1] = 3; if (conv_layer_one(3, 3, 8, 27, 32, form, 1, 2, c, two, 0, bwd)) return 1;
+        g_bcast = 10; c[0] = 1; c[1] = 10; if (conv_layer_one(2, 2, 8, 27, 16, form, 0, 2, c, two, 0, bwd)) return 1;
+        g_bcast = 10; c[0] = 4; c[1] = 40; if (conv_layer_one(2, 3, 8, 27, 16, form, 1, 2, c, two, 0, bwd)) return 1;
+        g_bcast = 3; c[0] = 4; c[1] = 12; if (conv_layer_one(3, 5, 4, 27, 16, form, 1, 2, c, two, 0, bwd)) return 1;
+        setenv("ICSG3D_NO_COND_FOLD", "1", 1);
+        g_bcast = 7; c[0] = 1; c[1] = 7; if (conv_layer_one(2, 3, 8, 27, 32, form, 1, 2, c, two, 0, bwd)) return 1;
+        unsetenv("ICSG3D_NO_COND_FOLD");
+        setenv("ICSG3D_NO_THIN_C", "1", 1);
+        g_bcast = 1; c[0] = 1; c[1] = 1; if (conv_layer_one(2, 2, 8, 27, 16, form, 1, 2, c, two, 0, bwd)) return 1;
+        unsetenv("ICSG3D_NO_THIN_C");
+      }
+    g_ranks = 2; g_bcast = 10; c[0] = 1; c[1] = 10;
+    if (conv_layer_one(2, 3, 8, 27, 16, 1, 1, 2, c, two, 0, 1)) return 1;
+    g_ranks = 0; g_bcast = 0;
+  }
   {
     ics_conv_layer a;
     float buf[8 * 4] = {0};
@@ -1308,6 +1338,24 @@ static int conv_layer_walk(void) {
     a.dw = buf; bad += ics_op_conv_layer(&a) == 0; a.dw = NULL;
     a.S = 1; a.src[0].up = 1; bad += ics_op_conv_layer(&a) == 0; a.S = 2; a.src[0].up = 0;
     a.w = NULL; bad += ics_op_conv_layer(&a) == 0; a.w = buf;
+    a.src[0].bcast = 4; bad += ics_op_conv_layer(&a) == 0; a.src[0].bcast = 0;      /* a condition is the last of TWO sources */
+    a.src[0].bcast = -1; bad += ics_op_conv_layer(&a) == 0; a.src[0].bcast = 0;
+    {   /* a well-formed condition layer (1 + 2 channels, S = 4, 3x3x3), then each thing a condition source may not have */
+      ics_conv_layer b = a;
+      float big[2 * 64 * 3 * 27] = {0}, ybuf[2 * 64 * 4], gbuf[2 * 64 * 4] = {0};
+      b.B = 2; b.max_batch = 2; b.S = 4; b.taps = 27; b.nsrc = 2; b.w = big; b.y = ybuf;
+      b.src[0].x = big; b.src[0].C = 1; b.src[1].x = big; b.src[1].C = 2; b.src[1].bcast = 2;
+      OK(ics_op_conv_layer(&b));
+      b.src[1].scale = big; b.src[1].shift = big; bad += ics_op_conv_layer(&b) == 0; b.src[1].scale = NULL; b.src[1].shift = NULL;
+      b.src[1].act = 1; bad += ics_op_conv_layer(&b) == 0; b.src[1].act = 0;
+      b.src[1].up = 1; bad += ics_op_conv_layer(&b) == 0; b.src[1].up = 0;
+      b.src[1].C = 3; bad += ics_op_conv_layer(&b) == 0; b.src[1].C = 2;           /* C = bcast * channels of the first */
+      b.src[0].bcast = 1; bad += ics_op_conv_layer(&b) == 0; b.src[0].bcast = 0;
+      b.dout = gbuf; b.src[1].dx = gbuf; bad += ics_op_conv_layer(&b) == 0;        /* no gradient w.r.t. the condition */
+      if (!strstr(ics_last_error(), "never differentiate")) { fprintf(stderr, "conv layer: dx of a condition refused without its reason\n"); return 1; }
+      b.src[1].dx = NULL;
+      OK(ics_op_conv_layer(&b));
+    }
     a.ranks = 5; bad += ics_op_conv_layer(&a) == 0;
     a.ranks = -1; bad += ics_op_conv_layer(&a) == 0;
     a.ranks = 2; a.max_batch = 0; bad += ics_op_conv_layer(&a) == 0; a.max_batch = 1; a.ranks = 0;   /* max_batch < B */
@@ -1532,6 +1580,67 @@ int main(void) {
     bad += ics_op_vae_loss(NULL, 0, 0, NULL, 0, 0.0, NULL, NULL, NULL, NULL, 0.5f, 3e-4f, 2, NULL, met) == 0;
     if (bad) { fprintf(stderr, "vae loss: %d invalid argument sets accepted\n", bad); return 1; }
     free(mulv); free(mse); free(pm);
+  }
+  {   /* the latent link: forward only and with the backward pass, handle = and > batch, buffers of the exact size */
+    const int shapes[4][4] = {{1, 1, 1, 1}, {3, 5, 20, 3}, {2, 2, 33, 7}, {5, 5, 256, 10}};
+    int bad = 0;
+    for (int k = 0; k < 4; ++k)
+      for (int bwd = 0; bwd < 2; ++bwd) {
+        const int B = shapes[k][0], lat = shapes[k][2], nc = shapes[k][3];
+        ics_vae_latent a;
+        memset(&a, 0, sizeof a);
+        a.B = B; a.max_batch = shapes[k][1]; a.latent = lat; a.ncond = nc; a.beta = 1e-2f;
+        a.h = calloc((size_t)B * lat, 4); a.eps = calloc((size_t)B * lat, 4); a.cond = calloc((size_t)B * nc, 4);
+        a.w_mean = calloc((size_t)lat * lat, 4); a.w_lv = calloc((size_t)lat * lat, 4);
+        if (k != 1) { a.b_mean = calloc(lat, 4); a.b_lv = calloc(lat, 4); }       /* the biases are optional */
+        a.mulv = malloc((size_t)B * 2 * lat * 4); a.z = malloc((size_t)B * lat * 4); a.zc = malloc((size_t)B * (lat + nc) * 4);
+        if (bwd) {
+          a.dzc = calloc((size_t)B * (lat + nc), 4);
+          a.dmulv = malloc((size_t)B * 2 * lat * 4); a.dw_mean = malloc((size_t)lat * lat * 4); a.dw_lv = malloc((size_t)lat * lat * 4);
+          a.dbias = malloc((size_t)2 * lat * 4); a.dh = malloc((size_t)B * lat * 4);
+        }
+        OK(ics_op_vae_latent(&a));
+        if (k == 1 && bwd) {
+          setenv("ICSG3D_NO_VAE_SIDE_WGRAD", "1", 1);
+          OK(ics_op_vae_latent(&a));
+          unsetenv("ICSG3D_NO_VAE_SIDE_WGRAD");
+          a.max_batch = 2; bad += ics_op_vae_latent(&a) == 0; a.max_batch = 5;
+          a.latent = 0; bad += ics_op_vae_latent(&a) == 0; a.latent = lat;
+          a.ncond = 0; bad += ics_op_vae_latent(&a) == 0; a.ncond = nc;
+          { const float* t = a.h; a.h = NULL; bad += ics_op_vae_latent(&a) == 0; a.h = t; }
+          { const float* t = a.eps; a.eps = NULL; bad += ics_op_vae_latent(&a) == 0; a.eps = t; }
+          { const float* t = a.dzc; a.dzc = NULL; bad += ics_op_vae_latent(&a) == 0; a.dzc = t; }   /* gradients without dzc */
+          bad += ics_op_vae_latent(NULL) == 0;
+          OK(ics_op_vae_latent(&a));
+        }
+        free((void*)a.h); free((void*)a.eps); free((void*)a.cond); free((void*)a.w_mean); free((void*)a.w_lv);
+        free((void*)a.b_mean); free((void*)a.b_lv); free((void*)a.dzc); free(a.mulv); free(a.z); free(a.zc);
+        free(a.dmulv); free(a.dw_mean); free(a.dw_lv); free(a.dbias); free(a.dh);
+      }
+    if (bad) { fprintf(stderr, "vae latent: %d invalid argument sets accepted\n", bad); return 1; }
+  }
+  {   /* the squared-error partial sums: with and without the gradient, accumulating, blocks past the sample's end */
+    const int B = 3, per[3] = {4100, 4099, 8}, bps[3] = {1, 16, 256};
+    int bad = 0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        float *x = calloc((size_t)B * per[i], 4), *y = calloc((size_t)B * per[i], 4), *g = calloc((size_t)B * per[i], 4);
+        double* part = malloc((size_t)B * bps[j] * 8);
+        OK(ics_op_sqdiff(x, y, B, per[i], bps[j], 0.f, 0, NULL, part));
+        OK(ics_op_sqdiff(x, y, B, per[i], bps[j], 0.5f, 0, g, part));
+        OK(ics_op_sqdiff(x, y, B, per[i], bps[j], 0.5f, 1, g, part));
+        if (i == 0 && j == 0) {
+          bad += ics_op_sqdiff(NULL, y, B, per[i], bps[j], 0.f, 0, NULL, part) == 0;
+          bad += ics_op_sqdiff(x, y, B, per[i], bps[j], 0.f, 0, NULL, NULL) == 0;
+          bad += ics_op_sqdiff(x, y, 0, per[i], bps[j], 0.f, 0, NULL, part) == 0;
+          bad += ics_op_sqdiff(x, y, B, 0, bps[j], 0.f, 0, NULL, part) == 0;
+          bad += ics_op_sqdiff(x, y, B, per[i], 0, 0.f, 0, NULL, part) == 0;
+          bad += ics_op_sqdiff(x, y, B, per[i], bps[j], 0.f, 1, NULL, part) == 0;    /* nothing to accumulate into */
+          bad += ics_op_sqdiff(x, y, B, per[i], bps[j], 0.f, 2, g, part) == 0;
+        }
+        free(x); free(y); free(g); free(part);
+      }
+    if (bad) { fprintf(stderr, "sqdiff: %d invalid argument sets accepted\n", bad); return 1; }
   }
   {   /* connected components on host arrays */
     const int B = 2, d = 16;

@@ -740,7 +740,9 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     activated / upsampled sources, the statistics epilogue, workspaces sized for max_batch.
 
     sources: one or two dicts {"x": (B,s,s,s,C) with s = S, or S/2 with "up": 1; "scale", "shift": (C,) or absent;
-    "act": 0/1/2}.  w (k,k,k,Cin,Cout) with Cin the sum of the sources' C.  dout (B,S,S,S,Cout): gradient w.r.t. the
+    "act": 0/1/2}.  The last of two sources may be a condition, {"x": (B, ncond), "bcast": ncond, "C": channels it stands
+    for}: spatially constant, channel c = x[b][c % ncond] (K.tile), built as the VAE's e0 -- folded where the engine folds
+    it; its entry of dx is None.  w (k,k,k,Cin,Cout) with Cin the sum of the sources' C.  dout (B,S,S,S,Cout): gradient w.r.t. the
     layer's output (post_act(BN(y)), or y without BatchNorm); None runs the forward pass only.
 
     Returns a dict: y; with has_bn mean, rstd, scale, shift, moving_mean, moving_var, rows_per_block, blocks; with dout
@@ -780,7 +782,7 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
         raise ValueError("the batch does not divide into %d equal shards" % R)
     B = NB // max(R, 1)
     S = x0.shape[1] * (2 if srcs[0].get("up") else 1)
-    if sum(_f32(s["x"]).shape[4] for s in srcs) != w.shape[3]:
+    if sum(int(s["C"]) if s.get("bcast") else _f32(s["x"]).shape[4] for s in srcs) != w.shape[3]:
         raise ValueError("the sources' channels do not add up to the kernel's Cin")
     a.B, a.max_batch, a.S, a.taps, a.Cout = B, int(max_batch or B), S, taps, Cout
     a.pre_act, a.has_bn, a.post_act, a.pad_input, a.nsrc = int(pre_act), int(bool(has_bn)), int(post_act), int(bool(pad_input)), len(srcs)
@@ -788,11 +790,18 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     for i, s in enumerate(srcs):
         x = _f32(s["x"])
         up = 1 if s.get("up") else 0
-        if x.shape[:4] != (NB,) + (S // 2 if up else S,) * 3:
+        bcast = int(s.get("bcast", 0))
+        if bcast:
+            if x.shape != (NB, bcast):
+                raise ValueError("source %d has shape %s, a bcast source is (B, bcast)" % (i, x.shape))
+        elif x.shape[:4] != (NB,) + (S // 2 if up else S,) * 3:
             raise ValueError("source %d has shape %s" % (i, x.shape))
         a.src[i].x, a.src[i].scale, a.src[i].shift = f(x), f(s.get("scale")), f(s.get("shift"))
-        a.src[i].C, a.src[i].up, a.src[i].act = x.shape[4], up, int(s.get("act", 0))
-        if dout is not None and want_dx:
+        a.src[i].C, a.src[i].up, a.src[i].act = int(s["C"]) if bcast else x.shape[4], up, int(s.get("act", 0))
+        a.src[i].bcast = bcast
+        if bcast:
+            dxs.append(None)           # the engines never differentiate with respect to the condition
+        elif dout is not None and want_dx:
             dxs.append(out(x.shape))
             a.src[i].dx = L.fptr(dxs[-1])
     a.w, a.bias, a.gamma, a.beta, a.dout = f(w), f(bias), f(gamma), f(beta), f(dout)
@@ -935,6 +944,57 @@ def vae_loss(mulv=None, mse_partial=(), n_elems=1.0, pm_partials=((), (), (), ()
     L.check(lib.ics_op_vae_loss(L.fptr(mulv), B, latent, dp(mse), int(mse.size), float(n_elems), dp(pm), n, per, L.fptr(w),
                                 float(alpha), float(beta), int(phase), s, L.fptr(m)))
     return np.array(list(s), np.float64) if phase == 1 else m
+
+
+def vae_latent(h, w_mean, w_lv, b_mean, b_lv, eps, cond, dzc=None, beta=3e-4, max_batch=None):
+    """Single-op entry (ics_op_vae_latent): the DFC-VAE's latent link -- the z_mean | z_log_var GEMM, sampling and, with
+    dzc (B, latent + ncond) = dLoss/d[z | cond], their backward pass with the KL gradient at weight beta.
+    h, eps (B, latent); w_mean, w_lv (latent, latent); b_mean, b_lv (latent,); cond (B, ncond).
+    Returns a dict: mulv (B, 2 latent), z, zc; with dzc also dmulv, dw_mean, dw_lv, dbias (2 latent,), dh."""
+    lib = L.load()
+    h, w_mean, w_lv, eps, cond = _f32(h), _f32(w_mean), _f32(w_lv), _f32(eps), _f32(cond)
+    B, lat = h.shape
+    nc = cond.shape[1]
+    if w_mean.shape != (lat, lat) or w_lv.shape != (lat, lat) or eps.shape != (B, lat) or cond.shape[0] != B:
+        raise ValueError("vae_latent: shapes do not fit h %s" % (h.shape,))
+    a = L.VaeLatentArgs()
+    a.B, a.max_batch, a.latent, a.ncond, a.beta = B, int(max_batch or B), lat, nc, float(beta)
+    keep = [_f32(v).reshape(lat) for v in (b_mean, b_lv)]
+    a.h, a.w_mean, a.w_lv, a.eps, a.cond = L.fptr(h), L.fptr(w_mean), L.fptr(w_lv), L.fptr(eps), L.fptr(cond)
+    a.b_mean, a.b_lv = L.fptr(keep[0]), L.fptr(keep[1])
+    r = {"mulv": np.empty((B, 2 * lat), np.float32), "z": np.empty((B, lat), np.float32),
+         "zc": np.empty((B, lat + nc), np.float32)}
+    if dzc is not None:
+        dzc = _f32(dzc)
+        if dzc.shape != (B, lat + nc):
+            raise ValueError("vae_latent: dzc has shape %s" % (dzc.shape,))
+        a.dzc = L.fptr(dzc)
+        r.update(dmulv=np.empty((B, 2 * lat), np.float32), dw_mean=np.empty((lat, lat), np.float32),
+                 dw_lv=np.empty((lat, lat), np.float32), dbias=np.empty(2 * lat, np.float32), dh=np.empty((B, lat), np.float32))
+    for k, v in r.items():
+        setattr(a, k, L.fptr(v))
+    L.check(lib.ics_op_vae_latent(C.byref(a)))
+    return r
+
+
+def sqdiff(a, b, blocks_per_sample, coef=0.0, grad=False, accumulate_into=None):
+    """Single-op entry (ics_op_sqdiff): per-sample partial sums of (a - b)^2, a and b (B, per_sample), as the VAE step takes
+    them for its squared error and perceptual terms.  Returns (partial (B, blocks_per_sample) float64, grad or None);
+    grad = coef * (b - a) (grad=True), added to accumulate_into (B, per_sample) where that is given."""
+    lib = L.load()
+    a, b = _f32(a), _f32(b)
+    B, per = a.shape
+    if b.shape != a.shape:
+        raise ValueError("sqdiff: a and b differ in shape")
+    part = np.empty((B, int(blocks_per_sample)), np.float64)
+    g = None
+    if accumulate_into is not None:
+        g = np.array(accumulate_into, np.float32, order="C").reshape(B, per)
+    elif grad:
+        g = np.empty((B, per), np.float32)
+    L.check(lib.ics_op_sqdiff(L.fptr(a), L.fptr(b), B, per, int(blocks_per_sample), float(coef),
+                              1 if accumulate_into is not None else 0, L.fptr(g), L.f64ptr(part)))
+    return part, g
 
 
 def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False,

@@ -682,7 +682,11 @@ int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int 
  *   o     = post_act(y * scale + shift), scale = gamma * rstd, shift = beta - mean * scale   (has_bn; batch statistics)
  *   dout  = gradient w.r.t. o (has_bn = 0: w.r.t. y), optional: without it only the forward pass runs
  *
- * Activations: 0 none, 1 ReLU, 2 LeakyReLU(0.3).  The broadcast / condition-fold source is not served.
+ * Activations: 0 none, 1 ReLU, 2 LeakyReLU(0.3).
+ * A condition source (src[1].bcast > 0) is the VAE encoder's Reshape -> K.tile -> Concatenate: spatially constant channels
+ * behind the x channels.  The layer is then built as vae_build builds e0 -- whether the condition fold serves it (one x
+ * channel, 16 or 32 filters, neither ICSG3D_NO_COND_FOLD nor ICSG3D_NO_THIN_C) is decided by the engine's own predicate,
+ * every other configuration goes through the broadcast loader or the materialised padded input.
  * The ICSG3D_NO_* switches are read when the call builds its handle, as for every handle.  With ICSG3D_DEBUG_CANARY=1 the
  * call checks the guard bytes behind every buffer of the handle and fails, naming the buffers, if any was written to. */
 typedef struct ics_conv_layer_src {
@@ -690,6 +694,10 @@ typedef struct ics_conv_layer_src {
   const float* scale; /* [C] per-channel affine, or NULL (then shift is NULL too)                        */
   const float* shift;
   int C, up, act;
+  int bcast;          /* > 0: a spatially constant source.  x is [B][bcast], C the number of channels it stands for
+                         (C = bcast * channels of src[0]) and channel c has the value x[b][c % bcast].  Only as the last
+                         of two sources, in a 3x3x3 layer, without affine, activation, up -- and without dx: the engines
+                         never differentiate with respect to the condition, the call refuses it                    */
   float* dx;          /* out, optional (needs dout): gradient w.r.t. act(x * scale + shift), shaped as x */
 } ics_conv_layer_src;
 typedef struct ics_conv_layer {
@@ -806,6 +814,34 @@ int ics_op_unet_metrics_from_sums(const double sums[7], float metrics[5]);
 int ics_op_vae_loss(const float* mulv, int B, int latent, const double* mse_partial, int n_mse, double n_elems,
                     const double* pm_partial, const int pm_n[4], const double pm_per[4], const float pm_w[4], float alpha,
                     float beta, int phase, double sums[5], float metrics[4]);
+/* The DFC-VAE's latent link on given inputs (kernel parity tests, tests/test_gpu_vae_latent.py): a temporary handle that
+ * holds the z_mean | z_log_var GEMM (one N = 2 * latent layer over two reference kernels) and the latent buffers, built,
+ * packed and run by the functions the engine's own encoder pass and train step call.
+ *   mulv = h [w_mean | w_lv] + [b_mean | b_lv];  (mu | lv) = mulv;  z = mu + exp(lv / 2) eps;  zc = [z | cond]
+ *   with dzc = dLoss/dzc (only its first `latent` columns are read) and KLD = mean_b(-1/2 sum_j(1 + lv - mu^2 - exp(lv))):
+ *   dmulv = (dz + beta mu / B | dz eps exp(lv / 2) / 2 - beta (1 - exp(lv)) / (2 B)), dw_mean = h^T dmulv[:, :latent],
+ *   dw_lv = h^T dmulv[:, latent:], dbias = column sums of dmulv, dh = dmulv [w_mean | w_lv]^T.
+ * dzc = NULL: the forward pass only.  Every output is optional.  ICSG3D_DEBUG_CANARY as in ics_op_conv_layer. */
+typedef struct ics_vae_latent {
+  int B, max_batch;   /* the step runs B <= max_batch samples; the handle is sized for max_batch                      */
+  int latent, ncond;
+  float beta;
+  const float* h;     /* [B][latent]: the encoder's dense output                                                    */
+  const float *w_mean, *w_lv;           /* [latent][latent] each                                                      */
+  const float *b_mean, *b_lv;           /* [latent] each, optional (zeros)                                            */
+  const float* eps;   /* [B][latent]                                                                                  */
+  const float* cond;  /* [B][ncond]                                                                                   */
+  const float* dzc;   /* [B][latent + ncond], or NULL                                                                 */
+  float *mulv, *z, *zc;                 /* out: [B][2 latent], [B][latent], [B][latent + ncond]                       */
+  float *dmulv, *dw_mean, *dw_lv, *dbias, *dh; /* out (need dzc): [B][2 latent], [latent][latent] x 2, [2 latent], [B][latent] */
+} ics_vae_latent;
+int ics_op_vae_latent(ics_vae_latent* a);
+/* The per-sample squared-error partial sums that feed mse_partial / pm_partial of ics_op_vae_loss, as the VAE step launches
+ * them: a, b [B][per_sample]; partial_out [B][blocks_per_sample] = sums of (a - b)^2 over the blocks' chunks (a sample is cut
+ * into blocks_per_sample chunks, rounded up to a multiple of 4 elements), accumulated in fp64.  grad_in_out [B][per_sample],
+ * optional: coef * (b - a), written (accumulate = 0) or added to what it holds (accumulate = 1). */
+int ics_op_sqdiff(const float* a, const float* b, int B, size_t per_sample, int blocks_per_sample, float coef, int accumulate,
+                  float* grad_in_out, double* partial_out);
 /* kernel micro-benchmark on device-resident constant data, HIP-event timed: mode 0 forward
  * (ablate 0 = full kernel, 1 = MFMA+LDS reads only, 2 = MFMA only), 1 backward-data, 2 backward-weight. */
 int ics_op_conv3d_bench(int B, int S, int Cin, int Cout, int taps, int mode, int ablate, int iters,

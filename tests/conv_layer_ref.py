@@ -74,9 +74,24 @@ def border_mask(S):
     return e[:, None, None] | e[None, :, None] | e[None, None, :]
 
 
+def materialised_condition(cond, C, shape, dtype=np.float64):
+    """The VAE encoder's Reshape -> K.tile -> Concatenate (lattice_vae.py:167-169; numpy_ref.VaeOracle.tile_cond): cond
+    (B, ncond) becomes C spatially constant channels, channel c = cond[b][c % ncond] -- np.tile, NOT np.repeat (the two
+    differ as soon as C > ncond, i.e. with more than one x channel).  shape: (B, S, S, S) of the layer's input."""
+    cond = np.asarray(cond, dtype)
+    B, ncond = cond.shape
+    assert C % ncond == 0 and shape[0] == B
+    return np.broadcast_to(np.tile(cond, (1, C // ncond))[:, None, None, None, :], tuple(shape) + (C,)).copy()
+
+
 def virtual_input(sources, dtype=np.float64):
+    """A condition source ("bcast": ncond, "C", "x": (B, ncond)) is materialised: the reference of such a layer IS the plain
+    reference applied to [x | tile(cond) broadcast over space], nothing cleverer."""
     parts = []
     for s in sources:
+        if s.get("bcast"):
+            parts.append(materialised_condition(s["x"], int(s["C"]), parts[0].shape[:4], dtype))
+            continue
         v = np.asarray(s["x"], dtype)
         if s.get("scale") is not None:
             v = v * np.asarray(s["scale"], dtype) + np.asarray(s["shift"], dtype)
@@ -193,10 +208,45 @@ def layer_backward(f, sources, w, gamma, dout, pre_act=0, has_bn=True, post_act=
     dV, out["dw"], out["dbias"] = R.conv3d_bwd(f["V"], w, dy)
     out["dx"], c0 = [], 0
     for s in sources:
+        if s.get("bcast"):               # no gradient w.r.t. the condition: the engines never take it
+            out["dx"].append(None)
+            continue
         C = np.asarray(s["x"]).shape[-1]
         g = dV[..., c0:c0 + C]
         out["dx"].append(R.upsample_bwd(g) if s.get("up") else g)
         c0 += C
+    return out
+
+
+def dw_row_groups(dw, C):
+    """The row groups of a condition layer's kernel gradient (k, k, k, Cin, Cout) -- they come from different kernels (the x
+    rows [0, C) from a stencil or GEMM reduction, the condition rows [C, Cin) from region sums of dy) and differ in scale
+    by the ratio |cond| / |x|; inside the condition rows the centre tap is the only one whose sum is total - border alone."""
+    dw = np.asarray(dw)
+    k = dw.shape[0] // 2
+    other = np.ones(dw.shape[:3], bool)
+    other[k, k, k] = False
+    return {"dw_x": dw[..., :C, :], "dw_cond": dw[..., C:, :], "dw_cond_centre": dw[k, k, k, C:, :],
+            "dw_cond_other": dw[other][:, C:, :]}
+
+
+def row_group_errors(got_dw, ref_dw, sources, kw, linear=False):
+    """name -> error of each row group of got_dw, relative to the largest entry of the same group of ref_dw.
+    One exception, decided from the inputs alone: behind a batch-statistics BatchNorm that follows the convolution directly
+    (no pre-activation, or a ReLU the reference finds open everywhere) dy sums to zero per channel over the batch, and the
+    centre tap -- valid for every voxel -- multiplies each condition by that sum's per-sample parts: when every sample has
+    the SAME condition its gradient is exactly zero and the reference holds rounding noise there.  It is then measured on
+    the scale of the condition rows (as the bias gradient of such a layer is measured on the kernel gradient's)."""
+    C = np.asarray(sources[0]["x"]).shape[-1]
+    cond = np.asarray(sources[1]["x"])
+    zero_centre = bool(kw["has_bn"]) and (not kw["pre_act"] or linear) and bool((cond == cond[0]).all())
+    g, r = dw_row_groups(got_dw, C), dw_row_groups(ref_dw, C)
+    out = {}
+    for k in r:
+        scale = np.abs(r[k]).max()
+        if k == "dw_cond_centre" and zero_centre:
+            scale = max(scale, np.abs(r["dw_cond"]).max())
+        out[k] = float(np.abs(np.asarray(g[k], np.float64) - r[k]).max() / max(scale, 1e-300))
     return out
 
 
@@ -378,17 +428,38 @@ def check_bn_affine(name, stored, scale, shift, gamma, beta):
 
 
 # ---- the inputs of a case, shared by the host and the GPU tests
-def make_case(B, S, src_spec, Cout, taps=27, form="unet", aff=True, seed=0, regime_off=None):
-    """src_spec: [(C, up), ...].  form "unet": ReLU, BN, none; sources affine, no activation.  "vae": none, BN,
+COND_REGIMES = ("same", "zero_sample", "huge")
+
+
+def make_case(B, S, src_spec, Cout, taps=27, form="unet", aff=True, seed=0, regime_off=None, cond_regime=None,
+              dout_mean=None):
+    """src_spec: [(C, up), ...], the last of two possibly (C, 0, ncond): a condition source (virtual_input), always plain.
+    form "unet": ReLU, BN, none; sources affine, no activation.  "vae": none, BN,
     LeakyReLU; sources affine + LeakyReLU.  "plain": no BatchNorm, plain sources, no activation.
     Source affines have scale in [0.5, 1.5] and |shift| in [0.5, 1] in every channel (a loader that pads before the affine
     is then wrong by act(shift) * sum of the border taps).  regime_off: None = ordinary values (bias ~ N(0, 1)); an int or a
-    regime's name: see regime_of."""
+    regime's name: see regime_of.
+    cond_regime (condition N(0, 1) otherwise): "same" every sample the same condition; "zero_sample" the last sample's all
+    zero; "huge" conditions of magnitude 1e3 next to x of magnitude 1.  dout_mean: added to dout per channel, +-dout_mean
+    (1 + 0.1 N(0, 1)) -- with has_bn = 0 dout is dy and its per-sample totals then do not cancel."""
     rng = np.random.default_rng(1000 + seed)
     k = 3 if taps == 27 else 1
-    Cin = sum(c for c, _ in src_spec)
+    Cin = sum(sp[0] for sp in src_spec)
     sources = []
-    for C, up in src_spec:
+    for sp in src_spec:
+        C, up = sp[0], sp[1]
+        if len(sp) > 2 and sp[2]:
+            cond = rng.standard_normal((B, sp[2])).astype(np.float32)
+            if cond_regime == "same":
+                cond[:] = cond[0]
+            elif cond_regime == "zero_sample":
+                cond[-1] = 0
+            elif cond_regime == "huge":
+                cond = (1e3 * rng.choice([-1.0, 1.0], cond.shape) * rng.uniform(0.5, 1.5, cond.shape)).astype(np.float32)
+            else:
+                assert cond_regime is None
+            sources.append({"x": cond, "bcast": int(sp[2]), "C": int(C), "up": 0, "act": 0})
+            continue
         s = S // 2 if up else S
         d = {"x": rng.standard_normal((B, s, s, s, C)).astype(np.float32), "up": int(up), "act": 0}
         if aff and form != "plain":
@@ -404,4 +475,17 @@ def make_case(B, S, src_spec, Cout, taps=27, form="unet", aff=True, seed=0, regi
     gamma = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
     beta = rng.uniform(-0.5, 0.5, Cout).astype(np.float32)
     dout = rng.standard_normal((B, S, S, S, Cout)).astype(np.float32)
+    if dout_mean is not None:
+        dout += (dout_mean * rng.choice([-1.0, 1.0], Cout) * (1 + 0.1 * rng.standard_normal(Cout))).astype(np.float32)
     return {"sources": sources, "w": w, "bias": bias, "gamma": gamma, "beta": beta, "dout": dout, "kw": kw}
+
+
+# ---- the condition cases of tests/test_gpu_conv_layer.py, here so that tests/test_conv_layer_host.py checks the reference
+# alone on the same inputs: (B, S, [(C, 0), (C * ncond, 0, ncond)], Cout)
+def _cond(B, S, C, ncond, Cout):
+    return (B, S, ((C, 0), (C * ncond, 0, ncond)), Cout)
+
+
+COND_FOLD_CASES = (_cond(2, 4, 1, 10, 16), _cond(3, 8, 1, 10, 16), _cond(5, 8, 1, 3, 32), _cond(2, 16, 1, 10, 16),
+                   _cond(2, 8, 1, 1, 16), _cond(2, 8, 1, 7, 32))
+COND_BCAST_CASES = (_cond(2, 8, 4, 10, 16), _cond(3, 4, 4, 3, 16), _cond(2, 8, 4, 1, 12))

@@ -176,3 +176,110 @@ def test_a_named_regime_fills_every_channel():
         assert (ratio > 15).all() and (ratio < 100).all(), ratio       # bias 30, conv part of std 0.45 .. 1.5 (LeakyReLU sources: less)
         assert form == "vae" or (f["y"] > 0).all()
         assert int((np.abs(f["bn"]) < 1e-4).sum()) < 8
+
+
+# ---- condition sources (the VAE's e0): the reference is the plain one on the materialised input; the fold's formulas are
+# written out here, and only here, to show on the CPU that the fold is an exact reassociation of that convolution
+def _valid(t, c):
+    """tap offset t - 1 from a voxel of class c (0 first plane, 1 interior, 2 last plane) stays inside the grid"""
+    return not ((t == 0 and c == 0) or (t == 2 and c == 2))
+
+
+def fold_forward(x, cond, w, bias):
+    """cond_bias_table_kernel + the pos_bias epilogue: the convolution of the x channels alone plus a bias that depends on
+    the sample and on the voxel's border class (first / interior / last plane per axis: 27 classes)"""
+    B, S, C = x.shape[0], x.shape[1], x.shape[-1]
+    ncond, Cout = cond.shape[1], w.shape[-1]
+    nfold = w.shape[3] - C
+    cv = np.tile(cond, (1, nfold // ncond))                                  # (B, nfold): channel j = cond[b][j % ncond]
+    y = R.conv3d_fwd(x, w[..., :C, :], np.zeros(Cout))
+    cls = np.where(np.arange(S) == 0, 0, np.where(np.arange(S) == S - 1, 2, 1))
+    T = np.zeros((B, 3, 3, 3, Cout)) + bias
+    for cz, cy, cx, tz, ty, tx in np.ndindex(3, 3, 3, 3, 3, 3):
+        if _valid(tz, cz) and _valid(ty, cy) and _valid(tx, cx):
+            T[:, cz, cy, cx] += cv @ w[tz, ty, tx, C:, :]
+    return y + T[:, cls[:, None, None], cls[None, :, None], cls[None, None, :]]
+
+
+def fold_dw_cond(dy, cond, nfold):
+    """sample_colsum / border_region_sums / cond_wgrad_kernel: the 26 border regions of dy summed directly, the interior one
+    as total - border, D[b][tap] = the sum of the regions the tap is valid for, dw[tap][C + j] = sum_b cond[b][j % ncond] D"""
+    B, S, Cout = dy.shape[0], dy.shape[1], dy.shape[-1]
+    sl = lambda c: slice(0, 1) if c == 0 else (slice(1, S - 1) if c == 1 else slice(S - 1, S))
+    Rg = np.zeros((B, 3, 3, 3, Cout))
+    for cz, cy, cx in np.ndindex(3, 3, 3):
+        if (cz, cy, cx) != (1, 1, 1):
+            Rg[:, cz, cy, cx] = dy[:, sl(cz), sl(cy), sl(cx)].sum((1, 2, 3))
+    Rg[:, 1, 1, 1] = dy.sum((1, 2, 3)) - Rg.sum((1, 2, 3))
+    cv = np.tile(cond, (1, nfold // cond.shape[1]))
+    dw = np.zeros((3, 3, 3, nfold, Cout))
+    for tz, ty, tx in np.ndindex(3, 3, 3):
+        D = sum(Rg[:, cz, cy, cx] for cz, cy, cx in np.ndindex(3, 3, 3) if _valid(tz, cz) and _valid(ty, cy) and _valid(tx, cx))
+        dw[tz, ty, tx] = cv.T @ D
+    return dw
+
+
+@pytest.mark.parametrize("S", (4, 8))
+@pytest.mark.parametrize("C,ncond", ((1, 1), (1, 3), (1, 10), (3, 1)))
+def test_condition_fold_is_an_exact_reassociation(S, C, ncond):
+    """fp64, forward and dw, S = 4 and 8, C * ncond in {1, 3, 10} (and 3 = 3 x channels x 1): the fold's formulas equal the
+    convolution over the materialised input to rounding.  dy has a per-channel mean of ~1: the totals do not cancel."""
+    rng = np.random.default_rng(10 * S + C + ncond)
+    B, Cout, nfold = 3, 5, C * ncond
+    x, cond = rng.standard_normal((B, S, S, S, C)), rng.standard_normal((B, ncond))
+    w, bias = rng.standard_normal((3, 3, 3, C + nfold, Cout)), rng.standard_normal(Cout)
+    dy = rng.standard_normal((B, S, S, S, Cout)) + 1.0
+    src = [{"x": x}, {"x": cond, "bcast": ncond, "C": nfold}]
+    f = CR.layer_forward(src, w, bias, has_bn=False)
+    assert f["V"].shape == (B, S, S, S, C + nfold)
+    assert _rel(fold_forward(x, cond, w, bias), f["y"]) <= TOL
+    b = CR.layer_backward(f, src, w, None, dy, has_bn=False)
+    assert b["dx"][1] is None and b["dx"][0].shape == x.shape
+    assert _rel(fold_dw_cond(dy, cond, nfold), b["dw"][..., C:, :]) <= TOL
+    g = CR.dw_row_groups(b["dw"], C)
+    assert g["dw_x"].shape == (3, 3, 3, C, Cout) and g["dw_cond_other"].shape == (26, nfold, Cout)
+    assert np.array_equal(g["dw_cond_centre"], b["dw"][1, 1, 1, C:, :])
+
+
+def test_condition_channels_are_tiled_not_repeated():
+    """at C = 4 np.tile and np.repeat differ; the reference's channel order is numpy_ref.VaeOracle's own e0 input"""
+    rng = np.random.default_rng(11)
+    B, d, C, ncond = 2, 4, 4, 3
+    v = R.VaeOracle(None, in_ch=C, cond=ncond, d=16)
+    cond = rng.standard_normal((B, ncond))
+    x = rng.standard_normal((B, d, d, d, C))
+    V = CR.virtual_input([{"x": x}, {"x": cond, "bcast": ncond, "C": C * ncond}])
+    want = np.concatenate([x, v.tile_cond(cond, d)], -1)
+    assert np.array_equal(V, want)
+    rep = np.broadcast_to(np.repeat(cond, C, axis=1)[:, None, None, None, :], (B, d, d, d, C * ncond))
+    assert not np.array_equal(V[..., C:], rep)
+    for c in range(C * ncond):
+        assert np.array_equal(V[:, 1, 2, 3, C + c], cond[:, c % ncond])
+
+
+def _cond_variants():
+    out = []
+    for name, cases in (("cond_fold", CR.COND_FOLD_CASES), ("cond_bcast", CR.COND_BCAST_CASES)):
+        for i, c in enumerate(cases):
+            out += [(name, i, c, form, None) for form in ("unet", "vae")]
+        out += [(name, 1, cases[1], form, reg) for form in ("unet", "vae") for reg in CR.COND_REGIMES]
+    return out
+
+
+@pytest.mark.parametrize("name,idx,case,form,regime", _cond_variants(), ids=lambda v: str(v) if not isinstance(v, tuple) else "c")
+def test_condition_cases_pin_few_decisions_and_have_a_yardstick(name, idx, case, form, regime):
+    """every condition case of test_gpu_conv_layer.py (seeds as there), the reference alone: the float32 evaluation's
+    activation decisions differ from the fp64 reference's at no more than 8 voxels per tensor -- the cap the GPU test puts
+    on pinned decisions -- and its gradients (with the fp64 decisions: rounding alone) are finite, non-zero yardsticks."""
+    B, S, src, Cout = case
+    seed = {"cond_fold": 90, "cond_bcast": 100}[name] + idx
+    c = CR.make_case(B, S, src, Cout, 27, form, False, seed, cond_regime=regime)
+    args = (c["sources"], c["w"], c["bias"], c["gamma"], c["beta"])
+    f64 = CR.layer_forward(*args, **c["kw"])
+    f32 = CR.layer_forward(*args, dtype=np.float32, **c["kw"])
+    pins = CR.layer_backward(f64, c["sources"], c["w"], c["gamma"], c["dout"], kink_y=f32["y"], kink_bn=f32["bn"], **c["kw"])
+    assert pins["pinned"] <= 8, pins["pinned"]
+    b64 = CR.layer_backward(f64, c["sources"], c["w"], c["gamma"], c["dout"], **c["kw"])
+    b32 = CR.layer_backward(f32, c["sources"], c["w"], c["gamma"], c["dout"], kink_y=f64["y"], kink_bn=f64["bn"], **c["kw"])
+    for k, e in CR.row_group_errors(b32["dw"], b64["dw"], c["sources"], c["kw"]).items():
+        assert np.isfinite(e) and 0 < e < 1e-3, (k, e)

@@ -8,8 +8,9 @@ returns, so a dispatch change cannot turn it into a test of another kernel.
 path -> cases (B, S, sources -> Cout) -> kernel ids: the PATHS table below (DESIGN.md section 21 has the same list).
 Deviations from the planned table, each because the path's own predicate decides otherwise:
   * thin-C serves PLAIN single-channel sources only (conv_thin_c_ok refuses an affine): its cases run with plain sources,
-    as U-Net c1 / VAE e0 see their input; the pad_input case (2, 8, 4 -> 32) is served by conv_fwd_kernel's thin loader --
-    the 4-channel stencil is reached through the condition fold only, which this op leaves out.
+    as U-Net c1 / VAE e0 see their input; the pad_input case (2, 8, 4 -> 32) is served by conv_fwd_kernel's thin loader.
+    The condition fold, which puts the K.tile'd condition of VAE e0 through the same stencil, has the paths cond_fold /
+    cond_bcast below.
   * split-K forward: the smallest S <= 4 geometry whose training plan splits K is (3, 4, 128 -> 40) (64 x 64 tile needs
     Npad % 64 == 0, conv_winog takes Cout % 64 == 0): 12 splits.  The kernel id is conv_fwd_kernel with and without the
     split; the case asserts that ICSG3D_NO_FWD_SPLITK changes the bits of y.
@@ -79,7 +80,29 @@ Mutations tried in a scratch copy of conv_wino64.hip, run against the wino64 and
     test_statistics_in_every_value_regime[thin_n-2-*] with var + eps off by 3.2e-5 / 1.2e-4 already at mean/std = 30
     (bound 1e-5; the launch in front of the mean/std = 1000 one) and test_gradients_at_mean_over_std_30[thin_n-2-*] with
     3.2e-5 / 2.8e-5 -- and the 23 others pass.
-Run time of this file on the MI355X machine: 6.0 s (172 tests; the fp64 references take 5 s of it on the host)."""
+Condition sources (VAE e0: x | K.tile'd condition, a source dict with "bcast"; the reference is conv_layer_ref's plain one on
+the materialised input, np.tile order): path cond_fold -- one x channel, 16 / 32 filters, (2, 4, 1+10 -> 16), (3, 8, 1+10 -> 16),
+(5, 8, 1+3 -> 32), (2, 16, 1+10 -> 16), (2, 8, 1+1 -> 16), (2, 8, 1+7 -> 32) -- asserts "cond_bias_table_kernel +
+conv_thin_c_fwd_kernel<1, N>" and "conv_thin_c_wgrad_kernel<N> + cond_wgrad_kernel" (the fold's two launch sites name both of
+their kernels), and under ICSG3D_NO_COND_FOLD / _NO_THIN_C conv_fwd_kernel / conv_wgrad_kernel with y AND dw required to
+differ in bits from the fold's; path cond_bcast -- four x channels, (2, 8, 4+40 -> 16) through the materialised input,
+(3, 4, 4+12 -> 16) and (2, 8, 4+4 -> 12) through the loader's broadcast branch.  On top of every check above: dw per row group
+(x rows | condition rows | their centre tap | their 26 other taps), each on its own scale at max(1e-5, 2 e32) (rule for the one
+group that can be exactly zero: conv_layer_ref.row_group_errors); test_condition_regimes (same condition in every sample, one
+sample's all zero, conditions of 1e3) on each of the four routes; test_condition_without_batchnorm (has_bn = 0, mean(dy) ~ 1).
+  Measured, worst over the condition cases (engine | e32): dw_x 1.11e-6 (5.1e-7), dw_cond 2.14e-6 (8.1e-6), centre tap
+  3.55e-6 (1.3e-5), other taps 1.85e-6 (7.9e-6) | max(1e-5, 2 e32); 0 pinned decisions in every condition case.
+  Mutations, each one line in a scratch copy, run against the 71 condition tests and against test_gpu_vae.py:
+  (a) cond_bias_table_kernel with the first and last class swapped on x: 31 fail, first at the border check of y with 0.35 ..
+      0.59 (bound 1e-5) -- every cond_fold test on the fold route; the switched routes and cond_bcast pass.
+  (b) cond_wgrad_kernel's interior as `tot` without `- border`: 29 fail with dw off by 0.62 .. 0.82 -- every backward test on
+      the fold route (the two forward-only regime tests pass).
+  (c) the loader's `cl % bcast` as `cl / C`: 19 fail, y border off by 0.41 .. 0.98 -- all of cond_bcast; cond_fold passes
+      even under its switches (with one x channel the two orders coincide), which is why the C = 4 path is there.
+  The whole-step test would have caught each of them too: test_gpu_vae.py fails under (a) ("activation signs of e0 differ",
+  6182 .. 12990 elements, C = 1), (b) (e0/kernel off by 0.44 .. 0.59, C = 1) and (c) (activation signs, C = 4 only).  What
+  the cases here add is the route (which kernel, which row group), shapes down to S = 4 and the regimes no step reaches.
+Run time of this file on the MI355X machine: 9.6 s (243 tests; the fp64 references take most of it on the host)."""
 import contextlib
 import functools
 import os
@@ -121,7 +144,8 @@ def UP3(stats, tile=r"\d"):
 
 
 def case(B, S, src, Cout, taps=27, pad=False, aff=True, env=()):
-    """env: switches the case always runs under (they route it to the kernel the path is about)"""
+    """env: switches the case always runs under (they route it to the kernel the path is about).  src: (C, up) per source;
+    (C, 0, ncond) is a condition source (conv_layer_ref.make_case)"""
     return {"B": B, "S": S, "src": tuple(src), "Cout": Cout, "taps": taps, "pad": pad, "aff": aff, "env": tuple(env)}
 
 
@@ -190,7 +214,22 @@ PATHS = {
              "ICSG3D_NO_UP3": K([IG, W64F], None, [WW, IGW]), "ICSG3D_NO_UPSPLIT": K([IG], None, ["conv_wgrad"])}),
     "up_only": dict(
         cases=UP_ONLY_CASES, ids_fn=_up_only_ids, env=("ICSG3D_NO_UP3N", "ICSG3D_NO_UPSPLIT"), regimes=(0, 2)),
+    # the VAE's e0: x | K.tile'd condition, padded input, plain sources.  One x channel and 16 / 32 filters: the fold
+    # (cond_bias_table_kernel + the stencil's pos_bias epilogue; the stencil reduction + sample_colsum / border_region_sums /
+    # cond_wgrad_kernel in ONE launch site); with either switch the same layers through the implicit-GEMM kernels -- the
+    # materialised padded input (1 + 10 -> 16, 1 + 1 -> 4 channels) or the loader's broadcast branch (1 + 3, 1 + 7: no padding)
+    "cond_fold": dict(
+        cases=[case(B, S, src, Cout, pad=True, aff=False) for B, S, src, Cout in CR.COND_FOLD_CASES],
+        ids=K(["cond_bias_table_kernel + conv_thin_c_fwd_kernel<1, "], None,
+              [re.compile(r"conv_thin_c_wgrad_kernel<\d+>.* \+ .*cond_wgrad_kernel")]),
+        env={"ICSG3D_NO_COND_FOLD": K([IG], None, [IGW]), "ICSG3D_NO_THIN_C": K([IG], None, [IGW])},
+        must_differ=("ICSG3D_NO_COND_FOLD", "ICSG3D_NO_THIN_C"), differ_dw=True),
+    # four x channels: never folded.  4 + 40 -> 64 materialised, 4 + 12 = 16 and 4 + 4 = 8 through the broadcast branch
+    "cond_bcast": dict(
+        cases=[case(B, S, src, Cout, pad=True, aff=False) for B, S, src, Cout in CR.COND_BCAST_CASES],
+        ids=K([IG], None, [IGW]), env={}),
 }
+COND_PATHS = ("cond_fold", "cond_bcast")
 ORDER = tuple(PATHS)
 ALL = [(p, i) for p, d in PATHS.items() for i in range(len(d["cases"]))]
 
@@ -247,11 +286,18 @@ def _well_conditioned(d):
     return True
 
 
+def _variant_kw(variant):
+    """variant: None, a condition regime of conv_layer_ref.COND_REGIMES, or "dy_mean1" (dout with a per-channel mean of ~1)"""
+    if variant is None:
+        return {}
+    return {"dout_mean": 1.0} if variant == "dy_mean1" else {"cond_regime": variant}
+
+
 @functools.lru_cache(maxsize=None)
-def _data(path, idx, form, regime_off=None):
+def _data(path, idx, form, regime_off=None, variant=None):
     c = _case(path, idx)
     seed = ORDER.index(path) * 10 + (9 if idx == "big" else idx)
-    d = CR.make_case(c["B"], c["S"], c["src"], c["Cout"], c["taps"], form, c["aff"], seed, regime_off)
+    d = CR.make_case(c["B"], c["S"], c["src"], c["Cout"], c["taps"], form, c["aff"], seed, regime_off, **_variant_kw(variant))
     while c["Cout"] <= 4 and form != "plain" and regime_off in (None, "ratio30") and not _well_conditioned(d):
         seed += 100
         d = CR.make_case(c["B"], c["S"], c["src"], c["Cout"], c["taps"], form, c["aff"], seed, regime_off)
@@ -259,9 +305,9 @@ def _data(path, idx, form, regime_off=None):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(path, idx, form, regime_off=None):
+def _reference(path, idx, form, regime_off=None, variant=None):
     """fp64 forward and backward (own decisions) and e32 per tensor, computed once per case, form and regime"""
-    d = _data(path, idx, form, regime_off)
+    d = _data(path, idx, form, regime_off, variant)
     args = (d["sources"], d["w"], d["bias"], d["gamma"], d["beta"])
     f64 = CR.layer_forward(*args, **d["kw"])
     b64 = CR.layer_backward(f64, d["sources"], d["w"], d["gamma"], d["dout"], **d["kw"])
@@ -272,7 +318,10 @@ def _reference(path, idx, form, regime_off=None):
     linear = bool(d["kw"]["pre_act"]) and bool((f64["y"] > 0).all())
     e32 = {k: _rel_grad(k, b32, b64, d["kw"], linear) for k in b64 if k not in ("dx", "pinned")}
     for i in range(len(b64["dx"])):
-        e32["dx%d" % i] = _rel(b32["dx"][i], b64["dx"][i])
+        if b64["dx"][i] is not None:
+            e32["dx%d" % i] = _rel(b32["dx"][i], b64["dx"][i])
+    if path in COND_PATHS:
+        e32.update(CR.row_group_errors(b32["dw"], b64["dw"], d["sources"], d["kw"], linear))
     return f64, b64, e32, linear
 
 
@@ -289,10 +338,10 @@ def _env(names):
             del os.environ[n]
 
 
-def _run(path, idx, form, max_batch=None, regime_off=None, backward=True):
+def _run(path, idx, form, max_batch=None, regime_off=None, backward=True, variant=None):
     from icsg3d_amd import engine as E
     c = _case(path, idx)
-    d = _data(path, idx, form, regime_off)
+    d = _data(path, idx, form, regime_off, variant)
     with _env(c["env"]):
         return E.conv_layer(d["sources"], d["w"], d["bias"], d["gamma"], d["beta"], dout=d["dout"] if backward else None,
                             pad_input=c["pad"], max_batch=max_batch, **d["kw"])
@@ -393,7 +442,11 @@ def _check_grads(r, d, ref, what):
     print("  %s: %d pinned activation decisions" % (what, pinned))
     assert pinned <= 8, (what, pinned)
     pairs = [(k, _rel_grad(k, r, b, kw, linear)) for k in ("dw", "dbias", "dgamma", "dbeta") if k in b]
-    pairs += [("dx%d" % i, _rel(r["dx"][i], b["dx"][i])) for i in range(len(b["dx"]))]
+    pairs += [("dx%d" % i, _rel(r["dx"][i], b["dx"][i])) for i in range(len(b["dx"])) if b["dx"][i] is not None]
+    if len(d["sources"]) == 2 and d["sources"][1].get("bcast"):
+        # the x rows and the condition rows come from different kernels and differ in scale: each on its own, and inside
+        # the condition rows the centre tap (the whole-sample totals) apart from the 26 others
+        pairs += sorted(CR.row_group_errors(r["dw"], b["dw"], d["sources"], kw, linear).items())
     for k, e in pairs:
         lim = max(TOL, 2 * e32[k])
         print("  %s %-6s engine %.3g  e32 %.3g" % (what, k, e, e32[k]))
@@ -401,11 +454,11 @@ def _check_grads(r, d, ref, what):
         assert e <= lim, (what, k, e, e32[k])
 
 
-def _full(path, idx, form, ids, what, max_batch=None, regime_off=None):
+def _full(path, idx, form, ids, what, max_batch=None, regime_off=None, variant=None):
     c = _case(path, idx)
-    d = _data(path, idx, form, regime_off)
-    ref = _reference(path, idx, form, regime_off)
-    r = _run(path, idx, form, max_batch=max_batch, regime_off=regime_off)
+    d = _data(path, idx, form, regime_off, variant)
+    ref = _reference(path, idx, form, regime_off, variant)
+    r = _run(path, idx, form, max_batch=max_batch, regime_off=regime_off, variant=variant)
     _check_ids(r["kernels"], ids, what)
     _check_y(r, ref[0], c["S"], what)
     _check_stats(r, d, what, regime_off=regime_off)
@@ -448,6 +501,8 @@ def test_layer_under_switch(path, env, form, monkeypatch):
         monkeypatch.delenv(env)
         if base is not None:
             assert not np.array_equal(base["y"], r["y"]), (path, env, "the switch did not change the summation")
+            if PATHS[path].get("differ_dw"):
+                assert not np.array_equal(base["dw"], r["dw"]), (path, env, "the switch did not change backward-weight")
 
 
 @pytest.mark.parametrize("path,idx", ALL, ids=lambda v: str(v))
@@ -468,8 +523,8 @@ def test_plain_form_equals_single_op_entry_points(path, idx, monkeypatch):
     b64 = CR.layer_backward(f64, d["sources"], d["w"], None, d["dout"], **d["kw"])
     assert _rel(r["dw"], b64["dw"]) <= TOL and _rel(r["dbias"], b64["dbias"]) <= TOL
     for got, want in zip(r["dx"], b64["dx"]):
-        assert _rel(got, want) <= TOL
-    if any(up for _, up in c["src"]):
+        assert want is None or _rel(got, want) <= TOL
+    if any(s[1] for s in c["src"]) or path in COND_PATHS:     # (a condition source has no counterpart there either)
         return
     x = d["sources"][0]["x"]
     with _env(c["env"]):
@@ -521,6 +576,41 @@ def test_gradients_at_mean_over_std_30(path, idx, form):
     c1 / c2 sums of BatchNorm backward, dgamma / dbeta and the inputs of backward-weight cancel there.  Same bounds, same
     pinned decisions and e32 as in the ordinary regime; behind the U-Net form's ReLU every voxel is open."""
     _full(path, idx, form, _ids(path, idx), "%s[%d] mean/std 30 %s" % (path, idx, form), regime_off="ratio30")
+
+
+# ---- condition sources: the regimes only they have.  One case per route: the B = 3 one of each path
+COND_ROUTES = [("cond_fold", None), ("cond_fold", "ICSG3D_NO_COND_FOLD"), ("cond_fold", "ICSG3D_NO_THIN_C"), ("cond_bcast", None)]
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("regime", CR.COND_REGIMES)
+@pytest.mark.parametrize("path,env", COND_ROUTES, ids=lambda v: str(v))
+def test_condition_regimes(path, env, regime, form, monkeypatch):
+    """every sample the same condition (behind BatchNorm the centre tap's condition rows are then exactly zero: see
+    conv_layer_ref.row_group_errors), one sample's condition all zero, conditions of 1e3 next to x of 1 (y nearly constant per
+    sample and border class: the mean >> std statistics bounds apply unchanged; the condition rows of dw are 1e3 x the x
+    rows, which only the per-group comparison sees).  Every check of the file, ids included."""
+    if env:
+        monkeypatch.setenv(env, "1")
+    idx = _big_idx(path)
+    _full(path, idx, form, _ids(path, idx, env), "%s[%d] %s cond %s %s" % (path, idx, env, regime, form), variant=regime)
+
+
+@pytest.mark.parametrize("path,env", COND_ROUTES, ids=lambda v: str(v))
+def test_condition_without_batchnorm(path, env, monkeypatch):
+    """has_bn = 0 and dout = dy with a per-channel mean of ~1: the per-sample totals and the interior = total - border sums
+    of cond_wgrad_kernel without BatchNorm's zero sum.  No engine runs e0 this way; it is the only regime in which the region
+    sums do not cancel over the batch.  Every case of the path."""
+    if env:
+        monkeypatch.setenv(env, "1")
+    for idx in range(len(PATHS[path]["cases"])):
+        what = "%s[%d] %s no BatchNorm, mean(dy) ~ 1" % (path, idx, env)
+        d = _data(path, idx, "plain", None, "dy_mean1")
+        ref = _reference(path, idx, "plain", None, "dy_mean1")
+        r = _run(path, idx, "plain", variant="dy_mean1")
+        _check_ids(r["kernels"], _ids(path, idx, env), what, plain=True)
+        _check_y(r, ref[0], _case(path, idx)["S"], what)
+        _check_grads(r, d, ref, what)
 
 
 def test_zz_report_worst_gaps():
