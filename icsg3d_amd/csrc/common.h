@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "up8.h"
+
 namespace ics {
 
 // Every kernel launch of the library goes through ICS_LAUNCH: a process-wide count of device kernels enqueued, the
@@ -126,6 +128,9 @@ enum ConvFlags : int {
   CF_NO_DGRAD_BNFUSE = 1 << 22,  // ICSG3D_NO_DGRAD_BNFUSE: c17 / c15 BatchNorm backward as its own pass behind c18 / c16 backward-data
   CF_NO_POOL_PRESUM = 1 << 23,   // ICSG3D_NO_POOL_PRESUM: pool-only layers (perceptual taps) keep the BatchNorm-backward reduce pass
   CF_NO_HEAD_LABELS = 1 << 24,   // ICSG3D_NO_HEAD_LABELS: inference labels from the stored probabilities (labels_kernel), not from the fused head's registers
+  CF_NO_UP8 = 1 << 25,           // ICSG3D_NO_UP8: up-split backward through the 27 tap copies of dy (pool27) instead of the 8 pooled volumes (up8.h)
+  CF_UP8 = 1 << 26,            // internal: the A operand (conv_fwd_kernel) / dY operand (conv_wgrad_kernel) of this coarse-grid GEMM is the
+                               // 8-volume layout of up8.h at the source / dy pointer
   CF_ZBATCH = 1 << 20,         // internal: conv_fwd_kernel runs gridDim.z independent GEMMs (launch_gemm_zbatch)
   // (131072 was CF_NO_TICKET, the per-layer bias-gradient finalize of round 3: removed in round 6 with the other switches
   // DESIGN.md records as rejected -- ICSG3D_SIDE_STREAM, ICSG3D_NO_ARENA)
@@ -173,6 +178,8 @@ int launch_conv_fwd(hipStream_t st, const ConvGeom& g, const ConvSrc* src, int n
 // bwd / bwd_blocks: see BwdStat; *bwd_blocks = number of row blocks written to bwd->partial, or 0 when this launch
 // could not fold the reductions (split-K or thin-N path) and the caller must run them separately
 size_t conv_fwd_workspace_floats(const ConvGeom& g, const ConvSrc* src, int nsrc);
+// whether the tile launch_conv_fwd picks for this (coarse-grid, taps = 1) geometry has an UP8 instantiation (up8.h)
+bool conv_fwd_up8_tile_ok(const ConvGeom& g);
 // Thin-C direct stencil forward (see conv_igemm.hip): plain single source with cin_log in {1,4,16} channels, Cout in
 // {16,32}; wstride = input channels per tap in the packed weights (>= cin_log)
 bool conv_thin_c_ok(const ConvGeom& g, const ConvSrc& s0, int nsrc, int cin_log);

@@ -75,6 +75,7 @@ int conv_flags_from_env() {
   if (getenv("ICSG3D_NO_DGRAD_BNFUSE")) f |= CF_NO_DGRAD_BNFUSE;
   if (getenv("ICSG3D_NO_POOL_PRESUM")) f |= CF_NO_POOL_PRESUM;
   if (getenv("ICSG3D_NO_HEAD_LABELS")) f |= CF_NO_HEAD_LABELS;
+  if (getenv("ICSG3D_NO_UP8")) f |= CF_NO_UP8;
   { const char* e = getenv("ICSG3D_UP3_BIG_MIN_WG"); if (e && *e && strtoul(e, nullptr, 10) <= 1) f |= CF_UP3_BIG_ALWAYS; }
   return f;
 }
@@ -222,13 +223,13 @@ __device__ __forceinline__ float gather_scalar(const ConvSrc& s0, const ConvSrc&
 // FOLD (backward-data launches only): the epilogue also sums the NEXT layer's BatchNorm-backward terms over the tile
 // (BwdStat) -- a compile-time variant so that the forward instantiations keep their register budget.
 template <int WM, int WN, int TM, int TN, bool VEC, int ABL = 0, bool AFF = true, bool UP = true, bool THIN = false,
-          bool REUSE = false, bool PAR = false, bool NOACT = false, bool FOLD = false>
+          bool REUSE = false, bool PAR = false, bool NOACT = false, bool FOLD = false, bool UP8 = false>
 __global__ __launch_bounds__(256, FOLD ? 2 : ((REUSE && PAR) ? 3 : 1)) void conv_fwd_kernel(ConvGeom g, ConvSrc s0, ConvSrc s1,
                                                         const float* __restrict__ wp,
                                                         const float* __restrict__ bias,
                                                         float* __restrict__ out, int ldo, int pre_act,
                                                         float* __restrict__ stat_partial, int gridM,
-                                                        int gridN, int accumulate, BwdStat bs) {
+                                                        int gridN, int accumulate, BwdStat bs, Up8Geom u8) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int B_FLOATS = 32 * BN;
   constexpr int RA = BM / 32;    // VEC: float4 A loads per thread per chunk
@@ -466,21 +467,27 @@ __global__ __launch_bounds__(256, FOLD ? 2 : ((REUSE && PAR) ? 3 : 1)) void conv
   // taps == 1 over same-resolution sources is a plain [M][K] x [K][N] GEMM (dense layers, the 1x1x1 heads, the
   // coarse-grid GEMMs of the up-split backward): row byte offsets are fixed, the channel offset is wave-uniform,
   // and rows >= M just re-read row M-1 (their outputs are never stored): no address or mask arithmetic per chunk.
+  // UP8 (the up-split backward-data GEMM, A = the 8 pooled volumes of up8.h at s0.p): the row offset is the PADDED row
+  // of the coarse voxel and the chunk pointer is volume base + row shift + channel offset of the chunk's tap -- still
+  // one wave-uniform pointer per chunk (a shift, a mask and the tap's entry of a 27-entry table in the kernel arguments:
+  // no vector ALU work) and per-thread offsets fixed for the kernel.
   unsigned rowG0[RA], rowG1[RA];
   if (VEC) {
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
       const unsigned mc = (unsigned)min(mrow_base + 32 * r, M - 1);
-      rowG0[r] = (mc * (unsigned)s0.C + (unsigned)(t & 7) * 4u) * 4u;
+      rowG0[r] = UP8 ? (up8_row_floats(mc, u8) + (unsigned)(t & 7) * 4u) * 4u
+                     : (mc * (unsigned)s0.C + (unsigned)(t & 7) * 4u) * 4u;
       rowG1[r] = (mc * (unsigned)s1.C + (unsigned)(t & 7) * 4u) * 4u;
     }
   }
   auto load_chunk_gemm = [&](int c) {
     load_b(c * 8);
     const int ci0 = c << 5;
-    const bool first = ci0 < s0.C;
+    const bool first = UP8 || ci0 < s0.C;
     const int cbase = first ? ci0 : ci0 - s0.C;
-    const char* sp = reinterpret_cast<const char*>(first ? s0.p : s1.p) + (size_t)cbase * 4;
+    const char* sp = UP8 ? reinterpret_cast<const char*>(s0.p) + up8_chunk_floats(c, u8) * 4
+                         : reinterpret_cast<const char*>(first ? s0.p : s1.p) + (size_t)cbase * 4;
     const float slope = first ? slope0 : slope1;
     v4f sc = v4f{1.f, 1.f, 1.f, 1.f}, sh = v4f{0.f, 0.f, 0.f, 0.f};
     if (AFF) {
@@ -675,8 +682,9 @@ __global__ __launch_bounds__(256, FOLD ? 2 : ((REUSE && PAR) ? 3 : 1)) void conv
 #pragma unroll
         for (int r = 0; r < NB; ++r) xb[r] = *reinterpret_cast<const v4f*>(wrow + bofs[r]);
         const int ci0 = c << 5;
-        const bool first = ci0 < s0.C;
-        const char* sp = reinterpret_cast<const char*>(first ? s0.p : s1.p) + (size_t)(first ? ci0 : ci0 - s0.C) * 4;
+        const bool first = UP8 || ci0 < s0.C;
+        const char* sp = UP8 ? reinterpret_cast<const char*>(s0.p) + up8_chunk_floats(c, u8) * 4
+                             : reinterpret_cast<const char*>(first ? s0.p : s1.p) + (size_t)(first ? ci0 : ci0 - s0.C) * 4;
 #pragma unroll
         for (int r = 0; r < RA; ++r) xa[r] = *reinterpret_cast<const v4f*>(sp + (first ? rowG0[r] : rowG1[r]));
       };
@@ -902,7 +910,7 @@ __global__ __launch_bounds__(256, FOLD ? 2 : ((REUSE && PAR) ? 3 : 1)) void conv
 }
 
 template <int WM, int WN, int TM, int TN, bool VEC, int ABL = 0, bool AFF = true, bool UP = true, bool THIN = false,
-          bool REUSE = false, bool PAR = false, bool NOACT = false, bool FOLD = false>
+          bool REUSE = false, bool PAR = false, bool NOACT = false, bool FOLD = false, bool UP8 = false>
 static int launch_fwd_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0, const ConvSrc& s1,
                           const float* wp, const float* bias, float* out, int ldo, int pre_act,
                           float* stat_partial, int* rows_per_block, int accumulate = 0, int ksplit = 1,
@@ -912,7 +920,7 @@ static int launch_fwd_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0, 
   const int gridM = (M + BM - 1) / BM, gridN = g.Npad / BN;
   const int arows = REUSE ? BM + (BM >> g.lgS) + 1 : BM;
   const size_t lds = (size_t)(arows * kLDA + 2 * 32 * BN) * sizeof(float);
-  auto kern = conv_fwd_kernel<WM, WN, TM, TN, VEC, ABL, AFF, UP, THIN, REUSE, PAR, NOACT, FOLD>;
+  auto kern = conv_fwd_kernel<WM, WN, TM, TN, VEC, ABL, AFF, UP, THIN, REUSE, PAR, NOACT, FOLD, UP8>;
   static DevOnce attr;
   int dev;
   if (attr.need(&dev)) {
@@ -925,12 +933,16 @@ static int launch_fwd_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0, 
   static const std::string id = std::string("conv_fwd_kernel<") + std::to_string(WM) + ", " + std::to_string(WN) + ", " +
                                 std::to_string(TM) + ", " + std::to_string(TN) + ", " + tf(VEC) + ", " +
                                 std::to_string(ABL) + ", " + tf(AFF) + ", " + tf(UP) + ", " + tf(THIN) + ", " +
-                                tf(REUSE) + ", " + tf(PAR) + ", " + tf(NOACT) + ", " + tf(FOLD) + ">";
+                                tf(REUSE) + ", " + tf(PAR) + ", " + tf(NOACT) + ", " + tf(FOLD) + (UP8 ? ", UP8>" : ">");
+  // (the label of an existing instantiation is what it was: tests/test_gpu_conv_link.py recognises a folded launch by a
+  // label that ends in "true>"; the UP8 variant names its last template parameter, as conv_wgrad_kernel's label does)
   g_last_kernel_id = id.c_str();
   BwdStat bs_arg;
   if (FOLD) bs_arg = *bwd;
+  Up8Geom u8;
+  if (UP8) u8 = up8_geom(g.B, g.S, g.lgS, g.Cin / 27);   // g is the coarse grid; K = 27 taps x the channels of dy
   ICS_LAUNCH(kern, dim3(gridM * gridN, PAR ? 8 : 1, ksplit), dim3(256), lds, st, g, s0, s1, wp, bias, out, ldo,
-                     pre_act, stat_partial, gridM, gridN, accumulate, bs_arg);
+                     pre_act, stat_partial, gridM, gridN, accumulate, bs_arg, u8);
   ICS_HIP(hipGetLastError());
   return 0;
 }
@@ -947,6 +959,14 @@ static void pick_fwd_tile(const ConvGeom& g, int* bm, int* bn) {
   }
   *bm = BM;
   *bn = BN;
+}
+
+// The UP8 loader (up8.h) exists for the 64 x 64, 128 x 128 and 128 x 64 tiles only.
+static bool up8_tile(int bm, int bn) { return bm == 64 || bn == 128 || bn == 64; }
+bool conv_fwd_up8_tile_ok(const ConvGeom& g) {
+  int bm, bn;
+  pick_fwd_tile(g, &bm, &bn);
+  return up8_tile(bm, bn);
 }
 
 static bool fwd_is_vec(const ConvGeom& g, const ConvSrc& s0, const ConvSrc& s1) {
@@ -1864,6 +1884,23 @@ static int launch_conv_fwd_inner(hipStream_t st, const ConvGeom& g, const ConvSr
   int bm, bn;
   pick_fwd_tile(g, &bm, &bn);
 #define ICS_FWD_ARGS st, g, s0, s1, wp, bias, out, ldo, pre_act, stat_partial, rows_per_block, accumulate, ksplit, bwd
+  if (g.flags & CF_UP8) {   // the up-split backward-data GEMM over the 8 pooled volumes (up8.h): same tiles, same K order
+    ICS_CHECK(vec && !thin && variant == 0 && nsrc == 1 && g.taps == 1 && g.Cin % 27 == 0 && g.Kpad == g.Cin &&
+                  up8_shape_ok(2 * g.S, g.Cin / 27, (size_t)g.B << (3 * g.lgS), g.B),
+              "up8 backward-data: shape outside the 8-volume layout");
+#define ICS_FWD8(WM, WN, TM, TN)                                                                                     \
+  do {                                                                                                               \
+    if (fold)                                                                                                        \
+      return launch_fwd_cfg<WM, WN, TM, TN, true, 0, false, false, false, false, false, false, true, true>(ICS_FWD_ARGS); \
+    return launch_fwd_cfg<WM, WN, TM, TN, true, 0, false, false, false, false, false, false, false, true>(ICS_FWD_ARGS); \
+  } while (0)
+    // the engine's up8_ok asks conv_fwd_up8_tile_ok for every batch of the handle before it lays dy out this way
+    ICS_CHECK(up8_tile(bm, bn), "up8 backward-data: no UP8 instantiation of this tile");
+    if (bm == 64) { ICS_FWD8(2, 2, 1, 1); }
+    if (bn == 128) { ICS_FWD8(2, 2, 2, 2); }
+    ICS_FWD8(2, 2, 2, 1);
+#undef ICS_FWD8
+  }
 #define ICS_FWD(WM, WN, TM, TN)                                                                 \
   do {                                                                                          \
     if (thin) return launch_fwd_cfg<WM, WN, TM, TN, true, 0, true, true, true>(ICS_FWD_ARGS);   \
@@ -2043,12 +2080,12 @@ int launch_conv_fwd_ablate(hipStream_t st, const ConvGeom& g, const ConvSrc* src
 // Backward-weight kernel: ws[split][k][n] = sum_{m in split} A[m][k] * dy[m][n]
 // =====================================================================================
 template <int WM, int WN, int TM, int TN, bool VEC, bool DYVEC, bool AFF = true, bool UP = true, bool THIN = false,
-          int ABL = 0>
+          int ABL = 0, bool UP8 = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0, ConvSrc s1,
                                                           const float* __restrict__ dy, int ldy,
                                                           int n_load,
                                                           float* __restrict__ ws, int ktiles,
-                                                          int ntiles, int rows_per_split) {
+                                                          int ntiles, int rows_per_split, Up8Geom u8) {
   constexpr int KT = WM * TM * 32, NT = WN * TN * 32;
   constexpr int A_FLOATS = 32 * KT, D_FLOATS = 32 * NT;
   constexpr int AF4 = KT / 4, ATOT = 32 * AF4, APASS = ATOT / 256;   // 256 % AF4 == 0
@@ -2174,7 +2211,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0,
   // up-split backward, the heads): a plain A^T x dY.  Wave-uniform chunk pointers + per-thread byte offsets fixed
   // for the kernel, no validity arithmetic (a thread whose k >= K loads column 0; its rows are never written).
   const bool gemm = VEC && DYVEC && !UP && !THIN && ABL == 0 && g.taps == 1 && (M & 31) == 0 &&
-                    (rows_per_split & 31) == 0 && n0 + NT <= n_load;
+                    (rows_per_split & 31) == 0 && (UP8 || n0 + NT <= n_load);
   const bool noact_g = slope == 1.f;
   unsigned aoffg[VEC ? APASS : 1], doffg[DPASS];
   if (VEC) {
@@ -2184,13 +2221,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0,
 #pragma unroll
   for (int p = 0; p < DPASS; ++p) {
     const int idx = t + 256 * p;
-    doffg[p] = (unsigned)((idx / DF4) * ldy + n0 + (idx % DF4) * 4) * 4u;
+    // UP8 (dY = the 8 pooled volumes of up8.h at dy): a float4 column lies inside one tap, so its volume base and row
+    // shift are per-thread constants; the 5 low bits of a coarse row are whole (z,y,x) digits (Sh >= 4), so the padded
+    // row of chunk row r adds to the padded row of the 32-aligned chunk base without carries.  Columns past n_load (a
+    // partial last N tile) re-read the last real column: their sums are never stored.
+    doffg[p] = UP8 ? (up8_prow((unsigned)(idx / DF4), u8.lgSh, u8.P) * (unsigned)u8.N +
+                      up8_col_floats(min(n0 + (idx % DF4) * 4, n_load - 4), u8)) * 4u
+                   : (unsigned)((idx / DF4) * ldy + n0 + (idx % DF4) * 4) * 4u;
   }
   auto load_chunk_gemm = [&](int c, auto noact_tag) {
     constexpr bool NA = decltype(noact_tag)::value;
     const int mbase = m_begin + (c << 5);
     const char* abase = reinterpret_cast<const char*>(sp) + (size_t)mbase * (size_t)sC * 4;
-    const char* dbase = reinterpret_cast<const char*>(dy) + (size_t)mbase * (size_t)ldy * 4;
+    const char* dbase = reinterpret_cast<const char*>(dy) +
+                        (UP8 ? up8_chunk_base_floats((unsigned)mbase, u8) : (size_t)mbase * (size_t)ldy) * 4;
     if (VEC) {
 #pragma unroll
       for (int p = 0; p < APASS; ++p) {
@@ -2286,7 +2330,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0,
     auto loadS = [&](int c, v4f (&xa)[APASS], v4f (&xd)[DPASS]) {
       const int mbase = m_begin + (c << 5);
       const char* abase = reinterpret_cast<const char*>(sp) + (size_t)mbase * (size_t)sC * 4;
-      const char* dbase = reinterpret_cast<const char*>(dy) + (size_t)mbase * (size_t)ldy * 4;
+      const char* dbase = reinterpret_cast<const char*>(dy) +
+                        (UP8 ? up8_chunk_base_floats((unsigned)mbase, u8) : (size_t)mbase * (size_t)ldy) * 4;
 #pragma unroll
       for (int p = 0; p < APASS; ++p) xa[p] = *reinterpret_cast<const v4f*>(abase + aoffg[p]);
 #pragma unroll
@@ -2885,12 +2930,12 @@ size_t conv_wgrad_workspace_floats(const ConvGeom& g, const ConvSrc* src, int ns
 }
 
 template <int WM, int WN, int TM, int TN, bool VEC, bool DYVEC, bool AFF = true, bool UP = true, bool THIN = false,
-          int ABL = 0>
+          int ABL = 0, bool UP8 = false>
 static int launch_wgrad_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0, const ConvSrc& s1,
                             const float* dy, int ldy, int n_load, float* ws, const WgradPlan& p) {
   constexpr int KT = WM * TM * 32, NT = WN * TN * 32;
   const size_t lds = (size_t)2 * 32 * (KT + NT) * sizeof(float);
-  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, VEC, DYVEC, AFF, UP, THIN, ABL>;
+  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, VEC, DYVEC, AFF, UP, THIN, ABL, UP8>;
   static DevOnce attr;
   int dev;
   if (attr.need(&dev)) {
@@ -2901,10 +2946,12 @@ static int launch_wgrad_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0
   static const std::string id = std::string("conv_wgrad_kernel<") + std::to_string(WM) + ", " + std::to_string(WN) +
                                 ", " + std::to_string(TM) + ", " + std::to_string(TN) + ", " + tf(VEC) + ", " +
                                 tf(DYVEC) + ", " + tf(AFF) + ", " + tf(UP) + ", " + tf(THIN) + ", " +
-                                std::to_string(ABL) + ">";
+                                std::to_string(ABL) + (UP8 ? ", UP8>" : ">");
   g_last_kernel_id = id.c_str();
+  Up8Geom u8;
+  if (UP8) u8 = up8_geom(g.B, g.S, g.lgS, g.Cout / 27);   // g is the coarse grid; N = 27 taps x the channels of dy
   ICS_LAUNCH(kern, dim3(p.ktiles * p.ntiles * p.ksplit), dim3(256), lds, st, g, s0, s1, dy,
-                     ldy, n_load, ws, p.ktiles, p.ntiles, p.rows_per_split);
+                     ldy, n_load, ws, p.ktiles, p.ntiles, p.rows_per_split, u8);
   ICS_HIP(hipGetLastError());
   return 0;
 }
@@ -3053,7 +3100,23 @@ int launch_conv_wgrad(hipStream_t st, const ConvGeom& g, const ConvSrc* src, int
     else if (aff) ICS_TRY((launch_wgrad_cfg<WM, WN, TM, TN, true, DV, true, false>(ICS_WG_ARGS))); \
     else ICS_TRY((launch_wgrad_cfg<WM, WN, TM, TN, true, DV, false, false>(ICS_WG_ARGS)));         \
   } while (0)
-  if (!dy_vec) {
+  if (g.flags & CF_UP8) {   // the up-split backward-weight GEMM over the 8 pooled volumes (up8.h): same plan, same row order
+    const int M8 = g.B << (3 * g.lgS);
+    ICS_CHECK(dy_vec && p.vec && !p.thin && !up && g.taps == 1 && g.Cout % 27 == 0 && n_load == g.Cout && M8 % 32 == 0 &&
+                  p.rows_per_split % 32 == 0 && up8_shape_ok(2 * g.S, g.Cout / 27, (size_t)M8, g.B),
+              "up8 backward-weight: shape outside the 8-volume layout");
+#define ICS_WG8(WM, WN, TM, TN)                                                                                  \
+  do {                                                                                                           \
+    if (aff) ICS_TRY((launch_wgrad_cfg<WM, WN, TM, TN, true, true, true, false, false, 0, true>(ICS_WG_ARGS)));  \
+    else ICS_TRY((launch_wgrad_cfg<WM, WN, TM, TN, true, true, false, false, false, 0, true>(ICS_WG_ARGS)));     \
+  } while (0)
+    // N = 27 * Cout >= 864 columns: plan_wgrad gives every K tile the 128-wide N tile
+    // and Cu % 64 == 0 (up8_ok) a K tile of 64 or 128
+    ICS_CHECK(p.nt == 128 && p.kt >= 64, "up8 backward-weight: no UP8 instantiation of this tile");
+    if (p.kt == 128) ICS_WG8(2, 2, 2, 2);
+    else ICS_WG8(2, 2, 1, 2);
+#undef ICS_WG8
+  } else if (!dy_vec) {
     if (p.kt == 128) ICS_WG(4, 1, 1, 1, false);
     else if (p.kt == 64) ICS_WG(2, 2, 1, 1, false);
     else ICS_WG(1, 4, 1, 1, false);

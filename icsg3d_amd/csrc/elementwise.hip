@@ -2022,6 +2022,69 @@ int launch_pool27(hipStream_t st, const float* dy, int B, int S, int N, float* o
   ICS_HIP(hipGetLastError());
   return 0;
 }
+// The same sums as 8 volumes (up8.h): per axis only R[a] = dy[2a] + dy[2a+1] and Q[a] = dy[2a-1] + dy[2a] are distinct,
+// and tap offset d = -1 reads Q one coarse voxel further on.  One thread = one PADDED coarse position (j in [0, P)^3,
+// P = Sh + 1) x four channels: coordinates {2j-1, 2j, 2j+1} per axis, 27 float4 loads for 8 outputs.  The additions keep
+// pool27's association (x pair with the lower coordinate first, then the y pair, then 0 + first z + second z, planes
+// outside the grid skipped), so every value equals the tap copy it replaces bit for bit.
+__global__ __launch_bounds__(256) void pool8_kernel(const float* __restrict__ dy, int B, int S, int N, size_t total,
+                                                    float* __restrict__ out, Up8Geom u) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int Sh = S >> 1, N4 = N >> 2, P = u.P;
+  const int n = (int)(i % N4) * 4;
+  size_t r = i / N4;
+  const int jx = r % P; r /= P;
+  const int jy = r % P; r /= P;
+  const int jz = r % P;
+  const int b = (int)(r / P);
+  pf4 o[2][2][2];   // [kz][ky][kx], 0 = R, 1 = Q
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k >> 2][(k >> 1) & 1][k & 1] = pf4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int sz = 0; sz < 3; ++sz) {
+    const int z = 2 * jz - 1 + sz;
+    if ((unsigned)z >= (unsigned)S) continue;
+    pf4 lx[3][2];   // [sy][kx]
+#pragma unroll
+    for (int sy = 0; sy < 3; ++sy) {
+      const int y = 2 * jy - 1 + sy;
+      pf4 v[3];
+#pragma unroll
+      for (int sx = 0; sx < 3; ++sx) {
+        const int x = 2 * jx - 1 + sx;
+        const bool ok = (unsigned)y < (unsigned)S && (unsigned)x < (unsigned)S;
+        v[sx] = ok ? *reinterpret_cast<const pf4*>(dy + ((((size_t)b * S + z) * S + y) * S + x) * N + n) : pf4{0.f, 0.f, 0.f, 0.f};
+      }
+      lx[sy][1] = v[0] + v[1];   // Q
+      lx[sy][0] = v[1] + v[2];   // R
+    }
+#pragma unroll
+    for (int kx = 0; kx < 2; ++kx) {
+      const pf4 q = lx[0][kx] + lx[1][kx], rr = lx[1][kx] + lx[2][kx];
+      if (sz <= 1) o[1][1][kx] += q;    // Qz: planes 2jz-1, 2jz
+      if (sz <= 1) o[1][0][kx] += rr;
+      if (sz >= 1) o[0][1][kx] += q;    // Rz: planes 2jz, 2jz+1
+      if (sz >= 1) o[0][0][kx] += rr;
+    }
+  }
+  const size_t row = (((size_t)b * P + jz) * P + jy) * P + jx;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int kz = k >> 2, ky = (k >> 1) & 1, kx = k & 1;
+    // slot Sh of an R-type axis is not part of the volume's data
+    if ((kz == 0 && jz == Sh) || (ky == 0 && jy == Sh) || (kx == 0 && jx == Sh)) continue;
+    *reinterpret_cast<pf4*>(out + (size_t)k * u.vstride + row * N + n) = o[kz][ky][kx];
+  }
+}
+int launch_pool8(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up8Geom& u) {
+  ICS_CHECK(N % 4 == 0 && u.P == S / 2 + 1 && u.N == N && (size_t)u.vstride == up8_volume_floats(B, S / 2, N),
+            "pool8: layout does not match the shape");
+  const size_t total = (size_t)B * u.P * u.P * u.P * (N / 4);
+  ICS_LAUNCH(pool8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dy, B, S, N, total, out, u);
+  ICS_HIP(hipGetLastError());
+  return 0;
+}
 // dw[(tap*Cin + c_off + c)*N + n] = tmp[c*(27N) + tap*N + n]
 __global__ void permute_up_dw_kernel(const float* __restrict__ tmp, int Cu, int N, int Cin, int c_off,
                                      size_t total, float* __restrict__ dw) {

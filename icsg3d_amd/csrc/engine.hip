@@ -198,6 +198,8 @@ struct ConvLayer {
   float* w_up3n = nullptr;                     // the same for narrow outputs (conv_up3n.hip; layers without skip channels)
   float *dyS = nullptr;                        // [M/8][ldS] tap-pooled dy, ldS = 27*Cout rounded up to 32 (pad = 0)
   int ldS = 0;
+  bool up8 = false;                            // dy pooled into the 8 volumes of up8.h (dy8) instead of the 27 tap copies (dyS)
+  float *dy8 = nullptr;                        // [8][maxB * (S/2+1)^3][Cout]; a batch B uses volumes B * (S/2+1)^3 * Cout floats apart
   float *dA_skip = nullptr, *dxl = nullptr;    // [M][Cs] grad of the skip input; [M/8][Cu] grad of the low-res input
   float *dw_up = nullptr;                      // [Cu][27*Cout] GEMM result before the permute into G
 };
@@ -534,10 +536,10 @@ static ConvGeom geom_bwd(const ConvLayer& L, int B) {
 
 // up-split GEMM geometries (see ConvLayer::split_up)
 static ConvGeom geom_up_wgrad(const ConvLayer& L, int B) {   // dw_up[Cu][27N] = xl^T x dyS over the S/2 grid
-  return ConvGeom{B, L.S / 2, ilog2(L.S / 2), L.Cu, 27 * L.Cout, 1, round_up(L.Cu, 32), L.ldS, L.flags};
+  return ConvGeom{B, L.S / 2, ilog2(L.S / 2), L.Cu, 27 * L.Cout, 1, round_up(L.Cu, 32), L.ldS, L.flags | (L.up8 ? CF_UP8 : 0)};
 }
 static ConvGeom geom_up_dgrad(const ConvLayer& L, int B) {   // dxl[M/8][Cu] = dyS x W_up
-  return ConvGeom{B, L.S / 2, ilog2(L.S / 2), L.ldS, L.Cu, 1, L.ldS, round_up(L.Cu, 32), L.flags};
+  return ConvGeom{B, L.S / 2, ilog2(L.S / 2), L.ldS, L.Cu, 1, L.ldS, round_up(L.Cu, 32), L.flags | (L.up8 ? CF_UP8 : 0)};
 }
 static ConvGeom geom_skip_wgrad(const ConvLayer& L, int B) {
   return ConvGeom{B, L.S, ilog2(L.S), L.Cs, L.Cout, L.taps, round_up(L.taps * L.Cs, 32), L.Npad, L.flags};
@@ -552,6 +554,24 @@ static ConvGeom geom_par_fwd(const ConvLayer& L, int B) {    // one parity class
   return ConvGeom{B, L.S / 2, ilog2(L.S / 2), L.Cu, L.Cout, 8, 8 * L.Cu, L.Npad, L.flags};
 }
 static ConvSrc src_lowres(const ConvLayer& L) { ConvSrc u = L.src[L.nsrc - 1]; u.up = 0; return u; }
+
+// The 8-volume form of the pooled dy (up8.h) serves S >= 8 (a 32-row chunk of the coarse grid is whole (z,y,x) digits),
+// Cout = 32 * 2^k (a 32-channel K chunk of the backward-data GEMM lies inside one tap, found by a shift; a float4 column of
+// the backward-weight GEMM lies inside one tap for any N tile), whole 32-row chunks at every batch (Sh^3 >= 64) and a
+// buffer addressable with 32-bit byte offsets.  At S = 4 the volumes are no smaller than the tap copies; narrow layers
+// (Cout = 16, the VAE decoder) keep pool27.  ICSG3D_NO_UP8 restores the tap copies per handle.
+static bool up8_ok(const Net& n, const ConvLayer& L) {
+  if (n.flags & CF_NO_UP8) return false;
+  const size_t S3 = (size_t)(L.S / 2) * (L.S / 2) * (L.S / 2);
+  if (L.Cout % 32 || L.Cu % 64 || !up8_shape_ok(L.S, L.Cout, (size_t)n.maxB * S3, n.maxB)) return false;
+  // Only the 64- and 128-wide N tiles of the backward-data GEMM carry the UP8 loader (the 32- and 96-wide ones would need
+  // more registers than the instantiations they replace).  The layout is fixed when the handle is made and the tile is
+  // chosen per batch, so the dispatcher is asked about EVERY batch the handle can run: Cu = 192, 576, .. take the 96-wide
+  // tile once the batch is large enough and keep pool27.
+  for (int b = 1; b <= n.maxB; ++b)
+    if (!conv_fwd_up8_tile_ok(geom_up_dgrad(L, b))) return false;
+  return true;
+}
 
 // Layers whose (last) source is nearest-upsampled: [skip | up] concat convs (U-Net c13/c15/c17) and the VAE
 // decoder's d1..d3 (Cs = 0).
@@ -569,8 +589,15 @@ static int enable_split_up(Net& n, ConvLayer& L) {
   L.ldS = round_up(27 * L.Cout, 32);
   const size_t M = n.rows(L, n.maxB);
   ICS_TRY(n.alloc(&L.w_up, (size_t)L.ldS * round_up(L.Cu, 32)));
-  ICS_TRY(n.alloc(&L.dyS, M / 8 * L.ldS));
-  ICS_HIP(hipMemsetAsync(L.dyS, 0, M / 8 * L.ldS * sizeof(float), n.st));   // pad columns stay zero
+  L.up8 = up8_ok(n, L);
+  if (L.up8) {
+    const size_t n8 = 8 * up8_volume_floats(n.maxB, L.S / 2, L.Cout);
+    ICS_TRY(n.alloc(&L.dy8, n8));
+    ICS_HIP(hipMemsetAsync(L.dy8, 0, n8 * sizeof(float), n.st));
+  } else {
+    ICS_TRY(n.alloc(&L.dyS, M / 8 * L.ldS));
+    ICS_HIP(hipMemsetAsync(L.dyS, 0, M / 8 * L.ldS * sizeof(float), n.st));   // pad columns stay zero
+  }
   ICS_TRY(n.alloc(&L.dxl, M / 8 * L.Cu));
   ICS_TRY(n.alloc(&L.dw_up, (size_t)L.Cu * 27 * L.Cout));
   if (conv_up3_ok(geom_par_fwd(L, n.maxB), src_lowres(L)))
@@ -659,7 +686,7 @@ static int alloc_workspaces(Net& n, bool need_bwd) {
       const ConvSrc sdy = src_plain(L.dy, L.Cout);
       fw = std::max(fw, conv_fwd_workspace_floats(geom_bwd(L, b), &sdy, 1));
       if (L.split_up) {
-        const ConvSrc sd = src_plain(L.dyS, L.ldS);
+        const ConvSrc sd = src_plain(L.up8 ? L.dy8 : L.dyS, L.ldS);
         fw = std::max(fw, conv_fwd_workspace_floats(geom_up_dgrad(L, b), &sd, 1));
         if (L.Cs) fw = std::max(fw, conv_fwd_workspace_floats(geom_skip_dgrad(L, b), &sdy, 1));
       }
@@ -982,8 +1009,15 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
   const double fl_skip = 2.0 * M * 27 * L.Cs * L.Cout, fl_up = 2.0 * (M / 8) * 27 * L.Cu * L.Cout;
   const bool skipfuse = skip_bnfuse_ok(n, L, B);
   ConvLayer* P = L.skip_prod;
-  n.prof.begin(n.st, "pool27:" + L.name, 0, 4.0 * M * L.Cout * (1 + 27.0 / 8));
-  ICS_TRY(launch_pool27(n.st, L.dy, B, L.S, L.Cout, L.dyS, L.ldS));
+  const float* dyp = L.up8 ? L.dy8 : L.dyS;   // the pooled dy both coarse-grid GEMMs read (CF_UP8 in their geometry says which form)
+  if (L.up8) {
+    const double pr = (double)(L.S / 2 + 1) / (L.S / 2);
+    n.prof.begin(n.st, "pool8:" + L.name, 0, 4.0 * M * L.Cout * (1 + pr * pr * pr));
+    ICS_TRY(launch_pool8(n.st, L.dy, B, L.S, L.Cout, L.dy8, up8_geom(B, L.S / 2, ilog2(L.S / 2), L.Cout)));
+  } else {
+    n.prof.begin(n.st, "pool27:" + L.name, 0, 4.0 * M * L.Cout * (1 + 27.0 / 8));
+    ICS_TRY(launch_pool27(n.st, L.dy, B, L.S, L.Cout, L.dyS, L.ldS));
+  }
   n.prof.end(n.st);
   hipStream_t ws = side_begin(n);   // weight gradients: off the critical path (see Net::st2)
   if (L.Cs) {
@@ -1023,10 +1057,10 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
     const ConvSrc lo = src_lowres(L);
     n.prof.begin(ws, "conv_wgrad:" + L.name + ".up|", fl_up,
                  4.0 * (M / 8 * L.Cu + M / 8 * 27.0 * L.Cout + 27.0 * L.Cu * L.Cout));
-    ICS_TRY(launch_conv_wgrad(ws, g, &lo, 1, L.dyS, L.ldS, L.dw_up, 27 * L.Cout, n.ws_wgrad, n.ws_wgrad_n, 0, 0, 0, 1));
+    ICS_TRY(launch_conv_wgrad(ws, g, &lo, 1, dyp, L.ldS, L.dw_up, 27 * L.Cout, n.ws_wgrad, n.ws_wgrad_n, 0, 0, 0, 1));
     n.prof.end(ws);
     n.prof.begin(ws, "wgrad_reduce_splits", 0, 0);
-    ICS_TRY(launch_conv_wgrad(ws, g, &lo, 1, L.dyS, L.ldS, L.dw_up, 27 * L.Cout, n.ws_wgrad, n.ws_wgrad_n, 0, 0, 0, 2));
+    ICS_TRY(launch_conv_wgrad(ws, g, &lo, 1, dyp, L.ldS, L.dw_up, 27 * L.Cout, n.ws_wgrad, n.ws_wgrad_n, 0, 0, 0, 2));
     ICS_TRY(launch_permute_up_dw(ws, L.dw_up, L.Cu, L.Cout, L.Cin, L.Cs, n.tg(L.t_w)));
     n.prof.end(ws);
   }
@@ -1045,7 +1079,7 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
   }
   {
     const ConvGeom g = geom_up_dgrad(L, B);
-    ConvSrc sd = src_plain(L.dyS, L.ldS);
+    ConvSrc sd = src_plain(dyp, L.ldS);
     n.prof.begin(n.st, "conv_dgrad:" + L.name + ".up|", fl_up,
                  4.0 * (M / 8 * L.Cu + M / 8 * 27.0 * L.Cout + 27.0 * L.Cu * L.Cout));
     const BwdStat bs = bwd_stat_for(n, next, B);    // next = the producer of the upsampled channels
@@ -3605,8 +3639,9 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
   }
   if (a->kernels && a->kernels_cap > 0) {
     std::string txt;
-    for (const auto& r : n.prof.rows)
-      if (r.label.find('|') != std::string::npos) txt += r.label + "\n";
+    for (const auto& r : n.prof.rows)   // every conv launch, and which pooling of dy the up-split backward ran (pool8: / pool27:)
+      if (r.label.find('|') != std::string::npos || r.label.rfind("pool8:", 0) == 0 || r.label.rfind("pool27:", 0) == 0)
+        txt += r.label + "\n";
     std::strncpy(a->kernels, txt.c_str(), (size_t)a->kernels_cap - 1);
     a->kernels[a->kernels_cap - 1] = 0;
   }
