@@ -217,6 +217,13 @@ SIGNATURES = {
     "ics_unet_set_class_weights": (C.c_int, [_H, _F, C.c_int]),
     "ics_unet_get_class_weights": (C.c_int, [_H, _F, C.c_int, C.POINTER(C.c_int)]),
     "ics_op_label_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_int, _I64, _I64]),
+    "ics_op_confusion": (C.c_int, [C.c_void_p, C.c_int, _U8, _U8, C.c_size_t, C.c_int, _I64, _I64, _I64]),
+    "ics_op_confusion_grid": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ics_unet_confusion_open": (C.c_int, [_H]),
+    "ics_unet_confusion_reset": (C.c_int, [_H]),
+    "ics_unet_confusion_step": (C.c_int, [_H, C.c_float]),
+    "ics_unet_confusion_batch": (C.c_int, [_H, _F, _U8, C.c_int, C.c_float]),
+    "ics_unet_confusion_read": (C.c_int, [_H, _I64, _I64, _I64, _I64]),
     "ics_op_vae_loss": (C.c_int, [_F, C.c_int, C.c_int, _D, C.c_int, C.c_double, _D, C.POINTER(C.c_int), _D, _F, C.c_float,
                                   C.c_float, C.c_int, _D, _F]),
     "ics_op_vae_latent": (C.c_int, [C.POINTER(VaeLatentArgs)]),

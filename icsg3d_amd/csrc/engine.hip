@@ -14,6 +14,7 @@
 #include "render.h"
 #include "monitor.h"
 #include "feed.h"
+#include "confusion.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -307,6 +308,9 @@ struct Net {
                                       // head->s, 2 uint8 labels in head->dy) and for how many samples; any other forward
                                       // pass and a new resident batch clear it (ics_unet_render_slice_resident)
   int labels_batch = 0;               // U-Net: samples of the resident batch whose true labels are in `labels`
+  unsigned long long* conf_acc = nullptr;   // U-Net: the confusion accumulator [conf_acc_len(ncls)] (confusion.h); allocated
+  long long conf_voxels = 0;                // by the first ics_unet_confusion_open; the pairs enqueued since the last open / reset
+  hipEvent_t conf_ev = nullptr;             // ics_unet_confusion_batch: the upload has read the caller's arrays
   hipEvent_t timer_ev[2] = {nullptr, nullptr};   // ics_net_timer_start / _stop
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
@@ -335,6 +339,7 @@ struct Net {
     if (comm) ncclCommDestroy(comm);
     for (void* p : allocs) (void)hipFree(p);
     for (hipEvent_t e : timer_ev) if (e) (void)hipEventDestroy(e);
+    if (conf_ev) (void)hipEventDestroy(conf_ev);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
     if (st2) (void)hipStreamDestroy(st2);
@@ -2600,6 +2605,81 @@ int ics_unet_predict_resident(ics_net* net, int labels_only, float thresh) {
   }
   ICS_TRY(unet_head_loss(n, batch, 0, 0));
   n.pred_kind = 1; n.pred_batch = batch;
+  return 0;
+}
+
+// ---- the confusion accumulator (include/icsg3d.h "confusion matrix", confusion.h): eval-mode passes only
+static int conf_get(ics_net* net, const char* who, bool opened) {
+  const std::string w = std::string(who) + ": ";
+  ICS_CHECK(net != nullptr, w + "null handle");
+  ICS_CHECK(net->n.kind == 0, w + "wrong engine kind: a U-Net engine is required");
+  ICS_CHECK(net->n.ncls >= kConfMinCls && net->n.ncls <= kConfMaxCls, w + "num_classes must be in [2, 127]");
+  ICS_CHECK(!opened || net->n.conf_acc != nullptr, w + "the engine has no open accumulator (ics_unet_confusion_open)");
+  ICS_HIP(hipSetDevice(net->n.device));
+  return 0;
+}
+static int conf_zero(Net& n) {
+  ICS_HIP(hipMemsetAsync(n.conf_acc, 0, conf_acc_len(n.ncls) * sizeof(unsigned long long), n.st));
+  n.conf_voxels = 0;
+  return 0;
+}
+int ics_unet_confusion_open(ics_net* net) {
+  ICS_TRY(conf_get(net, "ics_unet_confusion_open", false));
+  Net& n = net->n;
+  if (n.conf_ev == nullptr) ICS_HIP(hipEventCreateWithFlags(&n.conf_ev, hipEventDisableTiming));
+  if (n.conf_acc == nullptr) ICS_TRY(n.alloc(&n.conf_acc, conf_acc_len(n.ncls)));
+  return conf_zero(n);
+}
+int ics_unet_confusion_reset(ics_net* net) {
+  ICS_TRY(conf_get(net, "ics_unet_confusion_reset", true));
+  return conf_zero(net->n);
+}
+static int conf_step(Net& n, float thresh) {
+  const int batch = n.resident_batch;
+  ICS_TRY(unet_forward_trunk(n, batch, false, false, false, n.x_in));
+  const size_t M = n.rows(*n.head, batch);
+  unsigned char* d_species = reinterpret_cast<unsigned char*>(n.head->dy);   // where a labels predict leaves them
+  ICS_TRY(unet_head_labels(n, batch, thresh, d_species, d_species + M, n.st));
+  n.pred_kind = 2; n.pred_batch = batch;
+  n.prof.begin(n.st, "confusion", 0, 3.0 * M);
+  ICS_TRY(launch_confusion(n.st, n.labels, FEED_LABELS_U8, d_species, d_species + M, M, n.ncls, n.conf_acc));
+  n.prof.end(n.st);
+  n.conf_voxels += (long long)M;
+  return 0;
+}
+int ics_unet_confusion_step(ics_net* net, float thresh) {
+  ICS_TRY(conf_get(net, "ics_unet_confusion_step", true));
+  Net& n = net->n;
+  ICS_CHECK(n.resident_batch > 0, "ics_unet_confusion_step: no resident batch: call ics_unet_upload_batch or ics_unet_voxelise_batch first");
+  ICS_CHECK(n.labels_batch >= n.resident_batch, "ics_unet_confusion_step: the resident batch was uploaded without labels");
+  return conf_step(n, thresh);
+}
+int ics_unet_confusion_batch(ics_net* net, const float* x, const uint8_t* labels, int batch, float thresh) {
+  ICS_TRY(conf_get(net, "ics_unet_confusion_batch", true));
+  Net& n = net->n;
+  ICS_CHECK(x && labels, "ics_unet_confusion_batch: null argument");
+  ICS_CHECK(batch >= 1 && batch <= n.maxB, "ics_unet_confusion_batch: batch exceeds max_batch (or is below 1)");
+  ICS_TRY(unet_upload(n, x, labels, batch));
+  ICS_HIP(hipEventRecord(n.conf_ev, n.st));
+  ICS_TRY(conf_step(n, thresh));
+  // The one wait: until the upload has read x and labels, so that the caller may reuse them at once.  It also waits for
+  // the batch before (the upload is ordered behind it), never for this one: the host loads batch k + 1 while k runs.
+  ICS_HIP(hipEventSynchronize(n.conf_ev));
+  return 0;
+}
+int ics_unet_confusion_read(ics_net* net, int64_t* matrix, int64_t occupancy[4], int64_t* out_of_range, int64_t* voxels) {
+  ICS_TRY(conf_get(net, "ics_unet_confusion_read", true));
+  Net& n = net->n;
+  ICS_CHECK(matrix && occupancy && out_of_range && voxels, "ics_unet_confusion_read: null argument");
+  const size_t len = conf_acc_len(n.ncls), nn = (size_t)n.ncls * n.ncls;
+  std::vector<unsigned long long> host(len);
+  ICS_HIP(hipMemcpyAsync(host.data(), n.conf_acc, len * sizeof(unsigned long long), hipMemcpyDeviceToHost, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  for (size_t i = 0; i < nn; ++i) matrix[i] = (int64_t)host[i];
+  *out_of_range = (int64_t)host[nn];
+  for (int k = 0; k < 4; ++k) occupancy[k] = (int64_t)host[nn + 1 + k];
+  *voxels = (int64_t)n.conf_voxels;
   return 0;
 }
 

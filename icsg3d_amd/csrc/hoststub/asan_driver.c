@@ -945,6 +945,96 @@ static int label_counts_walk(void) {
   return 0;
 }
 
+/* The confusion matrix: the op on buffers of the exact size (every id kind, lengths that are no multiple of a 16-byte
+ * load, the empty array, with and without a mask) and its refusals with guarded outputs; then the engine's accumulator --
+ * every entry point before open, open / batch / step / read twice / reset / re-open, a resident batch without labels, a
+ * VAE handle, null arguments -- after which the engine still trains. */
+static int confusion_walk(ics_net* unet, ics_net* vae, int ncls, int d, const float* x, const uint8_t* lab, int B) {
+  const size_t ns[6] = {0, 1, 15, 16, 1037, 4099};
+  const int cols[3] = {2, 95, 127};
+  int bad = 0, a = 0, b = 0, c = 0;
+  OK(ics_op_confusion_grid(&a, &b, &c));
+  bad += ics_op_confusion_grid(NULL, &b, &c) == 0;
+  for (int kind = 1; kind <= 3; ++kind)
+    for (int i = 0; i < 6; ++i) {
+      const size_t n = ns[i], lb = kind == 1 ? 1 : kind == 2 ? 8 : 4;
+      const int k = cols[(kind + i) % 3];
+      void* t = n ? calloc(n, lb) : NULL;
+      uint8_t *p = n ? calloc(n, 1) : NULL, *m = n ? calloc(n, 1) : NULL;
+      int64_t* mat = (int64_t*)malloc((size_t)k * k * sizeof(int64_t));
+      int64_t occ[4], oor = -1;
+      OK(ics_op_confusion(t, kind, p, n ? m : (const uint8_t*)"", n, k, mat, occ, &oor));
+      OK(ics_op_confusion(t, kind, p, NULL, n, k, mat, NULL, &oor));
+      free(t); free(p); free(m); free(mat);
+    }
+  {
+    float t[16] = {0};
+    uint8_t p[16] = {0}, m[16] = {0};
+    int64_t mat[95 * 95], occ[4], oor;
+    bad += ics_op_confusion(t, 4, p, m, 16, 95, mat, occ, &oor) == 0;      /* one-hot: no class ids */
+    bad += ics_op_confusion(t, 0, p, m, 16, 95, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 5, p, m, 16, 95, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(NULL, 3, p, m, 16, 95, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 3, NULL, m, 16, 95, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 3, p, m, 16, 95, NULL, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 3, p, m, 16, 95, mat, occ, NULL) == 0;
+    bad += ics_op_confusion(t, 3, p, m, 16, 95, mat, NULL, &oor) == 0;     /* a mask without a table, a table without a mask */
+    bad += ics_op_confusion(t, 3, p, NULL, 16, 95, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 3, p, m, 16, 1, mat, occ, &oor) == 0;
+    bad += ics_op_confusion(t, 3, p, m, 16, 128, mat, occ, &oor) == 0;
+    bad += ics_op_confusion((const char*)t + 2, 3, p, m, 15, 95, mat, occ, &oor) == 0;   /* unaligned float labels */
+    OK(ics_op_confusion(t, 3, p, m, 16, 95, mat, occ, &oor));
+  }
+  const size_t kk = (size_t)ncls * ncls;
+  int64_t* mat = (int64_t*)malloc(kk * sizeof(int64_t));
+  int64_t occ[4], oor = 0, vox = 0;
+  float mm[5];
+  bad += ics_unet_confusion_step(unet, 0.8f) == 0;                        /* before open */
+  bad += ics_unet_confusion_batch(unet, x, lab, B, 0.8f) == 0;
+  bad += ics_unet_confusion_read(unet, mat, occ, &oor, &vox) == 0;
+  bad += ics_unet_confusion_reset(unet) == 0;
+  OK(ics_unet_confusion_open(unet));
+  OK(ics_unet_confusion_batch(unet, x, lab, B, 0.8f));
+  OK(ics_unet_confusion_batch(unet, x, lab, 1, 0.8f));
+  OK(ics_unet_upload_batch(unet, x, lab, B));
+  OK(ics_unet_confusion_step(unet, 0.8f));
+  {
+    float* img = calloc((size_t)B * d * d * 4, 4);
+    float lut[256 * 3] = {0};
+    OK(ics_unet_render_slice_resident(unet, 1, 0, B, 2, d / 2, lut, NULL, 1, img));   /* the species are where a labels predict leaves them */
+    free(img);
+  }
+  OK(ics_unet_confusion_read(unet, mat, occ, &oor, &vox));
+  OK(ics_unet_confusion_read(unet, mat, occ, &oor, &vox));
+  if (vox != (int64_t)(2 * B + 1) * d * d * d) { fprintf(stderr, "confusion: %lld voxels counted\n", (long long)vox); return 1; }
+  OK(ics_unet_confusion_reset(unet));
+  OK(ics_unet_confusion_read(unet, mat, occ, &oor, &vox));
+  if (vox != 0) { fprintf(stderr, "confusion: voxels left after a reset\n"); return 1; }
+  OK(ics_unet_confusion_open(unet));                                        /* a second open: the same buffer, zeroed */
+  OK(ics_unet_upload_batch(unet, x, NULL, B));                              /* a resident batch without labels */
+  bad += ics_unet_confusion_step(unet, 0.8f) == 0;
+  bad += ics_unet_confusion_batch(unet, NULL, lab, B, 0.8f) == 0;
+  bad += ics_unet_confusion_batch(unet, x, NULL, B, 0.8f) == 0;
+  bad += ics_unet_confusion_batch(unet, x, lab, 0, 0.8f) == 0;
+  bad += ics_unet_confusion_batch(unet, x, lab, B + 100, 0.8f) == 0;
+  bad += ics_unet_confusion_read(unet, NULL, occ, &oor, &vox) == 0;
+  bad += ics_unet_confusion_read(unet, mat, NULL, &oor, &vox) == 0;
+  bad += ics_unet_confusion_read(unet, mat, occ, NULL, &vox) == 0;
+  bad += ics_unet_confusion_read(unet, mat, occ, &oor, NULL) == 0;
+  bad += ics_unet_confusion_open(NULL) == 0;
+  bad += ics_unet_confusion_open(vae) == 0;
+  bad += ics_unet_confusion_reset(vae) == 0;
+  bad += ics_unet_confusion_step(vae, 0.8f) == 0;
+  bad += ics_unet_confusion_batch(vae, x, lab, B, 0.8f) == 0;
+  bad += ics_unet_confusion_read(vae, mat, occ, &oor, &vox) == 0;
+  if (bad) { fprintf(stderr, "confusion: %d invalid calls accepted\n", bad); return 1; }
+  OK(ics_unet_confusion_batch(unet, x, lab, B, 0.8f));                      /* still usable */
+  OK(ics_unet_confusion_read(unet, mat, occ, &oor, &vox));
+  OK(ics_unet_train_step(unet, x, lab, B, mm));
+  free(mat);
+  return 0;
+}
+
 /* Fed steps: the pack op alone on buffers of the exact size (every dtype mix, every label kind, odd column counts), then the
  * whole feed on both engines -- open, slot, submit, fed train / test step, metrics (late and twice), close, re-open with
  * another layout -- and every refusal, after which the feed and the engine still work. */
@@ -1150,6 +1240,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_upload_batch(vae, x, cond, eps, B));
   OK(ics_vae_train_step_resident(vae, mv));
   if (class_weight_walk(unet, vae, uc.num_classes, x, lab, B, with_comm)) return 1;
+  if (confusion_walk(unet, vae, uc.num_classes, d, x, lab, B)) return 1;
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
   if (feed_walk(unet, vae, d, C, B, vc.cond_shape, vc.latent_dim)) return 1;

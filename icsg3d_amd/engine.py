@@ -312,6 +312,48 @@ def label_counts(labels, num_classes, label_kind=None):
     return counts, int(oor[0])
 
 
+def _label_kind_of(lab):
+    kinds = {np.dtype(np.uint8): "u8", np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+    if lab.dtype not in kinds:
+        raise ValueError("labels must be uint8, float32 or float64 class ids, not %s" % lab.dtype)
+    return kinds[lab.dtype]
+
+
+def confusion(true, pred, num_classes, mask=None, label_kind=None):
+    """Single-op entry (ics_op_confusion): the confusion matrix of (true label, predicted label) pairs, counted on the
+    device.  true: uint8 / float32 / float64 class ids of any shape (the kind follows the dtype unless label_kind says
+    otherwise; "onehot" is refused by the library); pred and mask: uint8 arrays of the same size.  Returns
+    (matrix int64 (num_classes, num_classes) [true, predicted], occupancy int64 (2, 2) [true != 0, mask != 0] or None
+    without a mask, out_of_range int): pairs whose true value is no class id (below 0, >= num_classes, non-integral,
+    NaN) or whose prediction is >= num_classes are counted in out_of_range and in no bin; the occupancy table covers
+    the pairs with a valid true label."""
+    lib = L.load()
+    t = np.asarray(true)
+    if label_kind is None:
+        label_kind = _label_kind_of(t)
+    if label_kind not in FEED_LABELS or label_kind == "none":
+        raise ValueError("label_kind must be one of u8, f32, f64")
+    t = np.ascontiguousarray(t, FEED_LABELS[label_kind][1]).reshape(-1)
+    p = np.ascontiguousarray(pred, np.uint8).reshape(-1)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if label_kind != "onehot" and (p.size != t.size or (m is not None and m.size != t.size)):
+        raise ValueError("true, pred and mask must have the same number of elements")
+    k = int(num_classes)
+    matrix = np.zeros((max(k, 0), max(k, 0)), np.int64)
+    occ = None if m is None else np.zeros((2, 2), np.int64)
+    oor = np.zeros(1, np.int64)
+    L.check(lib.ics_op_confusion(t.ctypes.data_as(C.c_void_p), FEED_LABELS[label_kind][0], L.u8ptr(p), L.u8ptr(m), p.size, k,
+                                 L.i64ptr(matrix), L.i64ptr(occ), L.i64ptr(oor)))
+    return matrix, occ, int(oor[0])
+
+
+def confusion_grid():
+    """(lanes per block, pairs per lane and pass, grid cap) of the confusion kernel (ics_op_confusion_grid)."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    L.check(L.load().ics_op_confusion_grid(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
 def comm_unique_id():
     buf = C.create_string_buffer(128)
     L.check(L.load().ics_comm_unique_id(buf))
@@ -418,6 +460,36 @@ class UnetEngine(_Net, _FeedMixin):
     def predict_resident(self, labels_only=False, thresh=0.8):
         """model.predict on the uploaded batch, enqueued only; the outputs stay in HBM (benchmark path)."""
         L.check(self._lib.ics_unet_predict_resident(self._h, 1 if labels_only else 0, float(thresh)))
+
+    # ---- the confusion accumulator (include/icsg3d.h "confusion matrix"): eval-mode passes only, nothing is trained
+    def confusion_open(self):
+        """A zeroed device accumulator in the engine's memory (allocated by the first open)."""
+        L.check(self._lib.ics_unet_confusion_open(self._h))
+
+    def confusion_reset(self):
+        L.check(self._lib.ics_unet_confusion_reset(self._h))
+
+    def confusion_step(self, thresh=0.8):
+        """Eval forward on the resident batch (uploaded WITH labels), argmax / sig >= thresh, and the count of
+        (label, species, mask) added to the accumulator.  Enqueued only."""
+        L.check(self._lib.ics_unet_confusion_step(self._h, float(thresh)))
+
+    def confusion_batch(self, x, labels, thresh=0.8):
+        """upload_batch + confusion_step for host arrays of any length (max_batch samples at a time)."""
+        x = self._check_x(x)
+        lab = self._labels(labels, x.shape[0])
+        for i in range(0, x.shape[0], self.max_batch):
+            xs, ls = x[i:i + self.max_batch], lab[i:i + self.max_batch]
+            L.check(self._lib.ics_unet_confusion_batch(self._h, L.fptr(xs), L.u8ptr(ls), xs.shape[0], float(thresh)))
+
+    def confusion_read(self):
+        """Waits for the stream -> dict(matrix int64 (K, K) [true, predicted], occupancy int64 (2, 2)
+        [true != 0, mask != 0], out_of_range, voxels).  Does not reset."""
+        k = self.num_classes
+        matrix, occ = np.zeros((k, k), np.int64), np.zeros((2, 2), np.int64)
+        oor, vox = np.zeros(1, np.int64), np.zeros(1, np.int64)
+        L.check(self._lib.ics_unet_confusion_read(self._h, L.i64ptr(matrix), L.i64ptr(occ), L.i64ptr(oor), L.i64ptr(vox)))
+        return {"matrix": matrix, "occupancy": occ, "out_of_range": int(oor[0]), "voxels": int(vox[0])}
 
     _n_metrics = 5
 

@@ -243,6 +243,43 @@ class _BestCheckpoint:
                 self.model.save(self.filepath)
 
 
+class _ClassReport:
+    """train_generator(class_report=True): on every new best val_loss (the monitors' rule: UnetMonitor.on_epoch_end) the
+    validation generator goes through the engine's confusion accumulator -- eval-mode passes, nothing is trained -- and
+    the writer rank leaves class_report_best.{json,csv} and confusion_best.npy in `sdir` (icsg3d_amd/classreport.py).
+    Runs on every rank: each scores its own validation shard and the integer counts are summed over the process group."""
+
+    def __init__(self, owner, val_gen, sdir, thresh=0.8):
+        self.o, self.val_gen, self.sdir, self.thresh = owner, val_gen, sdir, float(thresh)
+        self.min_val_loss = np.inf
+
+    def on_epoch_end(self, epoch, logs=None):
+        v = (logs or {}).get("val_loss")
+        if v is None or not v < self.min_val_loss:
+            return
+        self.min_val_loss = v
+        from .. import classreport
+        o, acc = self.o, None
+        for i in range(len(self.val_gen)):
+            X, y = self.val_gen[i]
+            X = np.asarray(X, np.float32)
+            eng = o._engine(len(X))
+            if acc is None:
+                eng.confusion_open()
+                acc = eng
+            eng.confusion_batch(X, _to_labels(y[0] if isinstance(y, (list, tuple)) else y, o.num_classes), self.thresh)
+        if acc is None:
+            return
+        r = acc.confusion_read()
+        dist = o._dp[0] if o._dp is not None and o._dp[2] > 1 else None
+        matrix, occ, tail = classreport.reduce_over_ranks(dist, [r["matrix"], r["occupancy"],
+                                                                 np.array([r["out_of_range"], r["voxels"]])])
+        if o._dp_is_writer():
+            classreport.write(self.sdir, matrix, occ, stem="_best", report_name="class_report",
+                              extra={"epoch": int(epoch), "val_loss": float(v), "thresh": self.thresh,
+                                     "out_of_range": int(tail[0]), "voxels_counted": int(tail[1])})
+
+
 class AtomUnet(DataParallelMixin):
     """U-Net for semantic segmentation of electron-density maps (unet/unet.py:224-391).
 
@@ -326,12 +363,17 @@ class AtomUnet(DataParallelMixin):
             self._host_weights.update({k: np.asarray(v, np.float32) for k, v in w.items()})
 
     # ---- reference methods
-    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/", monitor=False, feed=False):
+    def train_generator(self, train_gen, val_gen, epochs=100, output_dir="output/unet/", monitor=False, feed=False,
+                        class_report=False):
         """feed=True: fed steps, see fit_generator.
         monitor=True: the writer rank also draws TrainingPlot's pictures on the GPU (icsg3d_amd.monitor.UnetMonitor):
-        the segmentation sheets on a new best val_loss and the loss curve every epoch, without matplotlib."""
+        the segmentation sheets on a new best val_loss and the loss curve every epoch, without matplotlib.
+        class_report=True: on a new best val_loss the validation generator is scored per class on the GPU
+        (_ClassReport: class_report_best.{json,csv}, confusion_best.npy).  Neither changes a bit of the training."""
         print("Training...")
         callbacks = [_BestCheckpoint(self.model, self.filepath)]
+        if class_report and val_gen is not None:
+            callbacks.append(_ClassReport(self, val_gen, output_dir))
         if self._dp_is_writer():
             callbacks.append(TrainingPlot(val_gen, output_dir))
             if monitor:

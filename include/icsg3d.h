@@ -961,6 +961,50 @@ int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1,
  * (0 gives zeros); ncls 2 .. 127.  Synchronous, the calling thread's op stream and scratch. */
 int ics_op_label_counts(const void* labels, int label_kind, size_t n, int ncls, int64_t* counts, int64_t* out_of_range);
 
+/* ---- confusion matrix: the U-Net scored per species on the device (eval_unet.py, train_unet.py --class_report) ----
+ * The reference scores its segmentation with two global ratios (unet/unet.py:159-193, f1_m and wr_m), both dominated by
+ * the ~98 % background voxels.  A per-class table needs the argmax species of generate.py:221-222, the thresholded sigmoid
+ * of generate.py:224-225 and the true labels S of unet/data.py:81-100 side by side: all three are in device memory after
+ * a labels predict, so they are counted there.
+ *
+ * ics_op_confusion: n (true, predicted) pairs from host arrays.  true_labels are uint8, float64 or float32 ids
+ * (label_kind 1, 2, 3 of ics_feed_config; the one-hot kind 4 is refused), pred is uint8.  matrix [ncls*ncls] is OVERWRITTEN:
+ * [t * ncls + p] = the pairs whose values are both class ids -- t by ics_op_label_counts' rule in its own type
+ * (0 <= t < ncls, integral, no NaN), p < ncls; every other pair is counted in *out_of_range and indexes nothing, so
+ * sum(matrix) + *out_of_range = n.  With a mask (uint8, generate.py:224-225's sig >= thresh), occupancy[4] receives the
+ * 2 x 2 table [(t != 0) * 2 + (mask != 0)] over the pairs whose t is a class id (the sigmoid target is S != 0,
+ * unet/data.py:87); mask and occupancy are both NULL or both given.  n is arbitrary (0 gives zeros); ncls 2 .. 127.
+ * Alignment: true_labels must be aligned to its element size (1, 4 or 8 bytes); pred and mask are bytes.  Refused with
+ * nothing written: null arguments, ncls outside [2, 127], a one-hot or unknown kind, an unaligned label pointer.
+ * Synchronous, the calling thread's op stream and scratch. */
+int ics_op_confusion(const void* true_labels, int label_kind, const uint8_t* pred, const uint8_t* mask_or_null, size_t n,
+                     int ncls, int64_t* matrix, int64_t* occupancy_or_null, int64_t* out_of_range);
+/* The kernel's launch constants: lanes per block, pairs one lane takes per grid-stride pass, the grid cap.  A count
+ * above threads * lane_pairs * max_blocks pairs makes every lane pass more than once (tests size their inputs by it). */
+int ics_op_confusion_grid(int* threads, int* lane_pairs, int* max_blocks);
+/* An accumulator [ncls*ncls + 1 + 4] of 64-bit counts in the U-Net engine's own memory (num_classes must be <= 127).
+ * It is allocated by the first open -- an engine that never opens one keeps its memory layout -- and kept until the
+ * engine is destroyed; opening again, like ics_unet_confusion_reset, zeroes it.  Every entry point below runs eval-mode
+ * forward passes only (model.predict, generate.py:220): weights, BatchNorm moving statistics, Adam's moments and step
+ * count and the class-weight table are not touched.  A VAE handle, a null argument, and a reset / step / batch / read
+ * before open are refused with nothing written. */
+int ics_unet_confusion_open(ics_net* net);
+int ics_unet_confusion_reset(ics_net* net);
+/* On the resident batch, which must have been placed WITH labels (ics_unet_upload_batch with labels,
+ * ics_unet_voxelise_batch, a fed step): eval forward, argmax species and sig >= thresh (generate.py:221-225; the fused
+ * head at num_classes 95, GEMM + softmax + labels kernel otherwise), then the count of (label, species, mask) added to
+ * the accumulator.  Enqueued only, no host wait.  The species / mask volumes stay where a labels predict leaves them:
+ * ics_unet_render_slice_resident(which = 1) works afterwards. */
+int ics_unet_confusion_step(ics_net* net, float thresh);
+/* The upload of ics_unet_upload_batch(x, labels, batch) followed by ics_unet_confusion_step, for callers with host
+ * arrays.  Returns once the upload has read x and labels (the caller may reuse them); the forward pass and the count are
+ * enqueued only, so the host can load the next batch while this one runs. */
+int ics_unet_confusion_batch(ics_net* net, const float* x, const uint8_t* labels, int batch, float thresh);
+/* Waits for the engine's stream and copies the accumulator out: matrix [ncls*ncls], occupancy [4], *out_of_range,
+ * *voxels = the pairs counted since the last open / reset (sum(matrix) + *out_of_range).  May be called repeatedly; it
+ * does not reset. */
+int ics_unet_confusion_read(ics_net* net, int64_t* matrix, int64_t occupancy[4], int64_t* out_of_range, int64_t* voxels);
+
 #ifdef __cplusplus
 }
 #endif

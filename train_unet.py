@@ -51,6 +51,9 @@ if __name__ == "__main__":
                         "background 0) instead of the reference's scalar num_classes; the counts are taken on the GPU")
     p.add_argument("--monitor", action="store_true",
                    help="draw the reference's training pictures on the GPU into the output folder (icsg3d_amd/monitor.py)")
+    p.add_argument("--class_report", action="store_true",
+                   help="on every new best val_loss, score the validation set per class on the GPU: class_report_best.json / "
+                        ".csv and confusion_best.npy in the output folder (icsg3d_amd/classreport.py; eval_unet.py for a whole run)")
     p.add_argument("--gpus", type=int, default=0,
                    help="data parallel over N GPUs of this node: without torch.distributed.run the script starts its N "
                         "ranks itself (icsg3d_amd/launcher.py); 0 = whatever the environment says (default)")
@@ -109,7 +112,8 @@ if __name__ == "__main__":
     if dp:
         unet.enable_data_parallel(dp[0], rank, world, sync_bn=bool(a.sync_bn), force=world == 1)
     unet.train_generator(training_generator, validation_generator, epochs=a.epochs,
-                         output_dir=os.path.join("output", "unet", mode), monitor=a.monitor, feed=a.feed)
+                         output_dir=os.path.join("output", "unet", mode), monitor=a.monitor, feed=a.feed,
+                         class_report=a.class_report)
     if rank == 0:
         unet.save_(weights, os.path.splitext(weights)[0] + ".h5")
     if dp:
