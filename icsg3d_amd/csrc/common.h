@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "up8.h"
+#include "up125.h"
 
 namespace ics {
 
@@ -131,6 +132,8 @@ enum ConvFlags : int {
   CF_NO_UP8 = 1 << 25,           // ICSG3D_NO_UP8: up-split backward through the 27 tap copies of dy (pool27) instead of the 8 pooled volumes (up8.h)
   CF_UP8 = 1 << 26,            // internal: the A operand (conv_fwd_kernel) / dY operand (conv_wgrad_kernel) of this coarse-grid GEMM is the
                                // 8-volume layout of up8.h at the source / dy pointer
+  CF_NO_UP125 = 1 << 27,       // ICSG3D_NO_UP125: up-split backward of the large layers through pool8 and the 27-tap GEMMs, not the 125-product form (up125.h)
+  CF_FORCE_UP125 = 1 << 28,    // ICSG3D_FORCE_UP125: the 125-product form wherever its layout serves, whatever the size (tests)
   CF_ZBATCH = 1 << 20,         // internal: conv_fwd_kernel runs gridDim.z independent GEMMs (launch_gemm_zbatch)
   // (131072 was CF_NO_TICKET, the per-layer bias-gradient finalize of round 3: removed in round 6 with the other switches
   // DESIGN.md records as rejected -- ICSG3D_SIDE_STREAM, ICSG3D_NO_ARENA)
@@ -281,6 +284,14 @@ int launch_conv_wgrad_winog(hipStream_t st, const ConvGeom& g, const float* vt, 
                             int row_pitch, int row_off, float* z_scratch, float* m_scratch);
 // nz independent plain GEMMs out_z[M][N] = A_z[M][K] x W_z[K][N] (conv_igemm.hip; W_z packed [K/4][N][4])
 int launch_gemm_zbatch(hipStream_t st, int nz, int M, int K, int N, const float* A, const float* Wp, float* out, int flags);
+// nz independent backward-weight GEMMs ws_z[split][K][N] = sum over the split's rows of x_z[M][K]^T dy_z[M][N] (x, dy and
+// the partials advance by whole matrices per z; fixed-order split-K, the caller reduces).  *ksplit: splits per z.
+int wgrad_zbatch_splits(int nz, int M, int K, int N);
+int launch_wgrad_zbatch(hipStream_t st, int nz, int M, int K, int N, const float* x, const float* dy, float* ws, int ksplit);
+// the 27 class weight images of up125.h (up125_weight_floats(N, Cu) floats at dst)
+int launch_pack_up125(hipStream_t st, const float* w, int Cin_total, int N, int c_off, int Cu, float* dst);
+// the same outside a pack table (up125.hip)
+int launch_pack_up125_pieces(hipStream_t st, const float* w, int Cin_total, int N, int c_off, int Cu, float* dst);
 // the same 27-product form for NARROW outputs (Cout 16 / 32: the VAE decoder's d2 / d3), conv_up3n.hip; *stat_blocks = blocks
 // of 512 fine voxels written to stat_partial
 bool conv_up3n_ok(const ConvGeom& g, const ConvSrc& s0);

@@ -76,6 +76,8 @@ int conv_flags_from_env() {
   if (getenv("ICSG3D_NO_POOL_PRESUM")) f |= CF_NO_POOL_PRESUM;
   if (getenv("ICSG3D_NO_HEAD_LABELS")) f |= CF_NO_HEAD_LABELS;
   if (getenv("ICSG3D_NO_UP8")) f |= CF_NO_UP8;
+  if (getenv("ICSG3D_NO_UP125")) f |= CF_NO_UP125;
+  if (getenv("ICSG3D_FORCE_UP125")) f |= CF_FORCE_UP125;
   { const char* e = getenv("ICSG3D_UP3_BIG_MIN_WG"); if (e && *e && strtoul(e, nullptr, 10) <= 1) f |= CF_UP3_BIG_ALWAYS; }
   return f;
 }
@@ -1975,7 +1977,7 @@ int launch_conv_fwd_par(hipStream_t st, const ConvGeom& g, const ConvSrc& src, c
 // whatever their size.  The engine records the jobs once (the launch_pack_* calls below append to g_pack_rec
 // instead of launching) and replays them with ONE pack_table_kernel launch per step.
 struct PackJob {
-  int kind;                 // 0 fwd, 1 bwd, 2 sub, 3 fwd_sub, 4 par, 5 wino, 6 up3, 7 up3n
+  int kind;                 // 0 fwd, 1 bwd, 2 sub, 3 fwd_sub, 4 par, 5 wino, 6 up3, 7 up3n, 8 up125
   const float* w;
   float* dst;
   int a[9];
@@ -2080,7 +2082,7 @@ int launch_conv_fwd_ablate(hipStream_t st, const ConvGeom& g, const ConvSrc* src
 // Backward-weight kernel: ws[split][k][n] = sum_{m in split} A[m][k] * dy[m][n]
 // =====================================================================================
 template <int WM, int WN, int TM, int TN, bool VEC, bool DYVEC, bool AFF = true, bool UP = true, bool THIN = false,
-          int ABL = 0, bool UP8 = false>
+          int ABL = 0, bool UP8 = false, bool ZB = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0, ConvSrc s1,
                                                           const float* __restrict__ dy, int ldy,
                                                           int n_load,
@@ -2101,6 +2103,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(ConvGeom g, ConvSrc s0,
   const int S = g.S, lg = g.lgS;
   const int M = g.B << (3 * lg);
   const int K = g.taps * g.Cin;
+  // ZB (launch_wgrad_zbatch): gridDim.y INDEPENDENT GEMMs, one per y -- the classes of one group of the 125-product
+  // up-split backward (up125.h): x, dy and the split-K partials advance by whole matrices
+  if (ZB) {
+    s0.p += (size_t)blockIdx.y * (size_t)M * (size_t)s0.C;
+    dy += (size_t)blockIdx.y * (size_t)M * (size_t)ldy;
+    ws += (size_t)blockIdx.y * (size_t)(gridDim.x / (unsigned)(ktiles * ntiles)) * (size_t)K * (size_t)g.Cout;
+  }
 
   int bid = blockIdx.x;
   const int nt_i = bid % ntiles; bid /= ntiles;
@@ -2930,12 +2939,12 @@ size_t conv_wgrad_workspace_floats(const ConvGeom& g, const ConvSrc* src, int ns
 }
 
 template <int WM, int WN, int TM, int TN, bool VEC, bool DYVEC, bool AFF = true, bool UP = true, bool THIN = false,
-          int ABL = 0, bool UP8 = false>
+          int ABL = 0, bool UP8 = false, bool ZB = false>
 static int launch_wgrad_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0, const ConvSrc& s1,
-                            const float* dy, int ldy, int n_load, float* ws, const WgradPlan& p) {
+                            const float* dy, int ldy, int n_load, float* ws, const WgradPlan& p, int nz = 1) {
   constexpr int KT = WM * TM * 32, NT = WN * TN * 32;
   const size_t lds = (size_t)2 * 32 * (KT + NT) * sizeof(float);
-  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, VEC, DYVEC, AFF, UP, THIN, ABL, UP8>;
+  auto kern = conv_wgrad_kernel<WM, WN, TM, TN, VEC, DYVEC, AFF, UP, THIN, ABL, UP8, ZB>;
   static DevOnce attr;
   int dev;
   if (attr.need(&dev)) {
@@ -2946,11 +2955,11 @@ static int launch_wgrad_cfg(hipStream_t st, const ConvGeom& g, const ConvSrc& s0
   static const std::string id = std::string("conv_wgrad_kernel<") + std::to_string(WM) + ", " + std::to_string(WN) +
                                 ", " + std::to_string(TM) + ", " + std::to_string(TN) + ", " + tf(VEC) + ", " +
                                 tf(DYVEC) + ", " + tf(AFF) + ", " + tf(UP) + ", " + tf(THIN) + ", " +
-                                std::to_string(ABL) + (UP8 ? ", UP8>" : ">");
+                                std::to_string(ABL) + (UP8 ? ", UP8>" : (ZB ? ", ZB>" : ">"));
   g_last_kernel_id = id.c_str();
   Up8Geom u8;
   if (UP8) u8 = up8_geom(g.B, g.S, g.lgS, g.Cout / 27);   // g is the coarse grid; N = 27 taps x the channels of dy
-  ICS_LAUNCH(kern, dim3(p.ktiles * p.ntiles * p.ksplit), dim3(256), lds, st, g, s0, s1, dy,
+  ICS_LAUNCH(kern, dim3(p.ktiles * p.ntiles * p.ksplit, ZB ? nz : 1), dim3(256), lds, st, g, s0, s1, dy,
                      ldy, n_load, ws, p.ktiles, p.ntiles, p.rows_per_split, u8);
   ICS_HIP(hipGetLastError());
   return 0;
@@ -3138,6 +3147,31 @@ int launch_conv_wgrad(hipStream_t st, const ConvGeom& g, const ConvSrc* src, int
     ICS_TRY(launch_reduce_splits(st, workspace, p.ksplit, n_elems, g.Cout, dw, ldw, sub_rows, row_pitch, row_off));
   }
   return 0;
+}
+
+// nz independent plain backward-weight GEMMs on the 128 x 128 tile (see conv_wgrad_kernel ZB).  One round of the resident
+// workgroup slots over ALL z: every split costs the caller's reduction a pass over K x N per z.
+int wgrad_zbatch_splits(int nz, int M, int K, int N) {
+  const long base = (long)((K + 127) / 128) * ((N + 127) / 128) * nz;
+  const long ks_max = std::max<long>(1, M / 256);
+  return (int)std::max<long>(1, std::min<long>(std::min<long>(512 / base, ks_max), 512));
+}
+int launch_wgrad_zbatch(hipStream_t st, int nz, int M, int K, int N, const float* x, const float* dy, float* ws, int ksplit) {
+  ICS_CHECK(nz >= 1 && nz <= 65535 && M >= 1 && K % 32 == 0 && N % 4 == 0 && ksplit >= 1, "z-batched wgrad: K % 32, N % 4 required");
+  ICS_CHECK((size_t)M * (size_t)std::max(K, N) < ((size_t)1 << 30), "z-batched wgrad: matrix too large for 32-bit offsets");
+  const ConvGeom g{M, 1, 0, K, N, 1, K, (N + 31) / 32 * 32, 0};
+  const ConvSrc s0{x, nullptr, nullptr, K, 0, ACT_NONE, 0};
+  ConvSrc s1 = s0;
+  s1.C = 0;
+  WgradPlan p;
+  p.vec = true; p.thin = false;
+  p.kt = 128; p.nt = 128;
+  p.ktiles = (K + 127) / 128; p.ntiles = (N + 127) / 128;
+  p.rows_per_split = ((M + ksplit - 1) / ksplit + 31) / 32 * 32;
+  p.ksplit = (M + p.rows_per_split - 1) / p.rows_per_split;
+  ICS_CHECK(p.ksplit <= ksplit, "z-batched wgrad: split plan");
+  p.ksplit = ksplit;   // the partial stride the caller laid out; a split past the last row writes zeros
+  return launch_wgrad_cfg<2, 2, 2, 2, true, true, false, false, false, 0, false, true>(st, g, s0, s1, dy, N, N, ws, p, nz);
 }
 
 // =====================================================================================
@@ -3469,6 +3503,16 @@ int launch_pack_up3(hipStream_t st, const float* w, int Cin_total, int Cout, int
   return 0;
 }
 
+// the 27 class weight images of the 125-product up-split backward (up125.h): one job (or launch) of up125_pack_piece
+int launch_pack_up125(hipStream_t st, const float* w, int Cin_total, int N, int c_off, int Cu, float* dst) {
+  ICS_CHECK(N % 4 == 0, "up125 weights: Cout must be a multiple of 4");
+  if (g_pack_rec) {
+    g_pack_rec->push_back(PackJob{8, w, dst, {Cin_total, N, c_off, Cu, 0, 0, 0, 0, 0}, (unsigned long long)up125_pack_pieces(N, Cu), 0});
+    return 0;
+  }
+  return launch_pack_up125_pieces(st, w, Cin_total, N, c_off, Cu, dst);
+}
+
 // One launch for a whole table of pack jobs.  Destination buffers are zero-initialised at allocation and the
 // padding of a packed image never changes, so jobs only write their valid elements (two jobs may share a
 // destination: the head packs soft | sig side by side) -- no ordering between jobs is needed.
@@ -3504,6 +3548,7 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const PackJob* __restri
     case 5: pack_wino_pair(i, J.w, a[0], a[1], a[2], a[3], a[4], J.dst, a[5]); break;
     case 6: pack_up3_pair(i, J.w, a[0], a[1], a[2], a[3], J.dst); break;
     case 7: pack_up3n_pair_dev(i, J.w, a[0], a[1], a[2], a[3], J.dst); break;
+    case 8: up125_pack_piece(i, J.w, a[0], a[1], a[2], a[3], J.dst); break;
     default: J.dst[i] = pack_par_value(i, J.w, a[0], a[1], a[2], a[3], a[4], a[5]); break;
   }
 }

@@ -176,6 +176,16 @@ int launch_axpy(hipStream_t st, float* y, const float* x, size_t n, float a);
 int launch_pool27(hipStream_t st, const float* dy, int B, int S, int N, float* out, int ldo);
 // the same sums as the 8 volumes of up8.h; u = up8_geom(B, S / 2, log2(S / 2), N)
 int launch_pool8(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up8Geom& u);
+// ---- the 125-product form of the up-split backward (up125.h, up125.hip); u = up125_geom(B, S, N, Cu)
+int launch_pool125(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up125Geom& u);
+// the 27 x-class volumes of the low-res source s (affine and activation applied), class q at slot up125_slot(q)
+int launch_up125_xclass(hipStream_t st, const ConvSrc& s, float* out, const Up125Geom& u);
+// dxl[B (S/2)^3][Cu] from the 27 class outputs
+int launch_up125_combine(hipStream_t st, const float* cls, float* dxl, const Up125Geom& u);
+// split-K partials of the four class groups (launch_wgrad_zbatch): float offset of group g and its split count
+struct Up125Splits { unsigned long long off[4]; int ks[4]; };
+// dw_up[Cu][27 N] from the partials of the 125 block gradients
+int launch_up125_contract(hipStream_t st, const float* ws, const Up125Splits& p, float* dw, const Up125Geom& u);
 int launch_permute_up_dw(hipStream_t st, const float* tmp, int Cu, int N, int Cin, int c_off, float* dw);
 
 }  // namespace ics

@@ -201,6 +201,8 @@ struct ConvLayer {
   int ldS = 0;
   bool up8 = false;                            // dy pooled into the 8 volumes of up8.h (dy8) instead of the 27 tap copies (dyS)
   float *dy8 = nullptr;                        // [8][maxB * (S/2+1)^3][Cout]; a batch B uses volumes B * (S/2+1)^3 * Cout floats apart
+  bool up125 = false;                          // large batches of this layer take the 125-product form (up125.h; see up125_ok)
+  float *w125 = nullptr;                       // its 27 class weight images
   float *dA_skip = nullptr, *dxl = nullptr;    // [M][Cs] grad of the skip input; [M/8][Cu] grad of the low-res input
   float *dw_up = nullptr;                      // [Cu][27*Cout] GEMM result before the permute into G
 };
@@ -240,6 +242,10 @@ struct Net {
   float* ws_bwd = nullptr;   size_t ws_bwd_n = 0;
   float* ws_bwd2 = nullptr;  size_t ws_bwd2_n = 0;    // BN-backward sums folded into a backward-data epilogue
   float* ws_wgrad = nullptr; size_t ws_wgrad_n = 0;
+  // one scratch set of the 125-product up-split backward (up125.h) for the largest layer that takes it (the layers run
+  // one after another on one stream): pooled blocks, x classes, class outputs, split-K partials of the block gradients
+  float *u125_P = nullptr, *u125_X = nullptr, *u125_O = nullptr, *u125_ws = nullptr;
+  size_t u125_P_n = 0, u125_X_n = 0, u125_ws_n = 0;
   float* ws_fwd = nullptr;   size_t ws_fwd_n = 0;     // forward / backward-data split-K partial sums
   bool want_tie_stats = false;      // forward passes write the max-pool tie masks / sums although no weight gradients follow
                                     // (the perceptual U-Net's pass over the reconstruction inside a DFC-VAE train step)
@@ -578,6 +584,36 @@ static bool up8_ok(const Net& n, const ConvLayer& L) {
   return true;
 }
 
+// The 125-product form (up125.h) replaces pool8 and the two 27-tap coarse-grid GEMMs of a layer where the class GEMMs
+// are large enough to run like the GEMMs they replace: wide layers (Cout and Cu multiples of 128) at batches with
+// kUp125MinRows tile rows B (S/4)^3 or more (profiles/up125_ab.txt).  It needs the up8
+// conditions (smaller batches of the same handle run UP8), one stream (the scratch set is shared between the layers) and
+// up125_shape_ok.  ICSG3D_NO_UP125 restores UP8 per handle; ICSG3D_FORCE_UP125 engages the form wherever the layout
+// serves, whatever the size (tests).
+constexpr size_t kUp125MinRows = 2048;
+static bool up125_layer_ok(const Net& n, const ConvLayer& L) {
+  if ((n.flags & CF_NO_UP125) || !L.up8 || n.side_on || n.sync() != nullptr) return false;
+  if (!up125_shape_ok(L.S, L.Cout, L.Cu, n.maxB)) return false;
+  if (n.flags & CF_FORCE_UP125) return true;
+  return L.Cout % 128 == 0 && L.Cu % 128 == 0 && up125_geom(n.maxB, L.S, L.Cout, L.Cu).rows >= kUp125MinRows;
+}
+static bool up125_ok(const Net& n, const ConvLayer& L, int B) {
+  if (!L.up125) return false;
+  return (n.flags & CF_FORCE_UP125) || up125_geom(B, L.S, L.Cout, L.Cu).rows >= kUp125MinRows;
+}
+// split-K plan of the four z-batched backward-weight launches at batch B; returns the floats of partials they write
+static size_t up125_splits(const ConvLayer& L, int B, Up125Splits* sp) {
+  const int rows = (int)up125_geom(B, L.S, L.Cout, L.Cu).rows;
+  size_t off = 0;
+  for (int g = 0; g < 4; ++g) {
+    const int nz = up125_group_classes(g), nb = 8 >> g;
+    sp->off[g] = off;
+    sp->ks[g] = wgrad_zbatch_splits(nz, rows, L.Cu, nb * L.Cout);
+    off += (size_t)nz * sp->ks[g] * L.Cu * nb * L.Cout;
+  }
+  return off;
+}
+
 // Layers whose (last) source is nearest-upsampled: [skip | up] concat convs (U-Net c13/c15/c17) and the VAE
 // decoder's d1..d3 (Cs = 0).
 static int enable_split_up(Net& n, ConvLayer& L) {
@@ -602,6 +638,16 @@ static int enable_split_up(Net& n, ConvLayer& L) {
   } else {
     ICS_TRY(n.alloc(&L.dyS, M / 8 * L.ldS));
     ICS_HIP(hipMemsetAsync(L.dyS, 0, M / 8 * L.ldS * sizeof(float), n.st));   // pad columns stay zero
+  }
+  L.up125 = up125_layer_ok(n, L);
+  if (L.up125) {
+    ICS_TRY(n.alloc(&L.w125, up125_weight_floats(L.Cout, L.Cu)));
+    const size_t rows = up125_geom(n.maxB, L.S, L.Cout, L.Cu).rows;
+    n.u125_P_n = std::max(n.u125_P_n, up125_pooled_floats(rows, L.Cout));
+    n.u125_X_n = std::max(n.u125_X_n, up125_class_floats(rows, L.Cu));
+    Up125Splits sp;
+    for (int b = 1; b <= n.maxB; ++b)
+      if (up125_ok(n, L, b)) n.u125_ws_n = std::max(n.u125_ws_n, up125_splits(L, b, &sp));
   }
   ICS_TRY(n.alloc(&L.dxl, M / 8 * L.Cu));
   ICS_TRY(n.alloc(&L.dw_up, (size_t)L.Cu * 27 * L.Cout));
@@ -720,7 +766,13 @@ static int alloc_workspaces(Net& n, bool need_bwd) {
   if (need_bwd) {
     ICS_TRY(n.alloc(&n.ws_bwd, n.ws_bwd_n + 16));
     ICS_TRY(n.alloc(&n.ws_wgrad, wg + 16));
-    size_t b2 = 0;    // [2][Npad][ceil(M/64)] for the widest layer
+    if (n.u125_P_n && n.u125_P == nullptr) {
+      ICS_TRY(n.alloc(&n.u125_P, n.u125_P_n));
+      ICS_TRY(n.alloc(&n.u125_X, n.u125_X_n));
+      ICS_TRY(n.alloc(&n.u125_O, n.u125_X_n));
+      ICS_TRY(n.alloc(&n.u125_ws, n.u125_ws_n));
+    }
+    size_t b2 = 0;   // [2][Npad][ceil(M/64)] for the widest layer
     for (auto& Lp : n.layers)
       if (Lp->has_bn) b2 = std::max(b2, (size_t)2 * Lp->Npad * ((n.rows(*Lp, n.maxB) + 63) / 64));
     n.ws_bwd2_n = b2;
@@ -811,6 +863,7 @@ static int pack_layer(Net& n, ConvLayer& L, bool need_bwd) {
       ICS_TRY(launch_pack_sub(n.st, n.tp(L.t_w), L.taps, L.Cin, L.Cout, 0, L.Cs, 1, L.wf_skip, L.Kpad_b,
                               round_up(L.Cs, 32)));
     ICS_TRY(launch_pack_sub(n.st, n.tp(L.t_w), L.taps, L.Cin, L.Cout, L.Cs, L.Cu, 0, L.w_up, L.ldS, round_up(L.Cu, 32)));
+    if (L.up125) ICS_TRY(launch_pack_up125(n.st, n.tp(L.t_w), L.Cin, L.Cout, L.Cs, L.Cu, L.w125));
   }
   return 0;
 }
@@ -1015,7 +1068,20 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
   const bool skipfuse = skip_bnfuse_ok(n, L, B);
   ConvLayer* P = L.skip_prod;
   const float* dyp = L.up8 ? L.dy8 : L.dyS;   // the pooled dy both coarse-grid GEMMs read (CF_UP8 in their geometry says which form)
-  if (L.up8) {
+  // the 125-product form (up125.h): pool125, then per class group one z-batched GEMM each way over the tile rows
+  const bool u125 = up125_ok(n, L, B);
+  Up125Geom u5;
+  Up125Splits sp5{};
+  const double fl_up125 = 2.0 * (M / 64) * 125 * L.Cu * L.Cout;
+  static thread_local std::string id125;   // the class GEMMs' kernel id, marked " UP125" in the profile rows
+  auto mark125 = [&]() { id125 = std::string(conv_last_kernel_id()) + " UP125"; conv_set_last_kernel_id(id125.c_str()); };
+  if (u125) {
+    u5 = up125_geom(B, L.S, L.Cout, L.Cu);
+    ICS_CHECK(up125_pooled_floats(u5.rows, L.Cout) <= n.u125_P_n && up125_class_floats(u5.rows, L.Cu) <= n.u125_X_n &&
+                  up125_splits(L, B, &sp5) <= n.u125_ws_n, "up125 scratch smaller than the batch at hand");
+    n.prof.begin(n.st, "pool125:" + L.name, 0, 4.0 * M * L.Cout * (1 + 125.0 / 64));
+    ICS_TRY(launch_pool125(n.st, L.dy, B, L.S, L.Cout, n.u125_P, u5));
+  } else if (L.up8) {
     const double pr = (double)(L.S / 2 + 1) / (L.S / 2);
     n.prof.begin(n.st, "pool8:" + L.name, 0, 4.0 * M * L.Cout * (1 + pr * pr * pr));
     ICS_TRY(launch_pool8(n.st, L.dy, B, L.S, L.Cout, L.dy8, up8_geom(B, L.S / 2, ilog2(L.S / 2), L.Cout)));
@@ -1057,7 +1123,24 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
       P->deferred_skip = &L;
     }
   }
-  {
+  if (u125) {
+    const ConvSrc lo = src_lowres(L);
+    const size_t rows = u5.rows;
+    n.prof.begin(ws, "up125_xclass:" + L.name, 0, 4.0 * (M / 8 * L.Cu) * (1 + 27.0 / 8));
+    ICS_TRY(launch_up125_xclass(ws, lo, n.u125_X, u5));
+    n.prof.end(ws);
+    n.prof.begin(ws, "conv_wgrad:" + L.name + ".up|", fl_up125, 4.0 * rows * (27.0 * L.Cu + 125.0 * L.Cout));
+    for (int g = 0; g < 4; ++g)
+      ICS_TRY(launch_wgrad_zbatch(ws, up125_group_classes(g), (int)rows, L.Cu, (8 >> g) * L.Cout,
+                                  n.u125_X + (size_t)up125_group_slot0(g) * rows * L.Cu,
+                                  n.u125_P + (size_t)up125_group_block0(g) * rows * L.Cout, n.u125_ws + sp5.off[g], sp5.ks[g]));
+    mark125();
+    n.prof.end(ws);
+    n.prof.begin(ws, "wgrad_reduce_splits", 0, 0);
+    ICS_TRY(launch_up125_contract(ws, n.u125_ws, sp5, L.dw_up, u5));
+    ICS_TRY(launch_permute_up_dw(ws, L.dw_up, L.Cu, L.Cout, L.Cin, L.Cs, n.tg(L.t_w)));
+    n.prof.end(ws);
+  } else {
     const ConvGeom g = geom_up_wgrad(L, B);
     const ConvSrc lo = src_lowres(L);
     n.prof.begin(ws, "conv_wgrad:" + L.name + ".up|", fl_up,
@@ -1082,7 +1165,22 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
                             n.fws(), n.ws_fwd_n));
     n.prof.end(n.st);
   }
-  {
+  if (u125) {
+    const size_t rows = u5.rows;
+    n.prof.begin(n.st, "conv_dgrad:" + L.name + ".up|", fl_up125, 4.0 * rows * (27.0 * L.Cu + 125.0 * L.Cout));
+    for (int g = 0; g < 4; ++g)
+      ICS_TRY(launch_gemm_zbatch(n.st, up125_group_classes(g), (int)rows, (8 >> g) * L.Cout, L.Cu,
+                                 n.u125_P + (size_t)up125_group_block0(g) * rows * L.Cout,
+                                 L.w125 + (size_t)up125_group_block0(g) * L.Cout * L.Cu,
+                                 n.u125_O + (size_t)up125_group_slot0(g) * rows * L.Cu, L.flags));
+    mark125();
+    n.prof.end(n.st);
+    n.prof.begin(n.st, "up125_combine:" + L.name, 0, 4.0 * (M / 8 * L.Cu) * (1 + 27.0 / 8));
+    ICS_TRY(launch_up125_combine(n.st, n.u125_O, L.dxl, u5));
+    n.prof.end(n.st);
+    // the producer's BatchNorm-backward sums are not folded into these launches: its own reduce pass runs
+    bwd_stat_done(next, BwdStat{}, 0, round_up(L.Cu, 32));
+  } else {
     const ConvGeom g = geom_up_dgrad(L, B);
     ConvSrc sd = src_plain(dyp, L.ldS);
     n.prof.begin(n.st, "conv_dgrad:" + L.name + ".up|", fl_up,
@@ -3719,8 +3817,9 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
   }
   if (a->kernels && a->kernels_cap > 0) {
     std::string txt;
-    for (const auto& r : n.prof.rows)   // every conv launch, and which pooling of dy the up-split backward ran (pool8: / pool27:)
-      if (r.label.find('|') != std::string::npos || r.label.rfind("pool8:", 0) == 0 || r.label.rfind("pool27:", 0) == 0)
+    for (const auto& r : n.prof.rows)   // every conv launch, and which pooling of dy the up-split backward ran (pool125: / pool8: / pool27:)
+      if (r.label.find('|') != std::string::npos || r.label.rfind("pool8:", 0) == 0 || r.label.rfind("pool27:", 0) == 0 ||
+          r.label.rfind("pool125:", 0) == 0)
         txt += r.label + "\n";
     std::strncpy(a->kernels, txt.c_str(), (size_t)a->kernels_cap - 1);
     a->kernels[a->kernels_cap - 1] = 0;

@@ -820,7 +820,7 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     Returns a dict: y; with has_bn mean, rstd, scale, shift, moving_mean, moving_var, rows_per_block, blocks; with dout
     dw, dbias, (dgamma, dbeta), dx (a list, one array per source, shaped as its x); and kernels: {"fwd": [...],
     "dgrad": [...], "wgrad": [...]} -- "<launch site>|<kernel template instantiation>" of every conv launch -- and
-    "pool": the profiler row of the up-split backward's pooling of dy, "pool8:<layer>" or "pool27:<layer>".
+    "pool": the profiler row of the up-split backward's pooling of dy, "pool125:<layer>", "pool8:<layer>" or "pool27:<layer>".
 
     ranks = R in 1..4: R emulated data-parallel ranks with SyncBN (ics_conv_layer.ranks).  The sources' x and dout hold
     R * B samples, rank-major, and so do y and dx; the statistics, the moving statistics and the parameter gradients
@@ -901,7 +901,7 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     def kernels(i):
         lines = text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines()
         d = {k: [ln for ln in lines if ln.startswith("conv_%s:" % k)] for k in ("fwd", "dgrad", "wgrad")}
-        d["pool"] = [ln for ln in lines if ln.startswith(("pool8:", "pool27:"))]   # the up-split backward's pooling of dy
+        d["pool"] = [ln for ln in lines if ln.startswith(("pool125:", "pool8:", "pool27:"))]   # the up-split backward's pooling of dy
         return d
 
     r["kernels"] = [kernels(i) for i in range(R)] if R else kernels(0)
