@@ -245,6 +245,9 @@ SIGNATURES = {
     "ics_net_feed_metrics": (C.c_int, [_H, C.c_int, _F]),
     "ics_op_feed_pack": (C.c_int, [C.POINTER(FeedConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    _F, _U8]),
+    "ics_net_feed_submit_rot": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "ics_op_feed_pack_rot": (C.c_int, [C.POINTER(FeedConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                       C.c_int, C.c_int, C.c_int, _F, _U8]),
 }
 
 _lib = None

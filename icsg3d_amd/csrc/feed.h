@@ -10,7 +10,8 @@
 //
 // ORDERING RULES -- the whole correctness argument:
 //  1. submit(slot, batch):   feed_st waits on consumed[slot];
-//                            one hipMemcpyAsync per part, pinned -> device staging, of the bytes `batch` samples use;
+//                            one hipMemcpyAsync per part, pinned -> device staging, of the bytes `batch` samples use
+//                            (a rotation table's orientation bytes are one more part, the slot's last);
 //                            uploaded[slot] is recorded on feed_st.
 //  2. step_fed(slot):        the compute stream n.st waits on uploaded[slot];
 //                            the pack kernel runs ON n.st, reads staging, writes n.x_in, n.labels, n.cond_in, n.eps_in;
@@ -56,12 +57,18 @@ struct FeedPack {
   const float* tail_src[2] = {nullptr, nullptr};   // cond, eps: float32 passthrough
   float* tail_dst[2] = {nullptr, nullptr};
   size_t tail_n[2] = {0, 0};
+  const unsigned char* orient = nullptr;   // [nvox / d^3] orientation bytes (orient.h); null: no sample is rotated
+  int d = 0;                               // grid edge (read with orient only)
 };
 // bytes per voxel of a label source (0: none)
 size_t feed_label_bytes(int label_kind, int ncls);
 // the x parts and the label kind of a config (not its slot count); `who` prefixes the message
 int feed_config_check(const char* who, const ics_feed_config* cfg, int in_channels, int ncls, bool want_labels);
+// p.orient set: the rotating pack (feed_pack_rot_kernel); null: feed_pack_kernel
 int launch_feed_pack(hipStream_t st, const FeedPack& p);
+// a rotation table [batch][3] (entries -1..2) as one orientation byte a sample; *any: some sample is rotated.  An entry
+// outside -1..2 is refused, naming the sample and the value.
+int feed_orientations(const char* who, const int32_t* rot, int batch, unsigned char* out, bool* any);
 
 // ---- what feed.hip needs of the engine behind an ics_net; defined in engine.hip, where Net lives
 struct Feed;

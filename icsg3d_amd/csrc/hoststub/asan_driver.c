@@ -1079,8 +1079,25 @@ static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond
     t.label_kind = 5; bad += ics_op_feed_pack(&t, x0, x1, lab, 1, d, 95, out, lo) == 0; t = fc;
     if (bad) { fprintf(stderr, "feed pack: %d invalid argument sets accepted\n", bad); return 1; }
     OK(ics_op_feed_pack(&fc, x0, x1, lab, 1, d, 95, out, lo));
+    /* ics_op_feed_pack_rot: all 64 tables, no table, an entry on either side of -1..2 */
+    int32_t rt[3];
+    for (int c = 0; c < 64; ++c) {
+      rt[0] = c / 16 - 1; rt[1] = c / 4 % 4 - 1; rt[2] = c % 4 - 1;
+      OK(ics_op_feed_pack_rot(&fc, x0, x1, lab, rt, 1, d, 95, out, lo));
+    }
+    OK(ics_op_feed_pack_rot(&fc, x0, x1, lab, NULL, 1, d, 95, out, lo));
+    rt[1] = 3; bad += ics_op_feed_pack_rot(&fc, x0, x1, lab, rt, 1, d, 95, out, lo) == 0;
+    rt[1] = -2; bad += ics_op_feed_pack_rot(&fc, x0, x1, lab, rt, 1, d, 95, out, lo) == 0;
+    rt[1] = 0; bad += ics_op_feed_pack_rot(NULL, x0, x1, lab, rt, 1, d, 95, out, lo) == 0;
+    bad += ics_op_feed_pack_rot(&fc, x0, x1, lab, rt, 1, 12, 95, out, lo) == 0;
+    if (bad || !strstr(ics_last_error(), "ics_op_feed_pack_rot")) { fprintf(stderr, "feed pack rot: %d invalid argument sets accepted\n", bad); return 1; }
+    rt[1] = 3;
+    if (ics_op_feed_pack_rot(&fc, x0, x1, lab, rt, 1, d, 95, out, lo) == 0 || !strstr(ics_last_error(), "rotation index 3")) {
+      fprintf(stderr, "feed pack rot: the refusal does not name the rotation index\n"); return 1;
+    }
     free(x0); free(x1); free(lab); free(out); free(lo);
   }
+  int32_t* rot = (int32_t*)malloc((size_t)B * 3 * sizeof(int32_t));   /* exactly max_batch rows */
   for (int kind = 0; kind < 2; ++kind) {
     ics_net* net = kind ? vae : unet;
     for (int lay = 0; lay < 3; ++lay) {   /* raw files (float64 parts, float64 ids); one float32 part; one-hot labels */
@@ -1098,7 +1115,9 @@ static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond
         if (fc.x_parts == 2) memset(x1, 0, (size_t)B * V * 3 * 8); else if (x1) { fprintf(stderr, "feed: x1 of a one-part feed\n"); return 1; }
         if (kind == 0) memset(lab, 0, (size_t)B * V * (fc.label_kind == 2 ? 8 : fc.label_kind == 1 ? 1 : 95 * 4));
         else { if (lab) { fprintf(stderr, "feed: labels of a VAE feed\n"); return 1; } memset(cond, 0, (size_t)B * ncond * sizeof(float)); memset(eps, 0, (size_t)B * latent * sizeof(float)); }
-        OK(ics_net_feed_submit(net, slot, b));
+        for (int i = 0; i < b * 3; ++i) rot[i] = step == 4 ? -1 : (i + step + lay) % 4 - 1;
+        if (step % 2 == 0) OK(ics_net_feed_submit_rot(net, slot, b, step == 2 ? NULL : rot));   /* a table, none, all -1 */
+        else OK(ics_net_feed_submit(net, slot, b));                                              /* plain, after a table */
         if (kind == 0) OK(step == 3 ? ics_unet_test_step_fed(net, slot, &ticket[nt]) : ics_unet_train_step_fed(net, slot, &ticket[nt]));
         else OK(step == 3 ? ics_vae_test_step_fed(net, slot, &ticket[nt]) : ics_vae_train_step_fed(net, slot, &ticket[nt]));
         ++nt;
@@ -1122,8 +1141,16 @@ static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond
       bad += (kind ? ics_unet_train_step_fed(net, 1, &tk) : ics_vae_train_step_fed(net, 1, &tk)) == 0;   /* wrong kind */
       bad += (kind ? ics_unet_test_step_fed(net, 1, &tk) : ics_vae_test_step_fed(net, 1, &tk)) == 0;
       bad += (kind ? ics_vae_test_step_fed(net, 1, NULL) : ics_unet_test_step_fed(net, 1, NULL)) == 0;
-      OK(ics_net_feed_submit(net, 1, B));
-      bad += ics_net_feed_submit(net, 1, B) == 0;                              /* pending */
+      for (int i = 0; i < B * 3; ++i) rot[i] = i % 4 - 1;
+      bad += ics_net_feed_submit_rot(net, 1, B + 1, rot) == 0;
+      rot[B * 3 - 1] = 3; bad += ics_net_feed_submit_rot(net, 1, B, rot) == 0;
+      if (!strstr(ics_last_error(), "rotation index 3")) { fprintf(stderr, "feed: the refusal does not name the rotation index\n"); return 1; }
+      rot[B * 3 - 1] = -2; bad += ics_net_feed_submit_rot(net, 1, B, rot) == 0;
+      rot[B * 3 - 1] = 2;
+      bad += ics_net_feed_submit_rot(net, fc.slots, B, rot) == 0;
+      OK(ics_net_feed_submit_rot(net, 1, B, rot));                             /* the refused tables left the slot obtained */
+      bad += ics_net_feed_submit_rot(net, 1, B, rot) == 0;                     /* pending */
+      bad += ics_net_feed_submit(net, 1, B) == 0;
       bad += ics_net_feed_metrics(net, nt, m) == 0;
       bad += ics_net_feed_metrics(net, -1, m) == 0;
       bad += ics_net_feed_metrics(net, 0, NULL) == 0;
@@ -1155,6 +1182,9 @@ static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond
     bad += ics_net_feed_close(u2) == 0;
     bad += ics_net_feed_slot(u2, 0, NULL, NULL, NULL, NULL, NULL) == 0;
     bad += ics_net_feed_submit(u2, 0, 1) == 0;
+    rot[0] = rot[1] = rot[2] = 0;
+    bad += ics_net_feed_submit_rot(u2, 0, 1, rot) == 0;
+    bad += ics_net_feed_submit_rot(NULL, 0, 1, rot) == 0;
     bad += ics_unet_train_step_fed(u2, 0, &tk) == 0;
     bad += ics_net_feed_metrics(u2, 0, m) == 0;
     bad += ics_net_feed_open(NULL, &fc) == 0;
@@ -1170,6 +1200,7 @@ static int feed_walk(ics_net* unet, ics_net* vae, int d, int C, int B, int ncond
     OK(ics_net_feed_submit(u2, 0, B));
     OK(ics_net_destroy(u2));               /* with an open feed and an upload that no step consumed */
   }
+  free(rot);
   return 0;
 }
 

@@ -10,6 +10,7 @@
 // index (scipy.ndimage.rotate by 90 degrees with reshape=False is np.rot90: an index permutation), so writes stay in
 // output order and no second pass exists.  DESIGN.md section 12.
 #include "voxelise.h"
+#include "orient.h"    // rot_source: the rotation convention, shared with the feed's rotating pack
 #include "scratch.h"
 
 #include <algorithm>
@@ -44,17 +45,6 @@ struct VoxOut {
   int C;
   unsigned char* labels;      // engine: [job][d^3], optional
 };
-
-// np.rot90(X, 1, axes=(a0, a1)) reads out[idx] = X[src] with src[a0] = idx[a1], src[a1] = d-1-idx[a0]
-__device__ __forceinline__ void rot_source(int code, int d, int& i, int& j, int& k) {
-  int t;
-  switch (code) {
-    case 0: t = i; i = j; j = d - 1 - t; break;   // axes (0,1)
-    case 1: t = i; i = k; k = d - 1 - t; break;   // axes (0,2)
-    case 2: t = j; j = k; k = d - 1 - t; break;   // axes (1,2)
-    default: break;
-  }
-}
 
 struct Axis {
   double start, step, half, gstep;

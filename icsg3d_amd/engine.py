@@ -249,8 +249,13 @@ class _FeedMixin:
         out["eps"] = view(p[4], (B, getattr(self, "latent_dim", 0)), np.float32)
         return out
 
-    def feed_submit(self, slot, batch):
-        L.check(self._lib.ics_net_feed_submit(self._h, int(slot), int(batch)))
+    def feed_submit(self, slot, batch, rotations=None):
+        """rotations (batch,3) int32, entries -1..2 (icsg3d_amd.augment): the step that consumes the slot packs through
+        it; None is the plain submit"""
+        if rotations is None:
+            L.check(self._lib.ics_net_feed_submit(self._h, int(slot), int(batch)))
+        else:
+            L.check(self._lib.ics_net_feed_submit_rot(self._h, int(slot), int(batch), _rot_table(rotations, batch)))
 
     def _step_fed(self, fn, slot):
         t = C.c_int(-1)
@@ -263,9 +268,18 @@ class _FeedMixin:
         return m[:self._n_metrics]
 
 
-def feed_pack(x_parts, labels=None, label_kind="none", num_classes=0):
-    """Single-op entry (ics_op_feed_pack): the pack kernel alone on host arrays.  x_parts: one or two (B,d,d,d,c) float32 /
-    float64 arrays; labels as label_kind says.  Returns (x float32 (B,d,d,d,sum c), labels uint8 (B,d,d,d) | None)."""
+def _rot_table(rotations, batch):
+    """a (batch,3) rotation table as the int32 pointer of ics_net_feed_submit_rot / ics_op_feed_pack_rot"""
+    rot = np.ascontiguousarray(rotations, np.int32)
+    if rot.shape != (int(batch), 3):
+        raise ValueError("a rotation table is (batch, 3), not %s for a batch of %d" % (rot.shape, batch))
+    return rot.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def feed_pack(x_parts, labels=None, label_kind="none", num_classes=0, rotations=None):
+    """Single-op entry (ics_op_feed_pack / ics_op_feed_pack_rot): the pack kernel alone on host arrays.  x_parts: one or two
+    (B,d,d,d,c) float32 / float64 arrays; labels as label_kind says; rotations (B,3) int32, entries -1..2, or None.
+    Returns (x float32 (B,d,d,d,sum c), labels uint8 (B,d,d,d) | None)."""
     lib = L.load()
     parts = [np.ascontiguousarray(a) for a in x_parts]
     B, d = parts[0].shape[0], parts[0].shape[1]
@@ -282,8 +296,12 @@ def feed_pack(x_parts, labels=None, label_kind="none", num_classes=0):
     x = np.empty((B, d, d, d, sum(a.shape[4] for a in parts)), np.float32)
     out = np.empty((B, d, d, d), np.uint8) if lab is not None else None
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    L.check(lib.ics_op_feed_pack(C.byref(cfg), vp(parts[0]), vp(parts[1]) if len(parts) == 2 else None, vp(lab), B, d,
-                                 int(num_classes), L.fptr(x), L.u8ptr(out)))
+    if rotations is None:
+        L.check(lib.ics_op_feed_pack(C.byref(cfg), vp(parts[0]), vp(parts[1]) if len(parts) == 2 else None, vp(lab), B, d,
+                                     int(num_classes), L.fptr(x), L.u8ptr(out)))
+    else:
+        L.check(lib.ics_op_feed_pack_rot(C.byref(cfg), vp(parts[0]), vp(parts[1]) if len(parts) == 2 else None, vp(lab),
+                                         _rot_table(rotations, B), B, d, int(num_classes), L.fptr(x), L.u8ptr(out)))
     return x, out
 
 
@@ -744,8 +762,8 @@ class VaeEngine(_Net, _FeedMixin):
 
     _n_metrics = 4
 
-    def feed_submit(self, slot, batch):
-        super().feed_submit(slot, batch)
+    def feed_submit(self, slot, batch, rotations=None):
+        super().feed_submit(slot, batch, rotations)
         self._slot_batch[int(slot)] = int(batch)
 
     def train_step_fed(self, slot):

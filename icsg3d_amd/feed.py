@@ -16,10 +16,16 @@ import numpy as np
 from .engine import FEED_DTYPES
 
 
-def pack_reference(x_parts, labels=None, label_kind="none"):
+def pack_reference(x_parts, labels=None, label_kind="none", rotations=None):
     """What the pack kernel computes, in numpy: x = concatenate(astype(float32)) over the parts' channels; labels =
     argmax over the columns of a one-hot (the lowest index among equal maxima), else astype(uint8) of the ids.
+    rotations (B,3): sample b of every per-voxel array goes through the table rotations[b] first (augment.rotate_host).
     Returns (x float32 (B,d,d,d,C), labels uint8 (B,d,d,d) | None)."""
+    if rotations is not None:
+        from .augment import rotate_host
+        turn = lambda a: np.stack([rotate_host(s, r) for s, r in zip(np.asarray(a), np.asarray(rotations))])
+        x_parts = [turn(p) for p in x_parts]
+        labels = None if labels is None else turn(labels)
     x = np.concatenate([np.asarray(p).astype(np.float32) for p in x_parts], axis=-1)
     if label_kind == "none" or labels is None:
         return x, None
@@ -59,7 +65,8 @@ class Feeder:
     A generator that offers `feed_spec()` and `fill(index, views, map)` writes raw file payloads straight into the slot
     (`map` runs the per-sample copies on `workers` threads: disjoint rows of one slot).  Any other generator has `gen[i]`
     copied into the views -- X in its own dtype when that is float32 / float64, a float32 one-hot y as it is -- without a
-    host cast.
+    host cast.  When such a generator also offers `rotations(index)`, the batch's rotation table (B,3) goes to
+    `feed_submit` and the pack kernel rotates the raw payloads; for any other generator nothing is passed.
 
     Schedule: batch k+1 is filled and submitted right after step k was enqueued, and step k's metrics are read after
     step k+1 was enqueued, so the device always has a step queued while the host loads.  A slot is rewritten only after
@@ -169,7 +176,12 @@ class Feeder:
                 slot = k % self.slots
                 with self.watch():
                     views = self.engine.feed_slot(slot)   # returns once the slot's last upload has left the pinned memory
-                self.engine.feed_submit(slot, self._fill(k, views, item, pool_map))
+                B = self._fill(k, views, item, pool_map)
+                rot = gen.rotations(k) if item is None and hasattr(gen, "rotations") else None
+                if rot is None:
+                    self.engine.feed_submit(slot, B)
+                else:
+                    self.engine.feed_submit(slot, B, rot)
                 return slot
 
             slot = load(0, item)

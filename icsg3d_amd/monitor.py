@@ -351,6 +351,8 @@ class VaeMonitor:
         vae = self.vae
         bs = int(self.val_gen.batch_size)
         steps = len(self.val_gen.list_IDs) // bs
+        if getattr(self.val_gen, "augment", None) is not None:      # an augmented generator's epoch is its plan
+            steps = len(self.val_gen)
         if steps < 1:
             return
         need = -(-self.maxz // bs)                                  # batches until >= maxz codes, wrapping as the reference

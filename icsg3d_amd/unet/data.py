@@ -1,11 +1,16 @@
 """U-Net batch generators: same `__len__/__getitem__/on_epoch_end` contract as
 /root/reference/unet/data.py:20-100 (X (B,d,d,d,C), [y, b]) over the same on-disk layout
 data/<name>/matrices/{density_matrices,species_matrices,coordinate_grids}/<id>.npy.
-y is handed over as uint8 class ids (the engine's native label format) unless one_hot=True."""
+y is handed over as uint8 class ids (the engine's native label format) unless one_hot=True.
+
+augment (an icsg3d_amd.augment.AugmentPlan or a dict of its arguments): list_IDs are base ids, and every epoch follows a
+freshly drawn plan -- each id once as it is and n_rot times through a drawn rotation table (augment.epoch_plan).
+__getitem__ rotates on the host; fill writes the raw payloads and rotations(index) hands the batch's table to the feed."""
 import os
 
 import numpy as np
 
+from ..augment import AugmentPlan, rotate_host
 from ..synthetic import synthetic_batch
 
 
@@ -53,31 +58,44 @@ def _fill_x(data_path, ID, views, i):
 
 class UnetDataGenerator:
     def __init__(self, list_IDs, data_path, batch_size=2, dim=(32, 32, 32), n_channels=7, n_classes=95,
-                 shuffle=False, one_hot=False):
+                 shuffle=False, one_hot=False, augment=None):
         self.dim, self.batch_size, self.list_IDs = tuple(dim), batch_size, list(list_IDs)
         self.n_channels, self.n_classes, self.shuffle = n_channels, n_classes, shuffle
         self.data_path, self.one_hot = data_path, one_hot
+        self.augment = None if augment is None else AugmentPlan.of(augment)
         self.on_epoch_end()
 
     def __len__(self):
+        if self.augment is not None:
+            return len(self.indexes) // self.batch_size
         return int(np.floor(len(self.list_IDs) / self.batch_size))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
 
     def on_epoch_end(self):
+        if self.augment is not None:                 # the next epoch's plan, shuffled by its own generator
+            self.indexes, self.rot = self.augment.next_epoch(len(self.list_IDs), self.batch_size)
+            return
         self.indexes = np.arange(len(self.list_IDs))
         if self.shuffle:
             np.random.shuffle(self.indexes)
 
+    def rotations(self, index):
+        """the rotation table (B,3) of batch `index`, None without augment"""
+        return None if self.augment is None else self.rot[index * self.batch_size:(index + 1) * self.batch_size]
+
     def __getitem__(self, index):
         idx = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
+        rot = self.rotations(index)
         self.list_IDs_temp = [self.list_IDs[k] for k in idx]
         X = np.empty((self.batch_size, *self.dim, self.n_channels), np.float32)
         y = np.empty((self.batch_size, *self.dim), np.uint8)
         for i, ID in enumerate(self.list_IDs_temp):
             X[i] = self.create_lattice_meshgrid(ID, self.n_channels)
             y[i] = np.load(os.path.join(self.data_path, "species_matrices", ID)).reshape(self.dim)
+            if rot is not None:
+                X[i], y[i] = rotate_host(X[i], rot[i]).copy(), rotate_host(y[i], rot[i]).copy()
         b = (y != 0).astype(np.float32)[..., None]
         if self.one_hot:
             y = np.eye(self.n_classes, dtype=np.float32)[y]

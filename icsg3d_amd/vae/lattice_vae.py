@@ -217,8 +217,10 @@ class LatticeDFCVAE(DataParallelMixin):
         self.train_batch_size, self.val_batch_size = train_gen.batch_size, val_gen.batch_size
         self.batch_size = self.train_batch_size
         self.num_epochs = epochs
-        train_steps = int(len(train_gen.list_IDs) / self.train_batch_size)
-        val_steps = int(len(val_gen.list_IDs) / self.val_batch_size)
+        augmented = [g for g in (train_gen, val_gen) if getattr(g, "augment", None) is not None]
+        # an augmented generator's epoch is its plan (every id n_rot + 1 times), and it moves to the next plan each epoch
+        train_steps = len(train_gen) if train_gen in augmented else int(len(train_gen.list_IDs) / self.train_batch_size)
+        val_steps = len(val_gen) if val_gen in augmented else int(len(val_gen.list_IDs) / self.val_batch_size)
         print("Data size %d,    batch_size %d    steps per epoch %d"
               % (len(train_gen.list_IDs), self.train_batch_size, train_steps))
         self._set_model(weights, batch_size=self.train_batch_size)
@@ -249,6 +251,8 @@ class LatticeDFCVAE(DataParallelMixin):
                         mon.best(e)
                 if mon is not None and e % 10 == 0:
                     mon.losses(self.losses, e + 1)
+                for g in augmented:
+                    g.on_epoch_end()
         finally:
             if feed and self._eng is not None and self._eng._feed is not None:
                 self._eng.feed_close()

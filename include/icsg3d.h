@@ -939,6 +939,14 @@ int ics_net_feed_slot(ics_net* net, int slot, void** x0, void** x1, void** label
  * not obtained (ics_net_feed_slot) since its last submit, a slot whose submitted batch no step has consumed yet,
  * batch outside [1, max_batch]. */
 int ics_net_feed_submit(ics_net* net, int slot, int batch);
+/* ics_net_feed_submit plus a rotation table [batch][3] (entries -1..2, the r0,r1,r2 of ics_op_voxelise); rot == NULL is
+ * ics_net_feed_submit.  The table is read before the call returns. It belongs to this submit only: the step that
+ * consumes the slot packs through it, a later plain submit of the same slot packs unrotated.
+ * Entry r >= 0 is np.rot90(X, 1, axes=[(0,1),(0,2),(1,2)][r]) of the sample's three spatial axes, applied in the order r0,
+ * r1, r2 to every per-voxel array (all x parts, ids, one-hot rows): channels travel with their voxel and no value changes
+ * (the coordinate channels are neither swapped nor negated); cond and eps are untouched.  A table of -1 only takes the
+ * kernel of the plain submit.  An entry outside -1..2 is refused, naming the sample and the value. */
+int ics_net_feed_submit_rot(ics_net* net, int slot, int batch, const int32_t* rot);
 /* Pack the submitted slot into the engine's input buffers and run the resident step on it, enqueued only: *ticket names
  * the step's metrics.  Refused: a slot that was never submitted or whose batch a step has already consumed, the other
  * engine kind. */
@@ -954,6 +962,9 @@ int ics_net_feed_metrics(ics_net* net, int ticket, float* metrics);
  * Synchronous, the calling thread's op stream and scratch. */
 int ics_op_feed_pack(const ics_feed_config* cfg, const void* x0, const void* x1, const void* labels, int batch, int d,
                      int num_classes, float* x, uint8_t* out_labels);
+/* ics_op_feed_pack through a rotation table (NULL: none). */
+int ics_op_feed_pack_rot(const ics_feed_config* cfg, const void* x0, const void* x1, const void* labels,
+                         const int32_t* rot, int batch, int d, int num_classes, float* x, uint8_t* out_labels);
 /* Exact class counts of n label ids on the device (train_unet.py's inverse-frequency class weights): labels are uint8,
  * float64 or float32 ids (label_kind 1, 2, 3 of ics_feed_config; the one-hot kind 4 is refused), counts [ncls] is
  * OVERWRITTEN with the number of labels equal to each class id, and *out_of_range receives the number of values that are

@@ -9,6 +9,7 @@ train_unet.py:84) and --synthetic N (Gaussian-blob grids of SURVEY 8(d); no data
   python3 train_unet.py --name heusler --samples 5000 --epochs 100
   python3 train_unet.py --name demo --synthetic 64 --channels 1 --epochs 2 --batch_size 8
   python3 train_unet.py --name heusler --samples 5000 --epochs 100 --weighted_loss     (per-class loss weights)
+  python3 train_unet.py --name heusler --samples 5000 --epochs 100 --feed --augment    (rotations drawn per epoch, on the GPU)
 
 Data parallel (new; the reference is single-process): launch one process per GPU,
   python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train_unet.py ...
@@ -46,6 +47,11 @@ if __name__ == "__main__":
     p.add_argument("--sync_bn", type=int, default=0, help="data parallel: BatchNorm statistics over all ranks")
     p.add_argument("--feed", action="store_true",
                    help="fed steps: upload each batch through pinned staging slots while the previous step runs")
+    p.add_argument("--augment", action="store_true",
+                   help="rotate while a batch is packed instead of reading rotated copies: the dataset holds base ids only "
+                        "(create_matrices.py --nrot 0), every epoch draws --nrot fresh rotation tables per compound; with "
+                        "--feed the pack kernel rotates on the GPU, without it the loader threads do")
+    p.add_argument("--augment_seed", type=int, default=28, help="seed of the per-epoch rotation plans (--augment)")
     p.add_argument("--weighted_loss", action="store_true",
                    help="weigh each voxel's softmax loss by its class's inverse-frequency weight (class_weights.npy, "
                         "background 0) instead of the reference's scalar num_classes; the counts are taken on the GPU")
@@ -58,6 +64,8 @@ if __name__ == "__main__":
                    help="data parallel over N GPUs of this node: without torch.distributed.run the script starts its N "
                         "ranks itself (icsg3d_amd/launcher.py); 0 = whatever the environment says (default)")
     a = p.parse_args()
+    if a.augment and a.synthetic:
+        p.error("--augment rotates the files of a dataset: it cannot be combined with --synthetic, which has none")
 
     if a.gpus:                                   # before anything touches the GPU; exits with the ranks' status
         from icsg3d_amd.launcher import ensure_ranks
@@ -83,18 +91,26 @@ if __name__ == "__main__":
                                                       a.nclasses, seed=10 ** 6 + rank * 10 ** 7)
         class_weights = get_weights(n_classes=a.nclasses) if a.weighted_loss else get_weights()
     else:
-        training_ids, validation_ids = data_split(path, a.samples, frac=a.split, n_rot=a.nrot)
+        # --augment: base ids only (rotated files on disk, if any, are ignored); --nrot stays the number of rotated copies
+        # of a compound per epoch, so an epoch has the steps of a run over the rotated dataset
+        training_ids, validation_ids = data_split(path, a.samples, frac=a.split, n_rot=0 if a.augment else a.nrot)
         all_training_ids, all_validation_ids = training_ids, validation_ids
-        if world > 1:
+        if world > 1 and not a.augment:          # an augmented generator takes its rank's share of the epoch plan itself
             training_ids = shard_ids(training_ids, rank, world, a.batch_size)
             validation_ids = shard_ids(validation_ids, rank, world, a.batch_size)
         if rank == 0:                            # provenance: which files this run trained / validated on, in order
             with open(os.path.join("output", "unet", mode, "split_ids.json"), "w") as f:
-                json.dump({"train": all_training_ids, "val": all_validation_ids}, f)
+                split = {"train": all_training_ids, "val": all_validation_ids}
+                if a.augment:
+                    split["augment"] = {"n_rot": a.nrot, "seed": a.augment_seed}
+                json.dump(split, f)
+        plan = (lambda fixed: dict(n_rot=a.nrot, seed=a.augment_seed, rank=rank, world=world, fixed=fixed)) if a.augment \
+            else (lambda fixed: None)
         training_generator = UnetDataGenerator(training_ids, data_path=path, batch_size=a.batch_size, dim=(d, d, d),
-                                               n_channels=a.channels, shuffle=True)
+                                               n_channels=a.channels, shuffle=True, augment=plan(False))
+        # validation keeps ONE plan for all epochs: val_loss stays comparable and "best" means something
         validation_generator = UnetDataGenerator(validation_ids, data_path=path, batch_size=a.batch_size, dim=(d, d, d),
-                                                 n_channels=a.channels, shuffle=True)
+                                                 n_channels=a.channels, shuffle=True, augment=plan(True))
         try:
             class_weights = np.load(weights_dir + "/class_weights.npy")
         except Exception:
