@@ -9,6 +9,11 @@ scores (icsg3d_amd/classreport.py) to output/eval_unet/<name>/{confusion.npy,rep
 
 Same flags, paths and checkpoint conventions as train_unet.py; new: --which val|train, --thresh, --top.
 
+--atoms also scores the split atom by atom in the same forward passes: the connected components of the predictions and of
+the true labels are matched on the GPU (icsg3d_amd/atomscore.py; --atom_tol voxels, components above --min_voxels voxels,
+at most --max_atoms a sample) and atom_confusion.npy, atom_report.csv and atom_report.json are written next to the others
+(icsg3d_amd/atomreport.py).  Without --atoms nothing changes.
+
   python3 eval_unet.py --name heusler --samples 5000
   python3 eval_unet.py --name demo --synthetic 64 --channels 1 --d 16 --batch_size 8
 
@@ -23,7 +28,7 @@ import time
 
 import numpy as np
 
-from icsg3d_amd import classreport
+from icsg3d_amd import atomreport, classreport
 from icsg3d_amd.cli import checkpoint_paths
 
 
@@ -41,6 +46,10 @@ def parser():
     p.add_argument("--which", choices=("val", "train"), default="val", help="the split to score")
     p.add_argument("--thresh", type=float, default=0.8, help="threshold of the occupancy (sigmoid) head")
     p.add_argument("--top", type=int, default=20, help="how many of the largest confusions to report")
+    p.add_argument("--atoms", action="store_true", help="also score the split atom by atom (atom_report.*)")
+    p.add_argument("--atom_tol", type=float, default=2.0, help="--atoms: matching distance in voxels (strict)")
+    p.add_argument("--min_voxels", type=int, default=3, help="--atoms: predicted components of at most this many voxels are dropped")
+    p.add_argument("--max_atoms", type=int, default=512, help="--atoms: a sample with more components fails (at most 1024)")
     p.add_argument("--gpus", type=int, default=0,
                    help="data parallel over N GPUs of this node (icsg3d_amd/launcher.py); 0 = whatever the environment says")
     return p
@@ -72,15 +81,22 @@ def generators(a, rank=0, world=1):
     return gens
 
 
-def accumulate(engine, gens, num_classes, thresh):
-    """every batch of every generator through confusion_batch (enqueued only); returns the number of samples"""
+ATOM_FLAGS = ("atoms", "atom_tol", "min_voxels", "max_atoms")
+
+
+def accumulate(engine, gens, num_classes, thresh, atoms=False):
+    """every batch of every generator through confusion_batch -- with atoms through atom_score_batch, which counts the
+    voxels of the same labels too -- enqueued only; returns the number of samples"""
     from icsg3d_amd.unet.unet import _to_labels
     n = 0
     for gen in gens:
         for i in range(len(gen)):
             X, y = gen[i]
-            engine.confusion_batch(np.asarray(X, np.float32), _to_labels(y[0] if isinstance(y, (list, tuple)) else y, num_classes),
-                                   thresh)
+            X, lab = np.asarray(X, np.float32), _to_labels(y[0] if isinstance(y, (list, tuple)) else y, num_classes)
+            if atoms:
+                engine.atom_score_batch(X, lab, thresh, with_confusion=True)
+            else:
+                engine.confusion_batch(X, lab, thresh)
             n += len(X)
     return n
 
@@ -103,22 +119,40 @@ def main(argv=None):
     gens = generators(a, rank, world)
     eng = unet._engine(a.batch_size)
     eng.confusion_open()
+    if a.atoms:
+        eng.atom_score_open(a.atom_tol, a.min_voxels, a.max_atoms)
     t0 = time.time()
-    samples = accumulate(eng, gens, a.nclasses, a.thresh)
+    samples = accumulate(eng, gens, a.nclasses, a.thresh, a.atoms)
     acc = eng.confusion_read()                   # the one wait
+    tallies = eng.atom_score_read() if a.atoms else None
     seconds = time.time() - t0
     matrix, occ, tail = classreport.reduce_over_ranks(
         dp[0] if dp else None, [acc["matrix"], acc["occupancy"], np.array([acc["out_of_range"], acc["voxels"], samples])])
+    if a.atoms:                                  # integer sums over the ranks, like the voxel counts
+        keys = list(tallies)
+        tallies = dict(zip(keys, atomreport.reduce_over_ranks(dp[0] if dp else None, [tallies[k] for k in keys])))
     if rank == 0:
         sdir = os.path.join("output", "eval_unet", a.name)
-        run = {"args": vars(a), "checkpoint": weights if os.path.exists(weights) else None, "ranks": world,
+        args = {k: v for k, v in vars(a).items() if a.atoms or k not in ATOM_FLAGS}
+        run = {"args": args, "checkpoint": weights if os.path.exists(weights) else None, "ranks": world,
                "samples": int(tail[2]), "voxels": int(tail[1]), "out_of_range": int(tail[0]), "seconds_rank0": seconds,
                "grids_per_s_rank0": samples / seconds if seconds > 0 else None}
         r = classreport.write(sdir, matrix, occ, top=a.top, extra={"thresh": a.thresh, "which": a.which, "out_of_range": int(tail[0])})
+        if a.atoms:
+            ar = atomreport.write(sdir, tallies, tol=a.atom_tol, top=a.top,
+                                  extra={"thresh": a.thresh, "which": a.which, "atom_tol": a.atom_tol,
+                                         "min_voxels": a.min_voxels, "max_atoms": a.max_atoms})
+            o = ar["overall"]
+            run["atoms"] = {k: o[k] for k in ("samples", "failed", "perfect", "true_atoms", "pred_atoms", "detected", "typed",
+                                              "missed", "spurious", "dup", "shadowed")}
         with open(os.path.join(sdir, "run.json"), "w") as f:
             json.dump(run, f, indent=1)
         print(classreport.table(r, worst=10, top=min(a.top, 10)))
-        print("wrote %s/{confusion.npy,report.csv,report.json,run.json}" % sdir)
+        if a.atoms:
+            print(atomreport.table(ar, worst=10, top=min(a.top, 10)))
+            print("wrote %s/{confusion.npy,report.csv,report.json,run.json,atom_confusion.npy,atom_report.csv,atom_report.json}" % sdir)
+        else:
+            print("wrote %s/{confusion.npy,report.csv,report.json,run.json}" % sdir)
     if dp:
         dp[0].barrier()
         dp[0].destroy_process_group()

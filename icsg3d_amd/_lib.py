@@ -224,6 +224,16 @@ SIGNATURES = {
     "ics_unet_confusion_step": (C.c_int, [_H, C.c_float]),
     "ics_unet_confusion_batch": (C.c_int, [_H, _F, _U8, C.c_int, C.c_float]),
     "ics_unet_confusion_read": (C.c_int, [_H, _I64, _I64, _I64, _I64]),
+    "ics_op_atom_score": (C.c_int, [_D, _I32, _I32, _D, _I32, _I32, C.c_int, C.c_int, C.c_double, _I64, _I64, _I64, _I64,
+                                    _I64, _I64, _I64, _I32, _I32, _D]),
+    "ics_op_atom_score_volumes": (C.c_int, [_U8, _U8, _U8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _I64,
+                                            _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _D]),
+    "ics_op_atom_score_limits": (C.c_int, [C.POINTER(C.c_int)] * 4),
+    "ics_unet_atom_score_open": (C.c_int, [_H, C.c_double, C.c_int, C.c_int]),
+    "ics_unet_atom_score_reset": (C.c_int, [_H]),
+    "ics_unet_atom_score_step": (C.c_int, [_H, C.c_float, C.c_int]),
+    "ics_unet_atom_score_batch": (C.c_int, [_H, _F, _U8, C.c_int, C.c_float, C.c_int]),
+    "ics_unet_atom_score_read": (C.c_int, [_H, _I64, _I64, _I64, _I64, _I64, _I64, _I64]),
     "ics_op_vae_loss": (C.c_int, [_F, C.c_int, C.c_int, _D, C.c_int, C.c_double, _D, C.POINTER(C.c_int), _D, _F, C.c_float,
                                   C.c_float, C.c_int, _D, _F]),
     "ics_op_vae_latent": (C.c_int, [C.POINTER(VaeLatentArgs)]),

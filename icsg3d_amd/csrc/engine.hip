@@ -15,6 +15,7 @@
 #include "monitor.h"
 #include "feed.h"
 #include "confusion.h"
+#include "atomscore.h"
 #include "../../include/icsg3d.h"
 
 #include <rccl/rccl.h>
@@ -317,6 +318,14 @@ struct Net {
   unsigned long long* conf_acc = nullptr;   // U-Net: the confusion accumulator [conf_acc_len(ncls)] (confusion.h); allocated
   long long conf_voxels = 0;                // by the first ics_unet_confusion_open; the pairs enqueued since the last open / reset
   hipEvent_t conf_ev = nullptr;             // ics_unet_confusion_batch: the upload has read the caller's arrays
+  // U-Net: the atom-score accumulator (atomscore.h), allocated by the first ics_unet_atom_score_open: the counter block
+  // [atom_acc_len(ncls)] and the two segmentation workspaces (predictions, truth) for max_batch samples
+  unsigned long long* atom_acc = nullptr;
+  unsigned char *atom_ws_p = nullptr, *atom_ws_t = nullptr;
+  size_t atom_ws_bytes = 0;
+  int atom_min_voxels = 0, atom_max_atoms = 0;
+  double atom_tol2 = 0.0, atom_hist_scale = 0.0;
+  hipEvent_t atom_ev = nullptr;             // ics_unet_atom_score_batch: the upload has read the caller's arrays
   hipEvent_t timer_ev[2] = {nullptr, nullptr};   // ics_net_timer_start / _stop
   hipStream_t st_own = nullptr;                  // ics_net_share_stream: the stream this handle created (st then points at another handle's)
   int last_batch = 0;                 // batch of the most recent forward (activation export)
@@ -346,6 +355,7 @@ struct Net {
     for (void* p : allocs) (void)hipFree(p);
     for (hipEvent_t e : timer_ev) if (e) (void)hipEventDestroy(e);
     if (conf_ev) (void)hipEventDestroy(conf_ev);
+    if (atom_ev) (void)hipEventDestroy(atom_ev);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
     if (st2) (void)hipStreamDestroy(st2);
@@ -2778,6 +2788,124 @@ int ics_unet_confusion_read(ics_net* net, int64_t* matrix, int64_t occupancy[4],
   *out_of_range = (int64_t)host[nn];
   for (int k = 0; k < 4; ++k) occupancy[k] = (int64_t)host[nn + 1 + k];
   *voxels = (int64_t)n.conf_voxels;
+  return 0;
+}
+
+// ---- the atom-score accumulator (include/icsg3d.h "atom score", atomscore.h): eval-mode passes only
+static int atom_get(ics_net* net, const char* who, bool opened) {
+  const std::string w = std::string(who) + ": ";
+  ICS_CHECK(net != nullptr, w + "null handle");
+  ICS_CHECK(net->n.kind == 0, w + "wrong engine kind: a U-Net engine is required");
+  ICS_CHECK(net->n.ncls >= kAtomScoreMinCls && net->n.ncls <= kAtomScoreMaxCls, w + "num_classes must be in [2, 127]");
+  ICS_CHECK(!opened || net->n.atom_acc != nullptr, w + "the engine has no open accumulator (ics_unet_atom_score_open)");
+  ICS_HIP(hipSetDevice(net->n.device));
+  return 0;
+}
+static int atom_zero(Net& n) {
+  ICS_HIP(hipMemsetAsync(n.atom_acc, 0, atom_acc_len(n.ncls) * sizeof(unsigned long long), n.st));
+  return 0;
+}
+int ics_unet_atom_score_open(ics_net* net, double tol, int min_voxels, int max_atoms) {
+  ICS_TRY(atom_get(net, "ics_unet_atom_score_open", false));
+  Net& n = net->n;
+  double tol2, hist_scale;
+  ICS_TRY(atom_score_params("ics_unet_atom_score_open", n.ncls, tol, &tol2, &hist_scale));
+  ICS_CHECK(min_voxels >= 0, "ics_unet_atom_score_open: min_voxels must be >= 0");
+  ICS_CHECK(max_atoms >= 1 && max_atoms <= kAtomScoreMaxAtoms, "ics_unet_atom_score_open: max_atoms must be in [1, 1024]");
+  ICS_CHECK(n.d >= 16 && n.d <= 256 && (n.d & (n.d - 1)) == 0, "ics_unet_atom_score_open: the grid must be a power of two in [16, 256]");
+  ICS_CHECK((size_t)n.maxB * n.d * n.d * n.d < (1ull << 31), "ics_unet_atom_score_open: max_batch * d^3 must stay below 2^31 voxels");
+  ICS_CHECK(n.atom_acc == nullptr || max_atoms == n.atom_max_atoms,
+            "ics_unet_atom_score_open: max_atoms differs from the first open's (the workspaces are sized by it)");
+  if (n.atom_ev == nullptr) ICS_HIP(hipEventCreateWithFlags(&n.atom_ev, hipEventDisableTiming));
+  if (n.atom_acc == nullptr) {
+    const size_t wsb = align_up(segment_workspace_bytes(n.maxB, n.d, max_atoms, n.ncls), 256);
+    unsigned long long* acc = nullptr;
+    ICS_TRY(n.alloc(&n.atom_ws_p, wsb));
+    ICS_TRY(n.alloc(&n.atom_ws_t, wsb));
+    ICS_TRY(n.alloc(&acc, atom_acc_len(n.ncls)));
+    n.atom_ws_bytes = wsb; n.atom_max_atoms = max_atoms;
+    n.atom_acc = acc;                         // set last: a failed allocation leaves the accumulator closed
+  }
+  n.atom_tol2 = tol2; n.atom_hist_scale = hist_scale; n.atom_min_voxels = min_voxels;
+  return atom_zero(n);
+}
+int ics_unet_atom_score_reset(ics_net* net) {
+  ICS_TRY(atom_get(net, "ics_unet_atom_score_reset", true));
+  return atom_zero(net->n);
+}
+static int atom_step(Net& n, float thresh, int with_confusion) {
+  const int batch = n.resident_batch;
+  ICS_TRY(unet_forward_trunk(n, batch, false, false, false, n.x_in));
+  const size_t M = n.rows(*n.head, batch);
+  unsigned char* d_species = reinterpret_cast<unsigned char*>(n.head->dy);   // where a labels predict leaves them
+  unsigned char* d_mask = d_species + M;
+  ICS_TRY(unet_head_labels(n, batch, thresh, d_species, d_mask, n.st));
+  n.pred_kind = 2; n.pred_batch = batch;
+  int *cp, *sp, *ct, *stt;
+  n.prof.begin(n.st, "atom_segment", 0, 4.0 * M);
+  ICS_TRY(launch_segment_atoms(n.st, d_mask, d_species, batch, n.d, n.atom_min_voxels, n.atom_max_atoms, n.ncls, n.atom_ws_p,
+                               n.atom_ws_bytes, nullptr, &cp, &sp));
+  ICS_TRY(launch_segment_atoms(n.st, n.labels, n.labels, batch, n.d, 0, n.atom_max_atoms, n.ncls, n.atom_ws_t,
+                               n.atom_ws_bytes, nullptr, &ct, &stt));
+  n.prof.end(n.st);
+  n.prof.begin(n.st, "atom_score", 0, 2.0 * batch * n.atom_max_atoms * kSegStatInts * 4);
+  ICS_TRY(launch_atom_score_stats(n.st, stt, ct, sp, cp, batch, n.atom_max_atoms, n.ncls, n.atom_tol2, n.atom_hist_scale,
+                                  AtomScoreOut{n.atom_acc, nullptr, nullptr, nullptr}));
+  n.prof.end(n.st);
+  if (with_confusion) {
+    n.prof.begin(n.st, "confusion", 0, 3.0 * M);
+    ICS_TRY(launch_confusion(n.st, n.labels, FEED_LABELS_U8, d_species, d_mask, M, n.ncls, n.conf_acc));
+    n.prof.end(n.st);
+    n.conf_voxels += (long long)M;
+  }
+  return 0;
+}
+static int atom_step_check(Net& n, const std::string& who, int with_confusion) {
+  ICS_CHECK(with_confusion == 0 || with_confusion == 1, who + ": with_confusion must be 0 or 1");
+  ICS_CHECK(!with_confusion || n.conf_acc != nullptr,
+            who + ": with_confusion needs an open confusion accumulator (ics_unet_confusion_open)");
+  return 0;
+}
+int ics_unet_atom_score_step(ics_net* net, float thresh, int with_confusion) {
+  ICS_TRY(atom_get(net, "ics_unet_atom_score_step", true));
+  Net& n = net->n;
+  ICS_TRY(atom_step_check(n, "ics_unet_atom_score_step", with_confusion));
+  ICS_CHECK(n.resident_batch > 0, "ics_unet_atom_score_step: no resident batch: call ics_unet_upload_batch or ics_unet_voxelise_batch first");
+  ICS_CHECK(n.labels_batch >= n.resident_batch, "ics_unet_atom_score_step: the resident batch was uploaded without labels");
+  return atom_step(n, thresh, with_confusion);
+}
+int ics_unet_atom_score_batch(ics_net* net, const float* x, const uint8_t* labels, int batch, float thresh, int with_confusion) {
+  ICS_TRY(atom_get(net, "ics_unet_atom_score_batch", true));
+  Net& n = net->n;
+  ICS_TRY(atom_step_check(n, "ics_unet_atom_score_batch", with_confusion));
+  ICS_CHECK(x && labels, "ics_unet_atom_score_batch: null argument");
+  ICS_CHECK(batch >= 1 && batch <= n.maxB, "ics_unet_atom_score_batch: batch exceeds max_batch (or is below 1)");
+  ICS_TRY(unet_upload(n, x, labels, batch));
+  ICS_HIP(hipEventRecord(n.atom_ev, n.st));
+  ICS_TRY(atom_step(n, thresh, with_confusion));
+  ICS_HIP(hipEventSynchronize(n.atom_ev));      // the one wait: the upload has read x and labels (ics_unet_confusion_batch)
+  return 0;
+}
+int ics_unet_atom_score_read(ics_net* net, int64_t* matrix, int64_t* dist_q, int64_t* dist2_q, int64_t* dup, int64_t* shadowed,
+                             int64_t hist[16], int64_t totals[8]) {
+  ICS_TRY(atom_get(net, "ics_unet_atom_score_read", true));
+  Net& n = net->n;
+  ICS_CHECK(matrix && dist_q && dist2_q && dup && shadowed && hist && totals, "ics_unet_atom_score_read: null argument");
+  const int ncls = n.ncls;
+  const size_t len = atom_acc_len(ncls), KK = (size_t)(ncls + 1) * (ncls + 1);
+  std::vector<unsigned long long> host(len);
+  ICS_HIP(hipMemcpyAsync(host.data(), n.atom_acc, len * sizeof(unsigned long long), hipMemcpyDeviceToHost, n.st));
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  for (size_t i = 0; i < KK; ++i) matrix[i] = (int64_t)host[i];
+  const unsigned long long* h = host.data() + KK;
+  for (int s = 0; s < ncls; ++s) {
+    dist_q[s] = (int64_t)h[s]; dist2_q[s] = (int64_t)h[ncls + s];
+    dup[s] = (int64_t)h[2 * ncls + s]; shadowed[s] = (int64_t)h[3 * ncls + s];
+  }
+  h += 4 * (size_t)ncls;
+  for (int k = 0; k < kAtomScoreHistBins; ++k) hist[k] = (int64_t)h[k];
+  for (int k = 0; k < kAtomScoreTotals; ++k) totals[k] = (int64_t)h[kAtomScoreHistBins + k];
   return 0;
 }
 

@@ -1035,6 +1035,136 @@ static int confusion_walk(ics_net* unet, ics_net* vae, int ncls, int d, const fl
   return 0;
 }
 
+/* The atom score: the ragged op on buffers of the exact size (empty sets, the largest set, a batch that takes several
+ * launches, with and without the per-sample outputs) and each of its refusals with guarded outputs; the volumes op on a
+ * small and a regular grid; then the engine's accumulator -- every entry point before open, open / batch / step / read
+ * twice / reset / re-open, with and without the confusion accumulator, null arguments, a VAE handle -- after which the
+ * engine still trains.  Runs after confusion_walk, which leaves a confusion accumulator open. */
+static int atom_score_walk(ics_net* unet, ics_net* vae, int ncls, int d, const float* x, const uint8_t* lab, int B) {
+  int bad = 0, a = 0, b = 0, c = 0, e = 0;
+  OK(ics_op_atom_score_limits(&a, &b, &c, &e));
+  bad += ics_op_atom_score_limits(&a, NULL, &c, &e) == 0;
+  const size_t KK = 128 * 128;
+  int64_t* mat = (int64_t*)malloc(KK * sizeof(int64_t));
+  int64_t dq[127], d2q[127], dup[127], sh[127], hist[16], tot[8];
+  {
+    /* 40 samples: sample 0 empty on both sides, sample 1 of 1024 x 1024 atoms, the rest 900 x 800: several launches */
+    const int nb = 40;
+    int32_t *to = (int32_t*)malloc((nb + 1) * sizeof(int32_t)), *po = (int32_t*)malloc((nb + 1) * sizeof(int32_t));
+    to[0] = po[0] = 0;
+    for (int s = 0; s < nb; ++s) {
+      to[s + 1] = to[s] + (s == 0 ? 0 : s == 1 ? 1024 : 900);
+      po[s + 1] = po[s] + (s == 0 ? 0 : s == 1 ? 1024 : 800);
+    }
+    const size_t nt = (size_t)to[nb], np = (size_t)po[nb];
+    double *tx = (double*)calloc(3 * nt, sizeof(double)), *px = (double*)calloc(3 * np, sizeof(double));
+    int32_t *ts = (int32_t*)calloc(nt, sizeof(int32_t)), *ps = (int32_t*)calloc(np, sizeof(int32_t));
+    int32_t *match = (int32_t*)malloc(nt * sizeof(int32_t)), *st = (int32_t*)malloc((size_t)nb * 6 * sizeof(int32_t));
+    double* ds = (double*)malloc(nb * sizeof(double));
+    OK(ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds));
+    OK(ics_op_atom_score(tx, ts, to, px, ps, po, nb, 127, 2.0, mat, dq, d2q, dup, sh, hist, tot, NULL, NULL, NULL));
+    OK(ics_op_atom_score(tx, ts, to, px, ps, po, 1, 2, 0.5, mat, dq, d2q, dup, sh, hist, tot, match, NULL, ds));   /* one empty sample */
+    OK(ics_op_atom_score(NULL, NULL, to, NULL, NULL, po, 1, 2, 0.5, mat, dq, d2q, dup, sh, hist, tot, NULL, NULL, NULL));
+    bad += ics_op_atom_score(tx, ts, NULL, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, NULL, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(NULL, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, NULL, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, NULL, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, NULL, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, 0, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 1, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 128, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 0.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, __builtin_inf(), mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    to[0] = 1;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    to[0] = 0; po[3] = po[2] - 1;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    po[3] = po[2] + 800; po[2] += 1;                              /* sample 1 of 1025 predicted atoms */
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    po[2] -= 1; ts[nt - 1] = 17;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    ts[nt - 1] = 0; ps[0] = -1;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    ps[0] = 0; px[3 * np - 1] = __builtin_nan("");
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    px[3 * np - 1] = 0; tx[0] = 2e150;
+    bad += ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    tx[0] = 0;
+    OK(ics_op_atom_score(tx, ts, to, px, ps, po, nb, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds));
+    free(to); free(po); free(tx); free(px); free(ts); free(ps); free(match); free(st); free(ds);
+  }
+  for (int dv = 8; dv <= 16; dv += 8) {      /* a grid below the segmentation's 16 is padded on the host */
+    const size_t vox = (size_t)3 * dv * dv * dv;
+    uint8_t *l = (uint8_t*)calloc(vox, 1), *s = (uint8_t*)calloc(vox, 1), *m = (uint8_t*)calloc(vox, 1);
+    int32_t *match = (int32_t*)malloc(3 * 5 * sizeof(int32_t)), st[3 * 6];
+    double ds[3];
+    OK(ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds));
+    OK(ics_op_atom_score_volumes(l, s, m, 3, dv, 0, 1024, 127, 2.0, mat, dq, d2q, dup, sh, hist, tot, NULL, NULL, NULL));
+    bad += ics_op_atom_score_volumes(NULL, s, m, 3, dv, 3, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, NULL, 3, dv, 3, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 5, 17, 2.0, mat, dq, NULL, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 0, dv, 3, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv + 4, 3, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, -1, 5, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 0, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 1025, 17, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 5, 128, 2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    bad += ics_op_atom_score_volumes(l, s, m, 3, dv, 3, 5, 17, -2.0, mat, dq, d2q, dup, sh, hist, tot, match, st, ds) == 0;
+    free(l); free(s); free(m); free(match);
+  }
+  if (bad) { fprintf(stderr, "atom score ops: %d invalid calls accepted\n", bad); return 1; }
+  (void)ncls;
+  float mm[5];
+  bad += ics_unet_atom_score_step(unet, 0.8f, 0) == 0;                       /* before open */
+  bad += ics_unet_atom_score_batch(unet, x, lab, B, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, tot) == 0;
+  bad += ics_unet_atom_score_reset(unet) == 0;
+  bad += ics_unet_atom_score_open(unet, 0.0, 3, 64) == 0;
+  bad += ics_unet_atom_score_open(unet, 2.0, -1, 64) == 0;
+  bad += ics_unet_atom_score_open(unet, 2.0, 3, 0) == 0;
+  bad += ics_unet_atom_score_open(unet, 2.0, 3, 1025) == 0;
+  bad += ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, tot) == 0;   /* a refused open opened nothing */
+  OK(ics_unet_atom_score_open(unet, 2.0, 3, 64));
+  OK(ics_unet_atom_score_batch(unet, x, lab, B, 0.8f, 0));
+  OK(ics_unet_atom_score_batch(unet, x, lab, 1, 0.8f, 1));                   /* confusion_walk left its accumulator open */
+  OK(ics_unet_upload_batch(unet, x, lab, B));
+  OK(ics_unet_atom_score_step(unet, 0.8f, 1));
+  {
+    float* img = calloc((size_t)B * d * d * 4, 4);
+    float lut[256 * 3] = {0};
+    OK(ics_unet_render_slice_resident(unet, 1, 0, B, 2, d / 2, lut, NULL, 1, img));   /* the species are where a labels predict leaves them */
+    free(img);
+  }
+  OK(ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, tot));
+  OK(ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, tot));
+  OK(ics_unet_atom_score_reset(unet));
+  OK(ics_unet_atom_score_open(unet, 1.5, 0, 64));                            /* a second open: new tol and min_voxels */
+  bad += ics_unet_atom_score_open(unet, 1.5, 0, 65) == 0;                    /* ... but not another max_atoms */
+  bad += ics_unet_atom_score_step(unet, 0.8f, 2) == 0;
+  OK(ics_unet_upload_batch(unet, x, NULL, B));                               /* a resident batch without labels */
+  bad += ics_unet_atom_score_step(unet, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_batch(unet, NULL, lab, B, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_batch(unet, x, NULL, B, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_batch(unet, x, lab, 0, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_batch(unet, x, lab, B + 100, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_read(unet, NULL, dq, d2q, dup, sh, hist, tot) == 0;
+  bad += ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, NULL, tot) == 0;
+  bad += ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, NULL) == 0;
+  bad += ics_unet_atom_score_open(NULL, 2.0, 3, 64) == 0;
+  bad += ics_unet_atom_score_open(vae, 2.0, 3, 64) == 0;
+  bad += ics_unet_atom_score_reset(vae) == 0;
+  bad += ics_unet_atom_score_step(vae, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_batch(vae, x, lab, B, 0.8f, 0) == 0;
+  bad += ics_unet_atom_score_read(vae, mat, dq, d2q, dup, sh, hist, tot) == 0;
+  if (bad) { fprintf(stderr, "atom score accumulator: %d invalid calls accepted\n", bad); return 1; }
+  OK(ics_unet_atom_score_batch(unet, x, lab, B, 0.8f, 1));                   /* still usable */
+  OK(ics_unet_atom_score_read(unet, mat, dq, d2q, dup, sh, hist, tot));
+  OK(ics_unet_train_step(unet, x, lab, B, mm));
+  free(mat);
+  return 0;
+}
+
 /* Fed steps: the pack op alone on buffers of the exact size (every dtype mix, every label kind, odd column counts), then the
  * whole feed on both engines -- open, slot, submit, fed train / test step, metrics (late and twice), close, re-open with
  * another layout -- and every refusal, after which the feed and the engine still work. */
@@ -1272,6 +1402,7 @@ static int run(int d, int C, int B, int with_comm) {
   OK(ics_vae_train_step_resident(vae, mv));
   if (class_weight_walk(unet, vae, uc.num_classes, x, lab, B, with_comm)) return 1;
   if (confusion_walk(unet, vae, uc.num_classes, d, x, lab, B)) return 1;
+  if (atom_score_walk(unet, vae, uc.num_classes, d, x, lab, B)) return 1;
   if ((C == 1 || C == 4) && voxelise_walk(unet, vae, d, B, cond, eps)) return 1;
   if (interp_walk(unet, vae, &uc, x, cond, eps, B, d, C)) return 1;
   if (feed_walk(unet, vae, d, C, B, vc.cond_shape, vc.latent_dim)) return 1;

@@ -509,6 +509,38 @@ class UnetEngine(_Net, _FeedMixin):
         L.check(self._lib.ics_unet_confusion_read(self._h, L.i64ptr(matrix), L.i64ptr(occ), L.i64ptr(oor), L.i64ptr(vox)))
         return {"matrix": matrix, "occupancy": occ, "out_of_range": int(oor[0]), "voxels": int(vox[0])}
 
+    # ---- the atom-score accumulator (include/icsg3d.h "atom score"): eval-mode passes only, nothing is trained
+    def atom_score_open(self, tol=2.0, min_voxels=3, max_atoms=512):
+        """Zeroed device tallies and two segmentation workspaces in the engine's memory (allocated by the first open; a
+        later open may change tol and min_voxels, not max_atoms)."""
+        L.check(self._lib.ics_unet_atom_score_open(self._h, float(tol), int(min_voxels), int(max_atoms)))
+
+    def atom_score_reset(self):
+        L.check(self._lib.ics_unet_atom_score_reset(self._h))
+
+    def atom_score_step(self, thresh=0.8, with_confusion=False):
+        """Eval forward on the resident batch (uploaded WITH labels), argmax / sig >= thresh, the components of the
+        predictions and of the true labels, their matching and its tallies added to the accumulator; with_confusion also
+        adds the voxel counts to the open confusion accumulator.  Enqueued only."""
+        L.check(self._lib.ics_unet_atom_score_step(self._h, float(thresh), 1 if with_confusion else 0))
+
+    def atom_score_batch(self, x, labels, thresh=0.8, with_confusion=False):
+        """upload_batch + atom_score_step for host arrays of any length (max_batch samples at a time)."""
+        x = self._check_x(x)
+        lab = self._labels(labels, x.shape[0])
+        for i in range(0, x.shape[0], self.max_batch):
+            xs, ls = x[i:i + self.max_batch], lab[i:i + self.max_batch]
+            L.check(self._lib.ics_unet_atom_score_batch(self._h, L.fptr(xs), L.u8ptr(ls), xs.shape[0], float(thresh),
+                                                        1 if with_confusion else 0))
+
+    def atom_score_read(self):
+        """Waits for the stream -> the tallies of icsg3d_amd.atomscore.TALLIES as a dict of int64 arrays (matrix
+        (K + 1, K + 1) [true, predicted] with index K = no atom).  Does not reset."""
+        from .atomscore import empty_tallies
+        t = empty_tallies(self.num_classes)
+        L.check(self._lib.ics_unet_atom_score_read(self._h, *[L.i64ptr(t[k]) for k in t]))
+        return t
+
     _n_metrics = 5
 
     def train_step_fed(self, slot):

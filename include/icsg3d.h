@@ -1016,6 +1016,77 @@ int ics_unet_confusion_batch(ics_net* net, const float* x, const uint8_t* labels
  * does not reset. */
 int ics_unet_confusion_read(ics_net* net, int64_t* matrix, int64_t occupancy[4], int64_t* out_of_range, int64_t* voxels);
 
+/* ---- atom score: the U-Net scored atom by atom on the device (eval_unet.py --atoms) ----
+ * The confusion matrix above scores voxels.  What generate.py and eval.py consume is atoms: connected components of the
+ * thresholded mask with a majority species and a centroid.  These entry points match the predicted atoms of a sample to
+ * its true atoms and tally the result per species.
+ *
+ * THE RULE (the project's own, exact and deterministic).  A sample has n true and m predicted atoms, each an fp64 position
+ * in voxel units and a species id in [0, ncls).  d2 = ((dx*dx + dy*dy) + dz*dz) with dx = t.x - p.x and so on, in fp64, in
+ * this order, without FMA contraction.  A pair is admissible when d2 < tol*tol, strictly (tol*tol computed once on the
+ * host).  The matching is the greedy one under the strict total order (d2, true index, predicted index): walk the
+ * admissible pairs in ascending order and take a pair when both of its atoms are free.
+ *
+ * THE TALLIES, all int64 and OVERWRITTEN.  K = ncls + 1; index ncls means "no atom".
+ *   matrix [K*K]      [t*K + p] matched pairs by (true, predicted) species; [t*K + ncls] unmatched true atoms (missed);
+ *                     [ncls*K + p] unmatched predicted atoms (spurious)
+ *   dist_q [ncls]     by true species: sum over matched pairs of llrint(sqrt(d2) * 2^20) (sqrt correctly rounded, half to even)
+ *   dist2_q [ncls]    the same of llrint(d2 * 2^20)
+ *   dup [ncls]        by predicted species: unmatched predicted atoms with some true atom within tol ("found twice / split")
+ *   shadowed [ncls]   by true species: unmatched true atoms with some predicted atom within tol ("two atoms, one blob")
+ *   hist [16]         matched distances: bin min(15, (int)floor(sqrt(d2) * (16.0 / tol)))
+ *   totals [8]        samples, failed, perfect, true atoms, predicted atoms, matched, sum |n - m|, samples with no true atom;
+ *                     perfect: every atom of both sides matched and every pair agreeing in species; a failed sample
+ *                     (volumes and engine forms: more kept components than max_atoms on either side) adds to samples and
+ *                     failed and to nothing else
+ * PER-SAMPLE OUTPUTS, each optional (null): match int32 = the partner's index within the sample or -1, per true atom;
+ * sample_stats int32 [batch][6] = {n, m, matched, species_agree, dup, shadowed} ({n, m, -1, -1, -1, -1} when failed);
+ * dist_sum double [batch] = the sum of sqrt(d2) over the matched pairs in ascending true index, added serially (the same
+ * bits run to run; NaN when failed).
+ *
+ * ics_op_atom_score: ragged sets in ics_op_match_emd's layout -- t_xyz [t_off[batch]][3], t_species [t_off[batch]],
+ * t_off [batch + 1], and the same for p; match is [t_off[batch]].  Any batch (solved in chunks).  Refused with nothing
+ * written, naming the sample: null required arguments, batch < 1, ncls outside [2, 127], tol not finite, <= 0 or above 1e6,
+ * offsets that do not start at 0 or decrease, a set above 1024 atoms, a species outside [0, ncls), a coordinate that is not
+ * finite or exceeds 1e150 in magnitude.  Synchronous, the calling thread's op stream and scratch. */
+int ics_op_atom_score(const double* t_xyz, const int32_t* t_species, const int32_t* t_off, const double* p_xyz,
+                      const int32_t* p_species, const int32_t* p_off, int batch, int ncls, double tol, int64_t* matrix,
+                      int64_t* dist_q, int64_t* dist2_q, int64_t* dup, int64_t* shadowed, int64_t* hist, int64_t* totals,
+                      int32_t* match, int32_t* sample_stats, double* dist_sum);
+/* The same from volumes, without a network: true_labels, pred_species and pred_mask are uint8 [batch][d][d][d], d a power of
+ * two in [2, 256] (a grid below 16 is laid into the corner of a zeroed 16^3 one).  Predicted atoms are the components of
+ * pred_mask != 0 with more than min_voxels voxels, their species the majority vote of pred_species (0 when every voxel
+ * carries 0); true atoms are ALL components of true_labels != 0 with the label volume as species.  An atom's position is
+ * (x, y, z) = (sum x / voxels, sum y / voxels, sum z / voxels), one fp64 division each; atoms are numbered as
+ * ics_op_segment_atoms numbers them.  max_atoms <= 1024; match is [batch][max_atoms] (-1 behind a sample's atoms). */
+int ics_op_atom_score_volumes(const uint8_t* true_labels, const uint8_t* pred_species, const uint8_t* pred_mask, int batch,
+                              int d, int min_voxels, int max_atoms, int ncls, double tol, int64_t* matrix, int64_t* dist_q,
+                              int64_t* dist2_q, int64_t* dup, int64_t* shadowed, int64_t* hist, int64_t* totals,
+                              int32_t* match, int32_t* sample_stats, double* dist_sum);
+/* The kernel's constants: lanes per workgroup (one workgroup per sample), atoms per side and sample, and the samples and
+ * atoms (both sides) one launch of ics_op_atom_score takes at most (tests size their batches by them). */
+int ics_op_atom_score_limits(int* threads, int* max_atoms, int* chunk_samples, int* chunk_atoms);
+/* The accumulator in the U-Net engine's own memory (num_classes <= 127, d >= 16): the counter block and two segmentation
+ * workspaces for max_batch samples, allocated by the first open -- an engine that never opens one keeps its memory layout
+ * -- and kept until the engine is destroyed.  Open zeroes the counters; a later open may change tol and min_voxels and
+ * zeroes again, a different max_atoms is refused.  Every entry point runs eval-mode forward passes only: weights, BatchNorm
+ * moving statistics, Adam's moments and step count, the class-weight table and (unless with_confusion) an open confusion
+ * accumulator are not touched.  A VAE handle, a null argument and a reset / step / batch / read before open are refused. */
+int ics_unet_atom_score_open(ics_net* net, double tol, int min_voxels, int max_atoms);
+int ics_unet_atom_score_reset(ics_net* net);
+/* On the resident batch, placed WITH labels (as ics_unet_confusion_step): eval forward, argmax species and sig >= thresh,
+ * the components of the predictions (min_voxels) and of the true labels, the matching and its tallies ADDED to the
+ * accumulator.  Enqueued only, no host wait.  with_confusion = 1 also adds the voxel pairs of the same labels to the open
+ * confusion accumulator (one forward for both scores); without an open one it is refused.  Leaves the species / mask
+ * volumes where a labels predict leaves them. */
+int ics_unet_atom_score_step(ics_net* net, float thresh, int with_confusion);
+/* The upload of ics_unet_upload_batch(x, labels, batch) followed by the step; returns once the upload has read x and
+ * labels, like ics_unet_confusion_batch. */
+int ics_unet_atom_score_batch(ics_net* net, const float* x, const uint8_t* labels, int batch, float thresh, int with_confusion);
+/* Waits for the engine's stream and copies the tallies out (layout above).  May be called repeatedly; it does not reset. */
+int ics_unet_atom_score_read(ics_net* net, int64_t* matrix, int64_t* dist_q, int64_t* dist2_q, int64_t* dup, int64_t* shadowed,
+                             int64_t hist[16], int64_t totals[8]);
+
 #ifdef __cplusplus
 }
 #endif
