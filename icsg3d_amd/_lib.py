@@ -238,6 +238,7 @@ SIGNATURES = {
                                   C.c_float, C.c_int, _D, _F]),
     "ics_op_vae_latent": (C.c_int, [C.POINTER(VaeLatentArgs)]),
     "ics_op_sqdiff": (C.c_int, [_F, _F, C.c_int, C.c_size_t, C.c_int, C.c_float, C.c_int, _F, _D]),
+    "ics_op_up125_pool": (C.c_int, [_F, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
     "ics_op_conv_link": (C.c_int, [C.POINTER(ConvLinkArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

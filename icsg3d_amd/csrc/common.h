@@ -134,7 +134,8 @@ enum ConvFlags : int {
                                // 8-volume layout of up8.h at the source / dy pointer
   CF_NO_UP125 = 1 << 27,       // ICSG3D_NO_UP125: up-split backward of the large layers through pool8 and the 27-tap GEMMs, not the 125-product form (up125.h)
   CF_FORCE_UP125 = 1 << 28,    // ICSG3D_FORCE_UP125: the 125-product form wherever its layout serves, whatever the size (tests)
-  CF_ZBATCH = 1 << 20,         // internal: conv_fwd_kernel runs gridDim.z independent GEMMs (launch_gemm_zbatch)
+  CF_POOL125_V1 = 1 << 29,     // ICSG3D_POOL125_V1: the 125-product form pools dy with one wave per z type (pool125_kernel), not one per fine plane
+  CF_ZBATCH = 1 << 20,        // internal: conv_fwd_kernel runs gridDim.z independent GEMMs (launch_gemm_zbatch)
   // (131072 was CF_NO_TICKET, the per-layer bias-gradient finalize of round 3: removed in round 6 with the other switches
   // DESIGN.md records as rejected -- ICSG3D_SIDE_STREAM, ICSG3D_NO_ARENA)
 };

@@ -78,6 +78,7 @@ int conv_flags_from_env() {
   if (getenv("ICSG3D_NO_UP8")) f |= CF_NO_UP8;
   if (getenv("ICSG3D_NO_UP125")) f |= CF_NO_UP125;
   if (getenv("ICSG3D_FORCE_UP125")) f |= CF_FORCE_UP125;
+  if (getenv("ICSG3D_POOL125_V1")) f |= CF_POOL125_V1;
   { const char* e = getenv("ICSG3D_UP3_BIG_MIN_WG"); if (e && *e && strtoul(e, nullptr, 10) <= 1) f |= CF_UP3_BIG_ALWAYS; }
   return f;
 }

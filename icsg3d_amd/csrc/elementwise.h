@@ -177,7 +177,8 @@ int launch_pool27(hipStream_t st, const float* dy, int B, int S, int N, float* o
 // the same sums as the 8 volumes of up8.h; u = up8_geom(B, S / 2, log2(S / 2), N)
 int launch_pool8(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up8Geom& u);
 // ---- the 125-product form of the up-split backward (up125.h, up125.hip); u = up125_geom(B, S, N, Cu)
-int launch_pool125(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up125Geom& u);
+// v1: one wave per z type (pool125_kernel, CF_POOL125_V1) instead of one per fine plane (pool125_planes_kernel)
+int launch_pool125(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up125Geom& u, bool v1);
 // the 27 x-class volumes of the low-res source s (affine and activation applied), class q at slot up125_slot(q)
 int launch_up125_xclass(hipStream_t st, const ConvSrc& s, float* out, const Up125Geom& u);
 // dxl[B (S/2)^3][Cu] from the 27 class outputs

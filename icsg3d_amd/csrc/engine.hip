@@ -1090,7 +1090,7 @@ static int conv_grads_split_up(Net& n, ConvLayer& L, int B, ConvLayer* next) {
     ICS_CHECK(up125_pooled_floats(u5.rows, L.Cout) <= n.u125_P_n && up125_class_floats(u5.rows, L.Cu) <= n.u125_X_n &&
                   up125_splits(L, B, &sp5) <= n.u125_ws_n, "up125 scratch smaller than the batch at hand");
     n.prof.begin(n.st, "pool125:" + L.name, 0, 4.0 * M * L.Cout * (1 + 125.0 / 64));
-    ICS_TRY(launch_pool125(n.st, L.dy, B, L.S, L.Cout, n.u125_P, u5));
+    ICS_TRY(launch_pool125(n.st, L.dy, B, L.S, L.Cout, n.u125_P, u5, (n.flags & CF_POOL125_V1) != 0));
   } else if (L.up8) {
     const double pr = (double)(L.S / 2 + 1) / (L.S / 2);
     n.prof.begin(n.st, "pool8:" + L.name, 0, 4.0 * M * L.Cout * (1 + pr * pr * pr));

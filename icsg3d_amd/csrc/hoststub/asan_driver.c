@@ -1895,6 +1895,30 @@ int main(void) {
       }
     if (bad) { fprintf(stderr, "sqdiff: %d invalid argument sets accepted\n", bad); return 1; }
   }
+  {   /* the pooling pass of the 125-product up-split backward: both kernels, several tiles per wave and two channel groups */
+    const int shp[3][3] = {{2, 8, 32}, {1, 16, 64}, {1, 8, 512}};
+    int bad = 0;
+    for (int i = 0; i < 3; ++i) {
+      const int B = shp[i][0], S = shp[i][1], N = shp[i][2];
+      const size_t rows = (size_t)B * (S / 4) * (S / 4) * (S / 4);
+      float *dy = calloc((size_t)B * S * S * S * N, 4), *out = malloc(125 * rows * N * 4);
+      OK(ics_op_up125_pool(dy, B, S, N, 0, out));
+      OK(ics_op_up125_pool(dy, B, S, N, 1, out));
+      if (i == 0) {
+        bad += ics_op_up125_pool(NULL, B, S, N, 1, out) == 0;
+        bad += ics_op_up125_pool(dy, B, S, N, 1, NULL) == 0;
+        bad += ics_op_up125_pool(dy, B, S, N, 2, out) == 0;
+        bad += ics_op_up125_pool(dy, B, S, N, -1, out) == 0;
+        bad += ics_op_up125_pool(dy, 0, S, N, 1, out) == 0;
+        bad += ics_op_up125_pool(dy, B, 4, N, 1, out) == 0;
+        bad += ics_op_up125_pool(dy, B, 12, N, 1, out) == 0;
+        bad += ics_op_up125_pool(dy, B, S, 48, 1, out) == 0;
+        bad += ics_op_up125_pool(dy, B, S, 16, 1, out) == 0;
+      }
+      free(dy); free(out);
+    }
+    if (bad) { fprintf(stderr, "up125 pool: %d invalid argument sets accepted\n", bad); return 1; }
+  }
   {   /* connected components on host arrays */
     const int B = 2, d = 16;
     const size_t M = (size_t)B * d * d * d;

@@ -1,4 +1,4 @@
-// Layout of the 125-product form of the up-split backward (pool125_kernel, the class GEMMs, the combine / contraction
+// Layout of the 125-product form of the up-split backward (the pool125 kernels, the class GEMMs, the combine / contraction
 // kernels of up125.hip, engine.hip and hoststub/up125_check.cpp all take their arithmetic from here).
 //
 // up8.h: per axis, with a the coarse coordinate,  R[a] = dy[2a] + dy[2a+1],  Q[a] = dy[2a-1] + dy[2a]  and
@@ -112,6 +112,47 @@ ICS_UP125_HD bool up125_shape_ok(int S, int N, int Cu, int B) {
   const size_t rows = (size_t)B * (S / 4) * (S / 4) * (S / 4);
   const size_t w = (size_t)(8 * N > Cu ? 8 * N : Cu);
   return rows * w < ((size_t)1 << 30);
+}
+
+// ---- pooling of dy into the 125 blocks, one fine plane at a time (pool125_planes_kernel and hoststub/pool125_check.cpp
+// run these same functions; V is a float4 on the device and a float on the host).  The blocks are separable: per axis
+// the five types are +-1 combinations of the six window samples, so a plane fz of a tile's window is loaded, x-transformed
+// and (y, x)-accumulated ONCE into the 25 partial sums S_fz[ty][tx], and the z combination of the six sets comes last.
+enum { UP125_POOL_WAVES = 6, UP125_POOL_ROUNDS = 5, UP125_XCH_ELEMS = 6 * 5 * 64 };
+// lane of wave-sized group (bx, by) -> tile row and first channel: 2^lgc float4 columns of N per tile, 64 >> lgc tiles
+ICS_UP125_F void up125_pool_lane(int lgc, unsigned bx, unsigned by, int lane, unsigned* tile, int* n) {
+  *n = (int)(((by << lgc) + ((unsigned)lane & ((1u << lgc) - 1u))) * 4u);
+  *tile = bx * (64u >> lgc) + ((unsigned)lane >> lgc);
+}
+// element of one exchange round (one ty): plane fz, x type tx, lane -- a wave's 64 lanes adjoin
+ICS_UP125_HD int up125_xch_off(int fz, int tx, int lane) { return (fz * 5 + tx) * 64 + lane; }
+// stage 1, x transform of one line of six samples
+template <class V>
+ICS_UP125_F void up125_xline(const V* v, V* xr) {
+  const V q0 = v[0] + v[1], q1 = v[2] + v[3], q2 = v[4] + v[5];
+  xr[UP125_D1] = q0 - q1; xr[UP125_R0] = v[1] + v[2]; xr[UP125_Q1] = q1; xr[UP125_D2] = q1 - q2; xr[UP125_R1] = v[3] + v[4];
+}
+// stage 1, line fy of the plane enters the (ty, tx) sums S[ty * 5 + tx] with the sign of up125_coef(ty, fy)
+template <class V>
+ICS_UP125_F void up125_yacc(int fy, const V* xr, V* S) {
+#pragma unroll
+  for (int ty = 0; ty < 5; ++ty) {
+    const int s = up125_coef(ty, fy);
+    if (s == 0) continue;
+#pragma unroll
+    for (int tx = 0; tx < 5; ++tx) {
+      if (s > 0) S[ty * 5 + tx] += xr[tx]; else S[ty * 5 + tx] -= xr[tx];
+    }
+  }
+}
+// stage 2, z type tz from the planes' sums s[fz]; only the planes with up125_coef(tz, fz) != 0 are read
+template <class V>
+ICS_UP125_F V up125_zcomb(int tz, const V* s) {
+  return tz == UP125_D1 ? (s[0] + s[1]) - (s[2] + s[3])
+       : tz == UP125_R0 ? s[1] + s[2]
+       : tz == UP125_Q1 ? s[2] + s[3]
+       : tz == UP125_D2 ? (s[2] + s[3]) - (s[4] + s[5])
+                        : s[3] + s[4];
 }
 
 // ---- class weight images, as the pack jobs build them: piece i = ((tz * 5 + ty) * (N / 4) + n4) * Cu + c  (c fastest:

@@ -4,15 +4,19 @@
 #include "common.h"
 #include "elementwise.h"
 #include "up125.h"
+#include "scratch.h"
+#include "icsg3d.h"
 
 #include <algorithm>
+#include <string>
 
 namespace ics {
 
 typedef float qf4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------
-// pool125: one WAVE = one z type (blockDim = 5 waves), one lane = one tile x four channels.  A lane reads the 6 x 6 fine
+// pool125, one wave per z type (ICSG3D_POOL125_V1; the default is pool125_planes_kernel below, which reads each plane once):
+// one WAVE = one z type (blockDim = 5 waves), one lane = one tile x four channels.  A lane reads the 6 x 6 fine
 // samples of the <= 4 planes its z type needs (216 float4 for the five waves of a tile where dy holds 64 per tile; the
 // repeats are the same lines in the same workgroup), applies the x transform per line, and accumulates the 25 (y, x)
 // types with the +-1 coefficients of up125_coef.  Out-of-range samples are 0 (the borders of up8.h's Q).
@@ -79,14 +83,90 @@ __global__ __launch_bounds__(320) void pool125_kernel(const float* __restrict__ 
     default: pool125_body<4>(dy, S, u.N, b, jz, jy, jx, tile, n, out, u); break;
   }
 }
-int launch_pool125(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up125Geom& u) {
+// ------------------------------------------------------------------------------------------
+// pool125, every fine plane once: one WAVE = one plane fz of the tile's 6 x 6 x 6 window (blockDim = 6 waves), lanes as
+// above.  Stage 1 (up125_xline, up125_yacc): the wave loads its plane's 36 float4, and keeps the 25 (ty, tx) sums of
+// that plane in registers: 216 float4 loaded per tile and channel quad where the kernel above loads 504.  Stage 2
+// (up125_zcomb): the planes meet in LDS in five rounds of one ty each (6 planes x 5 tx x 64 lanes x 16 B = 30 KB, two
+// buffers so that a round's stores need not wait for the previous round's loads: one barrier per round); the wave
+// that owns z type tz (waves 0..4) reads the <= 4 planes of its type and stores the five blocks of the round.
+// EVERY wave reaches EVERY barrier: a plane outside the volume and a tile row past the end only turn loads into zeros
+// and switch the global stores off; nothing returns early and no barrier stands inside a condition.
+// ------------------------------------------------------------------------------------------
+template <int TZ>
+__device__ __forceinline__ void pool125_zstore(const qf4* __restrict__ buf, int lane, int ty, bool live, unsigned tile, int n,
+                                               float* __restrict__ out, const Up125Geom& u) {
+#pragma unroll
+  for (int tx = 0; tx < 5; ++tx) {
+    qf4 s[6];
+#pragma unroll
+    for (int fz = 0; fz < 6; ++fz)
+      s[fz] = up125_coef(TZ, fz) != 0 ? buf[up125_xch_off(fz, tx, lane)] : qf4{0.f, 0.f, 0.f, 0.f};
+    const qf4 v = up125_zcomb(TZ, s);
+    const int q = up125_cls(TZ) * 9 + up125_cls(ty) * 3 + up125_cls(tx);
+    if (live) *reinterpret_cast<qf4*>(out + up125_pooled_off(u, q, tile, up125_block(q, TZ, ty, tx), n)) = v;
+  }
+}
+__global__ __launch_bounds__(64 * UP125_POOL_WAVES) void pool125_planes_kernel(const float* __restrict__ dy, int S, int lgc,
+                                                                               float* __restrict__ out, Up125Geom u) {
+  __shared__ qf4 xch[2][UP125_XCH_ELEMS];
+  const int fz = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned tile;
+  int n;
+  up125_pool_lane(lgc, blockIdx.x, blockIdx.y, lane, &tile, &n);
+  const bool live = tile < u.rows;   // a tile row past the end: no global access, but every barrier below
+  const int T = u.T, lg = u.lgT, N = u.N;
+  const int jx = tile & (T - 1), jy = (tile >> lg) & (T - 1), jz = (tile >> (2 * lg)) & (T - 1), b = tile >> (3 * lg);
+  // stage 1: this wave's plane
+  qf4 Sa[25];
+#pragma unroll
+  for (int k = 0; k < 25; ++k) Sa[k] = qf4{0.f, 0.f, 0.f, 0.f};
+  const int z = 4 * jz - 1 + fz;
+  const bool zok = live && (unsigned)z < (unsigned)S;
+#pragma unroll
+  for (int fy = 0; fy < 6; ++fy) {
+    const int y = 4 * jy - 1 + fy;
+    const bool yok = zok && (unsigned)y < (unsigned)S;
+    const float* line = dy + (yok ? ((((size_t)b * S + z) * S + y) * S) * (size_t)N + n : (size_t)0);
+    qf4 v[6];
+#pragma unroll
+    for (int fx = 0; fx < 6; ++fx) {
+      const int x = 4 * jx - 1 + fx;
+      const bool ok = yok && (unsigned)x < (unsigned)S;
+      v[fx] = ok ? *reinterpret_cast<const qf4*>(line + (size_t)(ok ? x : 0) * N) : qf4{0.f, 0.f, 0.f, 0.f};
+    }
+    qf4 xr[5];
+    up125_xline(v, xr);
+    up125_yacc(fy, xr, Sa);
+  }
+  // stage 2: five rounds of one ty
+#pragma unroll
+  for (int ty = 0; ty < UP125_POOL_ROUNDS; ++ty) {
+    qf4* buf = xch[ty & 1];
+#pragma unroll
+    for (int tx = 0; tx < 5; ++tx) buf[up125_xch_off(fz, tx, lane)] = Sa[ty * 5 + tx];
+    __syncthreads();
+    // buf is written again in round ty + 2, behind the barrier of round ty + 1, which every reader of this round has passed
+    switch (fz) {   // wave-uniform; wave 5 owns no z type
+      case 0: pool125_zstore<0>(buf, lane, ty, live, tile, n, out, u); break;
+      case 1: pool125_zstore<1>(buf, lane, ty, live, tile, n, out, u); break;
+      case 2: pool125_zstore<2>(buf, lane, ty, live, tile, n, out, u); break;
+      case 3: pool125_zstore<3>(buf, lane, ty, live, tile, n, out, u); break;
+      case 4: pool125_zstore<4>(buf, lane, ty, live, tile, n, out, u); break;
+      default: break;
+    }
+  }
+}
+int launch_pool125(hipStream_t st, const float* dy, int B, int S, int N, float* out, const Up125Geom& u, bool v1) {
   ICS_CHECK(up125_shape_ok(S, N, u.Cu, B) && u.T == S / 4 && u.N == N && (1 << u.lgT) == u.T &&
                 u.rows == (unsigned)B * (unsigned)(u.T * u.T * u.T),
             "pool125: layout does not match the shape");
   int lgc = 0;
   while ((1 << lgc) < std::min(N / 4, 64)) ++lgc;   // float4 columns of a tile per wave (N = 32 * 2^k: a power of two)
   const unsigned tpw = 64u >> lgc;
-  ICS_LAUNCH(pool125_kernel, dim3((u.rows + tpw - 1) / tpw, (unsigned)((N / 4) >> lgc)), dim3(320), 0, st, dy, S, lgc, out, u);
+  const dim3 grid((u.rows + tpw - 1) / tpw, (unsigned)((N / 4) >> lgc));
+  if (v1) ICS_LAUNCH(pool125_kernel, grid, dim3(320), 0, st, dy, S, lgc, out, u);
+  else ICS_LAUNCH(pool125_planes_kernel, grid, dim3(64 * UP125_POOL_WAVES), 0, st, dy, S, lgc, out, u);
   ICS_HIP(hipGetLastError());
   return 0;
 }
@@ -252,3 +332,31 @@ int launch_pack_up125_pieces(hipStream_t st, const float* w, int Cin_total, int 
 }
 
 }  // namespace ics
+
+using namespace ics;
+
+extern "C" {
+
+// the pooling pass alone on a host array (include/icsg3d.h)
+int ics_op_up125_pool(const float* dy, int B, int S, int N, int variant, float* out) {
+  const std::string op = "ics_op_up125_pool: ";
+  ICS_CHECK(dy && out, op + "dy and out are required");
+  ICS_CHECK(variant == 0 || variant == 1, op + "variant is 0 (one wave per z type) or 1 (one wave per fine plane)");
+  ICS_CHECK(up125_shape_ok(S, N, 64, B), op + "need S a power of two >= 8, N = 32 * 2^k and B (S/4)^3 * 8 N < 2^30");
+  const Up125Geom u = up125_geom(B, S, N, 64);
+  const size_t cnt = (size_t)B * S * S * S * N, pooled = up125_pooled_floats(u.rows, N);
+  hipStream_t st;
+  ICS_TRY(op_stream(&st));
+  Layout L;
+  const auto s_dy = L.add<float>(cnt);
+  const auto s_out = L.add<float>(pooled);
+  float *d_dy, *d_out;
+  ICS_TRY(L.reserve(s_dy, &d_dy, s_out, &d_out));
+  ICS_TRY(L.upload(s_dy, dy, cnt, st));
+  ICS_TRY(launch_pool125(st, d_dy, B, S, N, d_out, u, variant == 0));
+  ICS_TRY(L.download(out, s_out, pooled, st));
+  ICS_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+}  // extern "C"

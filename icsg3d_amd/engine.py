@@ -1122,6 +1122,20 @@ def sqdiff(a, b, blocks_per_sample, coef=0.0, grad=False, accumulate_into=None):
     return part, g
 
 
+def up125_pool(dy, variant=1):
+    """Single-op entry (ics_op_up125_pool): the pooling pass of the 125-product up-split backward alone.  dy (B,S,S,S,N)
+    float32; variant 0: one wave per z type, 1: one wave per fine plane.  Returns the 125 blocks of every 4x4x4 tile as
+    one flat float32 array of 125 * B (S/4)^3 * N elements in the class-major layout of csrc/up125.h."""
+    lib = L.load()
+    dy = _f32(dy)
+    if dy.ndim != 5 or dy.shape[1] != dy.shape[2] or dy.shape[1] != dy.shape[3]:
+        raise ValueError("up125_pool: dy must be (B, S, S, S, N), got %s" % (dy.shape,))
+    B, S, N = dy.shape[0], dy.shape[1], dy.shape[4]
+    out = np.empty(125 * B * (S // 4) ** 3 * N, np.float32)
+    L.check(lib.ics_op_up125_pool(L.fptr(dy), B, S, N, int(variant), L.fptr(out)))
+    return out
+
+
 def unet_head(x, wsoft, bsoft, wsig, bsig, labels, mode=1, fused=True, loss_weight=0.0, bce_from_logits=False,
               class_weights=None):
     """Single-op entry (kernel parity tests): the heads + losses + metrics on a given trunk output x (M,128).

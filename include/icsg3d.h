@@ -842,6 +842,12 @@ int ics_op_vae_latent(ics_vae_latent* a);
  * optional: coef * (b - a), written (accumulate = 0) or added to what it holds (accumulate = 1). */
 int ics_op_sqdiff(const float* a, const float* b, int B, size_t per_sample, int blocks_per_sample, float coef, int accumulate,
                   float* grad_in_out, double* partial_out);
+/* The pooling pass of the 125-product up-split backward alone: dy [B][S][S][S][N] -> out, the 125 blocks of every
+ * 4 x 4 x 4 fine tile, 125 * B (S/4)^3 * N floats in the class-major layout of csrc/up125.h (up125_pooled_off).
+ * variant 0: one wave per z type; variant 1: one wave per fine plane, every plane of a tile's window read once.
+ * Refused before anything is launched: S not a power of two >= 8, N not 32 * 2^k, a batch whose blocks leave 32-bit
+ * offsets.  Synchronous, the calling thread's op stream and scratch. */
+int ics_op_up125_pool(const float* dy, int B, int S, int N, int variant, float* out);
 /* kernel micro-benchmark on device-resident constant data, HIP-event timed: mode 0 forward
  * (ablate 0 = full kernel, 1 = MFMA+LDS reads only, 2 = MFMA only), 1 backward-data, 2 backward-weight. */
 int ics_op_conv3d_bench(int B, int S, int Cin, int Cout, int taps, int mode, int ablate, int iters,
