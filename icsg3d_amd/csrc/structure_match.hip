@@ -10,42 +10,32 @@
 // counts over the sorted queries numbers all pairs, and the device finds a pair's query by bisection of that prefix: no
 // pair list is uploaded.  Structures of up to 64 atoms sort first, so pair numbers below a boundary go to the wave kernel
 // (four pairs per 256-thread workgroup) and the rest to the workgroup kernel (one pair per 256 threads).
-// Kernel: atoms are stored sorted by (species, index); A and B of a compared pair have the same sorted species list, so
-// thread k owns A's k-th sorted atom and scans the run [lo, hi) of its species in B, where the lower slot is the lower
-// atom index.  Wrapped fractional coordinates of A and B live in LDS.  The (op, anchor) loop is uniform over the owning
-// wave / workgroup; a combination is dropped at the first ballot that shows an atom beyond 2 tol.  Injectivity is an
-// integer LDS exchange of a per-combination tag; sums are wave butterflies combined in wave order, so results are the
-// same bits run to run.  Pair results of a chunk are reduced per query by a second kernel (one wave per query) into a
+// Kernel: A and B of a compared pair have the same sorted species list, so thread k owns A's k-th sorted atom and scans
+// the run of its species in B; the scan and the test of one (op, anchor) combination are structure_map.h's, shared with
+// structure_symmetry.hip.  The (op, anchor) loop is uniform over the owning wave / workgroup and keeps the best
+// (rms, op, anchor).  Pair results of a chunk are reduced per query by a second kernel (one wave per query) into a
 // per-query state that is merged by key -- (partner) for duplicates, (rms, partner) for references -- so neither the
 // chunking nor any arrival order shows in the result.
-#include "scratch.h"
+#include "structure_map.h"
 #include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 
 namespace ics {
 namespace {
 
-constexpr int kMatchMaxAtoms = 256;   // atoms per structure: one thread per atom of A
-constexpr int kMatchSmall = 64;       // atoms one wave takes
 constexpr int kMatchOps = 48;
-constexpr int kMatchMaxSpecies = 94;
 constexpr long long kMatchChunkPairs = 1 << 20;        // pair results per chunk: 16 B each
 constexpr size_t kMatchTableBudget = (size_t)1 << 31;  // resident structure tables
 constexpr int kCell = 16;                              // doubles per structure: M[9], G[6] (00 01 02 11 12 22), pad
 constexpr int kStateI = 6;                             // ints per query: dup k, op, anchor; ref k, op, anchor
 
 long long chunk_pairs() {
-  static const long long v = [] {
-    const char* e = std::getenv("ICSG3D_MATCH_CHUNK_PAIRS");
-    const long long r = e ? std::atoll(e) : 0;
-    return r >= 1 && r < kMatchChunkPairs ? r : kMatchChunkPairs;
-  }();
+  static const long long v = env_cap("ICSG3D_MATCH_CHUNK_PAIRS", kMatchChunkPairs);
   return v;
 }
 
@@ -54,29 +44,6 @@ __device__ __forceinline__ double sel3(double a, double b, double c, int i) { re
 __device__ __forceinline__ double sym3(const double* g, int k, int l) {
   const int lo = min(k, l), hi = max(k, l);
   return g[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
-}
-
-// Sums of a, b, c and the maximum of m over the owning group (wave butterfly, then the wave slots in wave order).
-template <int NW>
-__device__ __forceinline__ void group_reduce(double& a, double& b, double& c, double& m, double (*red)[NW][4], int& ph,
-                                             int wave, int lane) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-    c += __shfl_xor(c, o, 64);
-    m = fmax(m, __shfl_xor(m, o, 64));
-  }
-  if (NW > 1) {
-    if (lane == 0) { red[ph][wave][0] = a; red[ph][wave][1] = b; red[ph][wave][2] = c; red[ph][wave][3] = m; }
-    __syncthreads();
-    a = red[ph][0][0]; b = red[ph][0][1]; c = red[ph][0][2]; m = red[ph][0][3];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {
-      a += red[ph][w][0]; b += red[ph][w][1]; c += red[ph][w][2]; m = fmax(m, red[ph][w][3]);
-    }
-    ph ^= 1;   // the other buffer next: a slot is rewritten only after a barrier every reader of it has passed
-  }
 }
 
 template <int G>
@@ -163,32 +130,14 @@ __global__ __launch_bounds__(256) void structure_match_kernel(
                  pz = s2 * sel3(a0x, a0y, a0z, p2k);
     for (int js = alo; js < ahi; ++js) {
       const double tx = fb[grp][0][js] - px, ty = fb[grp][1][js] - py, tz = fb[grp][2][js] - pz;
-      const double x = qx + tx, y = qy + ty, z = qz + tz;
-      double bd2 = kInf, ux = 0.0, uy = 0.0, uz = 0.0;
-      int br = rlo;
-      for (int r = rlo; r < rhi; ++r) {
-        double da = fb[grp][0][r] - x, db = fb[grp][1][r] - y, dc = fb[grp][2][r] - z;
-        da -= rint(da); db -= rint(db); dc -= rint(dc);
-        const double vx = da * mb[0] + db * mb[3] + dc * mb[6], vy = da * mb[1] + db * mb[4] + dc * mb[7],
-                     vz = da * mb[2] + db * mb[5] + dc * mb[8];
-        const double d2 = vx * vx + vy * vy + vz * vz;
-        if (d2 < bd2) { bd2 = d2; ux = vx; uy = vy; uz = vz; br = r; }
+      double bd2, ux, uy, uz, rms, sx, sy, sz;
+      const int br = nearest_in_run(fb[grp][0], fb[grp][1], fb[grp][2], rlo, rhi, qx + tx, qy + ty, qz + tz, mb, bd2, ux,
+                                    uy, uz);
+      const int tag = o * kMapMaxAtoms + (js - alo) + 1;
+      if (map_test<NW>(have, br, bd2, ux, uy, uz, tol, tag, mark[grp], dn, red, ph, wave, lane, rms, sx, sy, sz) &&
+          rms < best) {
+        best = rms; best_op = o; best_anchor = bidx[grp][js];
       }
-      const bool far = have && !(sqrt(bd2) <= 2.0 * tol);                          // (a)
-      if (NW == 1) {
-        if (__ballot(far) != 0ull) continue;
-      }
-      const int tag = o * kMatchMaxAtoms + (js - alo) + 1;
-      const bool twice = have && atomicExch(&mark[grp][br], tag) == tag;          // (b): a second atom on the same nb
-      double sx = have ? ux : 0.0, sy = have ? uy : 0.0, sz = have ? uz : 0.0, bad = (far || twice) ? 1.0 : 0.0;
-      group_reduce<NW>(sx, sy, sz, bad, red, ph, wave, lane);
-      if (bad != 0.0) continue;
-      const double rx = ux - sx / dn, ry = uy - sy / dn, rz = uz - sz / dn;
-      double r2 = have ? rx * rx + ry * ry + rz * rz : 0.0, z0 = 0.0, z1 = 0.0, mx = r2;
-      group_reduce<NW>(r2, z0, z1, mx, red, ph, wave, lane);
-      if (!(sqrt(mx) <= tol)) continue;                                            // (c)
-      const double rms = sqrt(r2 / dn);
-      if (rms < best) { best = rms; best_op = o; best_anchor = bidx[grp][js]; }
     }
   }
   if (active && gt == 0) {
@@ -255,19 +204,6 @@ int launch_match(hipStream_t st, long long p0, int npairs, const long long* pref
   return 0;
 }
 
-// lattice rows -> volume and the norms of the columns of the inverse
-void cell_norms(const double* M, double* vol, double g[3]) {
-  const double* va = M; const double* vb = M + 3; const double* vc = M + 6;
-  auto cross = [](const double* u, const double* v, double* o) {
-    o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
-  };
-  auto norm = [](const double* u) { return std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]); };
-  double bc[3], ca[3], ab[3];
-  cross(vb, vc, bc); cross(vc, va, ca); cross(va, vb, ab);
-  *vol = va[0] * bc[0] + va[1] * bc[1] + va[2] * bc[2];
-  g[0] = norm(bc) / *vol; g[1] = norm(ca) / *vol; g[2] = norm(ab) / *vol;
-}
-
 // The op list of `ops_mode` (0..2): perm[k][3], sign[k][3] with f'_k = sign_k f[perm_k]; returns the count (1, 24, 48).
 // Order: lexicographic over (permutation, sign pattern) -- permutations (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0), and
 // per permutation the sign patterns (+,+,+) (+,+,-) (+,-,+) (+,-,-) (-,+,+) (-,+,-) (-,-,+) (-,-,-).  Index 0 is the
@@ -300,33 +236,7 @@ int structure_match_check(const int32_t* offsets, const int32_t* species, const 
   ICS_CHECK(std::isfinite(tol) && tol > 0.0, op + "tol must be finite and > 0");
   ICS_CHECK(std::isfinite(ltol) && ltol > 0.0, op + "ltol must be finite and > 0");
   ICS_CHECK(ops_mode >= 0 && ops_mode <= 2, op + "ops_mode must be 0 (identity), 1 (rotations) or 2 (all 48)");
-  const int ns = nq + nref;
-  ICS_CHECK(offsets[0] == 0, op + "offsets[0] must be 0");
-  for (int s = 0; s < ns; ++s)
-    ICS_CHECK(offsets[s + 1] >= offsets[s], op + "offsets decrease at structure " + std::to_string(s));
-  ICS_CHECK((species && frac) || offsets[ns] == 0, op + "null species or frac");
-  for (int s = 0; s < ns; ++s) {
-    if (!eligible[s]) continue;
-    const std::string who = op + "eligible structure " + std::to_string(s);
-    const long long n = (long long)offsets[s + 1] - offsets[s];
-    ICS_CHECK(n >= 1, who + " has no atoms");
-    ICS_CHECK(n <= kMatchMaxAtoms, who + " has " + std::to_string(n) + " atoms, above the limit of " +
-                                       std::to_string(kMatchMaxAtoms));
-    const double* M = lattice + 9 * (size_t)s;
-    for (int k = 0; k < 9; ++k) ICS_CHECK(std::isfinite(M[k]), who + " has a non-finite lattice entry");
-    for (long long k = 3LL * offsets[s]; k < 3LL * offsets[s + 1]; ++k)
-      ICS_CHECK(std::isfinite(frac[k]) && std::fabs(frac[k]) <= 1e15,
-                who + " has a non-finite or out-of-range (> 1e15) fractional coordinate");
-    for (long long k = offsets[s]; k < offsets[s + 1]; ++k)
-      ICS_CHECK(species[k] >= 1 && species[k] <= kMatchMaxSpecies, who + " has a species outside 1..94");
-    double vol, g[3];
-    cell_norms(M, &vol, g);
-    ICS_CHECK(vol > 0.0 && std::isfinite(vol), who + " has a lattice volume <= 0");
-    for (int k = 0; k < 3; ++k)
-      ICS_CHECK(2.0 * tol * g[k] < 0.5, who + ": the cell is too thin for tol (2 tol times an inverse-column norm "
-                                                  "reaches 0.5: another image could lie within 2 tol)");
-  }
-  return 0;
+  return check_structures(op, offsets, species, frac, lattice, eligible, nq + nref, tol);
 }
 
 }  // namespace
@@ -359,13 +269,12 @@ extern "C" int ics_op_structure_match(const int32_t* offsets, const int32_t* spe
   const int ne = (int)order.size();
   if (ne == 0) return 0;
   const size_t natoms_all = (size_t)offsets[ns];
-  std::vector<int> sperm(natoms_all), sz(natoms_all);   // at the structure's own offsets: sorted atom -> atom, its species
+  // at the structure's own offsets: sorted atom -> atom, its species, its run word; per structure the anchor run
+  std::vector<int> sperm(natoms_all), sz(natoms_all), srun(natoms_all), anchor(2 * (size_t)ns);
   for (int s : order) {
-    const int a0 = offsets[s], n = offsets[s + 1] - a0;
-    int* p = sperm.data() + a0;
-    for (int k = 0; k < n; ++k) p[k] = k;
-    std::stable_sort(p, p + n, [&](int a, int b) { return species[a0 + a] < species[a0 + b]; });
-    for (int k = 0; k < n; ++k) sz[a0 + k] = species[a0 + p[k]];
+    const int a0 = offsets[s];
+    sort_atoms(species + a0, offsets[s + 1] - a0, sperm.data() + a0, sz.data() + a0, srun.data() + a0, &anchor[2 * s],
+               &anchor[2 * s + 1]);
   }
   auto key_cmp = [&](int a, int b) {   // <0, 0, >0 on (atom count, sorted species)
     const int na = offsets[a + 1] - offsets[a], nb = offsets[b + 1] - offsets[b];
@@ -380,7 +289,7 @@ extern "C" int ics_op_structure_match(const int32_t* offsets, const int32_t* spe
   // ---- buckets, sorted queries and the pair prefix
   std::vector<int> qrec;          // per sorted query: slot, b0, r0, r1
   std::vector<long long> pref(1, 0);
-  long long psmall = 0;           // pairs of structures of up to kMatchSmall atoms come first
+  long long psmall = 0;           // pairs of structures of up to kMapSmall atoms come first
   for (int b0 = 0; b0 < ne;) {
     int b1 = b0 + 1;
     while (b1 < ne && key_cmp(order[b0], order[b1]) == 0) ++b1;
@@ -392,7 +301,7 @@ extern "C" int ics_op_structure_match(const int32_t* offsets, const int32_t* spe
       qrec.insert(qrec.end(), {s, b0, r0, b1});
       pref.push_back(pref.back() + (s - b0) + (b1 - r0));
     }
-    if (offsets[order[b0] + 1] - offsets[order[b0]] <= kMatchSmall) psmall = pref.back();
+    if (offsets[order[b0] + 1] - offsets[order[b0]] <= kMapSmall) psmall = pref.back();
     b0 = b1;
   }
   const int nqs = (int)qrec.size() / 4;
@@ -428,24 +337,11 @@ extern "C" int ics_op_structure_match(const int32_t* offsets, const int32_t* spe
     const double* M = lattice + 9 * (size_t)s;
     double* c = hc + (size_t)kCell * k;
     std::memcpy(c, M, 72);
-    int gi = 9;
-    for (int i = 0; i < 3; ++i)
-      for (int j = i; j < 3; ++j) c[gi++] = M[3 * i] * M[3 * j] + M[3 * i + 1] * M[3 * j + 1] + M[3 * i + 2] * M[3 * j + 2];
-    // species runs in sorted order; the anchor species: the smallest count, ties to the lower Z (= the earlier run)
-    int alo = 0, ahi = n;
-    for (int lo = 0; lo < n;) {
-      int hi = lo + 1;
-      while (hi < n && sz[a0 + hi] == sz[a0 + lo]) ++hi;
-      for (int i = lo; i < hi; ++i) hrun[at + i] = lo | (hi << 16);
-      if (lo == 0 || hi - lo < ahi - alo) { alo = lo; ahi = hi; }
-      lo = hi;
-    }
-    for (int i = 0; i < n; ++i) {
-      const int a = sperm[a0 + i];
-      hperm[at + i] = a;
-      std::memcpy(hf + 3 * (at + i), frac + 3 * (size_t)(a0 + a), 24);
-    }
-    hinfo[k] = make_int4((int)at, n, alo, ahi);
+    cell_gram(M, c + 9);
+    std::memcpy(hperm + at, sperm.data() + a0, (size_t)n * 4);
+    std::memcpy(hrun + at, srun.data() + a0, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) std::memcpy(hf + 3 * (at + i), frac + 3 * (size_t)(a0 + sperm[a0 + i]), 24);
+    hinfo[k] = make_int4((int)at, n, anchor[2 * s], anchor[2 * s + 1]);
     at += n;
   }
   std::memcpy(hpref, pref.data(), (size_t)(nqs + 1) * 8);

@@ -8,35 +8,30 @@
 //   decodes its code, keeps determinant +-1 and tests W^T G W against G in fp64; the admissible codes are compacted in code
 //   order by ballot + wave prefix + the four wave totals.
 // Stage 2 (sym_ops_kernel<G>, unit = (structure, admissible W)): one wave (G = 64, four units per workgroup) or one
-//   256-thread workgroup per unit, lane = atom in sorted order.  The wrapped coordinates live in LDS and the species run
-//   of an atom is scanned as same-address broadcasts.  The anchor loop is uniform over the owning wave / workgroup; a
-//   combination is dropped at the first ballot that shows an atom beyond 2 tol; injectivity is an integer LDS exchange of
-//   a per-combination tag; sums are wave butterflies combined in wave order.  Every (W, anchor) gets one entry of the
-//   candidate table (t*, rms or -1).  sym_scan_kernel (one workgroup per structure) walks the table in (code, anchor) order
-//   and gives each passing combination its slot by ballot + prefix, so the order of the operation list holds by
-//   construction; it also counts n_ops, n_point, n_trans and the rotation types over ALL passing combinations.
+//   256-thread workgroup per unit, lane = atom in sorted order.  The scan of an atom's species run and the test of one
+//   (W, anchor) combination are structure_map.h's, shared with structure_match.hip; the anchor loop is uniform over the
+//   owning wave / workgroup.  Every (W, anchor) gets one entry of the candidate table (t*, rms or -1).  sym_scan_kernel
+//   (one workgroup per structure) walks the table in (code, anchor) order and gives each passing combination its slot by
+//   ballot + prefix, so the order of the operation list holds by construction; it also counts n_ops, n_point, n_trans
+//   and the rotation types over ALL passing combinations.
 // Stage 3 (sym_group_kernel, one workgroup per structure whose reason is still 0): recomputes nb_g per stored operation
 //   (one byte per atom, kept in device memory for the closure test), sums the projection in operation order, tests
 //   closure over all ordered pairs through a (lattice operation, anchor) -> slot table in LDS, then orbits,
 //   multiplicities, sym_G, sym_shift and sym_resid.
 // The candidate table, the maps and the operation lists are chunked over structures under a byte cap; no result depends
 // on the chunking, and no floating-point atomic is used anywhere: the same bits run to run.
-#include "scratch.h"
+#include "structure_map.h"
 #include "../../include/icsg3d.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 
 namespace ics {
 
-constexpr int kSymMaxAtoms = 256;      // atoms per structure: one thread per atom
-constexpr int kSymSmall = 64;          // atoms one wave takes
 constexpr int kSymLatCap = 64;         // admissible lattice operations kept per structure
-constexpr int kSymMaxSpecies = 94;
 constexpr int kSymMaxOpsLimit = 4096;  // largest max_ops accepted
 constexpr int kSymCodes = 19683;       // 3^9 matrices with entries in {-1, 0, 1}
 constexpr int kSymIdentityCode = 16484;
@@ -65,35 +60,8 @@ constexpr int kCounts = 16;   // ints per structure: n_ops, n_point, n_trans, re
 constexpr int kOpBytes = 4 + 4 + 4 + 24 + 8;   // code, anchor, (slot | lattice op << 16), t*, rms
 
 size_t chunk_bytes() {
-  static const size_t v = [] {
-    const char* e = std::getenv("ICSG3D_SYMMETRY_CHUNK_BYTES");
-    const long long r = e ? std::atoll(e) : 0;
-    return r >= 1 && (size_t)r < kSymChunkBytes ? (size_t)r : kSymChunkBytes;
-  }();
+  static const size_t v = (size_t)env_cap("ICSG3D_SYMMETRY_CHUNK_BYTES", (long long)kSymChunkBytes);
   return v;
-}
-
-// Sums of a, b, c and the maximum of m over the owning group (wave butterfly, then the wave slots in wave order).
-template <int NW>
-__device__ __forceinline__ void group_reduce(double& a, double& b, double& c, double& m, double (*red)[NW][4], int& ph,
-                                             int wave, int lane) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-    c += __shfl_xor(c, o, 64);
-    m = fmax(m, __shfl_xor(m, o, 64));
-  }
-  if (NW > 1) {
-    if (lane == 0) { red[ph][wave][0] = a; red[ph][wave][1] = b; red[ph][wave][2] = c; red[ph][wave][3] = m; }
-    __syncthreads();
-    a = red[ph][0][0]; b = red[ph][0][1]; c = red[ph][0][2]; m = red[ph][0][3];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {
-      a += red[ph][w][0]; b += red[ph][w][1]; c += red[ph][w][2]; m = fmax(m, red[ph][w][3]);
-    }
-    ph ^= 1;   // the other buffer next: a slot is rewritten only after a barrier every reader of it has passed
-  }
 }
 
 // The maximum of v over a 256-thread workgroup, to every thread.
@@ -111,24 +79,6 @@ __device__ __forceinline__ void apply_w(const double* w, double x, double y, dou
   ox = w[0] * x + w[1] * y + w[2] * z;
   oy = w[3] * x + w[4] * y + w[5] * z;
   oz = w[6] * x + w[7] * y + w[8] * z;
-}
-
-// The atom of the species run [rlo, rhi) nearest to (x, y, z) by wrapped-image distance with lattice rows m (ties to the
-// lower slot = the lower atom index), its squared distance and Cartesian vector.
-__device__ __forceinline__ int nearest_in_run(const double* fx, const double* fy, const double* fz, int rlo, int rhi,
-                                              double x, double y, double z, const double* m, double& bd2, double& ux,
-                                              double& uy, double& uz) {
-  int br = rlo;
-  bd2 = __builtin_inf(); ux = uy = uz = 0.0;
-  for (int r = rlo; r < rhi; ++r) {
-    double da = fx[r] - x, db = fy[r] - y, dc = fz[r] - z;
-    da -= rint(da); db -= rint(db); dc -= rint(dc);
-    const double vx = da * m[0] + db * m[3] + dc * m[6], vy = da * m[1] + db * m[4] + dc * m[7],
-                 vz = da * m[2] + db * m[5] + dc * m[8];
-    const double d2 = vx * vx + vy * vy + vz * vz;
-    if (d2 < bd2) { bd2 = d2; ux = vx; uy = vy; uz = vz; br = r; }
-  }
-  return br;
 }
 
 // ---------------------------------------------------------------- stage 1: the lattice operations
@@ -180,13 +130,13 @@ __global__ __launch_bounds__(256) void sym_lattice_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------- stage 2: the operations
+// The second launch bound is the waves per SIMD the kernel has always had (96 and 108 VGPRs): the wave form sits one
+// register off the step from 5 to 4, and the allocator is to stay on this side of it.
 template <int G>
-__global__ __launch_bounds__(256) void sym_ops_kernel(int s0, int nsc, const int4* __restrict__ sinfo,
-                                                      const double* __restrict__ scell, const double* __restrict__ afrac,
-                                                      const int* __restrict__ arun, const int* __restrict__ nlat,
-                                                      const int* __restrict__ latcode,
-                                                      const long long* __restrict__ candoff, double tol,
-                                                      double4* __restrict__ cand) {
+__global__ __launch_bounds__(256, G == 64 ? 5 : 4) void sym_ops_kernel(
+    int s0, int nsc, const int4* __restrict__ sinfo, const double* __restrict__ scell, const double* __restrict__ afrac,
+    const int* __restrict__ arun, const int* __restrict__ nlat, const int* __restrict__ latcode,
+    const long long* __restrict__ candoff, double tol, double4* __restrict__ cand) {
   constexpr int NT = 256, NG = NT / G, NW = G / 64;
   __shared__ double fa[NG][3][G];
   __shared__ int mark[NG][G];
@@ -236,34 +186,17 @@ __global__ __launch_bounds__(256) void sym_ops_kernel(int s0, int nsc, const int
   const int na = ahi - alo;
   double4* out = cand + (active ? candoff[s] - candoff[s0] + (long long)l * na : 0);
   int ph = 0;
-  for (int js = alo; js < ahi; ++js) {      // alo = ahi = 0 for an idle group
+  for (int a = 0; a < na; ++a) {            // na = 0 for an idle group
+    const int js = alo + a;
     const double tx = fa[grp][0][js] - px, ty = fa[grp][1][js] - py, tz = fa[grp][2][js] - pz;
-    double bd2, ux, uy, uz;
+    double bd2, ux, uy, uz, rms, sx, sy, sz;
     const int br = nearest_in_run(fa[grp][0], fa[grp][1], fa[grp][2], rlo, rhi, qx + tx, qy + ty, qz + tz, m, bd2, ux, uy, uz);
-    const bool far = have && !(sqrt(bd2) <= 2.0 * tol);                            // (a)
-    bool ok = true;
-    double rms = -1.0, sx = 0.0, sy = 0.0, sz = 0.0;
-    if (NW == 1) ok = __ballot(far) == 0ull;
-    if (ok) {
-      const int tag = (js - alo) + 1;
-      const bool twice = have && atomicExch(&mark[grp][br], tag) == tag;          // (b): a second atom on the same nb
-      sx = have ? ux : 0.0; sy = have ? uy : 0.0; sz = have ? uz : 0.0;
-      double bad = (far || twice) ? 1.0 : 0.0;
-      group_reduce<NW>(sx, sy, sz, bad, red, ph, wave, lane);
-      ok = bad == 0.0;
-    }
-    if (ok) {
-      sx /= dn; sy /= dn; sz /= dn;
-      const double rx = ux - sx, ry = uy - sy, rz = uz - sz;
-      double r2 = have ? rx * rx + ry * ry + rz * rz : 0.0, z0 = 0.0, z1 = 0.0, mx = r2;
-      group_reduce<NW>(r2, z0, z1, mx, red, ph, wave, lane);
-      if (sqrt(mx) <= tol) rms = sqrt(r2 / dn);                                    // (c)
-    }
+    map_test<NW>(have, br, bd2, ux, uy, uz, tol, a + 1, mark[grp], dn, red, ph, wave, lane, rms, sx, sy, sz);
     if (gt == 0) {
-      // t* = t + inv(M)^T ubar
+      // t* = t + inv(M)^T ubar; a combination that failed leaves rms = -1 and a t* nobody reads
       const double t0 = tx + (sx * mi[0] + sy * mi[3] + sz * mi[6]), t1 = ty + (sx * mi[1] + sy * mi[4] + sz * mi[7]),
                    t2 = tz + (sx * mi[2] + sy * mi[5] + sz * mi[8]);
-      out[js - alo] = make_double4(t0 - floor(t0), t1 - floor(t1), t2 - floor(t2), rms);
+      out[a] = make_double4(t0 - floor(t0), t1 - floor(t1), t2 - floor(t2), rms);
     }
   }
 }
@@ -351,9 +284,9 @@ __global__ __launch_bounds__(256) void sym_group_kernel(
     const int* __restrict__ latcode, const long long* __restrict__ mapoff, int max_ops, int* __restrict__ counts,
     const int* __restrict__ op_slot, const double* __restrict__ op_t, unsigned char* __restrict__ maps,
     int* __restrict__ orbit, int* __restrict__ mult, double* __restrict__ sym_frac, double* __restrict__ sres) {
-  __shared__ double f[3][kSymMaxAtoms], fh[3][kSymMaxAtoms], tmp[2][3][kSymMaxAtoms];
-  __shared__ short slot_tab[kSymLatCap * kSymMaxAtoms];
-  __shared__ int wl[kSymLatCap][9], lcode[kSymLatCap], orb[kSymMaxAtoms];
+  __shared__ double f[3][kMapMaxAtoms], fh[3][kMapMaxAtoms], tmp[2][3][kMapMaxAtoms];
+  __shared__ short slot_tab[kSymLatCap * kMapMaxAtoms];
+  __shared__ int wl[kSymLatCap][9], lcode[kSymLatCap], orb[kMapMaxAtoms];
   __shared__ double red4[4];
   const int sl = blockIdx.x, s = s0 + sl, tid = threadIdx.x;
   int* cnt = counts + (size_t)kCounts * s;
@@ -517,26 +450,6 @@ __global__ __launch_bounds__(256) void sym_group_kernel(
   }
 }
 
-// lattice rows -> volume, the norms of the columns of the inverse and the inverse itself
-void cell_inverse(const double* M, double* vol, double g[3], double inv[9]) {
-  const double* va = M; const double* vb = M + 3; const double* vc = M + 6;
-  auto cross = [](const double* u, const double* v, double* o) {
-    o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
-  };
-  auto norm = [](const double* u) { return std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]); };
-  double bc[3], ca[3], ab[3];
-  cross(vb, vc, bc); cross(vc, va, ca); cross(va, vb, ab);
-  *vol = va[0] * bc[0] + va[1] * bc[1] + va[2] * bc[2];
-  g[0] = norm(bc) / *vol; g[1] = norm(ca) / *vol; g[2] = norm(ab) / *vol;
-  if (inv)
-    for (int r = 0; r < 3; ++r) { inv[3 * r] = bc[r] / *vol; inv[3 * r + 1] = ca[r] / *vol; inv[3 * r + 2] = ab[r] / *vol; }
-}
-
-void metric(const double* M, double G[9]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) G[3 * i + j] = M[3 * i] * M[3 * j] + M[3 * i + 1] * M[3 * j + 1] + M[3 * i + 2] * M[3 * j + 2];
-}
-
 // The argument rules of ics_op_structure_symmetry for its inputs, every structure checked before anything is written: 0,
 // or -1 with the error set naming the structure.
 int structure_symmetry_check(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
@@ -548,32 +461,7 @@ int structure_symmetry_check(const int32_t* offsets, const int32_t* species, con
   ICS_CHECK(std::isfinite(tol) && tol > 0.0, op + "tol must be finite and > 0");
   ICS_CHECK(std::isfinite(ltol) && ltol > 0.0, op + "ltol must be finite and > 0");
   ICS_CHECK(max_ops >= 1 && max_ops <= kSymMaxOpsLimit, op + "max_ops must be in 1..4096");
-  ICS_CHECK(offsets[0] == 0, op + "offsets[0] must be 0");
-  for (int s = 0; s < ns; ++s)
-    ICS_CHECK(offsets[s + 1] >= offsets[s], op + "offsets decrease at structure " + std::to_string(s));
-  ICS_CHECK((species && frac) || offsets[ns] == 0, op + "null species or frac");
-  for (int s = 0; s < ns; ++s) {
-    if (!eligible[s]) continue;
-    const std::string who = op + "eligible structure " + std::to_string(s);
-    const long long n = (long long)offsets[s + 1] - offsets[s];
-    ICS_CHECK(n >= 1, who + " has no atoms");
-    ICS_CHECK(n <= kSymMaxAtoms, who + " has " + std::to_string(n) + " atoms, above the limit of " +
-                                     std::to_string(kSymMaxAtoms));
-    const double* M = lattice + 9 * (size_t)s;
-    for (int k = 0; k < 9; ++k) ICS_CHECK(std::isfinite(M[k]), who + " has a non-finite lattice entry");
-    for (long long k = 3LL * offsets[s]; k < 3LL * offsets[s + 1]; ++k)
-      ICS_CHECK(std::isfinite(frac[k]) && std::fabs(frac[k]) <= 1e15,
-                who + " has a non-finite or out-of-range (> 1e15) fractional coordinate");
-    for (long long k = offsets[s]; k < offsets[s + 1]; ++k)
-      ICS_CHECK(species[k] >= 1 && species[k] <= kSymMaxSpecies, who + " has a species outside 1..94");
-    double vol, g[3];
-    cell_inverse(M, &vol, g, nullptr);
-    ICS_CHECK(vol > 0.0 && std::isfinite(vol), who + " has a lattice volume <= 0");
-    for (int k = 0; k < 3; ++k)
-      ICS_CHECK(2.0 * tol * g[k] < 0.5, who + ": the cell is too thin for tol (2 tol times an inverse-column norm "
-                                                  "reaches 0.5: another image could lie within 2 tol)");
-  }
-  return 0;
+  return check_structures(op, offsets, species, frac, lattice, eligible, ns, tol);
 }
 
 }  // namespace
@@ -616,7 +504,10 @@ extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* 
         sym_frac[3 * (size_t)(a0 + i) + c] = x - std::floor(x);
       }
     }
-    metric(lattice + 9 * (size_t)s, sym_G + 9 * (size_t)s);
+    double g6[6];
+    double* G = sym_G + 9 * (size_t)s;
+    cell_gram(lattice + 9 * (size_t)s, g6);
+    G[0] = g6[0]; G[1] = G[3] = g6[1]; G[2] = G[6] = g6[2]; G[4] = g6[3]; G[5] = G[7] = g6[4]; G[8] = g6[5];
     sym_shift[s] = sym_resid[s] = 0.0;
   }
   std::vector<int> order;
@@ -647,7 +538,7 @@ extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* 
   int *hperm, *hrun;
   ICS_TRY(in.bind(hin.data(), hin.size(), i_cell, &hc, i_frac, &hf, i_cand, &hcand, i_map, &hmap, i_info, &hinfo, i_perm,
                   &hperm, i_run, &hrun));
-  std::vector<int> idx(kSymMaxAtoms);
+  std::vector<int> sz(kMapMaxAtoms);      // the sorted species of the structure at hand: not kept
   std::vector<size_t> cost(ne);
   size_t at = 0;
   hcand[0] = hmap[0] = 0;
@@ -655,26 +546,13 @@ extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* 
     const int s = order[k], a0 = offsets[s], n = offsets[s + 1] - a0;
     const double* M = lattice + 9 * (size_t)s;
     double* c = hc + (size_t)kCell * k;
-    double vol, g[3], G[9];
+    double vol, g[3];
+    int alo, ahi;
     std::memcpy(c, M, 72);
     cell_inverse(M, &vol, g, c + 9);
-    metric(M, G);
-    c[18] = G[0]; c[19] = G[1]; c[20] = G[2]; c[21] = G[4]; c[22] = G[5]; c[23] = G[8];
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.begin() + n, [&](int a, int b) { return species[a0 + a] < species[a0 + b]; });
-    // species runs in sorted order; the anchor species: the smallest count, ties to the lower Z (= the earlier run)
-    int alo = 0, ahi = n;
-    for (int lo = 0; lo < n;) {
-      int hi = lo + 1;
-      while (hi < n && species[a0 + idx[hi]] == species[a0 + idx[lo]]) ++hi;
-      for (int i = lo; i < hi; ++i) hrun[at + i] = lo | (hi << 16);
-      if (lo == 0 || hi - lo < ahi - alo) { alo = lo; ahi = hi; }
-      lo = hi;
-    }
-    for (int i = 0; i < n; ++i) {
-      hperm[at + i] = idx[i];
-      std::memcpy(hf + 3 * (at + i), frac + 3 * (size_t)(a0 + idx[i]), 24);
-    }
+    cell_gram(M, c + 18);
+    sort_atoms(species + a0, n, hperm + at, sz.data(), hrun + at, &alo, &ahi);
+    for (int i = 0; i < n; ++i) std::memcpy(hf + 3 * (at + i), frac + 3 * (size_t)(a0 + hperm[at + i]), 24);
     hinfo[k] = make_int4((int)at, n, alo, ahi);
     const size_t ncand = (size_t)kSymLatCap * (ahi - alo), nmap = std::min((size_t)max_ops, ncand) * n;
     hcand[k + 1] = hcand[k] + (long long)ncand;
@@ -686,10 +564,10 @@ extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* 
   std::vector<int> cuts(1, 0);
   size_t max_cand = 0, max_map = 0, max_ns = 0;
   for (int k = 0; k < ne;) {
-    const bool small = hinfo[k].y <= kSymSmall;
+    const bool small = hinfo[k].y <= kMapSmall;
     size_t bytes = 0;
     int e = k;
-    while (e < ne && (hinfo[e].y <= kSymSmall) == small && (e == k || bytes + cost[e] <= chunk_bytes())) bytes += cost[e++];
+    while (e < ne && (hinfo[e].y <= kMapSmall) == small && (e == k || bytes + cost[e] <= chunk_bytes())) bytes += cost[e++];
     cuts.push_back(e);
     max_cand = std::max(max_cand, (size_t)(hcand[e] - hcand[k]));
     max_map = std::max(max_map, (size_t)(hmap[e] - hmap[k]));
@@ -734,7 +612,7 @@ extern "C" int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* 
   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
     const int c0 = cuts[ci], c1 = cuts[ci + 1], nsc = c1 - c0;
     const unsigned units = (unsigned)nsc * kSymLatCap;
-    if (hinfo[c0].y <= kSymSmall)
+    if (hinfo[c0].y <= kMapSmall)
       ICS_LAUNCH(sym_ops_kernel<64>, dim3((units + 3) / 4), dim3(256), 0, st, c0, nsc, dinfo, dcell, dfrac, drun, dnlat,
                  dlcode, dcandoff, tol, dcand);
     else
