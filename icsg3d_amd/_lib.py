@@ -94,6 +94,19 @@ class ConvLinkArgs(C.Structure):
 
 
 _U8 = C.POINTER(C.c_uint8)
+
+
+class HeadLinkArgs(C.Structure):
+    """ics_head_link (include/icsg3d.h)."""
+    _fields_ = [("B", C.c_int), ("max_batch", C.c_int), ("S", C.c_int), ("C0", C.c_int), ("ncls", C.c_int), ("x0", _F),
+                ("w", _F), ("bias", _F), ("gamma", _F), ("beta", _F), ("wsoft", _F), ("bsoft", _F), ("wsig", _F), ("bsig", _F),
+                ("labels", _U8), ("loss_weight", C.c_float), ("class_weights", _F), ("bce_from_logits", C.c_int),
+                ("want_grad", C.c_int), ("y", _F), ("mean", _F), ("rstd", _F), ("scale", _F), ("shift", _F), ("dz", _F),
+                ("metrics", _F), ("sums", C.POINTER(C.c_double)), ("dwsoft", _F), ("dwsig", _F), ("dbias_head", _F),
+                ("dw", _F), ("dbias", _F), ("dgamma", _F), ("dbeta", _F), ("dy_p", _F), ("dx0", _F), ("dy_in_place", C.c_int),
+                ("sites", C.c_void_p), ("sites_cap", C.c_int), ("ranks", C.c_int)]
+
+
 _I32 = C.POINTER(C.c_int32)
 _I64 = C.POINTER(C.c_int64)
 _H = C.c_void_p
@@ -241,6 +254,7 @@ SIGNATURES = {
     "ics_op_up125_pool": (C.c_int, [_F, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv_layer": (C.c_int, [C.POINTER(ConvLayerArgs)]),
     "ics_op_conv_link": (C.c_int, [C.POINTER(ConvLinkArgs)]),
+    "ics_op_head_link": (C.c_int, [C.POINTER(HeadLinkArgs)]),
     "ics_op_conv3d_forward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "ics_op_conv3d_bench": (C.c_int, [C.c_int] * 8 + [_F]),
     "ics_op_conv3d_backward": (C.c_int, [_F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F]),

@@ -1103,8 +1103,12 @@ __global__ __launch_bounds__(256) void head_kernel(float* __restrict__ z, int ld
 //     ITS voxel n: the softmax reductions are 24 in-lane values + two xor-shuffles (16, 32), and dz leaves as six
 //     float4 stores.  The B operand is the voxel's own row, read straight from global memory (a 16-byte load = the
 //     operand of four k-steps); only the weights sit in LDS, class-major, pitch 132 (conflict-free ds_read_b128).
-//   * The producer's BatchNorm affine is folded into the weights: W' = W * scale[ch], b' = b + sum_ch W[ch] * shift[ch]
-//     (a 1x1x1 "convolution" has no padding, so this is exact algebra; rounding differs from the unfused path at 1e-7).
+//   * The producer's BatchNorm affine is applied to the row as it leaves its registers for the matrix cores:
+//     fmaf(s, scale[ch], shift[ch]), 32 per lane and tile next to 192 MFMAs, the two vectors in LDS.  It used to be folded
+//     into the weights (W' = W * scale[ch], b' = b + sum_ch W[ch] * shift[ch]: exact algebra, a 1x1x1 "convolution" has no
+//     padding).  With channels at mean/std ~ 1000 the folded products are 1e3 times the logit they cancel to, and the
+//     rounding of W' and b' -- the same for every voxel -- stayed in the loss as a bias: 1.2e-5 .. 1.5e-5 of it, over the
+//     1e-5 the metrics are held to (tests/test_gpu_head_link.py, regime ratio1000).
 //   * Waves are independent (no barrier after the weights are staged): while one wave does its softmax the other
 //     waves of the SIMD keep the matrix cores busy.  Loss arithmetic = head_kernel's, line for line.
 // Requires ncls + 1 == 96, 128 input channels, rows % 16 == 0, no activation between the BatchNorm and the head.
@@ -1132,20 +1136,15 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
   __shared__ float shc[4][NZ];
   __shared__ double shd[4][6];
   __shared__ float cwt[CW ? 128 : 1];
+  __shared__ __attribute__((aligned(16))) float aff[2][CH];     // the producer's BatchNorm affine: scale | shift
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (CW && tid < 128) cwt[tid] = tid < NC ? cw[tid] : 0.f;
+  if (scale && tid < CH) { aff[0][tid] = scale[tid]; aff[1][tid] = shift[tid]; }
   for (int i = tid; i < NZ * CH; i += 256) {
     const int cls = i >> 7, ch = i & 127;
-    const float w = cls < NC ? wsoft_k[ch * NC + cls] : wsig_k[ch];
-    Wt[cls * kHeadWP + ch] = scale ? w * scale[ch] : w;
+    Wt[cls * kHeadWP + ch] = cls < NC ? wsoft_k[ch * NC + cls] : wsig_k[ch];
   }
-  if (tid < NZ) {
-    float b = tid < NC ? bsoft[tid] : bsig[0];
-    if (shift) {
-      for (int ch = 0; ch < CH; ++ch) b += (tid < NC ? wsoft_k[ch * NC + tid] : wsig_k[ch]) * shift[ch];
-    }
-    biasp[tid] = b;
-  }
+  if (tid < NZ) biasp[tid] = tid < NC ? bsoft[tid] : bsig[0];
   __syncthreads();
 
   const int n = lane & 15, g = lane >> 4;
@@ -1175,6 +1174,15 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const float* __restr
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) xc[kk] = xb[kk];
     if (tile + nwaves < ntiles) xload(tile + nwaves);       // next tile's rows under this tile's work
+    if (scale) {                                             // fmaf(s, scale, shift) on the row's own 32 values, rounded once
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        const hv4 sc = *reinterpret_cast<const hv4*>(&aff[0][16 * kk + 4 * g]);
+        const hv4 sh = *reinterpret_cast<const hv4*>(&aff[1][16 * kk + 4 * g]);
+#pragma unroll
+        for (int sidx = 0; sidx < 4; ++sidx) xc[kk][sidx] = __builtin_fmaf(xc[kk][sidx], sc[sidx], sh[sidx]);
+      }
+    }
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
 #pragma unroll

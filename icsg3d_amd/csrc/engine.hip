@@ -1511,6 +1511,31 @@ static UnetRefs unet_refs(Net& n) {
   return r;
 }
 
+// The head's registration and buffers (unet_build; ics_op_head_link builds its two-layer handle from the same three).
+// heads: one 1x1x1 GEMM with N = num_classes + 1; params keep the reference's two layers
+static void unet_add_head(Net& n, int d) {
+  n.head = add_conv(n, "head", 128, n.ncls + 1, 1, d, ACT_NONE, 0, ACT_NONE, false, false);
+  const int t_sw = n.add_tensor("soft/kernel", {1, 1, 1, 128, n.ncls}, true);
+  const int t_gw = n.add_tensor("sig/kernel", {1, 1, 1, 128, 1}, true);
+  const int t_sb = n.add_tensor("soft/bias", {n.ncls}, true);   // soft/bias | sig/bias contiguous
+  n.add_tensor("sig/bias", {1}, true);
+  n.head->t_w = t_sw; n.head->t_b = t_sb; n.head->t_gamma = t_gw;   // t_gamma slot reused: sig kernel index
+}
+// the resident batch: x_in [maxB][d^3][C], labels [maxB][d^3]
+static int unet_alloc_batch(Net& n) {
+  const size_t M = (size_t)n.maxB * n.d * n.d * n.d;
+  ICS_TRY(n.alloc(&n.x_in, M * n.C));
+  ICS_TRY(n.alloc(&n.labels, M));
+  return 0;
+}
+static int unet_alloc_head(Net& n) {
+  ICS_TRY(alloc_layer(n, *n.head, true, false));
+  ICS_TRY(n.alloc(&n.head_bias_grad, (size_t)256));
+  ICS_TRY(n.alloc(&n.head_dw_tmp, (size_t)128 * (n.ncls + 1)));
+  ICS_TRY(n.alloc(&n.head_xs, (size_t)256));
+  return 0;
+}
+
 static int unet_build(Net& n, const ics_unet_config& cfg) {
   n.side_on = false;     // the U-Net's weight gradients stay on the engine's stream (see Net::st2)
   n.kind = 0; n.maxB = cfg.max_batch; n.d = cfg.d; n.C = cfg.in_channels; n.ncls = cfg.num_classes;
@@ -1528,22 +1553,11 @@ static int unet_build(Net& n, const ics_unet_config& cfg) {
       {"c17", 192, 128, d, false},           {"c18", 128, 128, d, false}};
   for (auto& s : specs)
     add_conv(n, s.name, s.cin, s.cout, 27, s.S, ACT_RELU, 1, ACT_NONE, false, true, /*pad_input=*/&s == &specs[0]);
-  // heads: one 1x1x1 GEMM with N = num_classes + 1; params keep the reference's two layers
-  n.head = add_conv(n, "head", 128, cfg.num_classes + 1, 1, d, ACT_NONE, 0, ACT_NONE, false, false);
-  const int t_sw = n.add_tensor("soft/kernel", {1, 1, 1, 128, cfg.num_classes}, true);
-  const int t_gw = n.add_tensor("sig/kernel", {1, 1, 1, 128, 1}, true);
-  const int t_sb = n.add_tensor("soft/bias", {cfg.num_classes}, true);   // soft/bias | sig/bias contiguous
-  n.add_tensor("sig/bias", {1}, true);
-  n.head->t_w = t_sw; n.head->t_b = t_sb; n.head->t_gamma = t_gw;   // t_gamma slot reused: sig kernel index
+  unet_add_head(n, d);
   ICS_TRY(alloc_params(n));
-  const size_t M = (size_t)n.maxB * d * d * d;
-  ICS_TRY(n.alloc(&n.x_in, M * n.C));
-  ICS_TRY(n.alloc(&n.labels, M));
+  ICS_TRY(unet_alloc_batch(n));
   for (int i = 0; i < 14; ++i) ICS_TRY(alloc_layer(n, *n.layers[i], true, specs[i].pooled));
-  ICS_TRY(alloc_layer(n, *n.head, true, false));
-  ICS_TRY(n.alloc(&n.head_bias_grad, (size_t)256));
-  ICS_TRY(n.alloc(&n.head_dw_tmp, (size_t)128 * (n.ncls + 1)));
-  ICS_TRY(n.alloc(&n.head_xs, (size_t)256));
+  ICS_TRY(unet_alloc_head(n));
   UnetRefs r = unet_refs(n);
   r.c1->src[0] = src_plain(n.x_in, n.C);
   r.c2->src[0] = src_layer(*r.c1, 0);
@@ -1571,7 +1585,8 @@ static int unet_build(Net& n, const ics_unet_config& cfg) {
 }
 
 static int unet_pack_jobs(Net& n) {
-  for (int i = 0; i < 14; ++i) ICS_TRY(pack_layer(n, *n.layers[i], true));
+  for (auto& Lp : n.layers)      // the 14 trunk layers (ics_op_head_link: the one producer); the head's images follow
+    if (Lp.get() != n.head) ICS_TRY(pack_layer(n, *Lp, true));
   ConvLayer& H = *n.head;
   const int ncls = n.ncls;
   const float* wsoft = n.tp(H.t_w);
@@ -1742,9 +1757,9 @@ static void reset_backward_state(Net& n) {
   n.colsum.n = 0;
 }
 
-static int unet_backward(Net& n, int B) {
-  reset_backward_state(n);
-  UnetRefs r = unet_refs(n);
+// The head's part of the backward pass: its weight and bias gradients and its backward-data launch, which leaves either
+// dLoss/d(c18's output) in H.dA or -- *dy_in_place -- c18's dy itself (c18: the Conv -> ReLU -> BN layer that feeds the head).
+static int unet_head_backward(Net& n, ConvLayer* c18, int B, bool* dy_in_place) {
   ConvLayer& H = *n.head;
   const size_t M = n.rows(H, B);
   const int nc1 = n.ncls + 1;
@@ -1755,8 +1770,8 @@ static int unet_backward(Net& n, int B) {
   // its result Q and the head's bias gradients a 128-thread kernel forms the head's weight gradients AND c18's
   // (c1, c2, dgamma, dbeta); the backward-data kernel then writes c18's dy directly.  With SyncBN the two sums are
   // all-reduced in between (256 doubles).  Only for the Conv -> ReLU -> BN shape the kernel hard-codes.
-  const bool bnfuse = !(n.flags & CF_NO_HEAD_BNFUSE) && r.c18->has_bn && r.c18->pre_act == ACT_RELU &&
-                      r.c18->post_act == ACT_NONE && r.c18->Cout == 128 && H.nsrc == 1 && head_dgrad_ok(n.ncls, 128, M, nullptr, n.flags);
+  const bool bnfuse = !(n.flags & CF_NO_HEAD_BNFUSE) && c18->has_bn && c18->pre_act == ACT_RELU &&
+                      c18->post_act == ACT_NONE && c18->Cout == 128 && H.nsrc == 1 && head_dgrad_ok(n.ncls, 128, M, nullptr, n.flags);
   {
     // one GEMM over the [soft | sig] columns (one pass over c18's activations), then split into the two tensors
     ConvGeom gs = gh; gs.Cout = nc1; gs.Npad = round_up(nc1, 32);
@@ -1765,8 +1780,12 @@ static int unet_backward(Net& n, int B) {
     if (bnfuse) {
       // xhat as an affine of c18's stored activation: written by the forward's BatchNorm finalize, except under SyncBN
       // (its statistics come from the rank-merge kernels)
-      float* xs = n.sync() ? n.head_xs : r.c18->xs;
-      if (n.sync()) ICS_TRY(launch_xhat_affine(n.st, r.c18->mean, r.c18->rstd, 128, xs));
+      float* xs = n.sync() ? n.head_xs : c18->xs;
+      if (n.sync()) {
+        n.prof.begin(n.st, "xhat_affine:head", 0, 0);
+        ICS_TRY(launch_xhat_affine(n.st, c18->mean, c18->rstd, 128, xs));
+        n.prof.end(n.st);
+      }
       hsrc.scale = xs; hsrc.shift = xs + 128;
     }
     n.prof.begin(ws, "conv_wgrad:head|", 2.0 * M * 128 * nc1, 4.0 * M * (128 + nc1));
@@ -1783,34 +1802,47 @@ static int unet_backward(Net& n, int B) {
     // soft/bias | sig/bias (contiguous): the loss kernel left per-block column sums of dz in ws_bwd
     ICS_LAUNCH(colsum_merge_kernel, dim3(nc1), dim3(256), 0, n.st, n.ws_bwd, n.head_nblk, nc1, n.tg(H.t_b));
     ICS_HIP(hipGetLastError());
-    if (bnfuse)
-      ICS_TRY(launch_head_bnfuse(n.st, n.head_dw_tmp, n.tg(H.t_b), n.tp(H.t_w), n.tp(H.t_gamma), n.tp(r.c18->t_gamma),
-                                 n.tp(r.c18->t_beta), (double)M, n.ncls, n.tg(H.t_w), n.tg(H.t_gamma), r.c18->c1c2,
-                                 n.tg(r.c18->t_gamma), n.tg(r.c18->t_beta), n.sync()));
+    if (bnfuse) {
+      if (n.sync()) n.prof.begin(n.st, "head_bnfuse_exchange", 0, 0);     // SyncBN only: the 256-double exchange is in there
+      ICS_TRY(launch_head_bnfuse(n.st, n.head_dw_tmp, n.tg(H.t_b), n.tp(H.t_w), n.tp(H.t_gamma), n.tp(c18->t_gamma),
+                                 n.tp(c18->t_beta), (double)M, n.ncls, n.tg(H.t_w), n.tg(H.t_gamma), c18->c1c2,
+                                 n.tg(c18->t_gamma), n.tg(c18->t_beta), n.sync()));
+      if (n.sync()) n.prof.end(n.st);
+    }
     const ConvGeom gb = geom_bwd(H, B);
     ConvSrc sdz = src_plain(H.s, nc1);
     n.prof.begin(n.st, "conv_dgrad:head|", 2.0 * M * 128 * nc1, 4.0 * M * (128 + nc1));
-    BwdStat bs = bwd_stat_for(n, r.c18, B);
+    BwdStat bs = bwd_stat_for(n, c18, B);
     int blocks = 0;
     if (bnfuse) {
-      bs.s = r.c18->s; bs.mean = r.c18->mean; bs.rstd = r.c18->rstd; bs.scale = r.c18->scale; bs.shift = r.c18->shift;
+      bs.s = c18->s; bs.mean = c18->mean; bs.rstd = c18->rstd; bs.scale = c18->scale; bs.shift = c18->shift;
       bs.partial = nullptr; bs.post_act = ACT_NONE; bs.ld = 128;
-      ICS_TRY(launch_head_dgrad(n.st, H.s, n.tp(H.t_w), n.tp(H.t_gamma), r.c18->dy, 128, M, &bs, gb.Npad, &blocks,
-                                r.c18->c1c2, r.c18->db_partial));
+      ICS_TRY(launch_head_dgrad(n.st, H.s, n.tp(H.t_w), n.tp(H.t_gamma), c18->dy, 128, M, &bs, gb.Npad, &blocks,
+                                c18->c1c2, c18->db_partial));
       n.prof.end(n.st);
-      ICS_CHECK((size_t)blocks <= r.c18->db_rows, "bias-gradient partial buffer too small for this batch");
-      ICS_TRY(colsum_push(n, r.c18->db_partial, blocks, 128, n.tg(r.c18->t_b)));
-      r.c18->db_blocks = blocks;
+      ICS_CHECK((size_t)blocks <= c18->db_rows, "bias-gradient partial buffer too small for this batch");
+      ICS_TRY(colsum_push(n, c18->db_partial, blocks, 128, n.tg(c18->t_b)));
+      c18->db_blocks = blocks;
     } else {
     if (head_dgrad_ok(n.ncls, 128, M, &bs, n.flags))
       ICS_TRY(launch_head_dgrad(n.st, H.s, n.tp(H.t_w), n.tp(H.t_gamma), H.dA, 128, M, &bs, gb.Npad, &blocks));
     else
       ICS_TRY(launch_conv_fwd(n.st, gb, &sdz, 1, H.wf, nullptr, H.dA, 128, ACT_NONE, nullptr, nullptr, 0, nullptr, 0, &bs,
                               &blocks));
-    bwd_stat_done(r.c18, bs, blocks, gb.Npad);
+    bwd_stat_done(c18, bs, blocks, gb.Npad);
     n.prof.end(n.st);
     }
   }
+  *dy_in_place = bnfuse;
+  return 0;
+}
+
+static int unet_backward(Net& n, int B) {
+  reset_backward_state(n);
+  UnetRefs r = unet_refs(n);
+  ConvLayer& H = *n.head;
+  bool bnfuse = false;           // c18's dy written by the head's backward-data launch
+  ICS_TRY(unet_head_backward(n, r.c18, B, &bnfuse));
   // last argument: the layer fed ONLY by this layer's backward-data output (BatchNorm-backward sums folded in)
   auto bw = [&](ConvLayer* L, GradSrc g0, GradSrc g1, bool need_dA, ConvLayer* next = nullptr) {
     return conv_backward(n, *L, B, g0, g1, nullptr, need_dA, true, -1, next);
@@ -3027,6 +3059,7 @@ int ics_unet_test_step(ics_net* net, const float* x, const uint8_t* labels, int 
   return 0;
 }
 
+static int cw_upload(Net& n, const float* w, int count);
 int ics_unet_set_class_weights(ics_net* net, const float* w, int count) {
   ICS_CHECK(net && net->n.kind == 0, "ics_unet_set_class_weights: a U-Net engine is required");
   Net& n = net->n;
@@ -3042,6 +3075,10 @@ int ics_unet_set_class_weights(ics_net* net, const float* w, int count) {
   ICS_CHECK(count == n.ncls, "ics_unet_set_class_weights: count must equal num_classes");
   for (int c = 0; c < count; ++c)
     ICS_CHECK(std::isfinite(w[c]) && w[c] >= 0.f, "ics_unet_set_class_weights: every weight must be finite and >= 0 (class " + std::to_string(c) + ")");
+  return cw_upload(n, w, count);
+}
+// the table and its flag onto the device (w checked by the caller: count == ncls, every weight finite and >= 0)
+static int cw_upload(Net& n, const float* w, int count) {
   ICS_TRY(cw_table(n));
   float host[Net::kCwFloats] = {};
   std::memcpy(host, w, sizeof(float) * (size_t)count);
@@ -4166,6 +4203,143 @@ int ics_op_conv_link(ics_conv_link* a) {
   };
   const int cmax = std::max(a->P.Cout, std::max(has_k ? a->K.Cout : 0, a->link != ICS_LINK_POOL ? a->L.Cout : 0));
   return run_emulated_ranks(op, a->ranks, cmax, 6, body);
+}
+
+// The last link of the U-Net, c18 -> head, through the engines' own construction and dispatch (include/icsg3d.h): a Net of a
+// producer P (in c18's place) and the head, registered, allocated, packed, run forward and backward by the functions
+// unet_build, the train step and unet_backward use (unet_add_head / unet_alloc_batch / unet_alloc_head, unet_pack,
+// conv_forward, unet_head_loss, unet_head_backward).  Nothing here chooses a kernel or evaluates a predicate.
+static int head_link_check(const ics_head_link* a, const std::string& op) {
+  ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
+  ICS_CHECK(a->S >= 1 && (a->S & (a->S - 1)) == 0, op + "S must be a power of two");
+  ICS_CHECK(a->C0 >= 1 && a->x0 != nullptr, op + "x0 and C0 are required");
+  ICS_CHECK(a->ncls >= 2 && a->ncls <= 127, op + "ncls must be in [2, 127] (ics_unet_config.num_classes)");
+  ICS_CHECK(a->w && a->gamma && a->beta, op + "P needs w, gamma and beta");
+  ICS_CHECK(a->wsoft && a->bsoft && a->wsig && a->bsig, op + "the head needs wsoft, bsoft, wsig and bsig");
+  ICS_CHECK(a->labels != nullptr, op + "labels are required");
+  ICS_CHECK(a->bce_from_logits == 0 || a->bce_from_logits == 1, op + "bce_from_logits must be 0 or 1");
+  ICS_CHECK(std::isfinite(a->loss_weight), op + "loss_weight must be finite (<= 0: ncls)");
+  const size_t M = (size_t)a->B * a->S * a->S * a->S * (size_t)std::max(a->ranks, 1);
+  for (size_t i = 0; i < M; ++i)
+    ICS_CHECK(a->labels[i] < a->ncls, op + "label " + std::to_string((int)a->labels[i]) + " is not below ncls");
+  if (a->class_weights)
+    for (int c = 0; c < a->ncls; ++c)
+      ICS_CHECK(std::isfinite(a->class_weights[c]) && a->class_weights[c] >= 0.f, op + "every class weight must be finite and >= 0");
+  return 0;
+}
+static int head_link_body(ics_head_link* a, BnSyncEmu* emu) {
+  const std::string op = "ics_op_head_link: ";
+  Net n;
+  ICS_TRY(op_prepare(n));
+  n.side_on = false;             // as unet_build
+  n.kind = 0; n.maxB = a->max_batch; n.d = a->S; n.C = a->C0; n.ncls = a->ncls;
+  n.loss_weight = a->loss_weight > 0 ? a->loss_weight : (float)a->ncls;
+  n.bce_from_logits = a->bce_from_logits;
+  const int B = a->B, S = a->S, nc1 = a->ncls + 1;
+  ConvLayer* P = add_conv(n, "P", a->C0, 128, 27, S, ACT_RELU, 1, ACT_NONE, false);
+  unet_add_head(n, S);
+  ConvLayer& H = *n.head;
+  ICS_TRY(emu_attach(n, emu));
+  ICS_TRY(alloc_params(n));
+  ICS_TRY(unet_alloc_batch(n));
+  ICS_TRY(alloc_layer(n, *P, true, false));
+  ICS_TRY(unet_alloc_head(n));
+  const size_t M = n.rows(*P, B);
+  P->src[0] = src_plain(n.x_in, a->C0);
+  H.src[0] = src_layer(*P, 0);
+  use_padded_input(*P);
+  ICS_TRY(enable_wino(n, *P, true));
+  ICS_TRY(enable_winog(n, *P, true));
+  ICS_TRY(alloc_workspaces(n, true));
+  ICS_TRY(init_bn_defaults(n));
+  ICS_TRY(unet_upload(n, a->x0, a->labels, B));
+  if (a->class_weights) ICS_TRY(cw_upload(n, a->class_weights, a->ncls));
+  auto up = [&](int t, const float* host, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(n.tp(t), host, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
+    return 0;
+  };
+  const size_t wn = (size_t)27 * a->C0 * 128;
+  ICS_TRY(up(P->t_w, a->w, wn)); ICS_TRY(up(P->t_b, a->bias, 128));
+  ICS_TRY(up(P->t_gamma, a->gamma, 128)); ICS_TRY(up(P->t_beta, a->beta, 128));
+  ICS_TRY(up(H.t_w, a->wsoft, (size_t)128 * a->ncls)); ICS_TRY(up(H.t_gamma, a->wsig, 128));
+  ICS_TRY(up(H.t_b, a->bsoft, a->ncls));
+  ICS_HIP(hipMemcpyAsync(n.tp(H.t_b) + a->ncls, a->bsig, sizeof(float), hipMemcpyHostToDevice, n.st));
+  n.packed_valid = false;
+  ICS_TRY(unet_pack(n));
+  n.prof.on = true;              // every launch site becomes a row; the conv sites carry their kernel id
+  n.splitk = true;               // as inside a train step
+  n.want_wgrad_inputs = true;
+  ICS_TRY(conv_forward(n, *P, B, true, true, n.tp(P->t_b)));
+  ICS_TRY(unet_head_loss(n, B, 1, a->want_grad ? 1 : 0));
+  bool dy_in_place = false;
+  if (a->want_grad) {
+    // ---- backward: what unet_backward does for the head and c18
+    reset_backward_state(n);
+    ICS_TRY(unet_head_backward(n, P, B, &dy_in_place));
+    if (dy_in_place) ICS_TRY(conv_grads_from_dy(n, *P, B, true, true, nullptr));
+    else ICS_TRY(conv_backward(n, *P, B, gs_direct(H.dA, 128, 0), gs_none(), nullptr, true, true, -1, nullptr));
+    ICS_TRY(colsum_flush(n));
+    ICS_TRY(side_join(n));
+  }
+  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
+    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
+    return 0;
+  };
+  ICS_TRY(down(a->y, P->s, M * 128));
+  ICS_TRY(down(a->mean, P->mean, 128)); ICS_TRY(down(a->rstd, P->rstd, 128));
+  ICS_TRY(down(a->scale, P->scale, 128)); ICS_TRY(down(a->shift, P->shift, 128));
+  ICS_TRY(down(a->metrics, n.d_metrics, 5));
+  if (a->sums) ICS_HIP(hipMemcpyAsync(a->sums, n.d_red + 8, 7 * sizeof(double), hipMemcpyDeviceToHost, n.st));
+  if (a->want_grad) {
+    ICS_TRY(down(a->dz, H.s, M * nc1));
+    ICS_TRY(down(a->dwsoft, n.tg(H.t_w), (size_t)128 * a->ncls)); ICS_TRY(down(a->dwsig, n.tg(H.t_gamma), 128));
+    ICS_TRY(down(a->dbias_head, n.tg(H.t_b), nc1));
+    ICS_TRY(down(a->dw, n.tg(P->t_w), wn)); ICS_TRY(down(a->dbias, n.tg(P->t_b), 128));
+    ICS_TRY(down(a->dgamma, n.tg(P->t_gamma), 128)); ICS_TRY(down(a->dbeta, n.tg(P->t_beta), 128));
+    ICS_TRY(down(a->dy_p, P->dy, M * 128));
+    ICS_TRY(down(a->dx0, P->dA, M * a->C0));
+  }
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  a->dy_in_place = dy_in_place ? 1 : 0;
+  if (a->sites && a->sites_cap > 0) {
+    std::string txt;
+    for (const auto& r : n.prof.rows) txt += r.label + "\n";
+    std::strncpy(a->sites, txt.c_str(), (size_t)a->sites_cap - 1);
+    a->sites[a->sites_cap - 1] = 0;
+  }
+  if (n.canary_on) {
+    std::string msg;
+    const int bad = n.canaries_dirty(&msg);
+    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
+  }
+  return 0;
+}
+int ics_op_head_link(ics_head_link* a) {
+  const std::string op = "ics_op_head_link: ";
+  ICS_CHECK(a != nullptr, op + "null argument");
+  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(head_link_check(a, op));
+  if (a->ranks == 0) return head_link_body(a, nullptr);
+  const size_t M = (size_t)a->B * a->S * a->S * a->S, nc1 = (size_t)a->ncls + 1;
+  auto body = [&](int r, BnSyncEmu* emu) -> int {
+    ics_head_link v = *a;
+    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
+    v.x0 += (size_t)r * M * a->C0;
+    v.labels += (size_t)r * M;
+    off(v.y, M * 128); off(v.mean, 128); off(v.rstd, 128); off(v.scale, 128); off(v.shift, 128);
+    off(v.dz, M * nc1); off(v.metrics, 5);
+    if (v.sums) v.sums += (size_t)r * 7;
+    off(v.dwsoft, (size_t)128 * a->ncls); off(v.dwsig, 128); off(v.dbias_head, nc1);
+    off(v.dw, (size_t)27 * a->C0 * 128); off(v.dbias, 128); off(v.dgamma, 128); off(v.dbeta, 128);
+    off(v.dy_p, M * 128); off(v.dx0, M * a->C0);
+    if (v.sites) v.sites += (size_t)r * (v.sites_cap > 0 ? v.sites_cap : 0);
+    ICS_TRY(head_link_body(&v, emu));
+    a->dy_in_place = v.dy_in_place;
+    return 0;
+  };
+  // collectives: P's statistics gather, the head-fuse exchange or (without the fuse) P's backward all-reduce
+  return run_emulated_ranks(op, a->ranks, 128, 4, body);
 }
 
 // The two 1x1x1 heads + losses + metrics on a given trunk output (kernel parity tests against the reference's own formulas,

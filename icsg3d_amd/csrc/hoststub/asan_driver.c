@@ -1750,6 +1750,119 @@ static int conv_link_walk(void) {
   return 0;
 }
 
+/* ics_op_head_link: the routes of the c18 -> head link on a handle larger than the batch -- the fused route (ncls = 95, rows in
+ * sixteens), each switch that takes another, a row count and class counts the fused kernels refuse, a class-weight table,
+ * the forward alone, emulated ranks -- then every refusal. */
+static int head_link_one(int B, int maxB, int S, int C0, int ncls, int cw, int want_grad, const char* site, const char* absent) {
+  ics_head_link a;
+  const int R = g_ranks > 0 ? g_ranks : 1;
+  const int cap = 8192;
+  char* text = malloc((size_t)cap * R);
+  const size_t M = (size_t)R * B * S * S * S, nz = (size_t)ncls + 1;
+  memset(&a, 0, sizeof a);
+  a.ranks = g_ranks;
+  a.B = B; a.max_batch = maxB; a.S = S; a.C0 = C0; a.ncls = ncls; a.want_grad = want_grad;
+  a.x0 = calloc(M * C0, 4);
+  a.w = calloc((size_t)27 * C0 * 128, 4); a.bias = calloc(128, 4); a.gamma = calloc(128, 4); a.beta = calloc(128, 4);
+  a.wsoft = calloc((size_t)128 * ncls, 4); a.bsoft = calloc(ncls, 4); a.wsig = calloc(128, 4); a.bsig = calloc(1, 4);
+  a.labels = calloc(M, 1);
+  if (cw) a.class_weights = calloc(ncls, 4);
+  a.y = malloc(M * 128 * 4);
+  a.mean = malloc((size_t)R * 128 * 4); a.rstd = malloc((size_t)R * 128 * 4); a.scale = malloc((size_t)R * 128 * 4);
+  a.shift = malloc((size_t)R * 128 * 4);
+  a.dz = malloc(M * nz * 4); a.metrics = malloc((size_t)R * 5 * 4); a.sums = malloc((size_t)R * 7 * 8);
+  a.dwsoft = malloc((size_t)R * 128 * ncls * 4); a.dwsig = malloc((size_t)R * 128 * 4); a.dbias_head = malloc((size_t)R * nz * 4);
+  a.dw = malloc((size_t)R * 27 * C0 * 128 * 4); a.dbias = malloc((size_t)R * 128 * 4); a.dgamma = malloc((size_t)R * 128 * 4);
+  a.dbeta = malloc((size_t)R * 128 * 4);
+  a.dy_p = malloc(M * 128 * 4); a.dx0 = malloc(M * C0 * 4);
+  a.sites = text; a.sites_cap = cap;
+  OK(ics_op_head_link(&a));
+  for (int r = 0; r < R; ++r) {
+    const char* t = text + (size_t)r * cap;
+    if (!strstr(t, "conv_fwd:P|") || (site && !strstr(t, site)) || (absent && strstr(t, absent))) {
+      fprintf(stderr, "head link B %d S %d ncls %d ranks %d: launch sites (want %s, not %s) in\n%s", B, S, ncls, g_ranks,
+              site ? site : "-", absent ? absent : "-", t);
+      return 1;
+    }
+  }
+  a.sites_cap = 9;                                     /* truncated, still terminated */
+  OK(ics_op_head_link(&a));
+  for (int r = 0; r < R; ++r)
+    if (strlen(text + 9 * r) > 8) { fprintf(stderr, "head link: site text not truncated\n"); return 1; }
+  free(text);
+  free((void*)a.x0); free((void*)a.w); free((void*)a.bias); free((void*)a.gamma); free((void*)a.beta);
+  free((void*)a.wsoft); free((void*)a.bsoft); free((void*)a.wsig); free((void*)a.bsig); free((void*)a.labels);
+  free((void*)a.class_weights);
+  free(a.y); free(a.mean); free(a.rstd); free(a.scale); free(a.shift); free(a.dz); free(a.metrics); free(a.sums);
+  free(a.dwsoft); free(a.dwsig); free(a.dbias_head); free(a.dw); free(a.dbias); free(a.dgamma); free(a.dbeta);
+  free(a.dy_p); free(a.dx0);
+  return 0;
+}
+static int head_link_walk(void) {
+  const char *T = "conv_dgrad:head|head_dgrad_kernel<true>", *F = "conv_dgrad:head|head_dgrad_kernel", *G = "conv_dgrad:head|conv_fwd_kernel<";
+  for (int big = 0; big < 2; ++big) {
+    const int mb = big ? 5 : 2;
+    if (head_link_one(2, mb, 2, 16, 95, 0, 1, T, "bn_act_bwd:P")) return 1;          /* one tile                       */
+    if (head_link_one(2, mb + 4, 2, 16, 95, 1, 1, T, "bn_act_bwd:P")) return 1;      /* class-weight table             */
+    if (head_link_one(2, mb, 8, 16, 95, 0, 1, "head_fused", "head_softmax_loss")) return 1;
+    if (head_link_one(2, mb, 4, 8, 95, 0, 0, "head_fused", "conv_dgrad:")) return 1; /* the forward and the loss alone */
+    if (head_link_one(1, mb, 2, 16, 95, 0, 1, G, "head_fused")) return 1;            /* 8 rows: no fused kernel        */
+    if (head_link_one(2, mb, 4, 16, 31, 0, 1, G, "head_fused")) return 1;
+    if (head_link_one(2, mb, 4, 16, 20, 1, 1, G, "head_fused")) return 1;
+    if (head_link_one(2, mb, 4, 16, 127, 0, 1, "head_softmax_loss", "head_fused")) return 1;
+    if (head_link_one(2, mb, 4, 16, 2, 0, 1, "bn_act_bwd:P", "head_fused")) return 1;
+  }
+  setenv("ICSG3D_NO_HEAD_BNFUSE", "1", 1);
+  if (head_link_one(3, 5, 4, 16, 95, 0, 1, F, "<true>")) return 1;
+  setenv("ICSG3D_NO_BWD_FOLD", "1", 1);
+  if (head_link_one(3, 5, 4, 16, 95, 0, 1, "bn_act_bwd:P", "<true>")) return 1;
+  unsetenv("ICSG3D_NO_BWD_FOLD");
+  unsetenv("ICSG3D_NO_HEAD_BNFUSE");
+  setenv("ICSG3D_NO_FUSED_HEAD", "1", 1);
+  if (head_link_one(3, 5, 4, 16, 95, 0, 1, G, "head_fused")) return 1;
+  unsetenv("ICSG3D_NO_FUSED_HEAD");
+  setenv("ICSG3D_NO_FAST_BNBWD", "1", 1);
+  if (head_link_one(3, 5, 4, 16, 95, 0, 1, T, NULL)) return 1;
+  unsetenv("ICSG3D_NO_FAST_BNBWD");
+  for (g_ranks = 1; g_ranks <= 4; ++g_ranks) {
+    if (head_link_one(2, 3, 4, 16, 95, 0, 1, "xhat_affine:head", "bn_act_bwd:P")) return 1;
+    if (head_link_one(2, 3, 4, 16, 95, 0, 1, "head_bnfuse_exchange", "bn_act_bwd:P")) return 1;
+    if (head_link_one(1, 1, 2, 16, 95, 0, 1, G, "head_fused")) return 1;             /* 8 rows per rank: P's all-reduce */
+  }
+  g_ranks = 0;
+  {
+    ics_head_link a;
+    static float buf[27 * 4 * 128] = {0};
+    static uint8_t lab[8] = {0};
+    int bad = 0;
+    memset(&a, 0, sizeof a);
+    a.B = 1; a.max_batch = 1; a.S = 2; a.C0 = 4; a.ncls = 5; a.x0 = buf; a.w = buf; a.gamma = buf; a.beta = buf;
+    a.wsoft = buf; a.bsoft = buf; a.wsig = buf; a.bsig = buf; a.labels = lab; a.want_grad = 1;
+    OK(ics_op_head_link(&a));
+    bad += ics_op_head_link(NULL) == 0;
+    a.max_batch = 0; bad += ics_op_head_link(&a) == 0; a.max_batch = 1;
+    a.B = 0; bad += ics_op_head_link(&a) == 0; a.B = 1;
+    a.S = 3; bad += ics_op_head_link(&a) == 0; a.S = 2;
+    a.C0 = 0; bad += ics_op_head_link(&a) == 0; a.C0 = 4;
+    a.ncls = 1; bad += ics_op_head_link(&a) == 0;
+    a.ncls = 128; bad += ics_op_head_link(&a) == 0; a.ncls = 5;
+    a.x0 = NULL; bad += ics_op_head_link(&a) == 0; a.x0 = buf;
+    a.w = NULL; bad += ics_op_head_link(&a) == 0; a.w = buf;
+    a.gamma = NULL; bad += ics_op_head_link(&a) == 0; a.gamma = buf;
+    a.wsig = NULL; bad += ics_op_head_link(&a) == 0; a.wsig = buf;
+    a.bsoft = NULL; bad += ics_op_head_link(&a) == 0; a.bsoft = buf;
+    a.labels = NULL; bad += ics_op_head_link(&a) == 0; a.labels = lab;
+    lab[3] = 5; bad += ics_op_head_link(&a) == 0; lab[3] = 0;                         /* a label that is no class */
+    a.bce_from_logits = 2; bad += ics_op_head_link(&a) == 0; a.bce_from_logits = 0;
+    buf[2] = -1.f; a.class_weights = buf; bad += ics_op_head_link(&a) == 0; buf[2] = 0.f; a.class_weights = NULL;
+    a.ranks = 5; bad += ics_op_head_link(&a) == 0;
+    a.ranks = -1; bad += ics_op_head_link(&a) == 0; a.ranks = 0;
+    if (bad) { fprintf(stderr, "head link: %d invalid argument sets accepted\n", bad); return 1; }
+    OK(ics_op_head_link(&a));                                                         /* still usable */
+  }
+  return 0;
+}
+
 int main(void) {
   char name[256]; int cus; size_t hbm; int ndev = 0;
   OK(ics_device_count(&ndev));
@@ -1783,6 +1896,7 @@ int main(void) {
   }
   if (conv_layer_walk()) return 1;
   if (conv_link_walk()) return 1;
+  if (head_link_walk()) return 1;
   {   /* the op-level head: both launch sequences */
     const size_t M = 64;
     float *x = calloc(M * 128, 4), *ws = calloc(128 * 95, 4), *bs = calloc(95, 4), *wg = calloc(128, 4), bg[1] = {0.f};

@@ -1034,6 +1034,89 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
     return r
 
 
+def head_link(x0, P, head, labels, loss_weight=0.0, class_weights=None, bce_from_logits=False, want_grad=True,
+              max_batch=None, ranks=0):
+    """Single-op entry (ics_op_head_link): the U-Net's last link, a producer P in c18's place (Conv 3x3x3 C0 -> 128, ReLU,
+    BatchNorm) and the 1x1x1 head with its losses, forward (training) and backward through the engine's own functions.
+
+    x0 (B,S,S,S,C0); P {"w": (3,3,3,C0,128), "bias", "gamma", "beta"}; head {"wsoft": (128, ncls), "bsoft": (ncls,),
+    "wsig": (128,), "bsig": (1,)}; labels uint8 (B,S,S,S), each < ncls.  loss_weight <= 0: ncls; class_weights (ncls,): a
+    table in place of the scalar.
+
+    Returns a dict: y, mean, rstd, scale, shift (P); metrics (5,), sums (dict of METRIC_SUM_KEYS); with want_grad dz
+    (B,S,S,S,ncls+1), dwsoft, dwsig, dbias_head (ncls+1,), dw, dbias, dgamma, dbeta (P), dy_p, dx0, dy_in_place; and sites,
+    the profiler's rows in launch order.
+
+    ranks = R in 1..4: R emulated data-parallel ranks with SyncBN (ics_head_link.ranks): x0, labels, y, dz, dy_p and dx0
+    hold R * B samples, rank-major; every other output gets a leading (R,) -- metrics and sums are each rank's local ones,
+    sums a list of R dicts -- and sites becomes a list of R lists."""
+    lib = L.load()
+    R = int(ranks)
+    if not 0 <= R <= 4:
+        raise ValueError("ranks must be in 0..4")
+    lead = (R,) if R else ()
+    a = L.HeadLinkArgs()
+    a.ranks = R
+    keep = []
+
+    def f(v):
+        if v is None:
+            return None
+        v = _f32(v)
+        keep.append(v)
+        return L.fptr(v)
+
+    def out(shape):
+        v = np.empty(shape, np.float32)
+        keep.append(v)
+        return v
+
+    x0 = _f32(x0)
+    NB, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
+    if NB % max(R, 1):
+        raise ValueError("the batch does not divide into %d equal shards" % R)
+    B = NB // max(R, 1)
+    wsoft = _f32(head["wsoft"])
+    ncls = wsoft.shape[1]
+    w = _f32(P["w"])
+    if w.shape != (3, 3, 3, C0, 128) or wsoft.shape[0] != 128:
+        raise ValueError("head_link: P is (3,3,3,C0,128) and wsoft (128, ncls)")
+    lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(NB, S, S, S)
+    keep.append(lab)
+    a.B, a.max_batch, a.S, a.C0, a.ncls = B, int(max_batch or B), S, C0, ncls
+    a.x0, a.w, a.bias, a.gamma, a.beta = f(x0), f(w), f(P.get("bias")), f(P["gamma"]), f(P["beta"])
+    a.wsoft, a.bsoft, a.wsig, a.bsig = f(wsoft), f(np.reshape(head["bsoft"], ncls)), f(np.reshape(head["wsig"], 128)), f(np.reshape(head["bsig"], 1))
+    a.labels = L.u8ptr(lab)
+    a.loss_weight, a.bce_from_logits, a.want_grad = float(loss_weight), int(bool(bce_from_logits)), int(bool(want_grad))
+    if class_weights is not None:
+        cw = np.ascontiguousarray(class_weights, np.float32).reshape(-1)
+        if cw.size != ncls:
+            raise ValueError("class_weights must have %d entries, got %d" % (ncls, cw.size))
+        a.class_weights = f(cw)
+    r = {"y": out((NB, S, S, S, 128)), "metrics": out(lead + (5,))}
+    for k in ("mean", "rstd", "scale", "shift"):
+        r[k] = out(lead + (128,))
+    if want_grad:
+        r.update(dz=out((NB, S, S, S, ncls + 1)), dwsoft=out(lead + (128, ncls)), dwsig=out(lead + (128,)),
+                 dbias_head=out(lead + (ncls + 1,)), dw=out(lead + w.shape), dy_p=out((NB, S, S, S, 128)), dx0=out(x0.shape))
+        for k in ("dbias", "dgamma", "dbeta"):
+            r[k] = out(lead + (128,))
+    for k, v in r.items():
+        setattr(a, k, L.fptr(v))
+    sums = np.zeros(lead + (7,), np.float64)
+    a.sums = L.f64ptr(sums)
+    cap = 32768
+    text = C.create_string_buffer(cap * max(R, 1))
+    a.sites, a.sites_cap = C.cast(text, C.c_void_p), cap
+    L.check(lib.ics_op_head_link(C.byref(a)))
+    sites = [text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines() for i in range(max(R, 1))]
+    r["sites"] = sites if R else sites[0]
+    sd = [dict(zip(METRIC_SUM_KEYS, [float(v) for v in row])) for row in sums.reshape(-1, 7)]
+    r["sums"] = sd if R else sd[0]
+    r["dy_in_place"] = bool(a.dy_in_place)
+    return r
+
+
 def unet_metrics_from_sums(sums):
     """Single-op entry (ics_op_unet_metrics_from_sums): [Loss, lsoft, lsig, f1, wr] from the seven sums unet_head returns
     (a dict, or 7 numbers in its key order), e.g. added over the shards of a global batch."""

@@ -787,6 +787,60 @@ typedef struct ics_conv_link {
 } ics_conv_link;
 int ics_op_conv_link(ics_conv_link* a);
 
+/* The LAST link of the U-Net, c18 -> head, the way the engine runs it (kernel parity tests, tests/test_gpu_head_link.py): a
+ * producer P in c18's place -- Conv 3x3x3 C0 -> 128, Conv -> ReLU -> BatchNorm, fed by the plain tensor x0 -- and the 1x1x1
+ * head 128 -> ncls + 1 with the reference's two kernels and two biases, registered, allocated and packed by the functions
+ * unet_build uses.  The call runs conv_forward(P) in training mode, unet_head_loss(mode 1, want_grad) and, with want_grad,
+ * the head's part of unet_backward followed by what the engine runs for c18: conv_grads_from_dy(P) where the head's
+ * backward-data launch already wrote P's dy (dy_in_place = 1), else conv_backward(P, gs_direct(head.dA)).
+ *
+ *   o  = gamma xhat + beta, xhat = (y - mean) rstd, y = relu(conv(x0, w) + bias)            (batch statistics)
+ *   z  = o [wsoft | wsig] + [bsoft | bsig];  soft = softmax(z[:ncls]), sig = sigmoid(z[ncls])
+ *   Loss = mean_v(wcce) + mean_v(bce) with the scalar loss_weight (<= 0: ncls) or the class_weights table, as
+ *   ics_op_unet_head_weighted;  dz = dLoss/dz;  head dW = o^T dz, head dbias = column sums of dz;  d = dz [wsoft | wsig]^T;
+ *   P: dgamma = sum_v d xhat, dbeta = sum_v d, dy = relu'(y) gamma rstd (d - dbeta / n - xhat dgamma / n), then dw, dbias, dx0.
+ *
+ * Which kernels serve the call is decided by the engine's predicates alone (head_fused_ok, head_dgrad_ok, the bnfuse
+ * condition of unet_head_backward): ncls == 95 and B S^3 % 16 == 0 take head_fused_kernel, the weight-gradient GEMM on xhat,
+ * head_bnfuse_kernel and head_dgrad_kernel<true>; ICSG3D_NO_HEAD_BNFUSE takes head_dgrad_kernel<false> with P's two
+ * BatchNorm-backward sums folded in (ICSG3D_NO_BWD_FOLD: without them); ICSG3D_NO_FUSED_HEAD, every other ncls and every
+ * other row count take the 1x1x1 GEMM + head_kernel and the implicit-GEMM backward-data.  `sites` tells them apart: the row
+ * "head_fused" against "conv_fwd:head|<kernel>" + "head_softmax_loss", and "conv_dgrad:head|head_dgrad_kernel<true>",
+ * "conv_dgrad:head|head_dgrad_kernel" (the <false> instantiation) or "conv_dgrad:head|conv_fwd_kernel<...>".
+ * The ICSG3D_* switches, ICSG3D_DEBUG_CANARY and the refusals (before any launch, reason in ics_last_error) are those of
+ * ics_op_conv_link.  ranks = 1 .. 4: emulated SyncBN ranks as in ics_conv_layer.ranks -- B per rank, x0 / labels / y / dz /
+ * dy_p / dx0 rank-major, a leading [R] on every other output (metrics and sums included) and on `sites`; the collectives
+ * are P's statistics gather and the head-fuse exchange of 256 doubles (without the fuse: P's backward all-reduce).  The
+ * parameter gradients are each rank's local sums; P's dgamma / dbeta are, as in ics_op_conv_link, the local sums
+ * sum_v d xhat and sum_v d over the rank's own voxels with the GLOBAL statistics in xhat.  metrics and sums under ranks are
+ * each rank's LOCAL ones: the handle has no communicator (Net::comm is null), so the all-reduce of the seven sums that a
+ * data-parallel step runs is not part of this call -- add the sums and call ics_op_unet_metrics_from_sums. */
+typedef struct ics_head_link {
+  int B, max_batch, S; /* S a power of two; the handle and every workspace are sized for max_batch >= B                  */
+  int C0, ncls;        /* channels of x0; classes 2 .. 127                                                               */
+  const float* x0;     /* [B][S^3][C0]                                                                                   */
+  const float *w, *bias, *gamma, *beta;          /* P: [27][C0][128], [128] x 3; bias optional (zeros)                   */
+  const float *wsoft, *bsoft, *wsig, *bsig;      /* [128][ncls], [ncls], [128], [1]                                      */
+  const uint8_t* labels;                         /* [B][S^3], each < ncls                                                */
+  float loss_weight;   /* <= 0: ncls                                                                                     */
+  const float* class_weights;                    /* [ncls] finite, >= 0, or NULL (the scalar)                            */
+  int bce_from_logits; /* ics_unet_config.bce_from_logits                                                                */
+  int want_grad;       /* 0: forward and loss only (metrics, sums); 1: the backward pass too                             */
+  float *y, *mean, *rstd, *scale, *shift;        /* out, optional: P's stored activation [B][S^3][128], [128] x 4        */
+  float* dz;           /* out, optional: dLoss/dz [B][S^3][ncls + 1]                                                     */
+  float* metrics;      /* out, optional: [5] = [Loss, lsoft, lsig, f1, wr]                                               */
+  double* sums;        /* out, optional: [7] (ics_unet_metric_sums)                                                      */
+  float *dwsoft, *dwsig, *dbias_head;            /* out, optional: [128][ncls], [128], [ncls + 1]                        */
+  float *dw, *dbias, *dgamma, *dbeta;            /* out, optional: P's parameter gradients                               */
+  float* dy_p;         /* out, optional: P's gradient w.r.t. its convolution output (behind the ReLU) [B][S^3][128]      */
+  float* dx0;          /* out, optional: [B][S^3][C0]                                                                    */
+  int dy_in_place;     /* out: 1 when the head's backward-data launch wrote P's dy (head_dgrad_kernel<true>)             */
+  char* sites;         /* out, optional: every profiler row of the call, one per line, in first-launch order             */
+  int sites_cap;       /* bytes behind `sites` (truncated to fit, always NUL-terminated)                                 */
+  int ranks;           /* 0: no SyncBN; 1 .. 4: emulated data-parallel ranks with SyncBN, B per rank (see ics_conv_layer) */
+} ics_head_link;
+int ics_op_head_link(ics_head_link* a);
+
 /* The two 1x1x1 heads with their losses and metrics on a GIVEN trunk output (kernel parity tests against the reference's own
  * formulas): soft = softmax(x wsoft + bsoft), sig = sigmoid(x wsig + bsig) (unet/unet.py:339-352), then
  * weighted_categorical_crossentropy / binary_crossentropy / f1_m / wr_m (unet/unet.py:159-221,252-259).
