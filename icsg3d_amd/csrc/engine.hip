@@ -3734,43 +3734,6 @@ int ics_net_comm_allreduce_max(ics_net* net, double* value) {
 }
 
 // ---------------------------------------------------------------- single-op entry points
-int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int B, int S, int Cin, int Cout,
-                          int taps, int pre_act, float* y) {
-  ICS_CHECK(x && w && y && (taps == 27 || taps == 1) && S >= 1 && (S & (S - 1)) == 0, "bad conv arguments");
-  Net n;
-  ICS_TRY(op_prepare(n));
-  const size_t M = (size_t)B * S * S * S;
-  const int Kpad = round_up(taps * Cin, 32), Npad = round_up(Cout, 32);
-  float *dx, *dw, *db, *dwp, *dyv;
-  ICS_TRY(n.alloc(&dx, M * Cin)); ICS_TRY(n.alloc(&dw, (size_t)taps * Cin * Cout)); ICS_TRY(n.alloc(&db, (size_t)Cout));
-  ICS_TRY(n.alloc(&dwp, (size_t)Kpad * Npad)); ICS_TRY(n.alloc(&dyv, M * Cout));
-  ICS_HIP(hipMemcpyAsync(dx, x, M * Cin * 4, hipMemcpyHostToDevice, n.st));
-  ICS_HIP(hipMemcpyAsync(dw, w, (size_t)taps * Cin * Cout * 4, hipMemcpyHostToDevice, n.st));
-  if (bias) ICS_HIP(hipMemcpyAsync(db, bias, (size_t)Cout * 4, hipMemcpyHostToDevice, n.st));
-  ICS_TRY(launch_pack_fwd(n.st, dw, taps * Cin, Cout, dwp, Kpad, Npad, 0, 0, 1));
-  ConvGeom g{B, S, ilog2(S), Cin, Cout, taps, Kpad, Npad, n.flags};
-  ConvSrc s = src_plain(dx, Cin);
-  if (conv_wino_ok(g, &s, 1)) {          // the path the engine takes for this shape (ICSG3D_NO_WINO: the direct kernels)
-    float* ww = nullptr;
-    ICS_TRY(n.alloc(&ww, conv_wino_weight_floats(Cin, Cout)));
-    const int layout = conv_wino_layout(g);
-    ICS_TRY(launch_pack_wino(n.st, dw, Cin, Cout, 0, Cin, 0, ww, layout));
-    ICS_TRY(launch_conv_fwd_wino(n.st, g, s, ww, bias ? db : nullptr, dyv, Cout, pre_act, nullptr, nullptr, 0, layout));
-  } else if (conv_winog_ok(g, &s, 1)) {  // S = 4: Winograd-domain GEMMs (ICSG3D_NO_WINOG: the direct kernels)
-    float *wg = nullptr, *sv = nullptr, *sm = nullptr;
-    size_t v, m, z;
-    conv_winog_scratch_floats(g, &v, &m, &z);
-    ICS_TRY(n.alloc(&wg, conv_winog_weight_floats(Cin, Cout))); ICS_TRY(n.alloc(&sv, v)); ICS_TRY(n.alloc(&sm, m));
-    ICS_TRY(launch_pack_wino(n.st, dw, Cin, Cout, 0, Cin, 0, wg, 2));
-    ICS_TRY(launch_conv_fwd_winog(n.st, g, s, wg, bias ? db : nullptr, dyv, Cout, pre_act, nullptr, nullptr, sv, sm, nullptr));
-  } else {
-    ICS_TRY(launch_conv_fwd(n.st, g, &s, 1, dwp, bias ? db : nullptr, dyv, Cout, pre_act, nullptr, nullptr));
-  }
-  ICS_HIP(hipMemcpyAsync(y, dyv, M * Cout * 4, hipMemcpyDeviceToHost, n.st));
-  ICS_HIP(hipStreamSynchronize(n.st));
-  return 0;
-}
-
 // One layer through the engines' own construction and dispatch (include/icsg3d.h): a Net with a single ConvLayer, built,
 // packed and stepped by the functions unet_build / vae_build and the train steps use -- nothing here chooses a kernel.
 // The per-launch kernel ids come from the handle's profiler rows (labels ending in '|', see Profiler::begin).
@@ -3822,6 +3785,60 @@ static int run_emulated_ranks(const std::string& op, int R, int cmax, int cap, c
   }
   return 0;
 }
+// ---- the plumbing of every op that builds a temporary Net: copies on the handle's stream (a null host pointer skips one),
+// the switches of a train step, the end of the call, and rank r's view of an argument struct
+extern "C++" {                   // (templates: float everywhere, but head_link has double sums, uint8 labels and a char text)
+template <class T> static int op_up(Net& n, T* dev, const T* host, size_t cnt) {
+  if (host) ICS_HIP(hipMemcpyAsync(dev, host, cnt * sizeof(T), hipMemcpyHostToDevice, n.st));
+  return 0;
+}
+template <class T> static int op_down(Net& n, T* host, const T* dev, size_t cnt) {
+  if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(T), hipMemcpyDeviceToHost, n.st));
+  return 0;
+}
+// rank r's view: its B samples of every [ranks * B] tensor, its row of every per-rank [ranks] output
+struct OpRank {
+  int r;
+  static int check(int ranks, const std::string& op) {
+    ICS_CHECK(ranks >= 0 && ranks <= 4, op + "ranks must be in [0, 4]");
+    return 0;
+  }
+  template <class T> void operator()(T*& p, size_t cnt) const { if (p) p += (size_t)r * cnt; }
+};
+}
+static int op_upload_params(Net& n, ConvLayer& L, const float* w, const float* bias, const float* gamma, const float* beta) {
+  ICS_TRY(op_up(n, n.tp(L.t_w), w, (size_t)L.taps * L.Cin * L.Cout));
+  ICS_TRY(op_up(n, n.tp(L.t_b), bias, (size_t)L.Cout));
+  if (L.has_bn) {
+    ICS_TRY(op_up(n, n.tp(L.t_gamma), gamma, (size_t)L.Cout));
+    ICS_TRY(op_up(n, n.tp(L.t_beta), beta, (size_t)L.Cout));
+  }
+  return 0;
+}
+static void op_arm_step(Net& n, bool bwd, bool rows = true) {
+  n.prof.on = rows;              // every launch site of the step becomes a row; the conv sites carry their kernel id
+  n.splitk = true;               // as inside a train step
+  n.want_wgrad_inputs = bwd;
+}
+// waits for the stream; text (optional, cap bytes, truncated to fit): the profiler's rows, those `keep` accepts, one per line
+static int op_finish(Net& n, const std::string& op, char* text = nullptr, int cap = 0,
+                     bool (*keep)(const std::string&) = nullptr) {
+  ICS_HIP(hipStreamSynchronize(n.st));
+  n.prof.resolve();
+  if (text && cap > 0) {
+    std::string txt;
+    for (const auto& r : n.prof.rows)
+      if (!keep || keep(r.label)) txt += r.label + "\n";
+    std::strncpy(text, txt.c_str(), (size_t)cap - 1);
+    text[cap - 1] = 0;
+  }
+  if (n.canary_on) {
+    std::string msg;
+    const int bad = n.canaries_dirty(&msg);
+    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
+  }
+  return 0;
+}
 
 static int conv_layer_check(const ics_conv_layer* a, const std::string& op) {
   ICS_CHECK(a->B >= 1 && a->max_batch >= a->B, op + "need 1 <= B <= max_batch");
@@ -3832,8 +3849,6 @@ static int conv_layer_check(const ics_conv_layer* a, const std::string& op) {
   ICS_CHECK(a->w && a->y, op + "w and y are required");
   ICS_CHECK(!a->has_bn || (a->gamma && a->beta), op + "gamma and beta are required with has_bn");
   ICS_CHECK(a->has_bn || a->post_act == ACT_NONE, op + "post_act needs has_bn");
-  int Cin = 0;
-  bool want_dx = false;
   for (int i = 0; i < a->nsrc; ++i) {
     const ics_conv_layer_src& s = a->src[i];
     ICS_CHECK(s.x && s.C >= 1 && (s.up == 0 || s.up == 1) && act_ok(s.act), op + "bad source");
@@ -3849,13 +3864,12 @@ static int conv_layer_check(const ics_conv_layer* a, const std::string& op) {
       ICS_CHECK(a->taps == 27 && !a->src[0].up, op + "a bcast source needs a 3x3x3 layer and a same-resolution first source");
       ICS_CHECK(s.C == a->src[0].C * s.bcast, op + "a bcast source stands for C = (channels of the first source) * bcast channels");
     }
-    Cin += s.C;
-    want_dx = want_dx || s.dx != nullptr;
   }
   ICS_CHECK(a->dout || !(a->dw || a->dbias || a->dgamma || a->dbeta), op + "parameter gradients need dout");
   return 0;
 }
-static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
+// splitk = false: the step never splits K (ics_op_conv3d_forward / _backward, whose bits predate split-K)
+static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu, bool splitk = true) {
   const std::string op = "ics_op_conv_layer: ";
   int Cin = 0;
   bool want_dx = false;
@@ -3890,11 +3904,10 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
     // x of a bcast source is [B][bcast] (Net::cond_in), whatever number of channels it stands for
     const size_t cnt = s.bcast > 0 ? (size_t)B * s.bcast : src_rows[i] * s.C;
     ICS_TRY(n.alloc(&dx, s.bcast > 0 ? (size_t)n.maxB * s.bcast : (s.up ? Mmax / 8 : Mmax) * s.C));
-    ICS_HIP(hipMemcpyAsync(dx, s.x, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_up(n, dx, s.x, cnt));
     if (s.scale) {
       ICS_TRY(n.alloc(&dsc, (size_t)s.C)); ICS_TRY(n.alloc(&dsh, (size_t)s.C));
-      ICS_HIP(hipMemcpyAsync(dsc, s.scale, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
-      ICS_HIP(hipMemcpyAsync(dsh, s.shift, (size_t)s.C * sizeof(float), hipMemcpyHostToDevice, n.st));
+      ICS_TRY(op_up(n, dsc, s.scale, (size_t)s.C)); ICS_TRY(op_up(n, dsh, s.shift, (size_t)s.C));
     }
     srcs[i] = ConvSrc{dx, dsc, dsh, s.C, s.up, s.act, s.bcast};
     L.src[i] = srcs[i];
@@ -3909,51 +3922,42 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
   float* d_dout = nullptr;
   if (bwd) {
     ICS_TRY(n.alloc(&d_dout, Mmax * Cout));
-    ICS_HIP(hipMemcpyAsync(d_dout, a->dout, M * Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_up(n, d_dout, a->dout, M * Cout));
   }
-  const size_t wn = (size_t)a->taps * Cin * Cout;
-  ICS_HIP(hipMemcpyAsync(n.tp(L.t_w), a->w, wn * sizeof(float), hipMemcpyHostToDevice, n.st));
-  if (a->bias) ICS_HIP(hipMemcpyAsync(n.tp(L.t_b), a->bias, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
-  if (a->has_bn) {
-    ICS_HIP(hipMemcpyAsync(n.tp(L.t_gamma), a->gamma, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
-    ICS_HIP(hipMemcpyAsync(n.tp(L.t_beta), a->beta, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
-  }
+  ICS_TRY(op_upload_params(n, L, a->w, a->bias, a->gamma, a->beta));
   ICS_TRY(pack_layer(n, L, true));
-  n.prof.on = true;              // every launch site of the step becomes a row "site|kernel id"
-  n.splitk = true;               // as inside a train step
-  n.want_wgrad_inputs = bwd;
+  op_arm_step(n, bwd);
+  n.splitk = splitk;
   ICS_TRY(conv_forward(n, L, B, true, true, n.tp(L.t_b)));
   if (bwd) {
     ICS_TRY(conv_backward(n, L, B, gs_direct(d_dout, Cout, 0), gs_none(), nullptr, want_dx, true));
     ICS_TRY(colsum_flush(n));
     ICS_TRY(side_join(n));
   }
-  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
-    return 0;
-  };
-  ICS_TRY(down(a->y, L.s, M * Cout));
+  ICS_TRY(op_down(n, a->y, L.s, M * Cout));
   a->rows_per_block = 0; a->blocks = 0;
   if (a->has_bn) {
-    ICS_TRY(down(a->mean, L.mean, Cout)); ICS_TRY(down(a->rstd, L.rstd, Cout));
-    ICS_TRY(down(a->scale, L.scale, Cout)); ICS_TRY(down(a->shift, L.shift, Cout));
-    ICS_TRY(down(a->moving_mean, L.mm, Cout)); ICS_TRY(down(a->moving_var, L.mv, Cout));
+    ICS_TRY(op_down(n, a->mean, L.mean, Cout)); ICS_TRY(op_down(n, a->rstd, L.rstd, Cout));
+    ICS_TRY(op_down(n, a->scale, L.scale, Cout)); ICS_TRY(op_down(n, a->shift, L.shift, Cout));
+    ICS_TRY(op_down(n, a->moving_mean, L.mm, Cout)); ICS_TRY(op_down(n, a->moving_var, L.mv, Cout));
     a->rows_per_block = L.stat_rpb; a->blocks = L.stat_nblk;
   }
   std::vector<float> hA;         // the full-width input gradient of a layer that did not split its sources
   if (bwd) {
-    ICS_TRY(down(a->dw, n.tg(L.t_w), wn)); ICS_TRY(down(a->dbias, n.tg(L.t_b), Cout));
-    if (a->has_bn) { ICS_TRY(down(a->dgamma, n.tg(L.t_gamma), Cout)); ICS_TRY(down(a->dbeta, n.tg(L.t_beta), Cout)); }
+    ICS_TRY(op_down(n, a->dw, n.tg(L.t_w), (size_t)a->taps * Cin * Cout)); ICS_TRY(op_down(n, a->dbias, n.tg(L.t_b), Cout));
+    if (a->has_bn) { ICS_TRY(op_down(n, a->dgamma, n.tg(L.t_gamma), Cout)); ICS_TRY(op_down(n, a->dbeta, n.tg(L.t_beta), Cout)); }
     if (want_dx && L.split_up) {
-      if (L.Cs) ICS_TRY(down(a->src[0].dx, L.dA_skip, M * L.Cs));
-      ICS_TRY(down(a->src[a->nsrc - 1].dx, L.dxl, M / 8 * L.Cu));
+      if (L.Cs) ICS_TRY(op_down(n, a->src[0].dx, L.dA_skip, M * L.Cs));
+      ICS_TRY(op_down(n, a->src[a->nsrc - 1].dx, L.dxl, M / 8 * L.Cu));
     } else if (want_dx) {
       hA.resize(M * L.CinG);
-      ICS_TRY(down(hA.data(), L.dA, hA.size()));
+      ICS_TRY(op_down(n, hA.data(), L.dA, hA.size()));
     }
   }
-  ICS_HIP(hipStreamSynchronize(n.st));
-  n.prof.resolve();
+  // every conv launch, and which pooling of dy the up-split backward ran (pool125: / pool8: / pool27:)
+  ICS_TRY(op_finish(n, op, a->kernels, a->kernels_cap, [](const std::string& l) {
+    return l.find('|') != std::string::npos || l.rfind("pool8:", 0) == 0 || l.rfind("pool27:", 0) == 0 || l.rfind("pool125:", 0) == 0;
+  }));
   if (!hA.empty()) {
     // columns [c0, c0 + C) of dA belong to source i; an upsampled source receives the sum over its 8 children (what a
     // producer layer's backward pass does with GS_UP)
@@ -3980,50 +3984,57 @@ static int conv_layer_body(ics_conv_layer* a, BnSyncEmu* emu) {
             }
     }
   }
-  if (a->kernels && a->kernels_cap > 0) {
-    std::string txt;
-    for (const auto& r : n.prof.rows)   // every conv launch, and which pooling of dy the up-split backward ran (pool125: / pool8: / pool27:)
-      if (r.label.find('|') != std::string::npos || r.label.rfind("pool8:", 0) == 0 || r.label.rfind("pool27:", 0) == 0 ||
-          r.label.rfind("pool125:", 0) == 0)
-        txt += r.label + "\n";
-    std::strncpy(a->kernels, txt.c_str(), (size_t)a->kernels_cap - 1);
-    a->kernels[a->kernels_cap - 1] = 0;
-  }
-  if (n.canary_on) {
-    std::string msg;
-    const int bad = n.canaries_dirty(&msg);
-    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
-  }
   return 0;
 }
 int ics_op_conv_layer(ics_conv_layer* a) {
   const std::string op = "ics_op_conv_layer: ";
   ICS_CHECK(a != nullptr, op + "null argument");
-  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(OpRank::check(a->ranks, op));
   ICS_TRY(conv_layer_check(a, op));
   if (a->ranks == 0) return conv_layer_body(a, nullptr);
   int Cin = 0;
   for (int i = 0; i < a->nsrc; ++i) Cin += a->src[i].C;
   const size_t M = (size_t)a->B * a->S * a->S * a->S, C = (size_t)a->Cout, wn = (size_t)a->taps * Cin * C;
-  // rank r's view: its B samples of every [ranks * B] tensor, its row of every per-rank [ranks] output
   auto body = [&](int r, BnSyncEmu* emu) -> int {
     ics_conv_layer v = *a;
-    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
+    const OpRank off{r};
     for (int i = 0; i < v.nsrc; ++i) {
       const size_t cnt = v.src[i].bcast > 0 ? (size_t)a->B * v.src[i].bcast : (v.src[i].up ? M / 8 : M) * v.src[i].C;
-      v.src[i].x += (size_t)r * cnt;
-      off(v.src[i].dx, cnt);
+      off(v.src[i].x, cnt); off(v.src[i].dx, cnt);
     }
-    if (v.dout) v.dout += (size_t)r * M * C;
-    off(v.y, M * C);
+    off(v.dout, M * C); off(v.y, M * C);
     off(v.mean, C); off(v.rstd, C); off(v.scale, C); off(v.shift, C); off(v.moving_mean, C); off(v.moving_var, C);
     off(v.dw, wn); off(v.dbias, C); off(v.dgamma, C); off(v.dbeta, C);
-    if (v.kernels) v.kernels += (size_t)r * (v.kernels_cap > 0 ? v.kernels_cap : 0);
+    off(v.kernels, (size_t)std::max(v.kernels_cap, 0));
     ICS_TRY(conv_layer_body(&v, emu));
     a->rows_per_block = v.rows_per_block; a->blocks = v.blocks;
     return 0;
   };
   return run_emulated_ranks(op, a->ranks, a->Cout, 2, body);
+}
+// The two oldest ops (include/icsg3d.h): conv_forward / conv_backward on the one-layer handle above -- one plain source, no
+// BatchNorm, split-K off.  The body, not ics_op_conv_layer: the backward op has no y to give, and the body skips null outputs.
+static ics_conv_layer conv3d_plain_layer(const float* x, const float* w, int B, int S, int Cin, int Cout, int taps) {
+  ics_conv_layer a{};
+  a.B = a.max_batch = B; a.S = S; a.taps = taps; a.Cout = Cout; a.nsrc = 1;
+  a.src[0].x = x; a.src[0].C = Cin;
+  a.w = w;
+  return a;
+}
+int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int B, int S, int Cin, int Cout,
+                          int taps, int pre_act, float* y) {
+  ICS_CHECK(x && w && y && (taps == 27 || taps == 1) && S >= 1 && (S & (S - 1)) == 0, "bad conv arguments");
+  ics_conv_layer a = conv3d_plain_layer(x, w, B, S, Cin, Cout, taps);
+  a.bias = bias; a.pre_act = pre_act; a.y = y;
+  return conv_layer_body(&a, nullptr, false);
+}
+// a null dxo skips backward-data; the weight gradient always runs, a null dwo only leaves it on the device
+int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int B, int S, int Cin, int Cout,
+                           int taps, float* dxo, float* dwo) {
+  ICS_CHECK(x && w && dy && (taps == 27 || taps == 1) && S >= 1 && (S & (S - 1)) == 0, "bad conv arguments");
+  ics_conv_layer a = conv3d_plain_layer(x, w, B, S, Cin, Cout, taps);
+  a.dout = dy; a.src[0].dx = dxo; a.dw = dwo;
+  return conv_layer_body(&a, nullptr, false);
 }
 
 // A producer and its consumer(s) through the engines' own construction and dispatch (include/icsg3d.h): what unet_build,
@@ -4070,12 +4081,12 @@ static int conv_link_body(ics_conv_link* a, BnSyncEmu* emu) {
   const size_t M = n.rows(*P, B), Mmax = n.rows(*P, n.maxB);
   float *d_x0 = nullptr, *d_q = nullptr, *d_dout = nullptr, *d_dout_l = nullptr;
   ICS_TRY(n.alloc(&d_x0, Mmax * a->C0));
-  ICS_HIP(hipMemcpyAsync(d_x0, a->x0, M * a->C0 * sizeof(float), hipMemcpyHostToDevice, n.st));
+  ICS_TRY(op_up(n, d_x0, a->x0, M * a->C0));
   P->src[0] = src_plain(d_x0, a->C0);
   if (K) K->src[0] = src_plain(P->pooled, Cp);
   if (skip) {
     ICS_TRY(n.alloc(&d_q, Mmax / 8 * a->Cq));
-    ICS_HIP(hipMemcpyAsync(d_q, a->q, M / 8 * a->Cq * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_up(n, d_q, a->q, M / 8 * a->Cq));
     L->src[0] = src_layer(*P, 0); L->src[1] = ConvSrc{d_q, nullptr, nullptr, a->Cq, 1, ACT_NONE, 0}; L->nsrc = 2;
     L->skip_prod = P;
   } else if (L) {
@@ -4091,26 +4102,20 @@ static int conv_link_body(ics_conv_link* a, BnSyncEmu* emu) {
   {
     const size_t rows = n.rows(*last, B), rows_max = n.rows(*last, n.maxB);
     ICS_TRY(n.alloc(&d_dout, rows_max * last->Cout));
-    ICS_HIP(hipMemcpyAsync(d_dout, a->dout, rows * last->Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_up(n, d_dout, a->dout, rows * last->Cout));
   }
   if (skip) {
     ICS_TRY(n.alloc(&d_dout_l, Mmax * L->Cout));
-    ICS_HIP(hipMemcpyAsync(d_dout_l, a->dout_l, M * L->Cout * sizeof(float), hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_up(n, d_dout_l, a->dout_l, M * L->Cout));
   }
   struct Io { ConvLayer* l; ics_conv_link_layer* h; };
   const Io io[3] = {{P, &a->P}, {K, &a->K}, {L, &a->L}};
   for (const Io& e : io) {
     if (!e.l) continue;
-    const size_t wn = (size_t)27 * e.l->Cin * e.l->Cout, cb = (size_t)e.l->Cout * sizeof(float);
-    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_w), e.h->w, wn * sizeof(float), hipMemcpyHostToDevice, n.st));
-    if (e.h->bias) ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_b), e.h->bias, cb, hipMemcpyHostToDevice, n.st));
-    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_gamma), e.h->gamma, cb, hipMemcpyHostToDevice, n.st));
-    ICS_HIP(hipMemcpyAsync(n.tp(e.l->t_beta), e.h->beta, cb, hipMemcpyHostToDevice, n.st));
+    ICS_TRY(op_upload_params(n, *e.l, e.h->w, e.h->bias, e.h->gamma, e.h->beta));
     ICS_TRY(pack_layer(n, *e.l, true));
   }
-  n.prof.on = true;              // every launch site becomes a row; the conv sites carry their kernel id
-  n.splitk = true;               // as inside a train step
-  n.want_wgrad_inputs = true;
+  op_arm_step(n, true);
   for (auto& Lp : n.layers) ICS_TRY(conv_forward(n, *Lp, B, true, true, n.tp(Lp->t_b)));
   // ---- backward: the calls of unet_backward for this link (c18 -> c17 | c17 -> c16 | c3 -> c2 | c17, c3 -> c2)
   reset_backward_state(n);
@@ -4142,41 +4147,24 @@ static int conv_link_body(ics_conv_link* a, BnSyncEmu* emu) {
   }
   ICS_TRY(colsum_flush(n));
   ICS_TRY(side_join(n));
-  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
-    return 0;
-  };
   for (const Io& e : io) {
     if (!e.l) continue;
     const size_t C = (size_t)e.l->Cout;
-    ICS_TRY(down(e.h->y, e.l->s, n.rows(*e.l, B) * C));
-    ICS_TRY(down(e.h->mean, e.l->mean, C)); ICS_TRY(down(e.h->rstd, e.l->rstd, C));
-    ICS_TRY(down(e.h->scale, e.l->scale, C)); ICS_TRY(down(e.h->shift, e.l->shift, C));
-    ICS_TRY(down(e.h->dw, n.tg(e.l->t_w), (size_t)27 * e.l->Cin * C)); ICS_TRY(down(e.h->dbias, n.tg(e.l->t_b), C));
-    ICS_TRY(down(e.h->dgamma, n.tg(e.l->t_gamma), C)); ICS_TRY(down(e.h->dbeta, n.tg(e.l->t_beta), C));
+    ICS_TRY(op_down(n, e.h->y, e.l->s, n.rows(*e.l, B) * C));
+    ICS_TRY(op_down(n, e.h->mean, e.l->mean, C)); ICS_TRY(op_down(n, e.h->rstd, e.l->rstd, C));
+    ICS_TRY(op_down(n, e.h->scale, e.l->scale, C)); ICS_TRY(op_down(n, e.h->shift, e.l->shift, C));
+    ICS_TRY(op_down(n, e.h->dw, n.tg(e.l->t_w), (size_t)27 * e.l->Cin * C)); ICS_TRY(op_down(n, e.h->dbias, n.tg(e.l->t_b), C));
+    ICS_TRY(op_down(n, e.h->dgamma, n.tg(e.l->t_gamma), C)); ICS_TRY(op_down(n, e.h->dbeta, n.tg(e.l->t_beta), C));
   }
-  if (has_k) ICS_TRY(down(a->pooled, P->pooled, M / 8 * Cp));
-  ICS_TRY(down(a->dy_p, P->dy, M * Cp));
-  ICS_TRY(down(a->dx0, P->dA, M * a->C0));
-  ICS_HIP(hipStreamSynchronize(n.st));
-  n.prof.resolve();
-  if (a->sites && a->sites_cap > 0) {
-    std::string txt;
-    for (const auto& r : n.prof.rows) txt += r.label + "\n";
-    std::strncpy(a->sites, txt.c_str(), (size_t)a->sites_cap - 1);
-    a->sites[a->sites_cap - 1] = 0;
-  }
-  if (n.canary_on) {
-    std::string msg;
-    const int bad = n.canaries_dirty(&msg);
-    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
-  }
-  return 0;
+  if (has_k) ICS_TRY(op_down(n, a->pooled, P->pooled, M / 8 * Cp));
+  ICS_TRY(op_down(n, a->dy_p, P->dy, M * Cp));
+  ICS_TRY(op_down(n, a->dx0, P->dA, M * a->C0));
+  return op_finish(n, op, a->sites, a->sites_cap);
 }
 int ics_op_conv_link(ics_conv_link* a) {
   const std::string op = "ics_op_conv_link: ";
   ICS_CHECK(a != nullptr, op + "null argument");
-  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(OpRank::check(a->ranks, op));
   ICS_TRY(conv_link_check(a, op));
   if (a->ranks == 0) return conv_link_body(a, nullptr);
   const bool has_k = a->link == ICS_LINK_POOL || a->link == ICS_LINK_POOL_SKIP, skip = a->link == ICS_LINK_POOL_SKIP;
@@ -4185,7 +4173,7 @@ int ics_op_conv_link(ics_conv_link* a) {
   const size_t cin_l = Cp + (skip ? (size_t)a->Cq : 0);
   auto body = [&](int r, BnSyncEmu* emu) -> int {
     ics_conv_link v = *a;
-    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
+    const OpRank off{r};
     auto layer = [&](ics_conv_link_layer& l, size_t rows, size_t cin) {
       const size_t C = (size_t)l.Cout;
       off(l.y, rows * C);
@@ -4193,12 +4181,11 @@ int ics_op_conv_link(ics_conv_link* a) {
       off(l.dw, 27 * cin * C); off(l.dbias, C); off(l.dgamma, C); off(l.dbeta, C);
     };
     layer(v.P, M, (size_t)a->C0); layer(v.K, M / 8, Cp); layer(v.L, rows_l, cin_l);
-    v.x0 += (size_t)r * M * a->C0;
-    if (v.q) v.q += (size_t)r * (M / 8) * a->Cq;
-    v.dout += (size_t)r * (has_k ? (M / 8) * (size_t)a->K.Cout : rows_l * (size_t)a->L.Cout);
-    if (v.dout_l) v.dout_l += (size_t)r * M * a->L.Cout;
+    off(v.x0, M * a->C0); off(v.q, (M / 8) * a->Cq);
+    off(v.dout, has_k ? (M / 8) * (size_t)a->K.Cout : rows_l * (size_t)a->L.Cout);
+    off(v.dout_l, M * a->L.Cout);
     off(v.pooled, M / 8 * Cp); off(v.dy_p, M * Cp); off(v.dx0, M * a->C0);
-    if (v.sites) v.sites += (size_t)r * (v.sites_cap > 0 ? v.sites_cap : 0);
+    off(v.sites, (size_t)std::max(v.sites_cap, 0));
     return conv_link_body(&v, emu);
   };
   const int cmax = std::max(a->P.Cout, std::max(has_k ? a->K.Cout : 0, a->link != ICS_LINK_POOL ? a->L.Cout : 0));
@@ -4254,21 +4241,13 @@ static int head_link_body(ics_head_link* a, BnSyncEmu* emu) {
   ICS_TRY(init_bn_defaults(n));
   ICS_TRY(unet_upload(n, a->x0, a->labels, B));
   if (a->class_weights) ICS_TRY(cw_upload(n, a->class_weights, a->ncls));
-  auto up = [&](int t, const float* host, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(n.tp(t), host, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
-    return 0;
-  };
   const size_t wn = (size_t)27 * a->C0 * 128;
-  ICS_TRY(up(P->t_w, a->w, wn)); ICS_TRY(up(P->t_b, a->bias, 128));
-  ICS_TRY(up(P->t_gamma, a->gamma, 128)); ICS_TRY(up(P->t_beta, a->beta, 128));
-  ICS_TRY(up(H.t_w, a->wsoft, (size_t)128 * a->ncls)); ICS_TRY(up(H.t_gamma, a->wsig, 128));
-  ICS_TRY(up(H.t_b, a->bsoft, a->ncls));
-  ICS_HIP(hipMemcpyAsync(n.tp(H.t_b) + a->ncls, a->bsig, sizeof(float), hipMemcpyHostToDevice, n.st));
+  ICS_TRY(op_upload_params(n, *P, a->w, a->bias, a->gamma, a->beta));
+  ICS_TRY(op_up(n, n.tp(H.t_w), a->wsoft, (size_t)128 * a->ncls)); ICS_TRY(op_up(n, n.tp(H.t_gamma), a->wsig, 128));
+  ICS_TRY(op_up(n, n.tp(H.t_b), a->bsoft, a->ncls)); ICS_TRY(op_up(n, n.tp(H.t_b) + a->ncls, a->bsig, 1));
   n.packed_valid = false;
   ICS_TRY(unet_pack(n));
-  n.prof.on = true;              // every launch site becomes a row; the conv sites carry their kernel id
-  n.splitk = true;               // as inside a train step
-  n.want_wgrad_inputs = true;
+  op_arm_step(n, true);
   ICS_TRY(conv_forward(n, *P, B, true, true, n.tp(P->t_b)));
   ICS_TRY(unet_head_loss(n, B, 1, a->want_grad ? 1 : 0));
   bool dy_in_place = false;
@@ -4281,59 +4260,40 @@ static int head_link_body(ics_head_link* a, BnSyncEmu* emu) {
     ICS_TRY(colsum_flush(n));
     ICS_TRY(side_join(n));
   }
-  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
-    return 0;
-  };
-  ICS_TRY(down(a->y, P->s, M * 128));
-  ICS_TRY(down(a->mean, P->mean, 128)); ICS_TRY(down(a->rstd, P->rstd, 128));
-  ICS_TRY(down(a->scale, P->scale, 128)); ICS_TRY(down(a->shift, P->shift, 128));
-  ICS_TRY(down(a->metrics, n.d_metrics, 5));
-  if (a->sums) ICS_HIP(hipMemcpyAsync(a->sums, n.d_red + 8, 7 * sizeof(double), hipMemcpyDeviceToHost, n.st));
+  ICS_TRY(op_down(n, a->y, P->s, M * 128));
+  ICS_TRY(op_down(n, a->mean, P->mean, 128)); ICS_TRY(op_down(n, a->rstd, P->rstd, 128));
+  ICS_TRY(op_down(n, a->scale, P->scale, 128)); ICS_TRY(op_down(n, a->shift, P->shift, 128));
+  ICS_TRY(op_down(n, a->metrics, n.d_metrics, 5));
+  ICS_TRY(op_down(n, a->sums, n.d_red + 8, 7));
   if (a->want_grad) {
-    ICS_TRY(down(a->dz, H.s, M * nc1));
-    ICS_TRY(down(a->dwsoft, n.tg(H.t_w), (size_t)128 * a->ncls)); ICS_TRY(down(a->dwsig, n.tg(H.t_gamma), 128));
-    ICS_TRY(down(a->dbias_head, n.tg(H.t_b), nc1));
-    ICS_TRY(down(a->dw, n.tg(P->t_w), wn)); ICS_TRY(down(a->dbias, n.tg(P->t_b), 128));
-    ICS_TRY(down(a->dgamma, n.tg(P->t_gamma), 128)); ICS_TRY(down(a->dbeta, n.tg(P->t_beta), 128));
-    ICS_TRY(down(a->dy_p, P->dy, M * 128));
-    ICS_TRY(down(a->dx0, P->dA, M * a->C0));
+    ICS_TRY(op_down(n, a->dz, H.s, M * nc1));
+    ICS_TRY(op_down(n, a->dwsoft, n.tg(H.t_w), (size_t)128 * a->ncls)); ICS_TRY(op_down(n, a->dwsig, n.tg(H.t_gamma), 128));
+    ICS_TRY(op_down(n, a->dbias_head, n.tg(H.t_b), nc1));
+    ICS_TRY(op_down(n, a->dw, n.tg(P->t_w), wn)); ICS_TRY(op_down(n, a->dbias, n.tg(P->t_b), 128));
+    ICS_TRY(op_down(n, a->dgamma, n.tg(P->t_gamma), 128)); ICS_TRY(op_down(n, a->dbeta, n.tg(P->t_beta), 128));
+    ICS_TRY(op_down(n, a->dy_p, P->dy, M * 128));
+    ICS_TRY(op_down(n, a->dx0, P->dA, M * a->C0));
   }
-  ICS_HIP(hipStreamSynchronize(n.st));
-  n.prof.resolve();
   a->dy_in_place = dy_in_place ? 1 : 0;
-  if (a->sites && a->sites_cap > 0) {
-    std::string txt;
-    for (const auto& r : n.prof.rows) txt += r.label + "\n";
-    std::strncpy(a->sites, txt.c_str(), (size_t)a->sites_cap - 1);
-    a->sites[a->sites_cap - 1] = 0;
-  }
-  if (n.canary_on) {
-    std::string msg;
-    const int bad = n.canaries_dirty(&msg);
-    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
-  }
-  return 0;
+  return op_finish(n, op, a->sites, a->sites_cap);
 }
 int ics_op_head_link(ics_head_link* a) {
   const std::string op = "ics_op_head_link: ";
   ICS_CHECK(a != nullptr, op + "null argument");
-  ICS_CHECK(a->ranks >= 0 && a->ranks <= 4, op + "ranks must be in [0, 4]");
+  ICS_TRY(OpRank::check(a->ranks, op));
   ICS_TRY(head_link_check(a, op));
   if (a->ranks == 0) return head_link_body(a, nullptr);
   const size_t M = (size_t)a->B * a->S * a->S * a->S, nc1 = (size_t)a->ncls + 1;
   auto body = [&](int r, BnSyncEmu* emu) -> int {
     ics_head_link v = *a;
-    auto off = [r](float*& p, size_t cnt) { if (p) p += (size_t)r * cnt; };
-    v.x0 += (size_t)r * M * a->C0;
-    v.labels += (size_t)r * M;
+    const OpRank off{r};
+    off(v.x0, M * a->C0); off(v.labels, M);
     off(v.y, M * 128); off(v.mean, 128); off(v.rstd, 128); off(v.scale, 128); off(v.shift, 128);
-    off(v.dz, M * nc1); off(v.metrics, 5);
-    if (v.sums) v.sums += (size_t)r * 7;
+    off(v.dz, M * nc1); off(v.metrics, 5); off(v.sums, 7);
     off(v.dwsoft, (size_t)128 * a->ncls); off(v.dwsig, 128); off(v.dbias_head, nc1);
     off(v.dw, (size_t)27 * a->C0 * 128); off(v.dbias, 128); off(v.dgamma, 128); off(v.dbeta, 128);
     off(v.dy_p, M * 128); off(v.dx0, M * a->C0);
-    if (v.sites) v.sites += (size_t)r * (v.sites_cap > 0 ? v.sites_cap : 0);
+    off(v.sites, (size_t)std::max(v.sites_cap, 0));
     ICS_TRY(head_link_body(&v, emu));
     a->dy_in_place = v.dy_in_place;
     return 0;
@@ -4497,47 +4457,32 @@ int ics_op_vae_latent(ics_vae_latent* a) {
   ICS_TRY(n.alloc(&d_dzc, (size_t)n.maxB * W));
   Z.src[0] = src_plain(d_h, lat);
   ICS_TRY(alloc_workspaces(n, true));
-  auto up = [&](float* dev, const float* host, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(dev, host, cnt * sizeof(float), hipMemcpyHostToDevice, n.st));
-    return 0;
-  };
-  ICS_TRY(up(d_h, a->h, (size_t)B * lat));
-  ICS_TRY(up(n.eps_in, a->eps, (size_t)B * lat));
-  ICS_TRY(up(n.cond_in, a->cond, (size_t)B * nc));
-  ICS_TRY(up(d_dzc, a->dzc, (size_t)B * W));
-  ICS_TRY(up(n.tp(Z.t_w), a->w_mean, (size_t)lat * lat));
-  ICS_TRY(up(n.tp(Z.t_gamma), a->w_lv, (size_t)lat * lat));
-  ICS_TRY(up(n.tp(Z.t_b), a->b_mean, (size_t)lat));              // z_mean/bias | z_log_var/bias are contiguous
-  ICS_TRY(up(n.tp(Z.t_b) + lat, a->b_lv, (size_t)lat));
+  ICS_TRY(op_up(n, d_h, a->h, (size_t)B * lat));
+  ICS_TRY(op_up(n, n.eps_in, a->eps, (size_t)B * lat));
+  ICS_TRY(op_up(n, n.cond_in, a->cond, (size_t)B * nc));
+  ICS_TRY(op_up(n, d_dzc, a->dzc, (size_t)B * W));
+  ICS_TRY(op_up(n, n.tp(Z.t_w), a->w_mean, (size_t)lat * lat));
+  ICS_TRY(op_up(n, n.tp(Z.t_gamma), a->w_lv, (size_t)lat * lat));
+  ICS_TRY(op_up(n, n.tp(Z.t_b), a->b_mean, (size_t)lat));              // z_mean/bias | z_log_var/bias are contiguous
+  ICS_TRY(op_up(n, n.tp(Z.t_b) + lat, a->b_lv, (size_t)lat));
   ICS_TRY(vae_latent_pack(n, Z));
-  n.splitk = true;               // as inside a train step
-  n.want_wgrad_inputs = bwd;
+  op_arm_step(n, bwd, false);    // (no profiler rows: the call returns no sites text)
   ICS_TRY(vae_latent_forward(n, Z, B, true));
   if (bwd) {
     ICS_TRY(vae_latent_backward(n, Z, d_dzc, W, B));
     ICS_TRY(side_join(n));
   }
-  auto down = [&](float* host, const float* dev, size_t cnt) -> int {
-    if (host) ICS_HIP(hipMemcpyAsync(host, dev, cnt * sizeof(float), hipMemcpyDeviceToHost, n.st));
-    return 0;
-  };
-  ICS_TRY(down(a->mulv, Z.s, (size_t)B * 2 * lat));
-  ICS_TRY(down(a->z, n.z_buf, (size_t)B * lat));
-  ICS_TRY(down(a->zc, n.zc, (size_t)B * W));
+  ICS_TRY(op_down(n, a->mulv, Z.s, (size_t)B * 2 * lat));
+  ICS_TRY(op_down(n, a->z, n.z_buf, (size_t)B * lat));
+  ICS_TRY(op_down(n, a->zc, n.zc, (size_t)B * W));
   if (bwd) {
-    ICS_TRY(down(a->dmulv, n.dmulv, (size_t)B * 2 * lat));
-    ICS_TRY(down(a->dw_mean, n.tg(Z.t_w), (size_t)lat * lat));
-    ICS_TRY(down(a->dw_lv, n.tg(Z.t_gamma), (size_t)lat * lat));
-    ICS_TRY(down(a->dbias, n.tg(Z.t_b), (size_t)2 * lat));
-    ICS_TRY(down(a->dh, Z.dA, (size_t)B * lat));
+    ICS_TRY(op_down(n, a->dmulv, n.dmulv, (size_t)B * 2 * lat));
+    ICS_TRY(op_down(n, a->dw_mean, n.tg(Z.t_w), (size_t)lat * lat));
+    ICS_TRY(op_down(n, a->dw_lv, n.tg(Z.t_gamma), (size_t)lat * lat));
+    ICS_TRY(op_down(n, a->dbias, n.tg(Z.t_b), (size_t)2 * lat));
+    ICS_TRY(op_down(n, a->dh, Z.dA, (size_t)B * lat));
   }
-  ICS_HIP(hipStreamSynchronize(n.st));
-  if (n.canary_on) {
-    std::string msg;
-    const int bad = n.canaries_dirty(&msg);
-    ICS_CHECK(bad == 0, op + "guard bytes written behind " + std::to_string(bad) + " buffer(s): " + msg);
-  }
-  return 0;
+  return op_finish(n, op);
 }
 
 // sqdiff_kernel as the VAE step launches it for the squared error and the perceptual taps (include/icsg3d.h)
@@ -4635,70 +4580,6 @@ int ics_op_conv3d_bench(int B, int S, int Cin, int Cout, int taps, int mode, int
   ICS_HIP(hipEventElapsedTime(&ms, e0, e1));
   *ms_out = ms / iters;
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return 0;
-}
-
-int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int B, int S, int Cin, int Cout,
-                           int taps, float* dxo, float* dwo) {
-  ICS_CHECK(x && w && dy && (taps == 27 || taps == 1) && S >= 1 && (S & (S - 1)) == 0, "bad conv arguments");
-  Net n;
-  ICS_TRY(op_prepare(n));
-  const size_t M = (size_t)B * S * S * S;
-  const int Kpad_b = round_up(taps * Cout, 32), Npad_b = round_up(Cin, 32);
-  const int Kpad = round_up(taps * Cin, 32), Npad = round_up(Cout, 32);
-  float *dx, *dw, *ddy, *dwf, *dgx, *dgw, *ws;
-  ICS_TRY(n.alloc(&dx, M * Cin)); ICS_TRY(n.alloc(&dw, (size_t)taps * Cin * Cout)); ICS_TRY(n.alloc(&ddy, M * Cout));
-  ICS_TRY(n.alloc(&dwf, (size_t)Kpad_b * Npad_b)); ICS_TRY(n.alloc(&dgx, M * Cin));
-  ICS_TRY(n.alloc(&dgw, (size_t)taps * Cin * Cout));
-  ICS_HIP(hipMemcpyAsync(dx, x, M * Cin * 4, hipMemcpyHostToDevice, n.st));
-  ICS_HIP(hipMemcpyAsync(dw, w, (size_t)taps * Cin * Cout * 4, hipMemcpyHostToDevice, n.st));
-  ICS_HIP(hipMemcpyAsync(ddy, dy, M * Cout * 4, hipMemcpyHostToDevice, n.st));
-  ConvGeom g{B, S, ilog2(S), Cin, Cout, taps, Kpad, Npad, n.flags};
-  ConvSrc s = src_plain(dx, Cin);
-  const bool wino_w = conv_wino_wgrad_ok(g, &s, 1);
-  const size_t wsn = wino_w ? conv_wino_wgrad_workspace_floats(g) : conv_wgrad_workspace_floats(g, &s, 1);
-  ICS_TRY(n.alloc(&ws, wsn + 16));
-  if (dwo && conv_winog_wgrad_ok(g, &s, 1)) {
-    float *sv = nullptr, *sm = nullptr, *svt = nullptr, *sz = nullptr, *sdu = nullptr, *wg = nullptr, *tmp = nullptr;
-    size_t v, m, z;
-    conv_winog_scratch_floats(g, &v, &m, &z);
-    ICS_TRY(n.alloc(&sv, v)); ICS_TRY(n.alloc(&sm, m)); ICS_TRY(n.alloc(&svt, (size_t)64 * B * 8 * Cin)); ICS_TRY(n.alloc(&sz, z));
-    ICS_TRY(n.alloc(&sdu, (size_t)64 * Cin * Cout)); ICS_TRY(n.alloc(&wg, conv_winog_weight_floats(Cin, Cout)));
-    ICS_TRY(n.alloc(&tmp, M * Cout));
-    // the forward pass (as the engine runs it) leaves the transposed transform of x behind; its output is not needed here
-    ICS_TRY(launch_pack_wino(n.st, dw, Cin, Cout, 0, Cin, 0, wg, 2));
-    ICS_TRY(launch_conv_fwd_winog(n.st, g, s, wg, nullptr, tmp, Cout, ACT_NONE, nullptr, nullptr, sv, sm, svt));
-    ICS_TRY(launch_conv_wgrad_winog(n.st, g, svt, ddy, Cout, dgw, Cout, 0, 0, sz, sdu));
-    ICS_HIP(hipMemcpyAsync(dwo, dgw, (size_t)taps * Cin * Cout * 4, hipMemcpyDeviceToHost, n.st));
-  } else if (dwo) {
-    if (wino_w) {
-      ICS_TRY(launch_conv_wgrad_wino(n.st, g, s, ddy, Cout, dgw, Cout, ws, wsn, 0, 0, 0, 0));
-    } else
-    ICS_TRY(launch_conv_wgrad(n.st, g, &s, 1, ddy, Cout, dgw, Cout, ws, wsn));
-    ICS_HIP(hipMemcpyAsync(dwo, dgw, (size_t)taps * Cin * Cout * 4, hipMemcpyDeviceToHost, n.st));
-  }
-  if (dxo) {
-    ICS_TRY(launch_pack_bwd(n.st, dw, taps, Cin, Cout, dwf, Kpad_b, Npad_b, Cout, 0, 1));
-    ConvGeom gb{B, S, ilog2(S), Cout, Cin, taps, Kpad_b, Npad_b, n.flags};
-    ConvSrc sd = src_plain(ddy, Cout);
-    if (conv_wino_ok(gb, &sd, 1)) {
-      float* wwb = nullptr;
-      ICS_TRY(n.alloc(&wwb, conv_wino_weight_floats(Cin, Cout)));
-      const int layout = conv_wino_layout(gb);
-      ICS_TRY(launch_pack_wino(n.st, dw, Cin, Cout, 0, Cin, 1, wwb, layout));
-      ICS_TRY(launch_conv_fwd_wino(n.st, gb, sd, wwb, nullptr, dgx, Cin, ACT_NONE, nullptr, nullptr, 0, layout));
-    } else if (conv_winog_ok(gb, &sd, 1)) {
-      float *wgb = nullptr, *sv = nullptr, *sm = nullptr;
-      size_t v, m, z;
-      conv_winog_scratch_floats(gb, &v, &m, &z);
-      ICS_TRY(n.alloc(&wgb, conv_winog_weight_floats(Cin, Cout))); ICS_TRY(n.alloc(&sv, v)); ICS_TRY(n.alloc(&sm, m));
-      ICS_TRY(launch_pack_wino(n.st, dw, Cin, Cout, 0, Cin, 1, wgb, 2));
-      ICS_TRY(launch_conv_fwd_winog(n.st, gb, sd, wgb, nullptr, dgx, Cin, ACT_NONE, nullptr, nullptr, sv, sm, nullptr));
-    } else
-    ICS_TRY(launch_conv_fwd(n.st, gb, &sd, 1, dwf, nullptr, dgx, Cin, ACT_NONE, nullptr, nullptr));
-    ICS_HIP(hipMemcpyAsync(dxo, dgx, M * Cin * 4, hipMemcpyDeviceToHost, n.st));
-  }
-  ICS_HIP(hipStreamSynchronize(n.st));
   return 0;
 }
 

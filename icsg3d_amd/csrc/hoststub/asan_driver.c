@@ -1886,13 +1886,23 @@ int main(void) {
   if (render_walk()) return 1;
   if (monitor_walk(NULL, NULL, NULL, NULL, NULL, NULL, 0, 0)) return 1;
   if (tsne_walk(NULL, NULL, NULL, NULL, NULL, 0)) return 1;
-  {   /* single-op entry points */
-    const int B = 1, S = 8, Cin = 32, Cout = 64;
-    size_t nx = (size_t)B * S * S * S * Cin, ny = (size_t)B * S * S * S * Cout, nw = (size_t)27 * Cin * Cout;
-    float *x = calloc(nx, 4), *y = calloc(ny, 4), *w = calloc(nw, 4), *dx = calloc(nx, 4), *dw = calloc(nw, 4);
-    OK(ics_op_conv3d_forward(x, w, NULL, B, S, Cin, Cout, 27, 1, y));
-    OK(ics_op_conv3d_backward(x, w, y, B, S, Cin, Cout, 27, dx, dw));
-    free(x); free(y); free(w); free(dx); free(dw);
+  {   /* single-op entry points: one shape per dispatch class they reach through the one-layer handle -- Winograd, the
+         Winograd-domain GEMMs (backward-weight included: B % 4 == 0), the implicit GEMM, 1x1x1 -- buffers of the exact size */
+    static const int shapes[4][5] = {{1, 8, 32, 32, 27}, {4, 4, 64, 64, 27}, {1, 8, 11, 16, 27}, {1, 1, 32, 256, 1}};
+    for (int i = 0; i < 4; ++i) {
+      const int B = shapes[i][0], S = shapes[i][1], Cin = shapes[i][2], Cout = shapes[i][3], taps = shapes[i][4];
+      size_t nx = (size_t)B * S * S * S * Cin, ny = (size_t)B * S * S * S * Cout, nw = (size_t)taps * Cin * Cout;
+      float *x = calloc(nx, 4), *y = calloc(ny, 4), *w = calloc(nw, 4), *b = calloc(Cout, 4), *dx = calloc(nx, 4), *dw = calloc(nw, 4);
+      OK(ics_op_conv3d_forward(x, w, b, B, S, Cin, Cout, taps, 0, y));
+      OK(ics_op_conv3d_forward(x, w, NULL, B, S, Cin, Cout, taps, 1, y));
+      OK(ics_op_conv3d_backward(x, w, y, B, S, Cin, Cout, taps, dx, NULL));
+      OK(ics_op_conv3d_backward(x, w, y, B, S, Cin, Cout, taps, NULL, dw));
+      OK(ics_op_conv3d_backward(x, w, y, B, S, Cin, Cout, taps, dx, dw));
+      if (ics_op_conv3d_forward(x, w, b, B, S, Cin, Cout, 8, 0, y) == 0 || ics_op_conv3d_backward(x, w, NULL, B, S, Cin, Cout, taps, dx, dw) == 0) {
+        fprintf(stderr, "conv3d ops: invalid arguments accepted\n"); return 1;
+      }
+      free(x); free(y); free(w); free(b); free(dx); free(dw);
+    }
   }
   if (conv_layer_walk()) return 1;
   if (conv_link_walk()) return 1;

@@ -856,6 +856,41 @@ def conv3d_forward(x, w, bias=None, pre_act=0):
     return y
 
 
+class _OpArgs:
+    """What the wrappers of the struct-taking layer ops share: the arrays the struct points into, the shard split of
+    emulated ranks and the per-rank text buffer."""
+
+    def __init__(self, ranks):
+        self.R = int(ranks)
+        if not 0 <= self.R <= 4:
+            raise ValueError("ranks must be in 0..4")
+        self.lead = (self.R,) if self.R else ()
+        self.keep = []                                # arrays the struct points into
+
+    def f(self, v):
+        if v is None:
+            return None
+        self.keep.append(_f32(v))
+        return L.fptr(self.keep[-1])
+
+    def out(self, shape):
+        self.keep.append(np.empty(shape, np.float32))
+        return self.keep[-1]
+
+    def shard(self, NB):                              # B of each rank, from the NB samples in the tensors
+        if NB % max(self.R, 1):
+            raise ValueError("the batch does not divide into %d equal shards" % self.R)
+        return NB // max(self.R, 1)
+
+    def text(self, cap):                              # (pointer, cap) of a buffer of cap bytes per rank
+        self._text, self._cap = C.create_string_buffer(cap * max(self.R, 1)), cap
+        return C.cast(self._text, C.c_void_p), cap
+
+    def lines(self):                                  # the text's lines, one list per rank (one list without ranks)
+        raw, cap = self._text.raw, self._cap
+        return [raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines() for i in range(max(self.R, 1))]
+
+
 def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=0, has_bn=True, post_act=0,
                pad_input=False, max_batch=None, want_dx=True, ranks=0):
     """Single-op entry (ics_op_conv_layer): one layer through the engines' own construction and dispatch -- affine /
@@ -876,34 +911,16 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
     R * B samples, rank-major, and so do y and dx; the statistics, the moving statistics and the parameter gradients
     (each rank's local sums) get a leading (R,), and kernels becomes a list of R such dicts."""
     lib = L.load()
-    R = int(ranks)
-    if not 0 <= R <= 4:
-        raise ValueError("ranks must be in 0..4")
-    lead = (R,) if R else ()
+    op = _OpArgs(ranks)
+    f, out, lead, R = op.f, op.out, op.lead, op.R
     a = L.ConvLayerArgs()
     a.ranks = R
-    keep = []                                     # arrays the struct points into
-
-    def f(v):
-        if v is None:
-            return None
-        v = _f32(v)
-        keep.append(v)
-        return L.fptr(v)
-
-    def out(shape):
-        v = np.empty(shape, np.float32)
-        keep.append(v)
-        return v
-
     w = _f32(w)
     taps, Cout = w.shape[0] ** 3, w.shape[4]
     srcs = [dict(s) for s in sources]
     x0 = _f32(srcs[0]["x"])
-    NB = x0.shape[0]                              # samples in the tensors: B of each rank
-    if NB % max(R, 1):
-        raise ValueError("the batch does not divide into %d equal shards" % R)
-    B = NB // max(R, 1)
+    NB = x0.shape[0]                              # samples in the tensors
+    B = op.shard(NB)
     S = x0.shape[1] * (2 if srcs[0].get("up") else 1)
     if sum(int(s["C"]) if s.get("bcast") else _f32(s["x"]).shape[4] for s in srcs) != w.shape[3]:
         raise ValueError("the sources' channels do not add up to the kernel's Cin")
@@ -941,20 +958,18 @@ def conv_layer(sources, w, bias=None, gamma=None, beta=None, dout=None, pre_act=
             r["dgamma"], r["dbeta"] = out(lead + (Cout,)), out(lead + (Cout,))
             a.dgamma, a.dbeta = L.fptr(r["dgamma"]), L.fptr(r["dbeta"])
         r["dx"] = dxs
-    cap = 16384
-    text = C.create_string_buffer(cap * max(R, 1))
-    a.kernels, a.kernels_cap = C.cast(text, C.c_void_p), cap
+    a.kernels, a.kernels_cap = op.text(16384)
     L.check(lib.ics_op_conv_layer(C.byref(a)))
     if has_bn:
         r["rows_per_block"], r["blocks"] = a.rows_per_block, a.blocks
 
-    def kernels(i):
-        lines = text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines()
+    def kernels(lines):
         d = {k: [ln for ln in lines if ln.startswith("conv_%s:" % k)] for k in ("fwd", "dgrad", "wgrad")}
         d["pool"] = [ln for ln in lines if ln.startswith(("pool125:", "pool8:", "pool27:"))]   # the up-split backward's pooling of dy
         return d
 
-    r["kernels"] = [kernels(i) for i in range(R)] if R else kernels(0)
+    ks = [kernels(lines) for lines in op.lines()]
+    r["kernels"] = ks if R else ks[0]
     return r
 
 
@@ -977,31 +992,13 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
     dy_p and dx0 hold R * B samples, rank-major; the statistics and the parameter gradients (local sums) get a leading
     (R,); sites becomes a list of R lists."""
     lib = L.load()
-    R = int(ranks)
-    if not 0 <= R <= 4:
-        raise ValueError("ranks must be in 0..4")
-    lead = (R,) if R else ()
+    op = _OpArgs(ranks)
+    f, out, lead, R = op.f, op.out, op.lead, op.R
     a = L.ConvLinkArgs()
     a.ranks = R
-    keep = []
-
-    def f(v):
-        if v is None:
-            return None
-        v = _f32(v)
-        keep.append(v)
-        return L.fptr(v)
-
-    def out(shape):
-        v = np.empty(shape, np.float32)
-        keep.append(v)
-        return v
-
     x0 = _f32(x0)
     NB, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
-    if NB % max(R, 1):
-        raise ValueError("the batch does not divide into %d equal shards" % R)
-    B = NB // max(R, 1)
+    B = op.shard(NB)
     a.link, a.form = LINKS.index(link), {"unet": 0, "vae": 1}[form]
     a.B, a.max_batch, a.S, a.C0 = B, int(max_batch or B), S, C0
     a.pool_ties_all = int(bool(pool_ties_all))
@@ -1025,12 +1022,9 @@ def conv_link(link, x0, layers, dout, form="unet", q=None, dout_l=None, pool_tie
         a.pooled = L.fptr(r["pooled"])
     r["dy_p"], r["dx0"] = out((NB, S, S, S, Cp)), out(x0.shape)
     a.dy_p, a.dx0 = L.fptr(r["dy_p"]), L.fptr(r["dx0"])
-    cap = 32768
-    text = C.create_string_buffer(cap * max(R, 1))
-    a.sites, a.sites_cap = C.cast(text, C.c_void_p), cap
+    a.sites, a.sites_cap = op.text(32768)
     L.check(lib.ics_op_conv_link(C.byref(a)))
-    sites = [text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines() for i in range(max(R, 1))]
-    r["sites"] = sites if R else sites[0]
+    r["sites"] = op.lines() if R else op.lines()[0]
     return r
 
 
@@ -1051,38 +1045,20 @@ def head_link(x0, P, head, labels, loss_weight=0.0, class_weights=None, bce_from
     hold R * B samples, rank-major; every other output gets a leading (R,) -- metrics and sums are each rank's local ones,
     sums a list of R dicts -- and sites becomes a list of R lists."""
     lib = L.load()
-    R = int(ranks)
-    if not 0 <= R <= 4:
-        raise ValueError("ranks must be in 0..4")
-    lead = (R,) if R else ()
+    op = _OpArgs(ranks)
+    f, out, lead, R = op.f, op.out, op.lead, op.R
     a = L.HeadLinkArgs()
     a.ranks = R
-    keep = []
-
-    def f(v):
-        if v is None:
-            return None
-        v = _f32(v)
-        keep.append(v)
-        return L.fptr(v)
-
-    def out(shape):
-        v = np.empty(shape, np.float32)
-        keep.append(v)
-        return v
-
     x0 = _f32(x0)
     NB, S, C0 = x0.shape[0], x0.shape[1], x0.shape[4]
-    if NB % max(R, 1):
-        raise ValueError("the batch does not divide into %d equal shards" % R)
-    B = NB // max(R, 1)
+    B = op.shard(NB)
     wsoft = _f32(head["wsoft"])
     ncls = wsoft.shape[1]
     w = _f32(P["w"])
     if w.shape != (3, 3, 3, C0, 128) or wsoft.shape[0] != 128:
         raise ValueError("head_link: P is (3,3,3,C0,128) and wsoft (128, ncls)")
     lab = np.ascontiguousarray(labels, dtype=np.uint8).reshape(NB, S, S, S)
-    keep.append(lab)
+    op.keep.append(lab)
     a.B, a.max_batch, a.S, a.C0, a.ncls = B, int(max_batch or B), S, C0, ncls
     a.x0, a.w, a.bias, a.gamma, a.beta = f(x0), f(w), f(P.get("bias")), f(P["gamma"]), f(P["beta"])
     a.wsoft, a.bsoft, a.wsig, a.bsig = f(wsoft), f(np.reshape(head["bsoft"], ncls)), f(np.reshape(head["wsig"], 128)), f(np.reshape(head["bsig"], 1))
@@ -1105,12 +1081,9 @@ def head_link(x0, P, head, labels, loss_weight=0.0, class_weights=None, bce_from
         setattr(a, k, L.fptr(v))
     sums = np.zeros(lead + (7,), np.float64)
     a.sums = L.f64ptr(sums)
-    cap = 32768
-    text = C.create_string_buffer(cap * max(R, 1))
-    a.sites, a.sites_cap = C.cast(text, C.c_void_p), cap
+    a.sites, a.sites_cap = op.text(32768)
     L.check(lib.ics_op_head_link(C.byref(a)))
-    sites = [text.raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode().splitlines() for i in range(max(R, 1))]
-    r["sites"] = sites if R else sites[0]
+    r["sites"] = op.lines() if R else op.lines()[0]
     sd = [dict(zip(METRIC_SUM_KEYS, [float(v) for v in row])) for row in sums.reshape(-1, 7)]
     r["sums"] = sd if R else sd[0]
     r["dy_in_place"] = bool(a.dy_in_place)

@@ -664,7 +664,10 @@ int ics_net_set_sync_bn(ics_net* net, int on);
 int ics_net_comm_info(ics_net* net, int* rank, int* nranks, int* buckets_last_step);
 
 /* ---------------------------------------------------------------- single-op entry points
- * (kernel parity tests against oracle/; host buffers, NDHWC) */
+ * (kernel parity tests against oracle/; host buffers, NDHWC)
+ * The two conv3d ops run the engines' conv_forward / conv_backward on the one-layer handle of ics_op_conv_layer (below):
+ * one plain source, no BatchNorm, max_batch = B, split-K off.  y = pre_act(conv(x, w) + bias), bias optional (zeros);
+ * dx, dw optional: a NULL dx skips backward-data, a NULL dw is only not copied out. */
 int ics_op_conv3d_forward(const float* x, const float* w, const float* bias, int B, int S, int Cin,
                           int Cout, int taps, int pre_act, float* y);
 int ics_op_conv3d_backward(const float* x, const float* w, const float* dy, int B, int S, int Cin,

@@ -507,11 +507,12 @@ def test_layer_under_switch(path, env, form, monkeypatch):
 
 @pytest.mark.parametrize("path,idx", ALL, ids=lambda v: str(v))
 def test_plain_form_equals_single_op_entry_points(path, idx, monkeypatch):
-    """has_bn = 0, plain sources: the same kernels in the same instantiation as ics_op_conv3d_forward / _backward launch
-    them, so the same bits -- under ICSG3D_NO_FWD_SPLITK, since the two old entry points never split K and a train step
-    does.  An upsampled source has no counterpart there.  The old entry points hand the launchers no workspace, so the
-    two-stage single-channel kernels (forward at Cout = 1, backward-data at Cin = 1) are out of their reach, and a padded thin
-    single-channel input goes through another backward-weight kernel: those three comparisons are to the reference only."""
+    """has_bn = 0, plain sources, against ics_op_conv3d_forward / _backward.  Those two run conv_forward / conv_backward on
+    the same one-layer handle with split-K off, so under ICSG3D_NO_FWD_SPLITK the train-step form and the old entry points
+    are the same launches: the same kernels in the same instantiation, the same bits.  An upsampled source has no
+    counterpart there.  Three comparisons are to the reference only, as before the old entry points went through the handle
+    (they then handed the launchers no workspace): the two-stage single-channel kernels (forward at Cout = 1, backward-data
+    at Cin = 1), and backward-weight of a padded thin single-channel input, which the old entry points never pad."""
     from icsg3d_amd import engine as E
     c = _case(path, idx)
     d = _data(path, idx, "plain")
