@@ -161,6 +161,9 @@ SIGNATURES = {
     "ics_op_structure_symmetry": (C.c_int, [_I32, _I32, _D, _D, _I32, C.c_int, C.c_double, C.c_double, C.c_int,
                                             _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _D, _D, _I32, _I32, _D, _D, _D,
                                             _D]),
+    "ics_op_structure_fingerprint": (C.c_int, [_I32, _I32, _D, _D, _I32, C.c_int, C.c_double, C.c_int, C.c_double,
+                                               C.c_double, _D, _D, _I64, _D, _I32, _I32]),
+    "ics_op_fingerprint_nearest": (C.c_int, [_D, _I32, C.c_int, C.c_int, C.c_int, _I32, _D, _I32, _D, _I32, _D, _D, _I64]),
     "ics_op_render_density": (C.c_int, [_F, C.c_int, C.c_int, C.c_int, C.c_int, _F, C.c_int, C.c_float, C.c_float, _D,
                                         C.c_int, C.c_int, _F]),
     "ics_op_render_labels": (C.c_int, [_I32, C.c_int, C.c_int, _F, C.c_int, C.c_float, _D, C.c_int, C.c_int, _F]),

@@ -361,6 +361,94 @@ static int structure_symmetry_walk(void) {
   return 0;
 }
 
+/* Structure fingerprints: the argument checks, the packing (two kernel kinds, an ineligible entry, a cell whose image
+ * range is above 32, several chunks under the ICSG3D_FINGERPRINT_CHUNK_BYTES main sets) and one refusal of each kind.
+ * The nearest op folds its partners on the device; the kernels are no-ops here, so the partners read back are whatever the
+ * stand-in memory holds: the call may refuse them, it must not index with them. */
+static int structure_fingerprint_walk(void) {
+  enum { NS = 9, NB = 7, NA = NS * 70 };
+  static int32_t off[NS + 1], sp[NA], el[NS], cn[NA], reason[NS];
+  static double fr[NA * 3], lat[NS * 9], nn[NA], rdf[NS * 2 * NB], cnt[NS * NB];
+  static int64_t np_[NS];
+  int at = 0;
+  for (int s = 0; s < NS; ++s) {
+    const int n = s % 4 == 0 ? 70 : (s % 3 == 0 ? 5 : 3);
+    off[s] = at;
+    for (int i = 0; i < n; ++i, ++at) {
+      sp[at] = 1 + (i * 5) % 11;
+      fr[3 * at] = 0.013 * at - 3.0; fr[3 * at + 1] = 0.37 * i; fr[3 * at + 2] = 1.0 - 0.11 * i;
+    }
+    for (int k = 0; k < 9; ++k) lat[9 * s + k] = k % 4 == 0 ? (s == 7 ? 0.15 : 5.0 + k) : (k == 3 && s != 7 ? -1.5 : 0.0);
+    el[s] = s != 5;
+  }
+  off[NS] = at;
+#define FPR(o, z, f, l, e, ns, rm, nb, w, ct) ics_op_structure_fingerprint(o, z, f, l, e, ns, rm, nb, w, ct, rdf, cnt, np_, nn, cn, reason)
+  OK(FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1));
+  if (reason[5] != 1 || reason[7] != 2 || reason[0] != 0 || np_[5] != -1 || cn[off[7]] != -1 || nn[off[5]] == nn[off[5]] ||
+      rdf[7 * 2 * NB] == rdf[7 * 2 * NB]) {
+    fprintf(stderr, "structure fingerprint: the reason bits or the neutral outputs are wrong\n");
+    return 1;
+  }
+  OK(FPR(off, sp, fr, lat, el, 1, 3.0, 1, 2.0, 0.0));
+  { int32_t none[NS]; memset(none, 0, sizeof none); OK(FPR(off, sp, fr, lat, none, NS, 6.0, NB, 0.1, 0.1)); }
+  int bad = 0;
+  bad += FPR(off, sp, fr, lat, el, 0, 6.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(NULL, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, NULL, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, NULL, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, NULL, el, NS, 6.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, NULL, NS, 6.0, NB, 0.1, 0.1) == 0;
+  bad += ics_op_structure_fingerprint(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1, rdf, cnt, np_, NULL, cn, reason) == 0;
+  bad += ics_op_structure_fingerprint(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1, NULL, cnt, np_, nn, cn, reason) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, 0.0, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, NAN, NB, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, 6.0, 0, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, 6.0, 257, 0.1, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.0, 0.1) == 0;
+  bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, -0.1) == 0;
+  off[0] = 1; bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0; off[0] = 0;
+  fr[7] = NAN; bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0; fr[7] = 0.5;
+  lat[9 + 4] = -9.0; bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0; lat[9 + 4] = 9.0;   /* volume < 0 */
+  sp[1] = 95; bad += FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1) == 0; sp[1] = 6;
+  {   /* 257 atoms eligible: refused; ineligible: not looked at */
+    static int32_t bo[2] = {0, 257}, bs[257], be[1] = {1}, bcn[257];
+    static double bf[257 * 3], bnn[257], bl[9] = {20, 0, 0, 0, 20, 0, 0, 0, 20};
+    for (int i = 0; i < 257; ++i) bs[i] = 8;
+    bad += ics_op_structure_fingerprint(bo, bs, bf, bl, be, 1, 6.0, NB, 0.1, 0.1, rdf, cnt, np_, bnn, bcn, reason) == 0;
+    be[0] = 0;
+    OK(ics_op_structure_fingerprint(bo, bs, bf, bl, be, 1, 6.0, NB, 0.1, 0.1, rdf, cnt, np_, bnn, bcn, reason));
+    if (reason[0] != 1 || bcn[256] != -1) { fprintf(stderr, "structure fingerprint: 257 ineligible atoms not neutral\n"); return 1; }
+  }
+  if (bad) { fprintf(stderr, "structure fingerprint: %d invalid argument sets accepted\n", bad); return 1; }
+  OK(FPR(off, sp, fr, lat, el, NS, 6.0, NB, 0.1, 0.1));     /* still usable */
+#undef FPR
+  {
+    enum { NQ = 600, NR = 700, LEN = 9 };
+    static double fp[(NQ + NR) * LEN], qd[NQ], rd[NR], gd[NQ], dsum;
+    static int32_t valid[NQ + NR], qr[NQ], rq[NR], qq[NQ];
+    int64_t dpairs = 0;
+    for (int k = 0; k < (NQ + NR) * LEN; ++k) fp[k] = 0.001 * (k % 977);
+    for (int k = 0; k < NQ + NR; ++k) valid[k] = k % 11 != 3;
+#define NEAR(f, v, len, nq, nr) ics_op_fingerprint_nearest(f, v, len, nq, nr, qr, qd, rq, rd, qq, gd, &dsum, &dpairs)
+    (void)NEAR(fp, valid, LEN, NQ, NR);
+    (void)NEAR(fp, valid, LEN, NQ, 0);
+    (void)NEAR(fp, valid, 1, 1, 0);
+    { static int32_t none[NQ + NR]; OK(NEAR(fp, none, LEN, NQ, NR)); if (qr[0] != -1 || rq[NR - 1] != -1 || dpairs != 0) return 1; }
+    bad += NEAR(NULL, valid, LEN, NQ, NR) == 0;
+    bad += NEAR(fp, NULL, LEN, NQ, NR) == 0;
+    bad += NEAR(fp, valid, 0, NQ, NR) == 0;
+    bad += NEAR(fp, valid, LEN, 0, NR) == 0;
+    bad += NEAR(fp, valid, LEN, NQ, -1) == 0;
+    bad += ics_op_fingerprint_nearest(fp, valid, LEN, NQ, NR, qr, qd, NULL, rd, qq, gd, &dsum, &dpairs) == 0;
+    bad += ics_op_fingerprint_nearest(fp, valid, LEN, NQ, NR, qr, qd, rq, rd, qq, gd, NULL, &dpairs) == 0;
+    fp[5 * LEN + 2] = INFINITY; bad += NEAR(fp, valid, LEN, NQ, NR) == 0; fp[5 * LEN + 2] = 0.25;
+#undef NEAR
+    if (bad) { fprintf(stderr, "fingerprint nearest: %d invalid argument sets accepted\n", bad); return 1; }
+    if (!ics_last_error()[0]) { fprintf(stderr, "fingerprint nearest: no error message\n"); return 1; }
+  }
+  return 0;
+}
+
 /* view_results.py's pictures: the three ops over more than one picture and an image that is no multiple of the tile, an
  * empty atom set, every refusal, and the ops still usable afterwards. */
 static int render_walk(void) {
@@ -1870,6 +1958,8 @@ int main(void) {
   OK(ics_device_info(name, &cus, &hbm));
   printf("asan driver on %s (%s)\n", name, ics_version());
   setenv("ICSG3D_SYMMETRY_CHUNK_BYTES", "300000", 1);   /* the symmetry op over several chunks */
+  setenv("ICSG3D_FINGERPRINT_CHUNK_BYTES", "4000", 1);  /* the fingerprint op over several chunks of both kernel kinds */
+  setenv("ICSG3D_FINGERPRINT_CHUNK_PAIRS", "200000", 1); /* the nearest op one segment per launch */
   setenv("ICSG3D_MATCH_CHUNK_PAIRS", "7", 1);   /* the match planner over many chunks (read at the first match call) */
   setenv("ICSG3D_DGRAD_BNFUSE_MIN", "0", 1);   /* walk the BatchNorm-backward-in-backward-data fusion at these small sizes too */
   if (run(16, 1, 3, 0)) return 1;
@@ -1882,6 +1972,7 @@ int main(void) {
   if (structure_walk()) return 1;
   if (structure_match_walk()) return 1;
   if (structure_symmetry_walk()) return 1;
+  if (structure_fingerprint_walk()) return 1;
   if (latent_walk()) return 1;
   if (render_walk()) return 1;
   if (monitor_walk(NULL, NULL, NULL, NULL, NULL, NULL, 0, 0)) return 1;

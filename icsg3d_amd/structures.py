@@ -23,6 +23,12 @@ The reference builds a pymatgen Structure per sample; pymatgen is not a dependen
                     translations, orbits and the symmetrised structure (ics_op_structure_symmetry: the project's own
                     predicate; no parity with spglib or pymatgen's SpacegroupAnalyzer is claimed, no
                     space-group name or number is produced).
+- fingerprint, Fingerprinter, fingerprint_packed, fingerprint_nearest
+                    how close a written sample is to the training set and to the other samples: a radial distribution
+                    function per crystal (plain and Z-weighted) with every atom's nearest distance and coordination
+                    number (ics_op_structure_fingerprint), and the nearest partners by rms distance between fingerprints
+                    with the run's coverage and diversity (ics_op_fingerprint_nearest).  The project's own descriptor,
+                    DESIGN section 29; no parity with pymatgen's or matminer's fingerprints is claimed.  No host fallback.
 """
 from __future__ import annotations
 
@@ -299,6 +305,7 @@ class ReferenceSet:
         if not len(self.ids) == len(self.species) == len(self.frac):
             raise ValueError("ReferenceSet: ids, species and frac differ in length")
         self._screened = None
+        self._fingerprints = {}       # (r_max, n_bins, width, cn_tol) -> fingerprint(self.screened(), ...): Fingerprinter's
 
     @classmethod
     def from_sites(cls, folder):
@@ -571,6 +578,149 @@ class Symmetriser:
     def __call__(self, results):
         return symmetry(results, self.tol, self.ltol, self.max_ops, self.retries, self.shrink, self.packed)
 
+# ---------------------------------------------------------------- fingerprints (ics_op_structure_fingerprint / _nearest)
+FP_MAX_BINS = 256       # the largest n_bins the op accepts
+FP_NOT_ELIGIBLE, FP_IMAGE_RANGE = 1, 2      # the op's reason bits
+FP_REASONS = {FP_NOT_ELIGIBLE: "not eligible", FP_IMAGE_RANGE: "image range above 32"}
+FP_QUANTILES = (0.0, 0.1, 0.25, 0.5, 0.75, 0.9, 1.0)
+
+
+def fingerprint_reason_text(bits):
+    return ", ".join(t for bit, t in FP_REASONS.items() if bits & bit)
+
+
+def _fp_params(r_max, n_bins, width, cn_tol):
+    r_max, n_bins, width, cn_tol = float(r_max), int(n_bins), float(width), float(cn_tol)
+    if not (math.isfinite(r_max) and r_max > 0 and math.isfinite(width) and width > 0 and math.isfinite(cn_tol)
+            and cn_tol >= 0 and 1 <= n_bins <= FP_MAX_BINS):
+        raise ValueError("fingerprint: r_max and width must be finite and > 0, cn_tol finite and >= 0, n_bins in 1..%d"
+                         % FP_MAX_BINS)
+    return r_max, n_bins, width, cn_tol
+
+
+def fingerprint_packed(offsets, species, frac, lattice, eligible, r_max=6.0, n_bins=60, width=0.1, cn_tol=0.1):
+    """ics_op_structure_fingerprint on packed arrays: offsets (ns + 1,), species (N,), frac (N, 3), lattice (ns, 3, 3) with
+    rows va, vb, vc, eligible (ns,).  Returns the op's outputs as a dict of arrays: rdf (ns, 2, n_bins) = (g, gZ), count
+    (ns, n_bins), n_pairs (ns,) int64, nn_dist (N,), cn (N,) int32, reason (ns,)."""
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    species = np.ascontiguousarray(species, np.int32).reshape(-1)
+    frac = np.ascontiguousarray(frac, np.float64).reshape(-1, 3)
+    lattice = np.ascontiguousarray(lattice, np.float64).reshape(-1, 9)
+    eligible = np.ascontiguousarray(eligible, np.int32).reshape(-1)
+    r_max, n_bins, width, cn_tol = _fp_params(r_max, n_bins, width, cn_tol)
+    ns, N = len(offsets) - 1, len(species)
+    if ns < 1:
+        raise ValueError("fingerprint needs at least one structure")
+    if len(lattice) != ns or len(eligible) != ns or len(frac) != N or int(offsets[-1]) != N:
+        raise ValueError("fingerprint: array lengths do not agree (structures %d / %d / %d, atoms %d / %d / %d)"
+                         % (ns, len(lattice), len(eligible), N, len(frac), int(offsets[-1])))
+    A = max(N, 1)
+    out = {"rdf": np.zeros((ns, 2, n_bins)), "count": np.zeros((ns, n_bins)), "n_pairs": np.zeros(ns, np.int64),
+           "nn_dist": np.zeros(A), "cn": np.zeros(A, np.int32), "reason": np.zeros(ns, np.int32)}
+    L.check(L.load().ics_op_structure_fingerprint(
+        L.i32ptr(offsets), L.i32ptr(species), L.f64ptr(frac), L.f64ptr(lattice), L.i32ptr(eligible), ns, r_max, n_bins,
+        width, cn_tol, L.f64ptr(out["rdf"]), L.f64ptr(out["count"]), L.i64ptr(out["n_pairs"]), L.f64ptr(out["nn_dist"]),
+        L.i32ptr(out["cn"]), L.i32ptr(out["reason"])))
+    out["nn_dist"], out["cn"] = out["nn_dist"][:N], out["cn"][:N]
+    return out
+
+
+def fingerprint_nearest(fp, valid, nq, nref):
+    """ics_op_fingerprint_nearest: fp (nq + nref, len) float64, queries first; valid (nq + nref,).  Returns q_ref, q_ref_d,
+    q_q, q_q_d (nq,), ref_q, ref_q_d (nref,), div_sum, div_pairs."""
+    fp = np.ascontiguousarray(fp, np.float64)
+    valid = np.ascontiguousarray(valid, np.int32).reshape(-1)
+    nq, nref = int(nq), int(nref)
+    if fp.ndim != 2 or nq < 1 or nref < 0 or fp.shape[0] != nq + nref or len(valid) != nq + nref or fp.shape[1] < 1:
+        raise ValueError("fingerprint_nearest: fp must be (nq + nref, len >= 1) with nq >= 1, nref >= 0 and one valid flag "
+                         "per row (fp %s, valid %d, nq %d, nref %d)" % (fp.shape, len(valid), nq, nref))
+    m = max(nref, 1)
+    out = {"q_ref": np.full(nq, -1, np.int32), "q_ref_d": np.full(nq, np.inf), "ref_q": np.full(m, -1, np.int32),
+           "ref_q_d": np.full(m, np.inf), "q_q": np.full(nq, -1, np.int32), "q_q_d": np.full(nq, np.inf)}
+    div_sum, div_pairs = np.zeros(1), np.zeros(1, np.int64)
+    L.check(L.load().ics_op_fingerprint_nearest(
+        L.f64ptr(fp), L.i32ptr(valid), fp.shape[1], nq, nref, L.i32ptr(out["q_ref"]), L.f64ptr(out["q_ref_d"]),
+        L.i32ptr(out["ref_q"]), L.f64ptr(out["ref_q_d"]), L.i32ptr(out["q_q"]), L.f64ptr(out["q_q_d"]), L.f64ptr(div_sum),
+        L.i64ptr(div_pairs)))
+    out["ref_q"], out["ref_q_d"] = out["ref_q"][:nref], out["ref_q_d"][:nref]
+    out["div_sum"], out["div_pairs"] = float(div_sum[0]), int(div_pairs[0])
+    return out
+
+
+def fingerprint(results, r_max=6.0, n_bins=60, width=0.1, cn_tol=0.1):
+    """The fingerprint of every entry of `results` (the dicts screen returns, None = a failed sample) in one device call.
+    Eligible: not None, valid, 1..256 atoms, a finite lattice.  Returns one dict per entry: fp (the concatenation g || gZ,
+    length 2 n_bins, or None where fp_reason != 0), rdf (2, n_bins) or None, cn (n,) int32 and nn_dist (n,) or None,
+    fp_reason (the op's reason bits)."""
+    r_max, n_bins, width, cn_tol = _fp_params(r_max, n_bins, width, cn_tol)
+    ns = len(results)
+    out = [{"fp": None, "rdf": None, "cn": None, "nn_dist": None, "fp_reason": FP_NOT_ELIGIBLE} for _ in range(ns)]
+    ok = [r is not None and bool(r["valid"]) and 1 <= len(r["species"]) <= MATCH_MAX_ATOMS
+          and bool(np.all(np.isfinite(r["lattice"]))) for r in results]
+    if not any(ok):
+        return out
+    sp_l = [np.asarray(r["species"], np.int32) if e else np.zeros(0, np.int32) for r, e in zip(results, ok)]
+    fr_l = [np.asarray(r["frac"], np.float64).reshape(-1, 3) if e else np.zeros((0, 3)) for r, e in zip(results, ok)]
+    lat = np.zeros((ns, 3, 3))
+    for k, r in enumerate(results):
+        if ok[k]:
+            lat[k] = r["lattice"]
+    off = np.zeros(ns + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in sp_l])
+    o = fingerprint_packed(off, np.concatenate(sp_l), np.concatenate(fr_l), lat, np.array(ok, np.int32), r_max, n_bins,
+                           width, cn_tol)
+    for k in range(ns):
+        d, a0, a1 = out[k], int(off[k]), int(off[k + 1])
+        d["fp_reason"] = int(o["reason"][k])
+        if d["fp_reason"] == 0:
+            d["rdf"] = o["rdf"][k].copy()
+            d["fp"] = d["rdf"].reshape(-1).copy()
+            d["cn"], d["nn_dist"] = o["cn"][a0:a1].copy(), o["nn_dist"][a0:a1].copy()
+    return out
+
+
+class Fingerprinter:
+    """The fingerprint parameters ResultsWriter(fingerprinter=...) runs with: reference (a ReferenceSet or None:
+    sample-to-sample only), r_max, n_bins, width, cn_tol, and deltas, the distances coverage is reported at (none by
+    default: the scale of these distances on real data has not been measured).  A call fingerprints the samples and, once
+    and kept on the ReferenceSet, reference.screened(); then one fingerprint_nearest over both."""
+
+    def __init__(self, reference=None, r_max=6.0, n_bins=60, width=0.1, cn_tol=0.1, deltas=()):
+        self.r_max, self.n_bins, self.width, self.cn_tol = _fp_params(r_max, n_bins, width, cn_tol)
+        self.deltas = tuple(float(d) for d in deltas)
+        if not all(math.isfinite(d) and d >= 0 for d in self.deltas):
+            raise ValueError("Fingerprinter: deltas must be finite and >= 0")
+        self.reference = reference
+
+    @property
+    def params(self):
+        return {"r_max": self.r_max, "n_bins": self.n_bins, "width": self.width, "cn_tol": self.cn_tol}
+
+    def reference_fingerprints(self):
+        """The fingerprints of the reference set (computed once per parameter set, kept on the ReferenceSet)."""
+        if self.reference is None or not len(self.reference):
+            return []
+        cache, key = self.reference._fingerprints, (self.r_max, self.n_bins, self.width, self.cn_tol)
+        if key not in cache:
+            cache[key] = fingerprint(self.reference.screened(), *key)
+        return cache[key]
+
+    def __call__(self, results):
+        """{"samples": fingerprint()'s list, "references": the same for the reference set, "nearest": fingerprint_nearest's
+        dict over (samples, references) or None when there is no sample at all}."""
+        samples = fingerprint(results, self.r_max, self.n_bins, self.width, self.cn_tol)
+        refs = self.reference_fingerprints()
+        near = None
+        if samples:
+            both = samples + list(refs)
+            valid = np.array([d["fp"] is not None for d in both], np.int32)
+            fp = np.zeros((len(both), 2 * self.n_bins))
+            for k, d in enumerate(both):
+                if d["fp"] is not None:
+                    fp[k] = d["fp"]
+            near = fingerprint_nearest(fp, valid, len(samples), len(refs))
+        return {"samples": samples, "references": refs, "nearest": near}
+
 
 def reason_text(reason):
     return ", ".join(t for bit, t in REASONS.items() if reason & bit) or "valid"
@@ -786,14 +936,26 @@ class ResultsWriter:
     n_centring, sym_shift, sym_tol (the tol the result was found at), sym_reason ("" or why the sample has no symmetrised
     structure); cifs_sym/<id>.cif holds the symmetrised structure of every sample with an empty sym_reason, and
     symmetry_summary the counts by point group and crystal system and the number symmetrised.  Without symmetriser=
-    every file, column and count is what it is without it."""
+    every file, column and count is what it is without it.
+    With fingerprinter= (a Fingerprinter), finish() then fingerprints ALL written samples and, once, the reference set,
+    and finds every nearest partner in one device call; every row carries FINGERPRINT_COLUMNS after the others:
+    nearest_training (the reference's id) and nearest_training_dist, nearest_generated (the id of the nearest other row)
+    and nearest_generated_dist, cn_mean, cn_min, cn_max (the coordination numbers of its atoms), fp_reason ("" or why the
+    sample has no fingerprint).  fingerprints.npz holds ids, fp, rdf, the atom offsets, cn, nn_dist and the parameters;
+    fingerprint_summary the parameters, the numbers fingerprinted on both sides, diversity (the mean distance between two
+    samples), the quantiles FP_QUANTILES of the three nearest-distance arrays and, for every delta of the fingerprinter,
+    coverage_recall (the share of fingerprinted references with a sample within delta) and coverage_precision (the share of
+    fingerprinted samples with a reference within delta).  Without fingerprinter= nothing changes."""
     COLUMNS = ("formula", "id", "training", "target", "anon_formula", "electronegativity", "cif", "sample", "natoms",
                "min_distance", "volume")
     MATCH_COLUMNS = ("duplicate_of", "duplicate_rms", "training_match", "training_rms", "match_reason")
     SYMMETRY_COLUMNS = ("point_group", "crystal_system", "n_symops", "n_centring", "sym_shift", "sym_tol", "sym_reason")
+    FINGERPRINT_COLUMNS = ("nearest_training", "nearest_training_dist", "nearest_generated", "nearest_generated_dist",
+                           "cn_mean", "cn_min", "cn_max", "fp_reason")
 
     def __init__(self, out_dir, alpha=90, beta=90, gamma=90, tol=0.5, training_names=(), target_value=None, matcher=None,
-                 symmetriser=None):
+                 symmetriser=None, fingerprinter=None):
+        self.fingerprinter, self.fingerprint_summary, self.fingerprint_results = fingerprinter, None, None
         self.matcher, self.structs, self.match_summary = matcher, [], None
         self.symmetriser, self.symmetry_summary, self.symmetry_results = symmetriser, None, None
         self.out_dir, self.angles, self.tol = out_dir, (alpha, beta, gamma), tol
@@ -825,7 +987,7 @@ class ResultsWriter:
                   "electronegativity": average_electroneg(r["hist"]), "cif": path, "sample": int(k),
                   "natoms": int(len(r["species"])), "min_distance": r["min_dist"], "volume": r["volume"]}
             self.rows.append(rd)
-            if self.matcher is not None or self.symmetriser is not None:
+            if self.matcher is not None or self.symmetriser is not None or self.fingerprinter is not None:
                 self.structs.append(r)
             self.formulae.append(f)
             self.counts["written"] += 1
@@ -873,6 +1035,54 @@ class ResultsWriter:
         self.symmetry_summary = {"symmetrised": done, "by_point_group": by_group, "by_crystal_system": by_system}
         self.counts.update(symmetrised=done)
 
+    def _fingerprint_rows(self):
+        """The fingerprinter over all written samples: the extra columns into the rows, fingerprints.npz, the summary."""
+        fpr = self.fingerprinter
+        res = fpr(self.structs)
+        samples, refs, near = res["samples"], res["references"], res["nearest"]
+        nb = fpr.n_bins
+        for k, (rd, d) in enumerate(zip(self.rows, samples)):
+            ok = d["fp"] is not None
+            t = int(near["q_ref"][k]) if ok else -1
+            g = int(near["q_q"][k]) if ok else -1
+            rd["nearest_training"] = fpr.reference.ids[t] if t >= 0 else None
+            rd["nearest_training_dist"] = float(near["q_ref_d"][k]) if t >= 0 else None
+            rd["nearest_generated"] = self.rows[g]["id"] if g >= 0 else None
+            rd["nearest_generated_dist"] = float(near["q_q_d"][k]) if g >= 0 else None
+            rd["cn_mean"] = float(np.mean(d["cn"])) if ok else None
+            rd["cn_min"], rd["cn_max"] = (int(d["cn"].min()), int(d["cn"].max())) if ok else (None, None)
+            rd["fp_reason"] = None if ok else fingerprint_reason_text(d["fp_reason"])
+        n = len(samples)
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(r["species"]) for r in self.structs])
+        fp, rdf = np.full((n, 2 * nb), np.nan), np.full((n, 2, nb), np.nan)
+        cn, nnd = np.full(int(off[-1]), -1, np.int32), np.full(int(off[-1]), np.nan)
+        for k, d in enumerate(samples):
+            if d["fp"] is not None:
+                fp[k], rdf[k], cn[off[k]:off[k + 1]], nnd[off[k]:off[k + 1]] = d["fp"], d["rdf"], d["cn"], d["nn_dist"]
+        np.savez(os.path.join(self.out_dir, "fingerprints.npz"), ids=np.array([rd["id"] for rd in self.rows], dtype=str), fp=fp,
+                 rdf=rdf, offsets=off, cn=cn, nn_dist=nnd, r_max=fpr.r_max, n_bins=nb, width=fpr.width, cn_tol=fpr.cn_tol)
+
+        def quantiles(v):
+            v = np.asarray(v, np.float64)
+            v = v[np.isfinite(v)]
+            return [float(x) for x in np.quantile(v, FP_QUANTILES)] if len(v) else None
+        nq = sum(d["fp"] is not None for d in samples)
+        nr = sum(d["fp"] is not None for d in refs)
+        empty = np.zeros(0)
+        q_ref_d, ref_q_d, q_q_d = (near[k] for k in ("q_ref_d", "ref_q_d", "q_q_d")) if near else (empty, empty, empty)
+        summary = dict(fpr.params, samples=nq, references=nr, quantiles=list(FP_QUANTILES),
+                       diversity=near["div_sum"] / near["div_pairs"] if near and near["div_pairs"] else None,
+                       nearest_training_dist=quantiles(q_ref_d), nearest_sample_of_training_dist=quantiles(ref_q_d),
+                       nearest_generated_dist=quantiles(q_q_d), coverage=[])
+        for delta in fpr.deltas:
+            summary["coverage"].append({
+                "delta": delta,
+                "coverage_recall": float(np.sum(np.asarray(ref_q_d) <= delta)) / nr if nr else None,
+                "coverage_precision": float(np.sum(np.asarray(q_ref_d) <= delta)) / nq if nq and nr else None})
+        self.fingerprint_results, self.fingerprint_summary = res, summary
+        self.counts.update(fingerprinted=nq)
+
     def finish(self):
         columns = self.COLUMNS
         if self.matcher is not None:
@@ -881,6 +1091,9 @@ class ResultsWriter:
         if self.symmetriser is not None:
             self._symmetry_rows()
             columns = columns + self.SYMMETRY_COLUMNS
+        if self.fingerprinter is not None:
+            self._fingerprint_rows()
+            columns = columns + self.FINGERPRINT_COLUMNS
         order = sorted(range(len(self.rows)), key=lambda i: self.rows[i]["id"])
         with open(os.path.join(self.out_dir, "results.csv"), "w", newline="") as fh:
             w = csv.writer(fh)

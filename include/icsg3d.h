@@ -434,6 +434,62 @@ int ics_op_structure_symmetry(const int32_t* offsets, const int32_t* species, co
                               int32_t* n_ops, int32_t* n_point, int32_t* n_trans, int32_t* types, int32_t* reason,
                               int32_t* op_code, int32_t* op_anchor, double* op_t, double* op_rms, int32_t* orbit,
                               int32_t* mult, double* sym_frac, double* sym_G, double* sym_shift, double* sym_resid);
+/* A fixed-length structural fingerprint per crystal: the radial distribution function, plain and Z-weighted, with every
+ * atom's nearest distance and coordination number.  The descriptor is this library's own -- exact, deterministic -- and is
+ * pinned to a brute-force fp64 restatement (tests/structure_fingerprint_ref.py); NO parity with pymatgen's or matminer's
+ * fingerprints is claimed.
+ * Input: the packed table of ics_op_structure_match for ns structures: offsets, species (atomic numbers 1..94), frac
+ * [atoms][3] (any reals, wrapped internally: f - floor(f)), lattice [ns][9] = M (rows va, vb, vc), eligible [ns].
+ * Parameters (design parameters, not measured quantities): r_max > 0, the range in Angstrom; n_bins in 1..256; width = w
+ * > 0, the half-width of the deposit kernel in Angstrom; cn_tol >= 0, the neighbour-distance slack.
+ * With n atoms, V = det M, R = r_max + w and edges r_k = k r_max / n_bins:
+ *   Pairs.  All ordered triples (i, j, T), T an integer vector, with d = |(f_j - f_i + T) M| and 0 < d < R; this includes
+ *     an atom's own images (i = j, T != 0).  After wrapping, |T_k| <= floor(R g_k + 1) suffices, g_k the norm of column k
+ *     of inv(M); the definition does not depend on the wrapping.
+ *   Deposit.  A triangular kernel, so every output is a continuous function of every distance and a pair at d >= R
+ *     deposits exactly 0 (no cutoff discontinuity, no erf): H(t) = 0 for t <= -1, (1 + t)^2 / 2 for -1 < t <= 0,
+ *     1 - (1 - t)^2 / 2 for 0 < t < 1, 1 for t >= 1.  A pair adds H((r_{k+1} - d) / w) - H((r_k - d) / w) to bin k of
+ *     `count` -- nothing where d >= r_{k+1} + w or d <= r_k - w, which is compared first, so outside the support the
+ *     amount is exactly 0 -- and that amount times (Z_i Z_j) / (Zbar Zbar) to `countz`, Zbar the structure's mean Z.
+ *   Normalisation.  g_k = count_k / (n (n / V) 4 pi / 3 (r_{k+1}^3 - r_k^3)); gZ_k the same with countz.  Both tend to 1
+ *     at large r and do not depend on the choice of cell.
+ *   Neighbours (the minimum-distance rule; no radius table).  nn_dist[i] = the smallest d over (j, T) for atom i;
+ *     cn[i] = the number of (j, T) with d <= (1 + cn_tol) nn_dist[i].  This sweep is not limited to R: an atom's own image
+ *     along the shortest lattice vector, of length l, bounds nn_dist, so the sweep of a structure reaches
+ *     max(R, (1 + cn_tol) l) and its image range is |T_k| <= floor(max(R, (1 + cn_tol) l) g_k + 1).
+ * Outputs: rdf [ns][2][n_bins] (g, then gZ), count [ns][n_bins] (the raw unweighted sums), n_pairs [ns] (int64: triples
+ * with d < R), nn_dist [atoms], cn [atoms], reason [ns] with bits 1 = not eligible, 2 = the image range would exceed 32
+ * on an axis.  Where reason != 0, rdf / count / nn_dist are NaN and cn and n_pairs are -1.
+ * All arithmetic is fp64 with a fixed summation order and no floating-point atomics: a bin is the sum of its deposits in
+ * the order (i's block of 64 atoms, j, T lexicographic with Ta slowest, i), the blocks added in ascending order; the same
+ * bits run to run and for any chunking.  ICSG3D_FINGERPRINT_CHUNK_BYTES (read once per process) shrinks the bytes of
+ * tables and results held at a time.
+ * Refused, naming the structure, with nothing written: a null argument, ns < 1, a parameter outside its limits, offsets
+ * that do not start at 0 or decrease, and an ELIGIBLE structure with no atoms or more than 256, a non-finite lattice entry
+ * or coordinate (or one above 1e15), a species outside 1..94 or a lattice volume <= 0.  There is no thin-cell rule here.
+ * HOST pointers, all outputs required, any ns (chunked internally), synchronous, the calling thread's op stream. */
+int ics_op_structure_fingerprint(const int32_t* offsets, const int32_t* species, const double* frac, const double* lattice,
+                                 const int32_t* eligible, int ns, double r_max, int n_bins, double width, double cn_tol,
+                                 double* rdf, double* count, int64_t* n_pairs, double* nn_dist, int32_t* cn,
+                                 int32_t* reason);
+/* The nearest partners of fingerprints: fp [nq + nref][len] fp64, queries first; valid [nq + nref]; len >= 1, nq >= 1,
+ * nref >= 0.  D(a, b) = sqrt((1 / len) sum_k (a_k - b_k)^2), computed from the differences directly in ascending k -- not
+ * as |a|^2 + |b|^2 - 2 a.b, which cancels for the near-duplicates this op exists to rank.  D(a, b) and D(b, a) are the
+ * same bits; exact copies give exactly 0.
+ * Outputs (ties to the lower index; an invalid row is nobody's partner and comes back -1 / +inf, as does a row with no
+ * partner): q_ref, q_ref_d [nq] the nearest reference (0 .. nref-1) of each query; ref_q, ref_q_d [nref] the nearest
+ * query of each reference; q_q, q_q_d [nq] the nearest OTHER query; div_sum = sum of D over the valid query pairs q < q',
+ * div_pairs their count.  The order of div_sum: number the valid queries 0, 1, ... in index order and cut them into
+ * segments of 512; s_q = the sum over the segments, ascending, of (the sum of D(q, q') over the segment's q' > q,
+ * ascending); div_sum = the sum of s_q over q ascending.
+ * The same determinism contract as above: fixed order, no floating-point atomics, the same bits run to run and for any
+ * chunking.  ICSG3D_FINGERPRINT_CHUNK_PAIRS (read once per process) shrinks the row x partner pairs of one launch.
+ * Refused, with nothing written: a null argument (ref_q / ref_q_d may be null when nref == 0), len < 1, nq < 1,
+ * nref < 0, a non-finite entry in a valid row (naming the row).
+ * HOST pointers, any nq / nref (chunked internally), synchronous, the calling thread's op stream. */
+int ics_op_fingerprint_nearest(const double* fp, const int32_t* valid, int len, int nq, int nref, int32_t* q_ref,
+                               double* q_ref_d, int32_t* ref_q, double* ref_q_d, int32_t* q_q, double* q_q_d,
+                               double* div_sum, int64_t* div_pairs);
 
 /* ---------------------------------------------------------------- pictures (view_results.py)
  * The panels of view_results.py:152-183 -- viz.py:184-233 (the voxel panels of M, S and the watershed regions) and
